@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X Groth16 hot path.
 
-BASELINE.json's metric has two halves and the default line carries both:
+A plain run (`python bench.py --gpus N --steps K --warmup W`) measures the first half alone: it sets up, warms up, times K steps
+of the pipelined MSM and prints the line (`metric`, `value`, `ms_per_step`, ...); `--dump-outputs DIR` also writes the point the
+last timed step returned. Every other leg described here runs with `--full`.
+
+BASELINE.json's metric has two halves and the `--full` line carries both:
 
   "G1 MSM Mscalar/s at 2^20"  (the line's `metric` / `value`; configs[1] = "2^20 BLS12-381 G1 variable-base MSM,
       synthetic scalars/bases, 1 MI355X"). A step = one full MSM (digits -> sort -> bucket accumulate -> merge ->
@@ -11,7 +15,7 @@ BASELINE.json's metric has two halves and the default line carries both:
       PrivateTransfer circuit (BN254, D = 2^16, V = 35 175, P = 27) through mg_groth16_prove / _prove_batch --
       sequential latency, two host threads on one context, and batches of 256 -- with its own cpu_baseline.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 N > 1 (weak scaling, the line's `value`): the global MSM has N * 2^20 terms, sharded by contiguous base/scalar range,
@@ -75,7 +79,7 @@ def pmc_traffic():
         # hardware queues of their own, the neighbours' digit / sort kernels run beside the accumulate kernel and their bytes land in
         # its sample: 3.0 GB instead of 1.95 GB per launch, round 6)
         env = dict(os.environ, TMPDIR="/tmp", MANTA_BENCH_NO_PMC="1", MANTA_BENCH_DEPTH="1", MANTA_MSM_DEDICATED_QUEUES="0")
-        cmd = [exe, "--kernel-trace", "--pmc", counter, "-d", d, "-o", "m", "--", sys.executable, os.path.abspath(__file__), "--workload", "msm",
+        cmd = [exe, "--kernel-trace", "--pmc", counter, "-d", d, "-o", "m", "--", sys.executable, os.path.abspath(__file__), "--full", "--workload", "msm",
                "--quick", "--no-cpu-baseline", "--steps", "3", "--warmup", "1"]
         r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=600)
         dbs = [os.path.join(dp, f) for dp, _, fs in os.walk(d) for f in fs if f.endswith(".db")]
@@ -330,7 +334,8 @@ class MsmInstance:
         return res
 
     def timed(self, steps, depth, warmup=2, kernel_timing=False):
-        """-> (seconds for `steps` steps: max over ranks, list of accumulate-kernel durations in ms)"""
+        """-> (seconds for `steps` steps: max over ranks, list of accumulate-kernel durations in ms); the point of the last step
+        is kept in `self.last`"""
         env = self.env
         self.run(warmup, depth)
         acc = []
@@ -338,7 +343,7 @@ class MsmInstance:
             self.api.set_kernel_timing(True)
         env.barrier()
         t0 = time.perf_counter()
-        self.run(steps, depth, acc if kernel_timing else None)
+        self.last = self.run(steps, depth, acc if kernel_timing else None)
         env.barrier()
         dt = time.perf_counter() - t0
         if kernel_timing:
@@ -346,21 +351,58 @@ class MsmInstance:
         return env.max_over_ranks(dt), acc
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: what the timed path handed its caller in its last step, as DIR/<name>.npy, so that two builds can be
+    compared output for output (the inputs are seeded: the same arguments give the same inputs). Limbs and proof bytes are
+    unsigned integers; they are written as float64, exactly (64-bit limbs split into their 32-bit halves, little-endian first)."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype == np.uint64:
+            a = a.view(np.uint32)
+        assert a.dtype in (np.uint8, np.uint32), (name, a.dtype)
+        out[name] = a.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_CAP_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_CAP_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def msm_bench(args, env):
+    """The headline (pipelined 2^20 MSM) and, with --full, every other MSM leg. -> (line, instance)"""
     n = 1 << LOG_N
     inst = MsmInstance(env, env.world * n, WINDOW_BITS, seed=0x4D414E54)
-    # ---- correctness gate before any timing counts
-    result = inst.run(1, 1)
-    assert (result == inst.expected()).all(), "MSM result does not match the closed-form expectation"
+    result = None
+    if args.full:
+        # ---- correctness gate before any timing counts
+        result = inst.run(1, 1)
+        assert (result == inst.expected()).all(), "MSM result does not match the closed-form expectation"
 
     dt, acc_pipe = inst.timed(args.steps, DEPTH, warmup=args.warmup, kernel_timing=True)
+    if args.dump_outputs and env.rank == 0:
+        dump_outputs(args.dump_outputs, {"msm_result": inst.last})
     mhz_pipe = [v for v in inst.acc_mhz if v > 0]
     line = {
         "metric": "G1 MSM Mscalar/s at 2^%d" % LOG_N, "value": round(env.world * n * args.steps / dt / 1e6, 3),
         "unit": "Mscalar/s", "n_gpus": env.world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+        "config": {"workload": "2^%d BLS12-381 G1 variable-base MSM per GPU, uniform scalars resident in HBM" % LOG_N,
+                   "curve": "BLS12-381", "log_n": LOG_N, "window_bits": WINDOW_BITS, "msms_in_flight": DEPTH},
     }
+    if env.world > 1:
+        line["config"]["sharding"] = ("contiguous base/scalar ranges; partial points folded on the GPU, all_gather from device memory (RCCL), "
+                                      "N-term host sum" if inst.msm.device_path else
+                                      "contiguous base/scalar ranges, all_gather of partial points from host memory + N-term host sum")
+    else:
+        line["config"]["sharding"] = "none"
+    if not args.full:
+        return line, inst
     # ---- latency mode (one MSM at a time: nothing hides the merge / reduce / host-fold tail) doubles as the
     # stand-alone measurement of the dominant kernel: with one MSM in flight the HIP-event span IS the kernel's duration
     lat_steps = max(5, min(args.steps, 10))
@@ -409,19 +451,14 @@ def msm_bench(args, env):
                                       "pipelined_Mscalar_s": round(n * lat_steps / dt_b3 / 1e6, 2), "algorithmic_bytes_per_scalar": 96}}
         bn.bases.close()
         del bn
-    line["config"] = {
-        "workload": "2^%d BLS12-381 G1 variable-base MSM per GPU, uniform scalars resident in HBM" % LOG_N,
-        "curve": "BLS12-381", "log_n": LOG_N, "window_bits": WINDOW_BITS, "msms_in_flight": DEPTH,
+    line["config"].update({
         "precomputed_base_multiples": True, "bases_hbm_bytes": inst.bases.device_bytes(),
         "windows": -(-255 // WINDOW_BITS),
         "note": "headline = pipelined (%d MSMs in flight) against bases with precomputed 2^(%dw) multiples (a full 2^20 "
                 "BLS12-381 key needs 5 such tables, ~10 GB of the 288 GB)" % (DEPTH, WINDOW_BITS),
         "latency_mode": {"Mscalar_s": round(env.world * n * lat_steps / dt_lat / 1e6, 2), "ms_per_msm": round(dt_lat / lat_steps * 1e3, 4)},
         "plain_bases": plain,
-        "other_inputs_same_size": other,
-        "sharding": ("contiguous base/scalar ranges; partial points folded on the GPU, all_gather from device memory (RCCL), N-term host sum"
-                     if inst.msm.device_path else "contiguous base/scalar ranges, all_gather of partial points from host memory + N-term host sum")
-        if env.world > 1 else "none"}
+        "other_inputs_same_size": other})
 
     roofline = cpu = None
     if env.rank == 0:
@@ -1008,6 +1045,8 @@ def prove_bench(args, env, shape="private_transfer", full=True, profile="W", lit
     K = 256
     nb = K * (4 if full else 2)
     dt, pb, dts = ps.timed(env, nb, 2, K, reps=5 if full else (2 if lite else 1))  # (the headline: median of five repetitions)
+    if args.dump_outputs and env.rank == 0:
+        dump_outputs(args.dump_outputs, {"proofs": np.frombuffer(b"".join(pb), dtype=np.uint8).reshape(len(pb), -1)})
     assert pb[0] == first
     res["batched"] = _rate_stats(env, nb, dts, {"host_threads": 2, "proofs_per_call": K, "proofs": env.world * nb,
                       "ms_per_proof": round(dt / nb * 1e3, 4),
@@ -1093,7 +1132,7 @@ def prove_leg_in_child(args, env):
     cenv = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MANTA_BENCH_DEVICE=str(env.dev))
     for k in ("MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID", "GROUP_RANK", "LOCAL_WORLD_SIZE", "ROLE_RANK"):
         cenv.pop(k, None)
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", "prove", "--child", "--gpus", "1", "--steps", str(args.steps),
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--workload", "prove", "--child", "--gpus", "1", "--steps", str(args.steps),
            "--warmup", str(args.warmup)]
     if args.no_cpu_baseline or env.world > 1 or env.rank != 0:
         cmd.append("--no-cpu-baseline")
@@ -1117,7 +1156,7 @@ def prove_leg_in_child(args, env):
             return out
         res["witness_profiles"] = {"W": summary(res)}
         for prof in ("sparse", "dense"):
-            c3 = cmd[:2] + ["--workload", "prove", "--child", "--profile", prof, "--lite", "--gpus", "1", "--steps", str(args.steps),
+            c3 = cmd[:3] + ["--workload", "prove", "--child", "--profile", prof, "--lite", "--gpus", "1", "--steps", str(args.steps),
                             "--warmup", str(args.warmup)] + (["--no-cpu-baseline"] if args.no_cpu_baseline else [])
             o3 = subprocess.run(c3, env=cenv, capture_output=True, text=True)
             l3 = [ln for ln in o3.stdout.splitlines() if ln.startswith("{")]
@@ -1129,7 +1168,7 @@ def prove_leg_in_child(args, env):
         # SURVEY a-11: the other two shapes of the reference's benches, batched stream only
         res["shapes"] = {}
         for shape in ("to_private", "to_public"):
-            o2 = subprocess.run(cmd[:2] + ["--workload", "prove", "--child", "--shape", shape, "--batched-only", "--no-cpu-baseline", "--gpus", "1",
+            o2 = subprocess.run(cmd[:3] + ["--workload", "prove", "--child", "--shape", shape, "--batched-only", "--no-cpu-baseline", "--gpus", "1",
                                            "--steps", str(args.steps), "--warmup", str(args.warmup)], env=cenv, capture_output=True, text=True)
             l2 = [ln for ln in o2.stdout.splitlines() if ln.startswith("{")]
             if o2.returncode == 0 and l2:
@@ -1302,13 +1341,34 @@ def main():
     ap.add_argument("--lite", action="store_true", help=argparse.SUPPRESS)          # internal: sequential / six threads / batched only
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)         # internal: print the proofs object only
     ap.add_argument("--batched-only", action="store_true", help=argparse.SUPPRESS)  # internal: skip the single-proof legs
+    ap.add_argument("--full", action="store_true",
+                    help="every leg besides the headline: correctness gates, latency mode, other inputs and sizes, the proofs half, NTT, the "
+                         "2^20 proof, roofline and PMC traffic, strong scaling and the sharded proof (N > 1), CPU baselines. Without it a run "
+                         "sets up, warms up, times --steps steps of the headline MSM and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
-    cmd = launch_plan(args.gpus, os.environ, sys.argv[1:])
+    full_only = [name for name, given in (("--quick", args.quick), ("--workload", args.workload != "both"),
+                                          ("--shape", args.shape != "private_transfer"), ("--profile", args.profile != "W"),
+                                          ("--no-cpu-baseline", args.no_cpu_baseline), ("--detail", args.detail), ("--lite", args.lite),
+                                          ("--child", args.child), ("--batched-only", args.batched_only)) if given]
+    if full_only and not args.full:
+        ap.error("%s: option(s) of the full run, add --full" % " ".join(full_only))
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)  # the ranks below start in the repository root
+    cmd = launch_plan(args.gpus, os.environ, sys.argv[1:] + (["--dump-outputs", args.dump_outputs] if args.dump_outputs else []))
     if cmd is not None:  # `python bench.py --gpus N` with no launcher around it: become the launcher
         sys.exit(self_launch(cmd))
     if args.workload == "prove" and not args.batched_only and os.environ.get("MANTA_BENCH_DISTINCT", "1") != "0":
         precompute_assignments(args.shape, 256, args.profile)  # before anything initialises HIP in this process
     env = Env(args)
+    if not args.full:  # the plain run: the headline MSM and its line, nothing else
+        line, _ = msm_bench(args, env)
+        line["collective"] = env.collective
+        if env.rank == 0:
+            print(compact_line(line), flush=True)
+        env.close()
+        return
     if args.workload == "prove":
         res = prove_bench(args, env, args.shape, full=env.world == 1 and not args.batched_only and not args.lite, profile=args.profile,
                           lite=args.lite and env.world == 1)

@@ -299,3 +299,29 @@ def test_front_levels_inside_captured_passes(gpu, min_items):
         assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
         ok = [ln for ln in out.stdout.splitlines() if ln.endswith("8 proofs == oracle")]
         assert len(ok) == 5 and "libmantagpu_diag.so" in out.stdout, out.stdout[-2000:]
+
+
+def test_plain_bench_run_dumps_the_point_of_its_last_step(gpu, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (the plain run, at 2^12 here): the headline's keys, exactly K timed
+    steps, none of the --full legs, and the dumped point is the closed form sum_i k_i (S0 + i S1) times G, computed by the oracle."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    n, steps = 1 << 12, 5
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT,
+                         env=dict(os.environ, MANTA_BENCH_LOGN="12"))
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    line = json.loads(out.stdout.rstrip().splitlines()[-1])
+    assert line["metric"] == "G1 MSM Mscalar/s at 2^12" and line["unit"] == "Mscalar/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "u32" and line["steps"] == steps and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] * 1e3 / n - 1) < 0.01
+    assert not set(line) & {"proofs", "roofline", "cpu_baseline", "ntt", "config2", "hbm_copy_TBps", "verify"}
+    got = np.load(tmp_path / "msm_result.npy")
+    assert got.dtype == np.float64 and got.shape == (24,)
+    p = synth.FR_MODULUS[1]
+    sc = synth.limbs_to_ints(synth.msm_scalars(1, n, "U", seed=0x4D414E54))
+    t = sum(k * ((bench.S0 + i * bench.S1) % p) for i, k in enumerate(sc)) % p
+    want = O.fixed_base_mul(1, 1, O.generator(1, 1), synth.ints_to_limbs([t], 4)).reshape(-1)
+    assert (got.astype(np.uint32).view(np.uint64) == want).all()

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _run(extra_env, *args, port="29541"):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MANTA_BENCH_DEVICE="0", MANTA_BENCH_BACKEND="gloo", **extra_env)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
-                          "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", "2", *args],
+                          "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", *args],
                          capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -45,7 +45,7 @@ def test_two_ranks_on_one_gpu_weak_and_strong_scaling(gpu):
 
 
 def test_bench_gpus_2_starts_itself(gpu):
-    """exactly `python3 bench.py --gpus 2 --steps 2 --warmup 1` -- NO launcher -- is what a driver that builds
+    """`python3 bench.py --gpus 2 --steps 2 --warmup 1` (here with --full) -- NO launcher -- is what a driver that builds
     its N > 1 command like its N = 1 command runs. bench.py becomes the launcher, rank 0 prints the one line as the last line of
     stdout, and the line says what the collective saw. Both ranks sit on device 0 here (one GPU on the box), so the exchange is gloo
     and `devices` holds ONE id; on the 8-GPU node the same path reports nccl and N ids. The parity gate (sharded PrivateTransfer
@@ -53,7 +53,7 @@ def test_bench_gpus_2_starts_itself(gpu):
     env = dict(os.environ, MANTA_BENCH_DEVICE="0", MANTA_BENCH_LOGN="16")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MANTA_BENCH_BACKEND"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1"],
                          capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = json.loads(out.stdout.rstrip().splitlines()[-1])

@@ -192,10 +192,13 @@ for rep in range(4):  # a pass of 8 (two assignments): eager, eager, capture, re
     got = gpu.Groth16.prove_batch(ctx, np.stack([c.z, z2] * 4), np.stack([rs[0], rs[2]] * 4), np.stack([rs[1], rs[3]] * 4))
     print("BATCH", " ".join(g.hex() for g in got))
 import threading
+out_lock = threading.Lock()  # print() writes text and newline apart: two threads could merge their lines
 def worker(t):  # two host threads at once: single proofs beside another pass (slots of their own: eager, capture, replay)
     for i in range(10):
         j = (i + t) & 1
-        print("CONC %d %s" % (j, gpu.Groth16.prove_with_randomness(ctx, z2 if j else c.z, rs[2 * j], rs[2 * j + 1]).hex()), flush=True)
+        h = gpu.Groth16.prove_with_randomness(ctx, z2 if j else c.z, rs[2 * j], rs[2 * j + 1]).hex()
+        with out_lock:
+            print("CONC %d %s" % (j, h), flush=True)
 ts = [threading.Thread(target=worker, args=(t,)) for t in range(2)]
 [t.start() for t in ts]
 [t.join() for t in ts]

@@ -164,10 +164,13 @@ for rep in range(4):
     print("BATCH", " ".join(g.hex() for g in got))
 big = gpu.Groth16.prove_batch(ctx, np.stack([c.z, z2] * 40), np.stack([rs[0], rs[2]] * 40), np.stack([rs[1], rs[3]] * 40))  # three passes
 print("BIG", len(big), len(set(big[0::2])), len(set(big[1::2])), big[0].hex(), big[1].hex())
+out_lock = threading.Lock()  # print() writes text and newline apart: two threads could merge their lines
 def worker(t):
     for i in range(10):
         j = (i + t) & 1
-        print("CONC %d %s" % (j, gpu.Groth16.prove_with_randomness(ctx, z2 if j else c.z, rs[2 * j], rs[2 * j + 1]).hex()), flush=True)
+        h = gpu.Groth16.prove_with_randomness(ctx, z2 if j else c.z, rs[2 * j], rs[2 * j + 1]).hex()
+        with out_lock:
+            print("CONC %d %s" % (j, h), flush=True)
 ts = [threading.Thread(target=worker, args=(t,)) for t in range(3)]
 [t.start() for t in ts]
 [t.join() for t in ts]

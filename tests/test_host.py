@@ -353,6 +353,32 @@ def test_bench_rank_refuses_a_launcher_that_disagrees(tmp_path):
     assert out.returncode != 0 and "WORLD_SIZE=2 but --gpus 4" in out.stderr and "AssertionError" not in out.stderr
 
 
+@pytest.mark.parametrize("flag", [["--quick"], ["--workload", "msm"], ["--no-cpu-baseline"], ["--child"]])
+def test_bench_plain_run_refuses_options_of_the_full_run(flag):
+    """The plain run times the headline and nothing else; an option that selects legs of the full run without --full is a usage
+    error (a script expecting those legs must not get the plain line silently), before any device is touched."""
+    import subprocess
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + flag, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 2 and flag[0] in out.stderr and "--full" in out.stderr, out.stderr
+
+
+def test_bench_dump_outputs_is_exact(tmp_path):
+    """--dump-outputs writes float64 arrays that give back every bit of the limbs / bytes the timed path returned, and refuses
+    more than 64 MB in all without writing anything."""
+    import bench
+    limbs = np.array([[(1 << 64) - 1, 0x0123456789ABCDEF, 1], [1 << 63, 0, (1 << 32) + 7]], dtype=np.uint64)
+    proofs = np.arange(256, dtype=np.uint8).reshape(2, 128)
+    bench.dump_outputs(str(tmp_path / "d"), {"msm_result": limbs, "proofs": proofs})
+    a = np.load(tmp_path / "d" / "msm_result.npy")
+    assert a.dtype == np.float64 and a.shape == (2, 6)
+    assert (a.astype(np.uint32).view(np.uint64) == limbs).all()
+    b = np.load(tmp_path / "d" / "proofs.npy")
+    assert b.dtype == np.float64 and (b.astype(np.uint8) == proofs).all()
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros((bench.DUMP_CAP_BYTES // 8) + 1, dtype=np.uint32)})
+    assert not (tmp_path / "big").exists()
+
+
 def test_tuning_crosses_the_abi_and_the_library_reads_fifteen_variables():
     """VERDICT r5 item 7: what a deployment decides lives in `mg_tuning` (C header == Python mirror == Rust mirror, checked above);
     the shipped library reads the environment in ONE place -- the table behind mg_tuning_env_names (<= 15 names) -- and every

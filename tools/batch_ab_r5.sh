@@ -6,7 +6,7 @@ profiles=$1; shift
 for rep in 1 2; do
 for prof in $profiles; do
   for v in "$@"; do
-    r=$(env $v python bench.py --workload prove --child --batched-only --no-cpu-baseline --profile $prof 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%.0f (min %.0f max %.0f)' % (d['batched']['proofs_per_s'], d['batched']['min'], d['batched']['max']))")
+    r=$(env $v python bench.py --full --workload prove --child --batched-only --no-cpu-baseline --profile $prof 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%.0f (min %.0f max %.0f)' % (d['batched']['proofs_per_s'], d['batched']['min'], d['batched']['max']))")
     echo "rep $rep  $prof  [${v:-default}]  $r proofs/s"
   done
 done

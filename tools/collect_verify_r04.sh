@@ -2,7 +2,7 @@
 # dev tool: round-4 verification measurements on the GPU box -> gpurun_out/$1/ (run from the repo root): the driver-style bench line,
 # kernel statistics of single / batched verifications, timelines, building blocks
 R=$PWD; O=$R/gpurun_out/${1:-r04verify}; mkdir -p $O
-timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err
 tools/verify_timeline.sh > $O/verify_timeline.txt 2>&1
 for i in 1 2 3; do python tools/verify_profile.py 100 2>/dev/null | tail -1; done >> $O/verify_timeline.txt
 tools/verify_batch_timeline.sh > $O/verify_batch_timeline.txt 2>&1

@@ -5,7 +5,7 @@ out=${1:-gpurun_out/red_sweep}
 mkdir -p $out
 run() {
   name=$1; shift
-  env "$@" python bench.py --quick --no-cpu-baseline --steps 12 > $out/$name.json 2> $out/$name.err
+  env "$@" python bench.py --full --quick --no-cpu-baseline --steps 12 > $out/$name.json 2> $out/$name.err
   python - "$name" "$out/$name.json" <<'PY'
 import json, sys
 try:
