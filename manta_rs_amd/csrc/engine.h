@@ -196,6 +196,21 @@ struct BaseSet {
     size_t bytes = 0;
 };
 
+// What msm_launch staged for the fold of every window segment (msm_finish on the host, msm_fold_device / fold_windows on the
+// device), arkworks-format XYZZ points. The kinds:
+//   WINDOW_SUMS  one point per segment: the window sum (direct results, one scan tile per window)
+//   X_SUMS       (X, sumS) per segment: window = sumS + 2^6 X
+//   TWO_LEVELS   A1[T1] | S1[T1] | P0[nP] blocks over all segments: X = sum S1 + 2^6 sum_u u A1[u], window = sum P0 + 2^6 X
+enum MsmTailKind : u32 { TAIL_WINDOW_SUMS = 0, TAIL_X_SUMS = 1, TAIL_TWO_LEVELS = 2 };
+struct MsmTail {
+    static constexpr int MAX_EXTRA = 8;
+    MsmTailKind kind = TAIL_WINDOW_SUMS;
+    u32 T1 = 0, nP = 0, segs = 0; // T1, nP: TWO_LEVELS only; segs: window segments = scalar vectors x bucket windows
+    u32 tail_shift = 0, n_extra = 0, extra_shift[MAX_EXTRA] = {}; // front levels: window = 2^tail_shift * tail + sum_e 2^shift_e * extra_e
+    size_t extra_off_pts = 0;    // where the extras start in h_stage (points)
+    const u32 *d_tail = nullptr; // device copy of the staged tail (the extras are MsmWorkspace::extra)
+};
+
 // Per-call scratch for one MSM (device + pinned host staging). Pooled per engine.
 struct MsmWorkspace {
     DevBuf keys_in, keys_out, vals_in, vals_out, sort_tmp, buckets, pkeys[2], ppts[2], redA, redS, misc;
@@ -203,10 +218,6 @@ struct MsmWorkspace {
     // work-efficient front levels of the bucket reduce (msm_impl.h serial_reduce): per-lane (A, S) arrays and the
     // temporaries of the plain sums; `extra` = one staged point per (front level, window segment)
     DevBuf front, extra;
-    static constexpr int MAX_EXTRA = 8;
-    u32 tail_shift = 0, n_extra = 0, extra_shift[MAX_EXTRA] = {}; // window = 2^tail_shift * tail + sum_e 2^shift_e * extra_e
-    size_t extra_off_pts = 0;                                       // where the extras start in h_stage (points)
-    const u32 *d_tail = nullptr; // device copy of what msm_launch staged for the host fold (arkworks-format XYZZ points)
     DevBuf folded;               // msm_fold_device: one arkworks-format XYZZ point per batch member
     // kernel timing: (s_memtime ticks, wall-clock ticks) of the accumulate kernel's first wavefront, written by the kernel straight to
     // page-locked HOST memory and read after the `done` event -- no copy on the NULL stream, which would order itself against every
@@ -241,9 +252,10 @@ struct MsmWorkspace {
     u32 *h_flag = nullptr; // pinned, owned
     u32 *d_token = nullptr; // device word holding 1, owned
     float accumulate_ms = 0.f;
-    // host-side description of what was staged (filled by msm_launch, consumed by msm_finish)
+    // host-side description of what was staged (filled by msm_launch, consumed by msm_finish / msm_fold_device)
     MsmPlan plan;
-    u32 T1 = 0, nP = 0, batch = 1;
+    MsmTail tail;
+    u32 batch = 1;
     int pending = 0;
     int device = 0;
     ~MsmWorkspace();

@@ -445,15 +445,14 @@ __global__ __launch_bounds__(256) MG_TAIL_COOP_ATTR void reduce_level1_coop(cons
 // --------------------------------------------------------------------------------------------
 // K9 on the device: the fold msm_finish does on the host, for one bucket window per scalar vector (bases with precomputed
 // multiples). One wavefront per vector; every lane computes the same chain (a dozen additions and doublings), lane 0 stores.
-// Layouts (arkworks-format XYZZ points, as staged for the host): kind 0 = the window sum itself; kind 1 = (X, sumS) pairs,
-// window = sumS + 2^6 X; kind 2 = A1[T1] | S1[T1] | P0[nP] blocks over all vectors, X = sum S1 + 2^6 sum_u u A1[u],
-// window = sum P0 + 2^6 X. Front levels: window = 2^tail_shift * that + sum_e 2^shift_e * extra_e.
+// Layouts: engine.h MsmTail, as staged for the host.
 // --------------------------------------------------------------------------------------------
-struct FoldDesc {
+struct FoldDesc { // a kernel argument: field order and sizes are fixed
     const u32 *tail, *extra;
-    u32 kind, T1, nP, segs, n_extra, tail_shift;
+    u32 kind, T1, nP, segs, n_extra, tail_shift; // kind: MsmTailKind
     u32 extra_shift[8];
 };
+static_assert(sizeof(FoldDesc::extra_shift) == sizeof(MsmTail::extra_shift), "FoldDesc::extra_shift holds MsmTail::MAX_EXTRA shifts");
 template <class F>
 __global__ __launch_bounds__(64) void fold_windows(FoldDesc d, u32 *__restrict__ out, size_t out_stride) {
     MG_PRIO_FOR(F);
@@ -470,9 +469,9 @@ __global__ __launch_bounds__(64) void fold_windows(FoldDesc d, u32 *__restrict__
         return p;
     };
     XYZZ<F> win = XYZZ<F>::inf();
-    if (d.kind == 0) {
+    if (d.kind == TAIL_WINDOW_SUMS) {
         win = ld(d.tail + (size_t)q * SW);
-    } else if (d.kind == 1) {
+    } else if (d.kind == TAIL_X_SUMS) {
         win = pow2(ld(d.tail + ((size_t)q * 2 + 0) * SW), 6);
         win.add(ld(d.tail + ((size_t)q * 2 + 1) * SW));
     } else {
