@@ -465,6 +465,36 @@ int mg_pairing_check(mg_curve_t curve, const uint64_t *g1_affine, const uint64_t
  * encodings, points off the curve or outside the subgroup. */
 int mg_proof_decode(mg_curve_t curve, const uint8_t *proof_bytes, uint64_t *points_out);
 
+/* ---- batched point codec: arkworks 0.3 short-Weierstrass encodings on the GPU, one point per lane. Replaces per-point
+ *      `GroupAffine: CanonicalDeserialize` + `is_in_correct_subgroup_assuming_on_curve` (ark-ec 0.3) as run by
+ *      `Proof::deserialize`, `kzg::Accumulator`'s deserializer (manta-trusted-setup/src/groth16/kzg.rs:607-690, `C::check`
+ *      on every power) and `mpc::State::check` (groth16/mpc.rs:79-100), and `CanonicalSerialize` of the same points.
+ *      Encoding: x (G2: x.c0 || x.c1) little-endian canonical, flags in the two top bits of the LAST byte of the record
+ *      (bit 6 = infinity, bit 7 = y is the lexicographically larger root, c1 first then c0; both set is invalid);
+ *      uncompressed = x || y with the flags on y. Every coordinate read must be canonical, infinity's included. The
+ *      subgroup test is [r]P == O. Synchronous, thread-safe, on the calling thread's setup stream; the points go through
+ *      the GPU 65 536 at a time (device memory and pinned staging of a call < 26 MB whatever n); n = 0 succeeds. The return
+ *      value reports only operational failures: bad points are reported per point. ------------------------------------ */
+#define MG_POINT_OK 0
+#define MG_POINT_BAD_ENCODING 1    /* coordinate >= q, both flag bits set, or a bit above the modulus set */
+#define MG_POINT_NOT_ON_CURVE 2    /* uncompressed: y^2 != x^3 + b; compressed: x^3 + b has no square root */
+#define MG_POINT_NOT_IN_SUBGROUP 3 /* on the curve, [r]P != O */
+/* n encodings of 32/48 (G1) or 64/96 (G2) bytes each, doubled when uncompressed -> n affine Montgomery points (zeros for
+ * infinity and for every rejected point) and status[i] = MG_POINT_*; status and n_bad (rejected count) may be NULL.
+ * checked = 1: `CanonicalDeserialize::deserialize` (curve and subgroup); checked = 0: `deserialize_unchecked`, only for
+ * uncompressed input (as the proving-key reader): canonical coordinates and flags only. */
+int mg_points_decode(mg_curve_t curve, int group, const uint8_t *bytes, size_t n, int compressed, int checked,
+                     uint64_t *out_affine_mont, uint8_t *status, size_t *n_bad);
+/* `C::check` / `State::check` on n affine Montgomery points in memory (zeros = infinity): MG_POINT_BAD_ENCODING for a
+ * coordinate >= q, else curve, then subgroup. status must hold n bytes; n_bad may be NULL. */
+int mg_points_check(mg_curve_t curve, int group, const uint64_t *affine_mont, size_t n, uint8_t *status, size_t *n_bad);
+/* `CanonicalSerialize` of n affine Montgomery points, byte for byte mg_point_serialize, back to back into out. */
+int mg_points_encode(mg_curve_t curve, int group, const uint64_t *affine_mont, size_t n, int compressed, uint8_t *out);
+/* k compressed proofs a | b | c back to back (128 / 192 bytes each) -> k rows a | b | c of affine Montgomery limbs, as
+ * mg_proof_decode gives one: ok[i] = 1 iff that call would accept proof i; a rejected proof's row is zeros. Then
+ * mg_groth16_verify_batch on the accepted rows. */
+int mg_proofs_decode(mg_curve_t curve, const uint8_t *proof_bytes, size_t k, uint64_t *points_out, uint8_t *ok);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,7 @@ EXPORTS = [
     "mg_last_ntt_ms", "mg_hw_queues", "mg_last_prove_phases_ms", "mg_clock_probe", "mg_last_accumulate_mhz", "mg_ctx_create_task",
     "mg_ctx_opts_init", "mg_ctx_create_ex", "mg_ctx_create_from_bytes_ex", "mg_last_pass_host_ms",
     "mg_tuning_init", "mg_get_tuning", "mg_set_tuning", "mg_tuning_env_names",
+    "mg_points_decode", "mg_points_check", "mg_points_encode", "mg_proofs_decode",
 ]
 
 
@@ -822,6 +823,67 @@ def proof_decode(curve, proof_bytes) -> np.ndarray:
     out = np.zeros(2 * affine_limbs(curve, 1) + affine_limbs(curve, 2), dtype=np.uint64)
     _chk(LIB.mg_proof_decode(curve, bytes(proof_bytes), _p(out)), "mg_proof_decode")
     return out
+
+
+# per-point status of the batched codec (mantagpu.h MG_POINT_*)
+POINT_OK, POINT_BAD_ENCODING, POINT_NOT_ON_CURVE, POINT_NOT_IN_SUBGROUP = 0, 1, 2, 3
+
+
+def point_bytes(curve, group, compressed=True):
+    """bytes of one arkworks point encoding: 32 / 48 (G1), 64 / 96 (G2), twice that uncompressed"""
+    return FQ_LIMBS[curve] * 8 * (2 if group == 2 else 1) * (1 if compressed else 2)
+
+
+def _joined(data):
+    return bytes(data) if isinstance(data, (bytes, bytearray, memoryview)) else b"".join(bytes(d) for d in data)
+
+
+def points_decode(curve, group, data, compressed=True, checked=True):
+    """Batched `CanonicalDeserialize` of arkworks point encodings on the GPU (`mg_points_decode`): data = the encodings
+    back to back (or a sequence of them). Returns (points [n, limbs] affine Montgomery, zeros for infinity and for rejected
+    points; status [n] uint8, POINT_*). checked=False is `deserialize_unchecked` (uncompressed only)."""
+    data = _joined(data)
+    nb = point_bytes(curve, group, compressed)
+    if len(data) % nb:
+        raise ValueError(f"{len(data)} bytes is not a whole number of {nb}-byte encodings")
+    n = len(data) // nb
+    out = np.zeros((n, affine_limbs(curve, group)), dtype=np.uint64)
+    st = np.zeros(n, dtype=np.uint8)
+    _chk(LIB.mg_points_decode(curve, group, data, _sz(n), int(compressed), int(checked), _p(out), _p(st), None),
+         "mg_points_decode")
+    return out, st
+
+
+def points_check(curve, group, points) -> np.ndarray:
+    """`C::check` / `State::check` on the GPU (`mg_points_check`): status [n] uint8 (POINT_*) of affine Montgomery points."""
+    pts = _u64(points).reshape(-1, affine_limbs(curve, group))
+    st = np.zeros(pts.shape[0], dtype=np.uint8)
+    _chk(LIB.mg_points_check(curve, group, _p(pts), _sz(pts.shape[0]), _p(st), None), "mg_points_check")
+    return st
+
+
+def points_encode(curve, group, points, compressed=True) -> bytes:
+    """Batched `CanonicalSerialize` on the GPU (`mg_points_encode`): the encodings back to back, each byte for byte
+    `point_serialize`."""
+    pts = _u64(points).reshape(-1, affine_limbs(curve, group))
+    out = ctypes.create_string_buffer(max(1, pts.shape[0] * point_bytes(curve, group, compressed)))
+    _chk(LIB.mg_points_encode(curve, group, _p(pts), _sz(pts.shape[0]), int(compressed), out), "mg_points_encode")
+    return out.raw[:pts.shape[0] * point_bytes(curve, group, compressed)]
+
+
+def proofs_decode(curve, proofs):
+    """k proofs (byte strings, or their concatenation) decoded and checked on the GPU (`mg_proofs_decode`). Returns
+    (points [k, limbs] a | b | c rows as `proof_decode` gives, zeros where rejected; ok [k] bool: proof_decode would
+    accept proof i)."""
+    data = _joined(proofs)
+    pb = 4 * FQ_LIMBS[curve] * 8
+    if len(data) % pb:
+        raise ValueError(f"{len(data)} bytes is not a whole number of {pb}-byte proofs")
+    k = len(data) // pb
+    out = np.zeros((k, 2 * affine_limbs(curve, 1) + affine_limbs(curve, 2)), dtype=np.uint64)
+    ok = np.zeros(k, dtype=np.uint8)
+    _chk(LIB.mg_proofs_decode(curve, data, _sz(k), _p(out), _p(ok)), "mg_proofs_decode")
+    return out, ok.astype(bool)
 
 
 class VerifyingContext:

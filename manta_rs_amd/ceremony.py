@@ -10,6 +10,8 @@ manta-trusted-setup's hot loops, every group operation through the C ABI (`mg_ec
     same_ratio                  manta-crypto/src/arkworks/pairing.rs:88-109   e(a0, b1) == e(a1, b0) as one pairing product (`mg_pairing_check`)
     check_transform             groth16/mpc.rs:487-508                    the verifier's consistency checks of one contribution
     power_pairs / check_powers  util.rs:333-346, groth16/kzg.rs:508-521   consecutive powers differ by one ratio (kzg verifier)
+    state_check                 groth16/mpc.rs:79-100                     every point of a proving key on the curve and in the subgroup
+    Accumulator.encode / decode groth16/kzg.rs:560-690                    the accumulator's arkworks serialisation, checked (`C::check`)
 
 Scalars are Python integers (the ceremony's RNG stays with the caller); points are [n, limbs] uint64 affine Montgomery
 arrays, infinity = zeros -- the C ABI's format. Not used by the prover; a ceremony is a one-off, which is why SURVEY.md
@@ -159,6 +161,76 @@ class Accumulator:
             if not same(c, (lhs, t2[0]), (rhs, t2[1])):
                 return err
         return ""
+
+    FIELDS = (("tau_powers_g1", 1), ("tau_powers_g2", 2), ("alpha_tau_powers_g1", 1), ("beta_tau_powers_g1", 1), ("beta_g2", 2))
+
+    def encode(self, compressed=True) -> bytes:
+        """kzg.rs `serialize` / `serialize_uncompressed`: every point in field order, tau^i G1, tau^i G2, alpha tau^i G1,
+        beta tau^i G1, beta G2 -- encoded on the GPU."""
+        return b"".join(api.points_encode(self.curve, g, getattr(self, f), compressed) for f, g in self.FIELDS)
+
+    @classmethod
+    def decode(cls, curve, data, g1_powers, g2_powers, compressed=True):
+        """kzg.rs:607-690 `deserialize` / `deserialize_uncompressed`: the accumulator with g1_powers powers in G1 and
+        g2_powers in G2, every point checked (`C::check`: canonical, on the curve, in the subgroup) on the GPU -- all G1
+        points in one batch, all G2 points in another. A rejected point raises AccumulatorDecodeError naming it."""
+        counts = {"tau_powers_g1": g1_powers, "tau_powers_g2": g2_powers, "alpha_tau_powers_g1": g2_powers,
+                  "beta_tau_powers_g1": g2_powers, "beta_g2": 1}
+        data = bytes(data)
+        spans, off = {}, 0
+        for f, g in cls.FIELDS:
+            nb = counts[f] * api.point_bytes(curve, g, compressed)
+            spans[f] = (off, off + nb)
+            off += nb
+        if off != len(data):
+            raise ValueError(f"an accumulator of {g1_powers} / {g2_powers} powers is {off} bytes, not {len(data)}")
+        out = {}
+        for g in (1, 2):
+            fields = [f for f, gg in cls.FIELDS if gg == g]
+            pts, st = api.points_decode(curve, g, b"".join(data[slice(*spans[f])] for f in fields), compressed)
+            bad = np.flatnonzero(st)
+            if bad.size:
+                i = int(bad[0])
+                for f in fields:
+                    if i < counts[f]:
+                        raise AccumulatorDecodeError(f, i, int(st[bad[0]]))
+                    i -= counts[f]
+            o = 0
+            for f in fields:
+                out[f] = pts[o:o + counts[f]]
+                o += counts[f]
+        return cls(curve, out["tau_powers_g1"], out["tau_powers_g2"], out["alpha_tau_powers_g1"], out["beta_tau_powers_g1"],
+                   out["beta_g2"])
+
+
+class AccumulatorDecodeError(ValueError):
+    """a point of an accumulator's encoding was rejected: field name, index in it, status (api.POINT_*)"""
+
+    def __init__(self, field, index, status):
+        super().__init__(f"{field}[{index}]: status {status}")
+        self.field, self.index, self.status = field, index, status
+
+
+# mpc.rs:85-98: the order in which `State::check` visits the key's points
+STATE_G1 = ("alpha_g1", "gamma_abc_g1", "beta_g1", "delta_g1", "a_query", "b_g1_query", "h_query", "l_query")
+STATE_G2 = ("beta_g2", "gamma_g2", "delta_g2", "b_g2_query")
+
+
+def state_check(curve, pk):
+    """mpc.rs:79-100 `State::check`: every G1 and G2 point of the proving key on the curve and in the subgroup, on the GPU
+    (one batch per group). Returns None, or (query, index) of the first offending point in the reference's order."""
+    for group, names in ((1, STATE_G1), (2, STATE_G2)):
+        w = api.affine_limbs(curve, group)
+        parts = [np.asarray(getattr(pk, k), dtype=np.uint64).reshape(-1, w) for k in names]
+        st = api.points_check(curve, group, np.concatenate(parts))
+        bad = np.flatnonzero(st)
+        if bad.size:
+            i = int(bad[0])
+            for k, part in zip(names, parts):
+                if i < part.shape[0]:
+                    return k, i
+                i -= part.shape[0]
+    return None
 
 
 def lagrange_basis(curve, group, powers, D) -> np.ndarray:

@@ -799,3 +799,33 @@ MG_API int mg_proof_decode(mg_curve_t curve, const uint8_t *proof_bytes, uint64_
     return proof_decode((int)curve, proof_bytes, points_out);
     MG_CATCH
 }
+
+namespace mg {
+int points_decode(int curve, int group, const uint8_t *bytes, size_t n, int compressed, int checked, u64 *out,
+                  uint8_t *status, size_t *n_bad);
+int points_check(int curve, int group, const u64 *affine, size_t n, uint8_t *status, size_t *n_bad);
+int points_encode(int curve, int group, const u64 *affine, size_t n, int compressed, uint8_t *out);
+int proofs_decode(int curve, const uint8_t *bytes, size_t k, u64 *points_out, uint8_t *ok);
+} // namespace mg
+MG_API int mg_points_decode(mg_curve_t curve, int group, const uint8_t *bytes, size_t n, int compressed, int checked,
+                            uint64_t *out_affine_mont, uint8_t *status, size_t *n_bad) {
+    MG_TRY
+    return points_decode((int)curve, group, bytes, n, compressed, checked, out_affine_mont, status, n_bad);
+    MG_CATCH
+}
+MG_API int mg_points_check(mg_curve_t curve, int group, const uint64_t *affine_mont, size_t n, uint8_t *status,
+                           size_t *n_bad) {
+    MG_TRY
+    return points_check((int)curve, group, affine_mont, n, status, n_bad);
+    MG_CATCH
+}
+MG_API int mg_points_encode(mg_curve_t curve, int group, const uint64_t *affine_mont, size_t n, int compressed, uint8_t *out) {
+    MG_TRY
+    return points_encode((int)curve, group, affine_mont, n, compressed, out);
+    MG_CATCH
+}
+MG_API int mg_proofs_decode(mg_curve_t curve, const uint8_t *proof_bytes, size_t k, uint64_t *points_out, uint8_t *ok) {
+    MG_TRY
+    return proofs_decode((int)curve, proof_bytes, k, points_out, ok);
+    MG_CATCH
+}

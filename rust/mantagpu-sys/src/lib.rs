@@ -34,6 +34,11 @@ pub const MG_EC_MUL: c_int = 3;
 pub const MG_EC_SUB_MIXED: c_int = 4;
 pub const MG_EC_MUL_FIXED: c_int = 5;
 
+pub const MG_POINT_OK: u8 = 0;
+pub const MG_POINT_BAD_ENCODING: u8 = 1;
+pub const MG_POINT_NOT_ON_CURVE: u8 = 2;
+pub const MG_POINT_NOT_IN_SUBGROUP: u8 = 3;
+
 pub const MG_FIELD_ADD: c_int = 0;
 pub const MG_FIELD_SUB: c_int = 1;
 pub const MG_FIELD_MUL: c_int = 2;
@@ -381,4 +386,20 @@ extern "C" {
     ) -> c_int;
     pub fn mg_pairing_check(curve: mg_curve_t, g1_affine: *const u64, g2_affine: *const u64, n: usize, ok: *mut c_int) -> c_int;
     pub fn mg_proof_decode(curve: mg_curve_t, proof_bytes: *const u8, points_out: *mut u64) -> c_int;
+
+    // ---- batched point codec (arkworks 0.3 encodings, per-point status MG_POINT_*)
+    pub fn mg_points_decode(
+        curve: mg_curve_t,
+        group: c_int,
+        bytes: *const u8,
+        n: usize,
+        compressed: c_int,
+        checked: c_int,
+        out_affine_mont: *mut u64,
+        status: *mut u8,
+        n_bad: *mut usize,
+    ) -> c_int;
+    pub fn mg_points_check(curve: mg_curve_t, group: c_int, affine_mont: *const u64, n: usize, status: *mut u8, n_bad: *mut usize) -> c_int;
+    pub fn mg_points_encode(curve: mg_curve_t, group: c_int, affine_mont: *const u64, n: usize, compressed: c_int, out: *mut u8) -> c_int;
+    pub fn mg_proofs_decode(curve: mg_curve_t, proof_bytes: *const u8, k: usize, points_out: *mut u64, ok: *mut u8) -> c_int;
 }
