@@ -495,6 +495,40 @@ int mg_points_encode(mg_curve_t curve, int group, const uint64_t *affine_mont, s
  * mg_groth16_verify_batch on the accepted rows. */
 int mg_proofs_decode(mg_curve_t curve, const uint8_t *proof_bytes, size_t k, uint64_t *points_out, uint8_t *ok);
 
+/* ---- batched Poseidon over the scalar field and the hashing of manta's UTXO Merkle forest. Replaces, in bulk,
+ *      `Hasher<S, T, ARITY>::hash` (manta-pay/src/crypto/poseidon/hash.rs:111-153) and the Poseidon permutation
+ *      (poseidon/mod.rs:383-419), and the inner hashing of `merkle_tree::Full` (root, `Path`) of manta-pay's UTXO accumulator
+ *      (config/utxo.rs:1200-1301): one state per GPU lane. Field elements are Montgomery limbs (4 x u64) of Fr of `curve`.
+ *      Synchronous, thread-safe and re-entrant, on the calling thread's setup stream. permute / hash run at most
+ *      MG_POSEIDON_CHUNK states at a time: device memory of a call < MG_POSEIDON_CHUNK x 192 B (96 MiB) + the parameters,
+ *      whatever n, and no pinned host memory. A tree keeps every level on the device for its paths (about 2 n x 32 B); a
+ *      forest alternates two level buffers (about 1.5 x its leaves x 32 B). ------------------------------------------------ */
+#define MG_POSEIDON_CHUNK (1u << 19)
+typedef struct mg_poseidon mg_poseidon; /* a decoded parameter set (host memory only: creating one needs no GPU) */
+/* bytes = the manta codec of `Hasher<S, T, ARITY>` (hash.rs:155-192, mod.rs:465-506): (full_rounds + partial_rounds) x width
+ * additive round keys, the width x width MDS matrix row-major, the domain tag; 32-byte little-endian canonical elements each.
+ * MG_ERROR_INVALID_ARGUMENT, with nothing allocated, for width outside 3..6, full_rounds odd or <= 0, partial_rounds < 0, a
+ * length that does not match, or an element >= r. */
+int mg_poseidon_create(mg_curve_t curve, int width, int full_rounds, int partial_rounds, const uint8_t *bytes, size_t len,
+                       mg_poseidon **out);
+void mg_poseidon_destroy(mg_poseidon *h);
+/* n states of `width` words each, permuted in place */
+int mg_poseidon_permute(const mg_poseidon *h, uint64_t *states_mont, size_t n);
+/* n x (width - 1) inputs -> n digests: word 0 of the permutation of (domain tag, inputs) */
+int mg_poseidon_hash(const mg_poseidon *h, const uint64_t *inputs_mont, size_t n, uint64_t *out_mont);
+/* the same on HBM pointers (as mg_ntt_device), whole batch in one launch */
+int mg_poseidon_hash_device(const mg_poseidon *h, const uint64_t *d_inputs_mont, size_t n, uint64_t *d_out_mont);
+/* A tree of `height` (2..32) with n <= 2^(height - 1) leaves inserted left to right (leaf hash = identity, utxo.rs:1188);
+ * h must have width 3. A node whose subtree holds no leaf is 0, every other node is hash(left, right) with an absent child
+ * = 0. root_out: 4 limbs (0 for n = 0). For each of the k indices (< n) paths_out gets manta's `Path`: the leaf sibling,
+ * then the height - 2 inner siblings bottom-up, height - 1 digests in all, absent siblings = 0. */
+int mg_merkle_tree(const mg_poseidon *h, unsigned height, const uint64_t *leaves_mont, size_t n, uint64_t *root_out,
+                   const uint64_t *indices, size_t k, uint64_t *paths_out);
+/* n_trees trees of `height` at once: tree i holds leaves offsets[i] .. offsets[i + 1] - 1 (offsets[0] = 0, non-decreasing,
+ * at most 2^(height - 1) each) -> roots_out[i]. Routing leaves to trees stays with the caller (utxo.rs:1319-1337). */
+int mg_merkle_forest_roots(const mg_poseidon *h, unsigned height, const uint64_t *leaves_mont, const uint64_t *offsets,
+                           size_t n_trees, uint64_t *roots_out);
+
 #ifdef __cplusplus
 }
 #endif

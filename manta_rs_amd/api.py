@@ -72,6 +72,8 @@ EXPORTS = [
     "mg_ctx_opts_init", "mg_ctx_create_ex", "mg_ctx_create_from_bytes_ex", "mg_last_pass_host_ms",
     "mg_tuning_init", "mg_get_tuning", "mg_set_tuning", "mg_tuning_env_names",
     "mg_points_decode", "mg_points_check", "mg_points_encode", "mg_proofs_decode",
+    "mg_poseidon_create", "mg_poseidon_destroy", "mg_poseidon_permute", "mg_poseidon_hash", "mg_poseidon_hash_device",
+    "mg_merkle_tree", "mg_merkle_forest_roots",
 ]
 
 
@@ -884,6 +886,97 @@ def proofs_decode(curve, proofs):
     ok = np.zeros(k, dtype=np.uint8)
     _chk(LIB.mg_proofs_decode(curve, data, _sz(k), _p(out), _p(ok)), "mg_proofs_decode")
     return out, ok.astype(bool)
+
+
+POSEIDON_CHUNK = 1 << 19  # MG_POSEIDON_CHUNK: states per device pass of permute / hash
+# (full, partial) rounds per width of manta-pay's Poseidon specifications (manta-pay/src/config/poseidon.rs:26-48)
+POSEIDON_ROUNDS = {3: (8, 55), 4: (8, 55), 5: (8, 56), 6: (8, 56)}
+
+
+def poseidon_param_count(width, full_rounds, partial_rounds):
+    """field elements of a `Hasher` encoding: round keys, MDS matrix, domain tag"""
+    return (full_rounds + partial_rounds) * width + width * width + 1
+
+
+class PoseidonHasher:
+    """`Hasher<S, T, ARITY>` (manta-pay/src/crypto/poseidon/hash.rs) over Fr of `curve`, run on the GPU one state per lane:
+    `permute` (the Poseidon permutation), `hash` (word 0 of the permutation of (domain tag, inputs)) and `hash_device`.
+    Elements are [.., 4] uint64 Montgomery limbs."""
+
+    def __init__(self, curve, width, full_rounds, partial_rounds, data):
+        self._h = _vp()
+        self.curve, self.width, self.full_rounds, self.partial_rounds = curve, width, full_rounds, partial_rounds
+        data = bytes(data)
+        _chk(LIB.mg_poseidon_create(curve, int(width), int(full_rounds), int(partial_rounds), data, _sz(len(data)),
+                                    ctypes.byref(self._h)), "mg_poseidon_create")
+
+    @classmethod
+    def decode(cls, curve, data, width=None, full_rounds=None, partial_rounds=None):
+        """the manta codec of a `Hasher` (keys | MDS | tag, 32-byte canonical elements): the width follows from the length
+        and the round counts from the width (manta-pay's specifications) unless given"""
+        data = bytes(data)
+        if width is None:
+            fit = [w for w, (f, p) in POSEIDON_ROUNDS.items() if 32 * poseidon_param_count(w, f, p) == len(data)]
+            if not fit:
+                raise ValueError(f"{len(data)} bytes is no manta Poseidon parameter set of width 3..6")
+            width = fit[0]
+        f, p = POSEIDON_ROUNDS.get(width, (None, None))
+        return cls(curve, width, f if full_rounds is None else full_rounds, p if partial_rounds is None else partial_rounds, data)
+
+    def permute(self, states) -> np.ndarray:
+        """[n, width, 4] states -> the permuted states (mg_poseidon_permute)"""
+        st = np.array(_u64(states).reshape(-1, self.width, 4))
+        _chk(LIB.mg_poseidon_permute(self._h, _p(st), _sz(st.shape[0])), "mg_poseidon_permute")
+        return st
+
+    def hash(self, inputs) -> np.ndarray:
+        """[n, width - 1, 4] inputs -> [n, 4] digests (mg_poseidon_hash)"""
+        x = _u64(inputs).reshape(-1, self.width - 1, 4)
+        out = np.zeros((x.shape[0], 4), dtype=np.uint64)
+        _chk(LIB.mg_poseidon_hash(self._h, _p(x), _sz(x.shape[0]), _p(out)), "mg_poseidon_hash")
+        return out
+
+    def hash_device(self, d_inputs, n, d_out=None) -> "DeviceBuffer":
+        """n x (width - 1) inputs already in HBM -> n digests in HBM (mg_poseidon_hash_device); d_out is allocated if None"""
+        if d_out is None:
+            d_out = DeviceBuffer(max(1, n) * 32)
+        _chk(LIB.mg_poseidon_hash_device(self._h, _addr(d_inputs), _sz(n), _addr(d_out)), "mg_poseidon_hash_device")
+        return d_out
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            LIB.mg_poseidon_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def merkle_tree(hasher: PoseidonHasher, height, leaves, indices=()):
+    """`merkle_tree::Full` of `height` over the leaves (inserted left to right, [n, 4] Montgomery) with `hasher` (width 3) as
+    the inner hash, on the GPU (mg_merkle_tree). Returns (root [4], paths [k, height - 1, 4]): manta's `Path` of each index --
+    leaf sibling, then the inner siblings bottom-up, absent siblings 0."""
+    lv = _u64(leaves).reshape(-1, 4)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    root = np.zeros(4, dtype=np.uint64)
+    paths = np.zeros((idx.shape[0], max(0, int(height) - 1), 4), dtype=np.uint64)
+    _chk(LIB.mg_merkle_tree(hasher._h, ctypes.c_uint(int(height)), _p(lv), _sz(lv.shape[0]), _p(root), _p(idx), _sz(idx.shape[0]),
+                            _p(paths)), "mg_merkle_tree")
+    return root, paths
+
+
+def merkle_forest_roots(hasher: PoseidonHasher, height, leaves, offsets) -> np.ndarray:
+    """roots of len(offsets) - 1 trees of `height` (mg_merkle_forest_roots): tree i holds leaves[offsets[i]:offsets[i + 1]]"""
+    lv = _u64(leaves).reshape(-1, 4)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    nt = max(0, off.shape[0] - 1)
+    roots = np.zeros((nt, 4), dtype=np.uint64)
+    _chk(LIB.mg_merkle_forest_roots(hasher._h, ctypes.c_uint(int(height)), _p(lv), _p(off), _sz(nt), _p(roots)),
+         "mg_merkle_forest_roots")
+    return roots
 
 
 class VerifyingContext:

@@ -829,3 +829,50 @@ MG_API int mg_proofs_decode(mg_curve_t curve, const uint8_t *proof_bytes, size_t
     return proofs_decode((int)curve, proof_bytes, k, points_out, ok);
     MG_CATCH
 }
+
+namespace mg {
+int poseidon_create(int curve, int width, int full_rounds, int partial_rounds, const uint8_t *bytes, size_t len,
+                    mg_poseidon **out);
+void poseidon_destroy(mg_poseidon *h);
+int poseidon_permute(const mg_poseidon *h, u64 *states, size_t n);
+int poseidon_hash(const mg_poseidon *h, const u64 *inputs, size_t n, u64 *out);
+int poseidon_hash_device(const mg_poseidon *h, const u64 *d_in, size_t n, u64 *d_out);
+int merkle_tree(const mg_poseidon *h, unsigned height, const u64 *leaves, size_t n, u64 *root_out, const u64 *indices, size_t k,
+                u64 *paths_out);
+int merkle_forest_roots(const mg_poseidon *h, unsigned height, const u64 *leaves, const u64 *offsets, size_t n_trees,
+                        u64 *roots_out);
+} // namespace mg
+MG_API int mg_poseidon_create(mg_curve_t curve, int width, int full_rounds, int partial_rounds, const uint8_t *bytes, size_t len,
+                              mg_poseidon **out) {
+    MG_TRY
+    return poseidon_create((int)curve, width, full_rounds, partial_rounds, bytes, len, out);
+    MG_CATCH
+}
+MG_API void mg_poseidon_destroy(mg_poseidon *h) { poseidon_destroy(h); }
+MG_API int mg_poseidon_permute(const mg_poseidon *h, uint64_t *states_mont, size_t n) {
+    MG_TRY
+    return poseidon_permute(h, states_mont, n);
+    MG_CATCH
+}
+MG_API int mg_poseidon_hash(const mg_poseidon *h, const uint64_t *inputs_mont, size_t n, uint64_t *out_mont) {
+    MG_TRY
+    return poseidon_hash(h, inputs_mont, n, out_mont);
+    MG_CATCH
+}
+MG_API int mg_poseidon_hash_device(const mg_poseidon *h, const uint64_t *d_inputs_mont, size_t n, uint64_t *d_out_mont) {
+    MG_TRY
+    return poseidon_hash_device(h, d_inputs_mont, n, d_out_mont);
+    MG_CATCH
+}
+MG_API int mg_merkle_tree(const mg_poseidon *h, unsigned height, const uint64_t *leaves_mont, size_t n, uint64_t *root_out,
+                          const uint64_t *indices, size_t k, uint64_t *paths_out) {
+    MG_TRY
+    return merkle_tree(h, height, leaves_mont, n, root_out, indices, k, paths_out);
+    MG_CATCH
+}
+MG_API int mg_merkle_forest_roots(const mg_poseidon *h, unsigned height, const uint64_t *leaves_mont, const uint64_t *offsets,
+                                  size_t n_trees, uint64_t *roots_out) {
+    MG_TRY
+    return merkle_forest_roots(h, height, leaves_mont, offsets, n_trees, roots_out);
+    MG_CATCH
+}

@@ -68,6 +68,11 @@ pub struct mg_vk {
 pub struct mg_partials_job {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct mg_poseidon {
+    _private: [u8; 0],
+}
+pub const MG_POSEIDON_CHUNK: usize = 1 << 19;
 
 /// `ark_groth16::ProvingKey<E>` as the library reads it (groth16.rs:216-245, field list :253-264).
 #[repr(C)]
@@ -402,4 +407,37 @@ extern "C" {
     pub fn mg_points_check(curve: mg_curve_t, group: c_int, affine_mont: *const u64, n: usize, status: *mut u8, n_bad: *mut usize) -> c_int;
     pub fn mg_points_encode(curve: mg_curve_t, group: c_int, affine_mont: *const u64, n: usize, compressed: c_int, out: *mut u8) -> c_int;
     pub fn mg_proofs_decode(curve: mg_curve_t, proof_bytes: *const u8, k: usize, points_out: *mut u64, ok: *mut u8) -> c_int;
+
+    // ---- batched Poseidon over Fr and the UTXO Merkle forest's hashing (MG_POSEIDON_CHUNK states per device pass)
+    pub fn mg_poseidon_create(
+        curve: mg_curve_t,
+        width: c_int,
+        full_rounds: c_int,
+        partial_rounds: c_int,
+        bytes: *const u8,
+        len: usize,
+        out: *mut *mut mg_poseidon,
+    ) -> c_int;
+    pub fn mg_poseidon_destroy(h: *mut mg_poseidon);
+    pub fn mg_poseidon_permute(h: *const mg_poseidon, states_mont: *mut u64, n: usize) -> c_int;
+    pub fn mg_poseidon_hash(h: *const mg_poseidon, inputs_mont: *const u64, n: usize, out_mont: *mut u64) -> c_int;
+    pub fn mg_poseidon_hash_device(h: *const mg_poseidon, d_inputs_mont: *const u64, n: usize, d_out_mont: *mut u64) -> c_int;
+    pub fn mg_merkle_tree(
+        h: *const mg_poseidon,
+        height: c_uint,
+        leaves_mont: *const u64,
+        n: usize,
+        root_out: *mut u64,
+        indices: *const u64,
+        k: usize,
+        paths_out: *mut u64,
+    ) -> c_int;
+    pub fn mg_merkle_forest_roots(
+        h: *const mg_poseidon,
+        height: c_uint,
+        leaves_mont: *const u64,
+        offsets: *const u64,
+        n_trees: usize,
+        roots_out: *mut u64,
+    ) -> c_int;
 }
