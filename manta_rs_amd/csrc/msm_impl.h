@@ -25,7 +25,8 @@
 //   msm_common.h      includes, register-cap attributes shared by the kernels
 //   msm_digits.h      K5   digits_kernel
 //   msm_accumulate.h  K7a  accumulate_chunks / accumulate_single
-//   msm_reduce.h      K7b-K9 merge_partials*, tile_reduce*, serial_reduce*, reduce_level1*, fold_windows
+//   msm_reduce.h      K7b-K9 merge_partials*, tile_reduce*, serial_reduce*, reduce_level1* (each plain / _coop pair: one body, two
+//                     instantiations), fold_windows
 //   msm_tables.h      bases_to_internal, window / full tables, fixed-base, group NTT, element-wise kernels
 //   msm_engine.h      GroupEngineT: base sets, plan, launch, finish (host)
 #pragma once

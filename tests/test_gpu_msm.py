@@ -257,6 +257,65 @@ def test_msm_reduce_front_levels(gpu, curve, group, pres, env):
     assert out.returncode == 0 and "front levels ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
 
 
+_TWINS_SCRIPT = r'''
+import os, sys
+sys.path.insert(0, {root!r}); sys.path.insert(0, os.path.join({root!r}, "tests"))
+import numpy as np
+from manta_rs_amd import api as gpu
+gpu.init(0)
+d = np.load({data!r})
+b = gpu.Bases({curve}, {group}, d["pts"], precompute_window_bits={pre})
+for dist in ("U", "W"):
+    got = gpu.VariableBaseMSM.multi_scalar_mul(b, d["sc" + dist])
+    assert (got == d["want" + dist]).all(), dist
+print("tails ok", os.path.basename(gpu.LIB_PATH))
+'''
+
+_TAIL_TWINS = {"plain": {"MANTA_COOP_TILES": "0", "MANTA_COOP_WAVES": "0"},
+               "coop": {"MANTA_COOP_TILES": "1073741824", "MANTA_COOP_WAVES": "1073741824"},
+               "default": {}}
+
+
+@pytest.mark.parametrize("curve,group,n,pre,env", [
+    (0, 1, 1 << 12, 0, {}),                             # plain bases: one bucket set per window
+    (1, 1, 1 << 16, 13, {}),                            # window tables
+    (0, 2, 1 << 12, 6, {}),                             # G2: the additions are calls
+    (1, 2, 1 << 13, 0, {}),
+    (0, 1, 1 << 14, 13, {"MANTA_RED_MIN": "128"}),      # front levels on: serial_reduce / serial_reduce_coop
+    (0, 1, 1 << 12, -6, {}),                            # full tables: one key in all, the merge's last run leaves through std_final
+])
+def test_msm_tail_kernel_twins_agree(gpu, tmp_path, curve, group, n, pre, env):
+    """Every tail kernel (merge_partials, tile_reduce, serial_reduce, reduce_level1; msm_reduce.h) is one body instantiated with the
+    plain and with the cooperative addition, and which of the two runs is otherwise decided by size alone. The same MSMs with every
+    tail forced plain, forced cooperative and at the defaults (knobs are read once per process, hence the child processes; the
+    diagnosis twin reads them), each equal to the oracle and so to each other. The inputs reach the exceptional branches of both
+    adders: repeated bases (P + P inside a bucket), infinity, P and -P in one bucket, beside uniform and witness-like scalars."""
+    import subprocess
+    import sys
+    r = synth.FR_MODULUS[curve]
+    pts = H.random_points(curve, group, min(n, 1500), seed=91)
+    pts = np.concatenate([pts] * (-(-n // pts.shape[0])))[:n]   # every base repeated
+    pts[5] = 0
+    pts[17] = 0          # infinity entries
+    pts[40] = pts[41]
+    pts[50] = pts[51]
+    data = {"pts": pts}
+    for dist in ("U", "W"):
+        sc = synth.msm_scalars(curve, n, dist, seed=92)
+        sc[40] = sc[41] = np.array([1, 0, 0, 0], dtype=np.uint64)  # P + P in bucket "1"
+        sc[50] = synth.ints_to_limbs([5], 4)[0]
+        sc[51] = synth.ints_to_limbs([r - 5], 4)[0]                # [5]P + [-5]P = 0
+        data["sc" + dist] = sc
+        data["want" + dist] = O.msm(curve, group, pts, sc, algo=1)
+    path = str(tmp_path / "twins.npz")
+    np.savez(path, **data)
+    code = _TWINS_SCRIPT.format(root=ROOT, data=path, curve=curve, group=group, pre=pre)
+    for name, knobs in _TAIL_TWINS.items():
+        out = subprocess.run([sys.executable, "-c", code], env=H.knob_env(dict(knobs, **env)), capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0 and "tails ok" in out.stdout, name + ": " + out.stdout[-2000:] + out.stderr[-2000:]
+        assert not knobs or "libmantagpu_diag.so" in out.stdout, name  # the shipped library has the defaults compiled in
+
+
 @pytest.mark.parametrize("curve,group,n,pre", [(0, 1, 300, 5), (0, 1, 4000, 9), (0, 1, 3000, -6), (0, 2, 500, -4), (1, 1, 20000, 13), (1, 1, 1 << 15, 16), (0, 2, 900, 6),
                                                 (1, 2, 2500, 8)])
 def test_msm_result_folded_on_the_device(gpu, curve, group, n, pre):
