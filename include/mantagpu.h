@@ -529,6 +529,68 @@ int mg_merkle_tree(const mg_poseidon *h, unsigned height, const uint64_t *leaves
 int mg_merkle_forest_roots(const mg_poseidon *h, unsigned height, const uint64_t *leaves_mont, const uint64_t *offsets,
                            size_t n_trees, uint64_t *roots_out);
 
+/* ---- manta-pay's embedded curve and its Poseidon note encryption, one point / note per GPU lane. The curve is
+ *      `ed_on_bn254` (`Group = ed_on_bn254::EdwardsProjective`, manta-pay/src/config/mod.rs): a x^2 + y^2 = 1 + d x^2 y^2 over
+ *      BN254 Fr with a = 1, d = 168696 / 168700, cofactor 8, subgroup of prime order l (251 bits). Replaces, in bulk, ark-ec
+ *      0.3 `twisted_edwards_extended::{GroupAffine, GroupProjective}` (add, mul, CanonicalSerialize / CanonicalDeserialize,
+ *      `is_in_correct_subgroup_assuming_on_curve`) as used by address derivation and `StandardDiffieHellman` key agreement
+ *      (manta-accounting/src/transfer/utxo/protocol.rs:1396-1451), and `IncomingBaseEncryptionScheme` =
+ *      `FixedDuplexer<1, Poseidon3>` (manta-pay/src/config/utxo.rs:564-758, manta-pay/src/crypto/poseidon/encryption.rs,
+ *      manta-crypto/src/permutation/duplex.rs). Only MG_BN254; MG_BLS12_381 is MG_ERROR_INVALID_ARGUMENT.
+ *      Points are affine x | y Montgomery limbs of BN254 Fr (8 x u64), the identity is (0, 1). Embedded scalars are 4 x u64
+ *      canonical little-endian integers below l; a scalar >= l is MG_ERROR_INVALID_ARGUMENT (checked on the host before any
+ *      device work). The addition law is complete on the curve (d is a non-square), so points of small order need no special
+ *      case; input points that are not on the curve give meaningless output (mg_edwards_check tells). Synchronous,
+ *      thread-safe, on the calling thread's setup stream, MG_EDWARDS_CHUNK lanes at a time (device memory of a call < 32 MiB
+ *      whatever n); n = 0 succeeds.
+ *      Encoding (32 bytes): x little-endian canonical with bit 255 set iff y > -y as integers in [0, p) -- the ark-ec 0.3
+ *      layout, which manta-parameters' group-generator.dat confirms. x = 0 decodes to the identity whatever the flag and the
+ *      identity encodes as zeros, so the point of order two (0, -1) does not survive a round trip; this x = 0 rule restates
+ *      ark-ec 0.3's serializer from memory and is not confirmed by any file of the reference. ------------------------------ */
+#define MG_EDWARDS_CHUNK (1u << 16)
+/* n encodings -> n points and status[i] = MG_POINT_*: x >= p (with bit 255 cleared) is MG_POINT_BAD_ENCODING; no square root
+ * for y^2 = (1 - x^2) / (1 - d x^2) is MG_POINT_NOT_ON_CURVE; [l]P != O is MG_POINT_NOT_IN_SUBGROUP; checked = 0 skips only
+ * the subgroup test. A rejected point is returned as zeros. status and n_bad (rejected count) may be NULL. */
+int mg_edwards_decode(mg_curve_t curve, const uint8_t *bytes, size_t n, int checked, uint64_t *out_affine_mont, uint8_t *status,
+                      size_t *n_bad);
+/* n points -> n encodings of 32 bytes */
+int mg_edwards_encode(mg_curve_t curve, const uint64_t *affine_mont, size_t n, uint8_t *out);
+/* points in memory: a coordinate >= p, then the curve equation, then the subgroup, with the same statuses */
+int mg_edwards_check(mg_curve_t curve, const uint64_t *affine_mont, size_t n, uint8_t *status, size_t *n_bad);
+#define MG_EDWARDS_MUL_SHARED_SCALAR 0 /* n_scalars = 1: out[i] = points[i] * scalar (key agreement), n_points results */
+#define MG_EDWARDS_MUL_FIXED_BASE 1    /* n_points = 1: out[i] = point * scalars[i] (key derivation), n_scalars results */
+#define MG_EDWARDS_MUL_PAIRWISE 2      /* n_points = n_scalars: out[i] = points[i] * scalars[i] */
+int mg_edwards_mul(mg_curve_t curve, int mode, const uint64_t *points_affine_mont, size_t n_points, const uint64_t *scalars,
+                   size_t n_scalars, uint64_t *out_affine_mont);
+/* out[i] = a[i] + b[i] */
+int mg_edwards_add(mg_curve_t curve, const uint64_t *a_affine_mont, const uint64_t *b_affine_mont, size_t n,
+                   uint64_t *out_affine_mont);
+
+/* The incoming-note cipher. bytes = manta-parameters' incoming-base-encryption-scheme.dat (8 712 bytes): the width-4
+ * permutation (8 full and 55 partial rounds: 63 x 4 round keys, the 4 x 4 MDS matrix, no domain tag), a u64 4 and the four
+ * elements of `FixedEncryption::initial_state`, 32-byte little-endian canonical elements. generator = the group generator G
+ * (group-generator.dat decoded). Host only, no GPU needed: MG_ERROR_INVALID_ARGUMENT, with nothing allocated, for any other
+ * length, an element >= p, or a generator that is not on the curve. */
+typedef struct mg_note_cipher mg_note_cipher;
+int mg_note_cipher_create(mg_curve_t curve, const uint8_t *bytes, size_t len, const uint64_t *generator_affine_mont,
+                          mg_note_cipher **out);
+void mg_note_cipher_destroy(mg_note_cipher *h);
+/* `Hybrid` encryption of n notes: epk[i] = G * randomness[i], the sponge is keyed by (x, y) of recv_keys[i] * randomness[i];
+ * plaintexts / ciphertexts are 3 Montgomery elements per note (commitment randomness, asset id, asset value), tags one. The
+ * sponge: state <- initial state; words 1..3 += (x, y, 0), permute; permute again (the empty header is one all-zero setup
+ * block: manta-util/src/vec.rs `padded_chunks_with`); words 1..3 += plaintext = the ciphertext, permute; tag = word 1. */
+int mg_notes_encrypt(const mg_note_cipher *h, const uint64_t *recv_keys_affine_mont, const uint64_t *randomness,
+                     const uint64_t *plaintexts_mont, size_t n, uint64_t *epk_out_affine_mont, uint64_t *ciphertext_out_mont,
+                     uint64_t *tag_out_mont);
+#define MG_NOTE_OK 0
+#define MG_NOTE_BAD_TAG 1   /* the recomputed tag differs: not this key's note, or altered */
+#define MG_NOTE_BAD_VALUE 2 /* the tag matches but the asset value word is 2^128 or more (`try_into_u128`, utxo.rs:716-731) */
+/* `NoteOpen::open` of n notes against one viewing key: the sponge is keyed by epks[i] * viewing_key; ok[i] = 1 iff the note
+ * opens (status[i] = MG_NOTE_OK; status may be NULL), and the plaintext of a note that does not is zeros. */
+int mg_notes_decrypt(const mg_note_cipher *h, const uint64_t *viewing_key, const uint64_t *epks_affine_mont,
+                     const uint64_t *ciphertexts_mont, const uint64_t *tags_mont, size_t n, uint64_t *plaintext_out_mont,
+                     uint8_t *ok, uint8_t *status);
+
 #ifdef __cplusplus
 }
 #endif

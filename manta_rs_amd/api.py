@@ -74,6 +74,8 @@ EXPORTS = [
     "mg_points_decode", "mg_points_check", "mg_points_encode", "mg_proofs_decode",
     "mg_poseidon_create", "mg_poseidon_destroy", "mg_poseidon_permute", "mg_poseidon_hash", "mg_poseidon_hash_device",
     "mg_merkle_tree", "mg_merkle_forest_roots",
+    "mg_edwards_decode", "mg_edwards_encode", "mg_edwards_check", "mg_edwards_mul", "mg_edwards_add",
+    "mg_note_cipher_create", "mg_note_cipher_destroy", "mg_notes_encrypt", "mg_notes_decrypt",
 ]
 
 
@@ -977,6 +979,121 @@ def merkle_forest_roots(hasher: PoseidonHasher, height, leaves, offsets) -> np.n
     _chk(LIB.mg_merkle_forest_roots(hasher._h, ctypes.c_uint(int(height)), _p(lv), _p(off), _sz(nt), _p(roots)),
          "mg_merkle_forest_roots")
     return roots
+
+
+# ---- manta-pay's embedded curve (ed_on_bn254) and its Poseidon note encryption -------------------------------------------
+EDWARDS_CHUNK = 1 << 16  # MG_EDWARDS_CHUNK: lanes per device pass
+EDWARDS_ORDER = 2736030358979909402780800718157159386076813972158567259200215660948447373041  # l, the subgroup order
+EDWARDS_MUL_SHARED_SCALAR, EDWARDS_MUL_FIXED_BASE, EDWARDS_MUL_PAIRWISE = 0, 1, 2
+NOTE_OK, NOTE_BAD_TAG, NOTE_BAD_VALUE = 0, 1, 2
+
+
+def _ed_points(points):
+    return _u64(points).reshape(-1, 8)
+
+
+def edwards_decode(data, checked=True, curve=BN254):
+    """Batched ark-ec 0.3 `CanonicalDeserialize` of twisted Edwards points (`mg_edwards_decode`): data = 32-byte encodings back to
+    back (or a sequence of them). Returns (points [n, 8] affine x | y Montgomery, identity (0, 1), zeros where rejected; status
+    [n] uint8, POINT_*). checked=False skips only the subgroup test."""
+    data = _joined(data)
+    if len(data) % 32:
+        raise ValueError(f"{len(data)} bytes is not a whole number of 32-byte encodings")
+    n = len(data) // 32
+    out = np.zeros((n, 8), dtype=np.uint64)
+    st = np.zeros(n, dtype=np.uint8)
+    _chk(LIB.mg_edwards_decode(curve, data, _sz(n), int(checked), _p(out), _p(st), None), "mg_edwards_decode")
+    return out, st
+
+
+def edwards_encode(points, curve=BN254) -> bytes:
+    """[n, 8] affine Montgomery points -> their 32-byte encodings back to back (`mg_edwards_encode`)"""
+    pts = _ed_points(points)
+    out = ctypes.create_string_buffer(max(1, pts.shape[0] * 32))
+    _chk(LIB.mg_edwards_encode(curve, _p(pts), _sz(pts.shape[0]), out), "mg_edwards_encode")
+    return out.raw[:pts.shape[0] * 32]
+
+
+def edwards_check(points, curve=BN254) -> np.ndarray:
+    """status [n] uint8 (POINT_*) of affine Montgomery points: reduced, on the curve, in the subgroup (`mg_edwards_check`)"""
+    pts = _ed_points(points)
+    st = np.zeros(pts.shape[0], dtype=np.uint8)
+    _chk(LIB.mg_edwards_check(curve, _p(pts), _sz(pts.shape[0]), _p(st), None), "mg_edwards_check")
+    return st
+
+
+def edwards_scalars(values) -> np.ndarray:
+    """Python integers -> [n, 4] uint64 canonical little-endian limbs"""
+    return np.array([[(int(v) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)] for v in values],
+                    dtype=np.uint64).reshape(-1, 4)
+
+
+def edwards_mul(mode, points, scalars, curve=BN254) -> np.ndarray:
+    """`mg_edwards_mul`: EDWARDS_MUL_SHARED_SCALAR (n points x one scalar), EDWARDS_MUL_FIXED_BASE (one point x n scalars) or
+    EDWARDS_MUL_PAIRWISE; points [., 8] affine Montgomery, scalars [., 4] canonical limbs below EDWARDS_ORDER -> [n, 8]"""
+    pts, sc = _ed_points(points), _u64(scalars).reshape(-1, 4)
+    n = pts.shape[0] if mode == EDWARDS_MUL_SHARED_SCALAR else sc.shape[0]
+    out = np.zeros((n, 8), dtype=np.uint64)
+    _chk(LIB.mg_edwards_mul(curve, int(mode), _p(pts), _sz(pts.shape[0]), _p(sc), _sz(sc.shape[0]), _p(out)), "mg_edwards_mul")
+    return out
+
+
+def edwards_add(a, b, curve=BN254) -> np.ndarray:
+    """elementwise a[i] + b[i] of affine Montgomery points (`mg_edwards_add`)"""
+    a, b = _ed_points(a), _ed_points(b)
+    if a.shape != b.shape:
+        raise ValueError("edwards_add: as many points in a as in b")
+    out = np.zeros_like(a)
+    _chk(LIB.mg_edwards_add(curve, _p(a), _p(b), _sz(a.shape[0]), _p(out)), "mg_edwards_add")
+    return out
+
+
+class NoteCipher:
+    """`IncomingBaseEncryptionScheme` (manta-pay/src/config/utxo.rs:744-758: `Hybrid` Diffie-Hellman over the embedded curve and
+    `FixedDuplexer<1, Poseidon3>`) decoded from incoming-base-encryption-scheme.dat, with the group generator as an affine
+    Montgomery point. Decoding is host-only; `encrypt` / `decrypt` run on the GPU, one note per lane."""
+
+    def __init__(self, data, generator, curve=BN254):
+        self._h = _vp()
+        data = bytes(data)
+        g = _u64(generator).reshape(-1)
+        if g.size != 8:
+            raise ValueError("generator: one affine point (8 x u64)")
+        _chk(LIB.mg_note_cipher_create(curve, data, _sz(len(data)), _p(g), ctypes.byref(self._h)), "mg_note_cipher_create")
+
+    def encrypt(self, recv_keys, randomness, plaintexts):
+        """n notes: recv_keys [n, 8], randomness [n, 4] scalars, plaintexts [n, 3, 4] Montgomery -> (epk [n, 8], ciphertext
+        [n, 3, 4], tag [n, 4]) (`mg_notes_encrypt`)"""
+        rk, rnd, pt = _ed_points(recv_keys), _u64(randomness).reshape(-1, 4), _u64(plaintexts).reshape(-1, 3, 4)
+        n = rk.shape[0]
+        if rnd.shape[0] != n or pt.shape[0] != n:
+            raise ValueError("encrypt: one key, one randomness and one plaintext per note")
+        epk, ct, tag = (np.zeros(s, dtype=np.uint64) for s in ((n, 8), (n, 3, 4), (n, 4)))
+        _chk(LIB.mg_notes_encrypt(self._h, _p(rk), _p(rnd), _p(pt), _sz(n), _p(epk), _p(ct), _p(tag)), "mg_notes_encrypt")
+        return epk, ct, tag
+
+    def decrypt(self, viewing_key, epks, ciphertexts, tags):
+        """n notes against one viewing key ([4] scalar) -> (plaintext [n, 3, 4], zeros where the note does not open; ok [n] bool;
+        status [n] uint8 NOTE_*) (`mg_notes_decrypt`)"""
+        vk, ep, ct, tg = _u64(viewing_key).reshape(-1), _ed_points(epks), _u64(ciphertexts).reshape(-1, 3, 4), _u64(tags).reshape(-1, 4)
+        n = ep.shape[0]
+        if vk.size != 4 or ct.shape[0] != n or tg.shape[0] != n:
+            raise ValueError("decrypt: one viewing key; one epk, ciphertext and tag per note")
+        pt = np.zeros((n, 3, 4), dtype=np.uint64)
+        ok, st = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        _chk(LIB.mg_notes_decrypt(self._h, _p(vk), _p(ep), _p(ct), _p(tg), _sz(n), _p(pt), _p(ok), _p(st)), "mg_notes_decrypt")
+        return pt, ok.astype(bool), st
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            LIB.mg_note_cipher_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class VerifyingContext:

@@ -876,3 +876,67 @@ MG_API int mg_merkle_forest_roots(const mg_poseidon *h, unsigned height, const u
     return merkle_forest_roots(h, height, leaves_mont, offsets, n_trees, roots_out);
     MG_CATCH
 }
+
+namespace mg {
+int edwards_decode(int curve, const uint8_t *bytes, size_t n, int checked, u64 *out, uint8_t *status, size_t *n_bad);
+int edwards_check(int curve, const u64 *affine, size_t n, uint8_t *status, size_t *n_bad);
+int edwards_encode(int curve, const u64 *affine, size_t n, uint8_t *out);
+int edwards_mul(int curve, int mode, const u64 *points, size_t n_points, const u64 *scalars, size_t n_scalars, u64 *out);
+int edwards_add(int curve, const u64 *a_pts, const u64 *b_pts, size_t n, u64 *out);
+int note_cipher_create(int curve, const uint8_t *bytes, size_t len, const u64 *generator, mg_note_cipher **out);
+void note_cipher_destroy(mg_note_cipher *h);
+int notes_encrypt(const mg_note_cipher *h, const u64 *recv_keys, const u64 *randomness, const u64 *plaintexts, size_t n,
+                  u64 *epk_out, u64 *ciphertext_out, u64 *tag_out);
+int notes_decrypt(const mg_note_cipher *h, const u64 *viewing_key, const u64 *epks, const u64 *ciphertexts, const u64 *tags,
+                  size_t n, u64 *plaintext_out, uint8_t *ok, uint8_t *status);
+} // namespace mg
+MG_API int mg_edwards_decode(mg_curve_t curve, const uint8_t *bytes, size_t n, int checked, uint64_t *out_affine_mont,
+                             uint8_t *status, size_t *n_bad) {
+    MG_TRY
+    return edwards_decode((int)curve, bytes, n, checked, out_affine_mont, status, n_bad);
+    MG_CATCH
+}
+MG_API int mg_edwards_encode(mg_curve_t curve, const uint64_t *affine_mont, size_t n, uint8_t *out) {
+    MG_TRY
+    return edwards_encode((int)curve, affine_mont, n, out);
+    MG_CATCH
+}
+MG_API int mg_edwards_check(mg_curve_t curve, const uint64_t *affine_mont, size_t n, uint8_t *status, size_t *n_bad) {
+    MG_TRY
+    return edwards_check((int)curve, affine_mont, n, status, n_bad);
+    MG_CATCH
+}
+MG_API int mg_edwards_mul(mg_curve_t curve, int mode, const uint64_t *points_affine_mont, size_t n_points, const uint64_t *scalars,
+                          size_t n_scalars, uint64_t *out_affine_mont) {
+    MG_TRY
+    return edwards_mul((int)curve, mode, points_affine_mont, n_points, scalars, n_scalars, out_affine_mont);
+    MG_CATCH
+}
+MG_API int mg_edwards_add(mg_curve_t curve, const uint64_t *a_affine_mont, const uint64_t *b_affine_mont, size_t n,
+                          uint64_t *out_affine_mont) {
+    MG_TRY
+    return edwards_add((int)curve, a_affine_mont, b_affine_mont, n, out_affine_mont);
+    MG_CATCH
+}
+MG_API int mg_note_cipher_create(mg_curve_t curve, const uint8_t *bytes, size_t len, const uint64_t *generator_affine_mont,
+                                 mg_note_cipher **out) {
+    MG_TRY
+    return note_cipher_create((int)curve, bytes, len, generator_affine_mont, out);
+    MG_CATCH
+}
+MG_API void mg_note_cipher_destroy(mg_note_cipher *h) { note_cipher_destroy(h); }
+MG_API int mg_notes_encrypt(const mg_note_cipher *h, const uint64_t *recv_keys_affine_mont, const uint64_t *randomness,
+                            const uint64_t *plaintexts_mont, size_t n, uint64_t *epk_out_affine_mont,
+                            uint64_t *ciphertext_out_mont, uint64_t *tag_out_mont) {
+    MG_TRY
+    return notes_encrypt(h, recv_keys_affine_mont, randomness, plaintexts_mont, n, epk_out_affine_mont, ciphertext_out_mont,
+                         tag_out_mont);
+    MG_CATCH
+}
+MG_API int mg_notes_decrypt(const mg_note_cipher *h, const uint64_t *viewing_key, const uint64_t *epks_affine_mont,
+                            const uint64_t *ciphertexts_mont, const uint64_t *tags_mont, size_t n, uint64_t *plaintext_out_mont,
+                            uint8_t *ok, uint8_t *status) {
+    MG_TRY
+    return notes_decrypt(h, viewing_key, epks_affine_mont, ciphertexts_mont, tags_mont, n, plaintext_out_mont, ok, status);
+    MG_CATCH
+}

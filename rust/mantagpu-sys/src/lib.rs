@@ -73,6 +73,17 @@ pub struct mg_poseidon {
     _private: [u8; 0],
 }
 pub const MG_POSEIDON_CHUNK: usize = 1 << 19;
+#[repr(C)]
+pub struct mg_note_cipher {
+    _private: [u8; 0],
+}
+pub const MG_EDWARDS_CHUNK: usize = 1 << 16;
+pub const MG_EDWARDS_MUL_SHARED_SCALAR: c_int = 0;
+pub const MG_EDWARDS_MUL_FIXED_BASE: c_int = 1;
+pub const MG_EDWARDS_MUL_PAIRWISE: c_int = 2;
+pub const MG_NOTE_OK: u8 = 0;
+pub const MG_NOTE_BAD_TAG: u8 = 1;
+pub const MG_NOTE_BAD_VALUE: u8 = 2;
 
 /// `ark_groth16::ProvingKey<E>` as the library reads it (groth16.rs:216-245, field list :253-264).
 #[repr(C)]
@@ -439,5 +450,57 @@ extern "C" {
         offsets: *const u64,
         n_trees: usize,
         roots_out: *mut u64,
+    ) -> c_int;
+
+    // ---- the embedded curve (ed_on_bn254) and the Poseidon note cipher (MG_EDWARDS_CHUNK lanes per device pass)
+    pub fn mg_edwards_decode(
+        curve: mg_curve_t,
+        bytes: *const u8,
+        n: usize,
+        checked: c_int,
+        out_affine_mont: *mut u64,
+        status: *mut u8,
+        n_bad: *mut usize,
+    ) -> c_int;
+    pub fn mg_edwards_encode(curve: mg_curve_t, affine_mont: *const u64, n: usize, out: *mut u8) -> c_int;
+    pub fn mg_edwards_check(curve: mg_curve_t, affine_mont: *const u64, n: usize, status: *mut u8, n_bad: *mut usize) -> c_int;
+    pub fn mg_edwards_mul(
+        curve: mg_curve_t,
+        mode: c_int,
+        points_affine_mont: *const u64,
+        n_points: usize,
+        scalars: *const u64,
+        n_scalars: usize,
+        out_affine_mont: *mut u64,
+    ) -> c_int;
+    pub fn mg_edwards_add(curve: mg_curve_t, a_affine_mont: *const u64, b_affine_mont: *const u64, n: usize, out_affine_mont: *mut u64) -> c_int;
+    pub fn mg_note_cipher_create(
+        curve: mg_curve_t,
+        bytes: *const u8,
+        len: usize,
+        generator_affine_mont: *const u64,
+        out: *mut *mut mg_note_cipher,
+    ) -> c_int;
+    pub fn mg_note_cipher_destroy(h: *mut mg_note_cipher);
+    pub fn mg_notes_encrypt(
+        h: *const mg_note_cipher,
+        recv_keys_affine_mont: *const u64,
+        randomness: *const u64,
+        plaintexts_mont: *const u64,
+        n: usize,
+        epk_out_affine_mont: *mut u64,
+        ciphertext_out_mont: *mut u64,
+        tag_out_mont: *mut u64,
+    ) -> c_int;
+    pub fn mg_notes_decrypt(
+        h: *const mg_note_cipher,
+        viewing_key: *const u64,
+        epks_affine_mont: *const u64,
+        ciphertexts_mont: *const u64,
+        tags_mont: *const u64,
+        n: usize,
+        plaintext_out_mont: *mut u64,
+        ok: *mut u8,
+        status: *mut u8,
     ) -> c_int;
 }
