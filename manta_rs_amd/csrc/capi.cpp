@@ -1,6 +1,7 @@
 // C ABI of libmantagpu.so (include/mantagpu.h): thin, exception-free wrappers over the engines.
 #include "../../include/mantagpu.h"
 #include "engine.h"
+#include "staging.h"
 #include "tuning.h"
 #include <cstddef>
 #include "prover.h"
@@ -446,13 +447,13 @@ MG_API int mg_ntt(mg_curve_t curve, uint64_t *data, unsigned log_n, int inverse,
     MG_TRY
     if (!data || log_n > 32) return MG_ERROR_INVALID_ARGUMENT;
     const size_t bytes = ((size_t)1 << log_n) * 32;
-    void *d = nullptr;
-    MG_HIP(hipMalloc(&d, bytes));
-    int rc = MG_SUCCESS;
+    DevBlock m;
+    int rc = m.alloc({bytes}, "mg_ntt");
+    if (rc) return rc;
+    void *d = m.dev(0);
     if (memcpy_sync(d, data, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = MG_ERROR_HIP;
     if (!rc) rc = mg_ntt_device(curve, (uint64_t *)d, log_n, inverse, coset);
     if (!rc && memcpy_sync(data, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = MG_ERROR_HIP;
-    hipFree(d);
     return rc;
     MG_CATCH
 }

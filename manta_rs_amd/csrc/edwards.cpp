@@ -3,7 +3,7 @@
 #include "edwards.h"
 #include "edwards_dev.h"
 #include "host_ec.h"
-#include "point_codec.h"
+#include "staging.h"
 #include <cstring>
 #include <vector>
 
@@ -92,62 +92,14 @@ int top_bit(const u64 *k) {
     return -1;
 }
 
-struct DevMem { // one call's device memory, freed on every path
-    void *p = nullptr;
-    ~DevMem() {
-        if (p) hipFree(p);
-    }
-};
+constexpr Staging EDWARDS_STAGING{EDWARDS_CHUNK, false}; // pageable: copies go straight from and to the caller's arrays
 
-struct Span { // one per-lane array of a call: host pointer and bytes per lane
-    const void *src;
-    void *dst;
-    size_t stride;
-};
-
-// The lanes of a call, EDWARDS_CHUNK at a time on the calling thread's setup stream: `consts` (the same for every lane) is
-// uploaded once, each chunk's inputs are copied in, `launch(d_consts, d_in[], d_out[], count, stream)` enqueues kernels, the
-// outputs are copied back. Device memory of a call = consts + scratch + min(n, EDWARDS_CHUNK) x (sum of the strides + scratch).
-template <class Launch>
-int run_chunks(size_t n, const void *consts, size_t const_bytes, std::vector<Span> ins, std::vector<Span> outs,
-               size_t scratch_stride, Launch launch) {
-    if (n == 0) return MG_OK;
-    HeavyOp no_capture_meanwhile; // device memory is allocated and freed inside the call
-    hipStream_t s = setup_stream();
-    if (!s) return MG_ERR_OOM;
-    const size_t cap = n < EDWARDS_CHUNK ? n : EDWARDS_CHUNK;
-    const auto padded = [](size_t b) { return (b + 255) & ~size_t(255); }; // every array starts on a 256-byte boundary
-    size_t total = padded(const_bytes) + padded(cap * scratch_stride);
-    for (const Span &x : ins) total += padded(cap * x.stride);
-    for (const Span &x : outs) total += padded(cap * x.stride);
-    DevMem m;
-    MG_HIP(hipMalloc(&m.p, total));
-    uint8_t *p = (uint8_t *)m.p;
-    if (const_bytes) MG_HIP(hipMemcpyAsync(p, consts, const_bytes, hipMemcpyHostToDevice, s));
-    const uint8_t *d_consts = p;
-    p += padded(const_bytes);
-    std::vector<uint8_t *> d_in, d_out;
-    for (const Span &x : ins) d_in.push_back(p), p += padded(cap * x.stride);
-    for (const Span &x : outs) d_out.push_back(p), p += padded(cap * x.stride);
-    uint8_t *d_scratch = p;
-    for (size_t off = 0; off < n; off += cap) {
-        const size_t cnt = n - off < cap ? n - off : cap;
-        for (size_t q = 0; q < ins.size(); ++q)
-            MG_HIP(hipMemcpyAsync(d_in[q], (const uint8_t *)ins[q].src + off * ins[q].stride, cnt * ins[q].stride,
-                                  hipMemcpyHostToDevice, s));
-        MG_HIP(launch(d_consts, d_in, d_out, d_scratch, cnt, s));
-        for (size_t q = 0; q < outs.size(); ++q)
-            MG_HIP(hipMemcpyAsync((uint8_t *)outs[q].dst + off * outs[q].stride, d_out[q], cnt * outs[q].stride,
-                                  hipMemcpyDeviceToHost, s));
-        MG_HIP(hipStreamSynchronize(s));
-    }
-    return MG_OK;
-}
-
-size_t count_bad(const uint8_t *st, size_t n) {
-    size_t b = 0;
-    for (size_t i = 0; i < n; ++i) b += st[i] != PT_OK;
-    return b;
+EdwardsLaunch on_chunk(int op, const Chunk &c) { // the launch of `op` over one chunk; the caller adds the arrays
+    EdwardsLaunch a{};
+    a.op = op;
+    a.n = c.n;
+    a.stream = c.stream;
+    return a;
 }
 
 } // namespace
@@ -163,21 +115,14 @@ namespace mg {
 int edwards_decode(int curve, const uint8_t *bytes, size_t n, int checked, u64 *out, uint8_t *status, size_t *n_bad) {
     if (curve != 0 || (n && (!bytes || !out))) return MG_ERR_ARG;
     std::vector<uint8_t> own;
-    if (!status) {
-        own.resize(n);
-        status = own.data();
-    }
-    const int rc = run_chunks(n, nullptr, 0, {{bytes, nullptr, 32}}, {{nullptr, out, 64}, {nullptr, status, 1}}, 0,
-                              [&](const uint8_t *, std::vector<uint8_t *> &di, std::vector<uint8_t *> &dout, uint8_t *, size_t cnt,
-                                  hipStream_t s) {
-                                  EdwardsLaunch a{};
-                                  a.op = EdwardsLaunch::DECODE;
+    status = status_or_own(status, n, own);
+    const int rc = run_chunks(EDWARDS_STAGING, n, nullptr, 0, {Span::in(bytes, 32), Span::out(out, 64), Span::out(status, 1)}, 0,
+                              [&](const Chunk &c) {
+                                  EdwardsLaunch a = on_chunk(EdwardsLaunch::DECODE, c);
                                   a.checked = checked != 0;
-                                  a.a = (const u32 *)di[0];
-                                  a.out = (u32 *)dout[0];
-                                  a.status = dout[1];
-                                  a.n = cnt;
-                                  a.stream = s;
+                                  a.a = (const u32 *)c.a[0];
+                                  a.out = (u32 *)c.a[1];
+                                  a.status = c.a[2];
                                   return edwards_launch_bn254(a);
                               });
     if (rc == MG_OK && n_bad) *n_bad = count_bad(status, n);
@@ -187,38 +132,25 @@ int edwards_decode(int curve, const uint8_t *bytes, size_t n, int checked, u64 *
 int edwards_check(int curve, const u64 *affine, size_t n, uint8_t *status, size_t *n_bad) {
     if (curve != 0 || (n && !affine)) return MG_ERR_ARG;
     std::vector<uint8_t> own;
-    if (!status) {
-        own.resize(n);
-        status = own.data();
-    }
-    const int rc = run_chunks(n, nullptr, 0, {{affine, nullptr, 64}}, {{nullptr, status, 1}}, 0,
-                              [&](const uint8_t *, std::vector<uint8_t *> &di, std::vector<uint8_t *> &dout, uint8_t *, size_t cnt,
-                                  hipStream_t s) {
-                                  EdwardsLaunch a{};
-                                  a.op = EdwardsLaunch::CHECK;
-                                  a.a = (const u32 *)di[0];
-                                  a.status = dout[0];
-                                  a.n = cnt;
-                                  a.stream = s;
-                                  return edwards_launch_bn254(a);
-                              });
+    status = status_or_own(status, n, own);
+    const int rc = run_chunks(EDWARDS_STAGING, n, nullptr, 0, {Span::in(affine, 64), Span::out(status, 1)}, 0, [&](const Chunk &c) {
+        EdwardsLaunch a = on_chunk(EdwardsLaunch::CHECK, c);
+        a.a = (const u32 *)c.a[0];
+        a.status = c.a[1];
+        return edwards_launch_bn254(a);
+    });
     if (rc == MG_OK && n_bad) *n_bad = count_bad(status, n);
     return rc;
 }
 
 int edwards_encode(int curve, const u64 *affine, size_t n, uint8_t *out) {
     if (curve != 0 || (n && (!affine || !out))) return MG_ERR_ARG;
-    return run_chunks(n, nullptr, 0, {{affine, nullptr, 64}}, {{nullptr, out, 32}}, 0,
-                      [&](const uint8_t *, std::vector<uint8_t *> &di, std::vector<uint8_t *> &dout, uint8_t *, size_t cnt,
-                          hipStream_t s) {
-                          EdwardsLaunch a{};
-                          a.op = EdwardsLaunch::ENCODE;
-                          a.a = (const u32 *)di[0];
-                          a.out = (u32 *)dout[0];
-                          a.n = cnt;
-                          a.stream = s;
-                          return edwards_launch_bn254(a);
-                      });
+    return run_chunks(EDWARDS_STAGING, n, nullptr, 0, {Span::in(affine, 64), Span::out(out, 32)}, 0, [&](const Chunk &c) {
+        EdwardsLaunch a = on_chunk(EdwardsLaunch::ENCODE, c);
+        a.a = (const u32 *)c.a[0];
+        a.out = (u32 *)c.a[1];
+        return edwards_launch_bn254(a);
+    });
 }
 
 int edwards_mul(int curve, int mode, const u64 *points, size_t n_points, const u64 *scalars, size_t n_scalars, u64 *out) {
@@ -234,62 +166,45 @@ int edwards_mul(int curve, int mode, const u64 *points, size_t n_points, const u
     if (n == 0) return MG_OK;
     if (mode == 0) {
         const int top = top_bit(scalars);
-        return run_chunks(n, scalars, 32, {{points, nullptr, 64}}, {{nullptr, out, 64}}, 0,
-                          [&](const uint8_t *dc, std::vector<uint8_t *> &di, std::vector<uint8_t *> &dout, uint8_t *, size_t cnt,
-                              hipStream_t s) {
-                              EdwardsLaunch a{};
-                              a.op = EdwardsLaunch::MUL_SHARED;
-                              a.consts = (const u32 *)dc;
-                              a.top = top;
-                              a.a = (const u32 *)di[0];
-                              a.out = (u32 *)dout[0];
-                              a.n = cnt;
-                              a.stream = s;
-                              return edwards_launch_bn254(a);
-                          });
+        return run_chunks(EDWARDS_STAGING, n, scalars, 32, {Span::in(points, 64), Span::out(out, 64)}, 0, [&](const Chunk &c) {
+            EdwardsLaunch a = on_chunk(EdwardsLaunch::MUL_SHARED, c);
+            a.consts = (const u32 *)c.consts;
+            a.top = top;
+            a.a = (const u32 *)c.a[0];
+            a.out = (u32 *)c.a[1];
+            return edwards_launch_bn254(a);
+        });
     }
     if (mode == 1) {
         std::vector<u32> table;
         build_table(points, table);
-        return run_chunks(n, table.data(), table.size() * 4, {{scalars, nullptr, 32}}, {{nullptr, out, 64}}, 0,
-                          [&](const uint8_t *dc, std::vector<uint8_t *> &di, std::vector<uint8_t *> &dout, uint8_t *, size_t cnt,
-                              hipStream_t s) {
-                              EdwardsLaunch a{};
-                              a.op = EdwardsLaunch::MUL_FIXED;
-                              a.consts = (const u32 *)dc;
-                              a.b = (const u32 *)di[0];
-                              a.out = (u32 *)dout[0];
-                              a.n = cnt;
-                              a.stream = s;
+        return run_chunks(EDWARDS_STAGING, n, table.data(), table.size() * 4, {Span::in(scalars, 32), Span::out(out, 64)}, 0,
+                          [&](const Chunk &c) {
+                              EdwardsLaunch a = on_chunk(EdwardsLaunch::MUL_FIXED, c);
+                              a.consts = (const u32 *)c.consts;
+                              a.b = (const u32 *)c.a[0];
+                              a.out = (u32 *)c.a[1];
                               return edwards_launch_bn254(a);
                           });
     }
-    return run_chunks(n, nullptr, 0, {{points, nullptr, 64}, {scalars, nullptr, 32}}, {{nullptr, out, 64}}, 0,
-                      [&](const uint8_t *, std::vector<uint8_t *> &di, std::vector<uint8_t *> &dout, uint8_t *, size_t cnt,
-                          hipStream_t s) {
-                          EdwardsLaunch a{};
-                          a.op = EdwardsLaunch::MUL_PAIRWISE;
-                          a.a = (const u32 *)di[0];
-                          a.b = (const u32 *)di[1];
-                          a.out = (u32 *)dout[0];
-                          a.n = cnt;
-                          a.stream = s;
+    return run_chunks(EDWARDS_STAGING, n, nullptr, 0, {Span::in(points, 64), Span::in(scalars, 32), Span::out(out, 64)}, 0,
+                      [&](const Chunk &c) {
+                          EdwardsLaunch a = on_chunk(EdwardsLaunch::MUL_PAIRWISE, c);
+                          a.a = (const u32 *)c.a[0];
+                          a.b = (const u32 *)c.a[1];
+                          a.out = (u32 *)c.a[2];
                           return edwards_launch_bn254(a);
                       });
 }
 
 int edwards_add(int curve, const u64 *a_pts, const u64 *b_pts, size_t n, u64 *out) {
     if (curve != 0 || (n && (!a_pts || !b_pts || !out))) return MG_ERR_ARG;
-    return run_chunks(n, nullptr, 0, {{a_pts, nullptr, 64}, {b_pts, nullptr, 64}}, {{nullptr, out, 64}}, 0,
-                      [&](const uint8_t *, std::vector<uint8_t *> &di, std::vector<uint8_t *> &dout, uint8_t *, size_t cnt,
-                          hipStream_t s) {
-                          EdwardsLaunch a{};
-                          a.op = EdwardsLaunch::ADD;
-                          a.a = (const u32 *)di[0];
-                          a.b = (const u32 *)di[1];
-                          a.out = (u32 *)dout[0];
-                          a.n = cnt;
-                          a.stream = s;
+    return run_chunks(EDWARDS_STAGING, n, nullptr, 0, {Span::in(a_pts, 64), Span::in(b_pts, 64), Span::out(out, 64)}, 0,
+                      [&](const Chunk &c) {
+                          EdwardsLaunch a = on_chunk(EdwardsLaunch::ADD, c);
+                          a.a = (const u32 *)c.a[0];
+                          a.b = (const u32 *)c.a[1];
+                          a.out = (u32 *)c.a[2];
                           return edwards_launch_bn254(a);
                       });
 }
@@ -304,13 +219,10 @@ int note_cipher_create(int curve, const uint8_t *bytes, size_t len, const u64 *g
     u64 state_len;
     std::memcpy(&state_len, bytes + NP * 32, 8);
     if (state_len != 4) return MG_ERR_ARG;
-    std::vector<u32> prm((size_t)ED_CIPHER_ELEMS * 8);
-    for (size_t i = 0; i < (size_t)ED_CIPHER_ELEMS; ++i) {
-        H a;
-        std::memcpy(a.v, bytes + 32 * i + (i >= NP ? 8 : 0), 32); // little-endian canonical: a value >= p is refused
-        if (H::geq_p(a.v)) return MG_ERR_ARG;
-        H::to_mont(a).store_words(&prm[i * 8]);
-    }
+    std::vector<u32> prm((size_t)ED_CIPHER_ELEMS * 8); // the permutation, then (behind the length) the initial state
+    if (!decode_canonical_elements<Bn254FrCfg>(bytes, NP, prm.data()) ||
+        !decode_canonical_elements<Bn254FrCfg>(bytes + NP * 32 + 8, ED_CIPHER_ELEMS - NP, &prm[NP * 8]))
+        return MG_ERR_ARG;
     if (!coords_reduced(generator)) return MG_ERR_ARG;
     H gx, gy;
     std::memcpy(gx.v, generator, 32);
@@ -333,29 +245,26 @@ int notes_encrypt(const mg_note_cipher *h, const u64 *recv_keys, const u64 *rand
     std::vector<u32> consts(h->prm);
     consts.insert(consts.end(), h->table.begin(), h->table.end());
     const size_t prm_words = h->prm.size();
-    return run_chunks(n, consts.data(), consts.size() * 4, {{recv_keys, nullptr, 64}, {randomness, nullptr, 32}, {plaintexts, nullptr, 96}},
-                      {{nullptr, epk_out, 64}, {nullptr, ciphertext_out, 96}, {nullptr, tag_out, 32}}, 64,
-                      [&](const uint8_t *dc, std::vector<uint8_t *> &di, std::vector<uint8_t *> &dout, uint8_t *scratch, size_t cnt,
-                          hipStream_t s) {
-                          EdwardsLaunch a{};
-                          a.n = cnt;
-                          a.stream = s;
-                          a.op = EdwardsLaunch::MUL_FIXED; // epk = G * randomness
-                          a.consts = (const u32 *)dc + prm_words;
-                          a.b = (const u32 *)di[1];
-                          a.out = (u32 *)dout[0];
+    return run_chunks(EDWARDS_STAGING, n, consts.data(), consts.size() * 4,
+                      {Span::in(recv_keys, 64), Span::in(randomness, 32), Span::in(plaintexts, 96), Span::out(epk_out, 64),
+                       Span::out(ciphertext_out, 96), Span::out(tag_out, 32)},
+                      64, [&](const Chunk &c) {
+                          EdwardsLaunch a = on_chunk(EdwardsLaunch::MUL_FIXED, c); // epk = G * randomness
+                          a.consts = (const u32 *)c.consts + prm_words;
+                          a.b = (const u32 *)c.a[1];
+                          a.out = (u32 *)c.a[3];
                           hipError_t e = edwards_launch_bn254(a);
                           if (e != hipSuccess) return e;
                           a.op = EdwardsLaunch::MUL_PAIRWISE; // key = recv_key * randomness
-                          a.a = (const u32 *)di[0];
-                          a.out = (u32 *)scratch;
+                          a.a = (const u32 *)c.a[0];
+                          a.out = (u32 *)c.scratch;
                           if ((e = edwards_launch_bn254(a)) != hipSuccess) return e;
                           a.op = EdwardsLaunch::ENCRYPT;
-                          a.consts = (const u32 *)dc;
-                          a.a = (const u32 *)scratch;
-                          a.b = (const u32 *)di[2];
-                          a.out = (u32 *)dout[1];
-                          a.out2 = (u32 *)dout[2];
+                          a.consts = (const u32 *)c.consts;
+                          a.a = (const u32 *)c.scratch;
+                          a.b = (const u32 *)c.a[2];
+                          a.out = (u32 *)c.a[4];
+                          a.out2 = (u32 *)c.a[5];
                           return edwards_launch_bn254(a);
                       });
 }
@@ -365,36 +274,30 @@ int notes_decrypt(const mg_note_cipher *h, const u64 *viewing_key, const u64 *ep
     if (!h || !viewing_key || (n && (!epks || !ciphertexts || !tags || !plaintext_out || !ok))) return MG_ERR_ARG;
     if (!scalar_ok(viewing_key)) return MG_ERR_ARG;
     std::vector<uint8_t> own;
-    if (!status) {
-        own.resize(n);
-        status = own.data();
-    }
+    status = status_or_own(status, n, own);
     std::vector<u32> consts(h->prm);
     const size_t prm_words = consts.size();
     consts.resize(prm_words + 8);
     std::memcpy(&consts[prm_words], viewing_key, 32);
     const int top = top_bit(viewing_key);
-    const int rc = run_chunks(n, consts.data(), consts.size() * 4, {{epks, nullptr, 64}, {ciphertexts, nullptr, 96}, {tags, nullptr, 32}},
-                              {{nullptr, plaintext_out, 96}, {nullptr, status, 1}}, 64,
-                              [&](const uint8_t *dc, std::vector<uint8_t *> &di, std::vector<uint8_t *> &dout, uint8_t *scratch,
-                                  size_t cnt, hipStream_t s) {
-                                  EdwardsLaunch a{};
-                                  a.n = cnt;
-                                  a.stream = s;
-                                  a.op = EdwardsLaunch::MUL_SHARED; // key = epk * viewing key
-                                  a.consts = (const u32 *)dc + prm_words;
+    const int rc = run_chunks(EDWARDS_STAGING, n, consts.data(), consts.size() * 4,
+                              {Span::in(epks, 64), Span::in(ciphertexts, 96), Span::in(tags, 32), Span::out(plaintext_out, 96),
+                               Span::out(status, 1)},
+                              64, [&](const Chunk &c) {
+                                  EdwardsLaunch a = on_chunk(EdwardsLaunch::MUL_SHARED, c); // key = epk * viewing key
+                                  a.consts = (const u32 *)c.consts + prm_words;
                                   a.top = top;
-                                  a.a = (const u32 *)di[0];
-                                  a.out = (u32 *)scratch;
+                                  a.a = (const u32 *)c.a[0];
+                                  a.out = (u32 *)c.scratch;
                                   const hipError_t e = edwards_launch_bn254(a);
                                   if (e != hipSuccess) return e;
                                   a.op = EdwardsLaunch::DECRYPT;
-                                  a.consts = (const u32 *)dc;
-                                  a.a = (const u32 *)scratch;
-                                  a.b = (const u32 *)di[1];
-                                  a.c = (const u32 *)di[2];
-                                  a.out = (u32 *)dout[0];
-                                  a.status = dout[1];
+                                  a.consts = (const u32 *)c.consts;
+                                  a.a = (const u32 *)c.scratch;
+                                  a.b = (const u32 *)c.a[1];
+                                  a.c = (const u32 *)c.a[2];
+                                  a.out = (u32 *)c.a[3];
+                                  a.status = c.a[4];
                                   return edwards_launch_bn254(a);
                               });
     if (rc == MG_OK)

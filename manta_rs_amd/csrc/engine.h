@@ -32,15 +32,17 @@ typedef uint64_t u64;
 
 enum { MG_OK = 0, MG_ERR_ARG = 1, MG_ERR_HIP = 2, MG_ERR_OOM = 3, MG_ERR_DOMAIN = 4, MG_ERR_STATE = 5 };
 
+void set_last_hip_error(hipError_t e, const char *expr, const char *file, int line);
+// a failed HIP call -> the library's status; `what` and the caller's position are kept for mg_last_error()
+inline int hip_status(hipError_t e, const char *what, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
+    set_last_hip_error(e, what, file, line);
+    return e == hipErrorOutOfMemory ? MG_ERR_OOM : MG_ERR_HIP;
+}
 #define MG_HIP(expr)                                                                                              \
     do {                                                                                                          \
         hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) {                                                                                   \
-            mg::set_last_hip_error(e_, #expr, __FILE__, __LINE__);                                                \
-            return (e_ == hipErrorOutOfMemory) ? mg::MG_ERR_OOM : mg::MG_ERR_HIP;                                 \
-        }                                                                                                         \
+        if (e_ != hipSuccess) return mg::hip_status(e_, #expr);                                                   \
     } while (0)
-void set_last_hip_error(hipError_t e, const char *expr, const char *file, int line);
 void set_last_error_text(const char *text); // detail for mg_last_error() of a failure that is not a HIP status
 // When on, every MSM brackets its accumulate kernel with HIP events on the launch stream (bench.py's
 // roofline leg); off by default.

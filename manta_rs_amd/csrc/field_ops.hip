@@ -10,8 +10,8 @@
 //                   look like), and the result is brought back with to_std (canonical).
 // so that every function the Montgomery / lazy-reduction scheme consists of is compared with the CPU oracle (and with
 // the reference-held BLS12-381 Fr Poseidon known answers) on edge values, not only through whole MSMs.
-#include "engine.h"
 #include "fpr_dev.h"
+#include "staging.h"
 #include "params_gen.h"
 
 namespace mg {
@@ -82,25 +82,17 @@ __global__ __launch_bounds__(256) void field_op_kernel(int op, int repr, int laz
 
 template <class C> static int run(int op, int repr, int lazy_a, int lazy_b, const u32 *a, const u32 *b, size_t n, u32 *out) {
     const size_t bytes = n * Fp<C>::N * 4;
-    u32 *da = nullptr, *db = nullptr, *dout = nullptr;
-    hipError_t e = hipMalloc((void **)&da, bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&dout, bytes);
-    if (e == hipSuccess && b) e = hipMalloc((void **)&db, bytes);
-    if (e == hipSuccess) e = memcpy_sync(da, a, bytes, hipMemcpyHostToDevice);
+    DevBlock m; // a | out | b (binary operations only)
+    if (const int rc = m.alloc({bytes, bytes, b ? bytes : 0}, "mg_field_op")) return rc;
+    u32 *da = m.dev<u32>(0), *dout = m.dev<u32>(1), *db = m.dev<u32>(2);
+    hipError_t e = memcpy_sync(da, a, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess && b) e = memcpy_sync(db, b, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         hipLaunchKernelGGL((field_op_kernel<C>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, setup_stream(), op, repr, lazy_a, lazy_b, da, db,
                            dout, n);
         e = memcpy_sync(out, dout, bytes, hipMemcpyDeviceToHost);
     }
-    hipFree(da);
-    hipFree(db);
-    hipFree(dout);
-    if (e != hipSuccess) {
-        set_last_hip_error(e, "mg_field_op", __FILE__, __LINE__);
-        return e == hipErrorOutOfMemory ? MG_ERR_OOM : MG_ERR_HIP;
-    }
-    return MG_OK;
+    return e == hipSuccess ? MG_OK : hip_status(e, "mg_field_op");
 }
 
 int field_op(int field, int op, int repr, int lazy_a, int lazy_b, const u32 *a, const u32 *b, size_t n, u32 *out) {
@@ -158,27 +150,27 @@ int clock_probe(u32 iters, double *memtime_mhz, double *mad_issue_per_us_per_sim
     MG_HIP(hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, dev));
     const u32 blocks = (u32)cus * 2; // 256 threads = 4 wavefronts per block, two blocks per CU: two wavefronts per SIMD
     const size_t waves = (size_t)blocks * 4;
-    unsigned long long *d = nullptr;
-    MG_HIP(hipMalloc((void **)&d, waves * 3 * sizeof(unsigned long long)));
-    hipEvent_t e0, e1;
-    MG_HIP(hipEventCreate(&e0));
-    MG_HIP(hipEventCreate(&e1));
+    DevBlock m;
+    if (const int rc = m.alloc({waves * 3 * sizeof(unsigned long long)}, "clock probe")) return rc;
+    unsigned long long *d = m.dev<unsigned long long>(0);
+    struct Events { // destroyed on every path
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() {
+            if (e0) hipEventDestroy(e0);
+            if (e1) hipEventDestroy(e1);
+        }
+    } ev;
+    MG_HIP(hipEventCreate(&ev.e0));
+    MG_HIP(hipEventCreate(&ev.e1));
     hipLaunchKernelGGL(clock_probe_kernel, dim3(blocks), dim3(256), 0, setup_stream(), 64u, 1u, d); // warm-up
-    MG_HIP(hipEventRecord(e0, setup_stream()));
+    MG_HIP(hipEventRecord(ev.e0, setup_stream()));
     hipLaunchKernelGGL(clock_probe_kernel, dim3(blocks), dim3(256), 0, setup_stream(), iters, 2u, d);
-    MG_HIP(hipEventRecord(e1, setup_stream()));
-    hipError_t e = hipEventSynchronize(e1);
+    MG_HIP(hipEventRecord(ev.e1, setup_stream()));
+    MG_HIP(hipEventSynchronize(ev.e1));
     std::vector<unsigned long long> h(waves * 3);
-    if (e == hipSuccess) e = memcpy_sync(h.data(), d, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    MG_HIP(memcpy_sync(h.data(), d, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     float t = 0.f;
-    hipEventElapsedTime(&t, e0, e1);
-    hipFree(d);
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    if (e != hipSuccess) {
-        set_last_hip_error(e, "clock probe", __FILE__, __LINE__);
-        return MG_ERR_HIP;
-    }
+    hipEventElapsedTime(&t, ev.e0, ev.e1);
     double ratio = 0;
     for (size_t w = 0; w < waves; ++w) ratio += (double)h[3 * w] / (double)(h[3 * w + 1] ? h[3 * w + 1] : 1);
     ratio /= (double)waves;

@@ -2,6 +2,7 @@
 // Part of msm_impl.h.
 #pragma once
 #include "msm_common.h"
+#include "staging.h"
 #include "msm_digits.h"
 #include "msm_accumulate.h"
 #include "msm_reduce.h"
@@ -299,7 +300,7 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         if (e == hipSuccess) e = setup_sync();
         else (void)setup_sync();
         if (tmp) hipFree(tmp);
-        return e == hipSuccess ? MG_OK : hip_failure(e, "full-table kernels", e == hipErrorOutOfMemory ? MG_ERR_OOM : MG_ERR_HIP);
+        return e == hipSuccess ? MG_OK : hip_status(e, "full-table kernels");
     }
     void bases_destroy(BaseSet *bs) override {
         if (!bs) return;
@@ -568,44 +569,26 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
     int fixed_base_mul(const u32 *base_affine_host, const u32 *d_scalars, size_t n, u32 *d_out_affine,
                        hipStream_t s) override {
         if (!s) s = setup_stream(); // (never the NULL stream: engine.h)
-        u32 *d_base = nullptr, *tmp = nullptr;
-        MG_HIP(hipMalloc((void **)&d_base, AW_IO * 4));
-        hipError_t e = hipMalloc((void **)&tmp, n * XW_IO * 4);
-        if (e != hipSuccess) {
-            hipFree(d_base);
-            set_last_hip_error(e, "hipMalloc(fixed_base tmp)", __FILE__, __LINE__);
-            return MG_ERR_OOM;
-        }
+        DevBlock m, table; // base | XYZZ results; the 32 x 255 multiples of the base as XYZZ | affine
+        if (const int rc = m.alloc({AW_IO * 4, n * XW_IO * 4}, "hipMalloc(fixed_base_mul)")) return rc;
+        u32 *d_base = m.dev<u32>(0), *tmp = m.dev<u32>(1);
         hipMemcpyAsync(d_base, base_affine_host, AW_IO * 4, hipMemcpyHostToDevice, s);
         constexpr int KB = 16;
-        u32 *t_xyzz = nullptr, *t_aff = nullptr;
-        if (n >= msm_knobs().fixed_base_table_min) { // many multiples of one base: 32 table additions each instead of ~380 group operations
-            constexpr size_t TN = 32 * 255;
-            if (hipMalloc((void **)&t_xyzz, TN * XW_IO * 4) == hipSuccess && hipMalloc((void **)&t_aff, TN * AW_IO * 4) == hipSuccess) {
-                hipLaunchKernelGGL((fixed_base_table_kernel<FIO>), dim3(cdiv(TN, 256)), dim3(256), 0, s, d_base, t_xyzz);
-                hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(TN, KB), 256)), dim3(256), 0, s, t_xyzz, TN, t_aff,
-                                   (u32)AW_IO);
-                hipLaunchKernelGGL((fixed_base_mul_table_kernel<FIO>), dim3(cdiv(n, 256)), dim3(256), 0, s, t_aff, d_scalars, n, tmp);
-            } else {
-                (void)hipGetLastError();
-                if (t_xyzz) hipFree(t_xyzz);
-                t_xyzz = nullptr;
-            }
+        constexpr size_t TN = 32 * 255;
+        // many multiples of one base: 32 table additions each instead of ~380 group operations -- when the table's memory can be had
+        if (n >= msm_knobs().fixed_base_table_min && table.try_alloc({TN * XW_IO * 4, TN * AW_IO * 4})) {
+            u32 *t_xyzz = table.dev<u32>(0), *t_aff = table.dev<u32>(1);
+            hipLaunchKernelGGL((fixed_base_table_kernel<FIO>), dim3(cdiv(TN, 256)), dim3(256), 0, s, d_base, t_xyzz);
+            hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(TN, KB), 256)), dim3(256), 0, s, t_xyzz, TN, t_aff,
+                               (u32)AW_IO);
+            hipLaunchKernelGGL((fixed_base_mul_table_kernel<FIO>), dim3(cdiv(n, 256)), dim3(256), 0, s, t_aff, d_scalars, n, tmp);
+        } else {
+            hipLaunchKernelGGL((fixed_base_mul_kernel<FIO>), dim3(cdiv(n, 256)), dim3(256), 0, s, d_base, d_scalars, n, tmp);
         }
-        if (!t_xyzz)
-        hipLaunchKernelGGL((fixed_base_mul_kernel<FIO>), dim3(cdiv(n, 256)), dim3(256), 0, s, d_base, d_scalars, n, tmp);
         hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(n, KB), 256)), dim3(256), 0, s, tmp, n,
                            d_out_affine, (u32)AW_IO);
-        e = hipStreamSynchronize(s);
-        hipFree(d_base);
-        hipFree(tmp);
-        if (t_xyzz) hipFree(t_xyzz);
-        if (t_aff) hipFree(t_aff);
-        if (e != hipSuccess) {
-            set_last_hip_error(e, "fixed_base_mul", __FILE__, __LINE__);
-            return MG_ERR_HIP;
-        }
-        return MG_OK;
+        const hipError_t e = hipStreamSynchronize(s);
+        return e == hipSuccess ? MG_OK : hip_status(e, "fixed_base_mul");
     }
 
     int ec_elementwise(int op, const u32 *a_host, const u32 *b_host, size_t n, u32 *out_affine_host) override {
@@ -684,42 +667,33 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
     int ec_elementwise_impl(int op, const u32 *a_host, const u32 *b_host, size_t n, u32 *out_host, bool xyzz) {
         if (op < 0 || op > 5 || !a_host || !out_host || n == 0 || (op != 2 && !b_host)) return MG_ERR_ARG;
         const size_t ab = n * AW_IO * 4, bb = op == 3 ? n * 32 : (op == 5 ? 32 : ab);
-        u32 *da = nullptr, *db = nullptr, *tmp = nullptr, *dout = nullptr;
         // a stream of its own (not stream 0: a synchronous copy anywhere else in the process -- another thread creating a base
         // set, say -- would wait for this kernel, a millisecond of one-lane latency for 128-bit multipliers)
         hipStream_t st = stream_pool_get_normal(); // (pooled: the library destroys no stream, runtime.cpp)
-        hipError_t e = st ? hipSuccess : hipErrorOutOfMemory;
-        if (e == hipSuccess) e = hipMalloc((void **)&da, ab);
-        if (e == hipSuccess) e = hipMalloc((void **)&db, bb);
-        if (e == hipSuccess) e = hipMalloc((void **)&tmp, n * XW_IO * 4);
-        if (e == hipSuccess && !xyzz) e = hipMalloc((void **)&dout, ab);
-        if (e == hipSuccess) e = hipMemcpyAsync(da, a_host, ab, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && op != 2) e = hipMemcpyAsync(db, b_host, bb, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL((ec_elementwise_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, op, da, db, n, tmp);
-            if (xyzz) {
-                e = hipMemcpyAsync(out_host, tmp, n * XW_IO * 4, hipMemcpyDeviceToHost, st);
-            } else {
-                constexpr int KB = 16;
-                hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(n, KB), 256)), dim3(256), 0, st, tmp, n, dout,
-                                   (u32)AW_IO);
-                e = hipMemcpyAsync(out_host, dout, ab, hipMemcpyDeviceToHost, st);
+        if (!st) return hip_status(hipErrorOutOfMemory, "ec_elementwise");
+        DevBlock m; // a | b | XYZZ results | affine results
+        hipError_t e = hipSuccess;
+        int rc = m.alloc({ab, bb, n * XW_IO * 4, xyzz ? 0 : ab}, "ec_elementwise");
+        if (!rc) {
+            u32 *da = m.dev<u32>(0), *db = m.dev<u32>(1), *tmp = m.dev<u32>(2), *dout = m.dev<u32>(3);
+            e = hipMemcpyAsync(da, a_host, ab, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess && op != 2) e = hipMemcpyAsync(db, b_host, bb, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL((ec_elementwise_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, op, da, db, n, tmp);
+                if (xyzz) {
+                    e = hipMemcpyAsync(out_host, tmp, n * XW_IO * 4, hipMemcpyDeviceToHost, st);
+                } else {
+                    constexpr int KB = 16;
+                    hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(n, KB), 256)), dim3(256), 0, st, tmp, n, dout,
+                                       (u32)AW_IO);
+                    e = hipMemcpyAsync(out_host, dout, ab, hipMemcpyDeviceToHost, st);
+                }
             }
-        }
-        if (st) {
             const hipError_t e2 = hipStreamSynchronize(st);
             if (e == hipSuccess) e = e2;
-            stream_pool_put_normal(st);
         }
-        hipFree(da);
-        hipFree(db);
-        hipFree(tmp);
-        if (dout) hipFree(dout);
-        if (e != hipSuccess) {
-            set_last_hip_error(e, "ec_elementwise", __FILE__, __LINE__);
-            return e == hipErrorOutOfMemory ? MG_ERR_OOM : MG_ERR_HIP;
-        }
-        return MG_OK;
+        stream_pool_put_normal(st);
+        return rc ? rc : e == hipSuccess ? MG_OK : hip_status(e, "ec_elementwise");
     }
 
     // NTT over group elements: host affine in, host affine out (natural order both); tw = the Fr domain's device twiddle
@@ -728,13 +702,10 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
                   u32 *out_affine_host) override {
         if (!in_affine_host || !out_affine_host || lg > 26 || (lg > 0 && !d_twiddles_mont)) return MG_ERR_ARG;
         const size_t n = (size_t)1 << lg, ab = n * AW_IO * 4;
-        u32 *d_in = nullptr, *d_pts = nullptr, *d_std = nullptr, *d_out = nullptr, *d_sc = nullptr;
-        hipError_t e = hipMalloc((void **)&d_in, ab);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_pts, n * XW * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_std, n * XW_IO * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_out, ab);
-        if (e == hipSuccess && n_inv_canonical) e = hipMalloc((void **)&d_sc, 32);
-        if (e == hipSuccess) e = memcpy_sync(d_in, in_affine_host, ab, hipMemcpyHostToDevice);
+        DevBlock m; // affine in | working XYZZ | arkworks-format XYZZ | affine out | n^-1 (inverse transform only)
+        if (const int rc = m.alloc({ab, n * XW * 4, n * XW_IO * 4, ab, n_inv_canonical ? 32u : 0u}, "group_ntt")) return rc;
+        u32 *d_in = m.dev<u32>(0), *d_pts = m.dev<u32>(1), *d_std = m.dev<u32>(2), *d_out = m.dev<u32>(3), *d_sc = m.dev<u32>(4);
+        hipError_t e = memcpy_sync(d_in, in_affine_host, ab, hipMemcpyHostToDevice);
         if (e == hipSuccess && n_inv_canonical) e = memcpy_sync(d_sc, n_inv_canonical, 32, hipMemcpyHostToDevice);
         if (e == hipSuccess) {
             hipLaunchKernelGGL((group_ntt_load_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, setup_stream(), d_in, lg, d_pts);
@@ -745,25 +716,18 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
             hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(n, KB), 256)), dim3(256), 0, setup_stream(), d_std, n, d_out, (u32)AW_IO);
             e = memcpy_sync(out_affine_host, d_out, ab, hipMemcpyDeviceToHost);
         }
-        hipFree(d_in), hipFree(d_pts), hipFree(d_std), hipFree(d_out), hipFree(d_sc);
-        if (e != hipSuccess) {
-            set_last_hip_error(e, "group_ntt", __FILE__, __LINE__);
-            return e == hipErrorOutOfMemory ? MG_ERR_OOM : MG_ERR_HIP;
-        }
-        return MG_OK;
+        return e == hipSuccess ? MG_OK : hip_status(e, "group_ntt");
     }
 
     int sum_affine(const u32 *d_pts, size_t n, HostPoint *out) override {
         const u32 T = n < 4096 ? (u32)(n ? n : 1) : 4096;
-        u32 *tmp = nullptr;
-        MG_HIP(hipMalloc((void **)&tmp, (size_t)T * XW_IO * 4));
-        hipLaunchKernelGGL((sum_affine_kernel<FIO>), dim3(cdiv(T, 256)), dim3(256), 0, setup_stream(), d_pts, n, T, tmp);
         std::vector<u32> h((size_t)T * XW_IO);
-        hipError_t e = memcpy_sync(h.data(), tmp, h.size() * 4, hipMemcpyDeviceToHost);
-        hipFree(tmp);
-        if (e != hipSuccess) {
-            set_last_hip_error(e, "sum_affine", __FILE__, __LINE__);
-            return MG_ERR_HIP;
+        {
+            DevBlock m;
+            if (const int rc = m.alloc({h.size() * 4}, "hipMalloc(sum_affine)")) return rc;
+            hipLaunchKernelGGL((sum_affine_kernel<FIO>), dim3(cdiv(T, 256)), dim3(256), 0, setup_stream(), d_pts, n, T, m.dev<u32>(0));
+            const hipError_t e = memcpy_sync(h.data(), m.dev<u32>(0), h.size() * 4, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return hip_status(e, "sum_affine");
         }
         HP acc = HP::inf();
         for (u32 t = 0; t < T; ++t) acc = HP::add(acc, HP::from_xyzz_words(h.data() + (size_t)t * XW_IO));

@@ -3,8 +3,8 @@
 #pragma once
 #include <mutex>
 #include <vector>
-#include "engine.h"
 #include "pairing_coop.h"
+#include "staging.h"
 #include "verify.h"
 #include <cstring>
 #include <vector>
@@ -116,22 +116,18 @@ template <class K> class PairingEngineT : public PairingEngine {
 
     int prepare(const u32 *q_affine_host, size_t n, u32 **d_out) override {
         if (!q_affine_host || !n || !d_out) return MG_ERR_ARG;
-        u32 *dq = nullptr, *dc = nullptr;
         const size_t qb = n * 2 * P::F2W * 4, cb = n * (size_t)P::NCOEFF * P::COEFFW * 4;
-        hipError_t e = hipMalloc((void **)&dq, qb);
-        if (e == hipSuccess) e = hipMalloc((void **)&dc, cb);
-        if (e == hipSuccess) e = memcpy_sync(dq, q_affine_host, qb, hipMemcpyHostToDevice);
+        DevBlock q, c; // the points, needed for this call only; the coefficients, which become the caller's
+        int rc = q.alloc({qb}, "pairing prepare");
+        if (rc || (rc = c.alloc({cb}, "pairing prepare"))) return rc;
+        hipError_t e = memcpy_sync(q.dev(0), q_affine_host, qb, hipMemcpyHostToDevice);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL((g2_prepare_kernel<K>), dim3((unsigned)n), dim3(64), PW::prep_lds_bytes(), setup_stream(), dq, n, dc);
+            hipLaunchKernelGGL((g2_prepare_kernel<K>), dim3((unsigned)n), dim3(64), PW::prep_lds_bytes(), setup_stream(), q.dev<u32>(0), n,
+                               c.dev<u32>(0));
             e = setup_sync();
         }
-        hipFree(dq);
-        if (e != hipSuccess) {
-            hipFree(dc);
-            set_last_hip_error(e, "pairing prepare", __FILE__, __LINE__);
-            return e == hipErrorOutOfMemory ? MG_ERR_OOM : MG_ERR_HIP;
-        }
-        *d_out = dc;
+        if (e != hipSuccess) return hip_status(e, "pairing prepare");
+        *d_out = (u32 *)c.release();
         return MG_OK;
     }
 
@@ -201,8 +197,7 @@ template <class K> class PairingEngineT : public PairingEngine {
         if (e != hipSuccess) {
             hipStreamSynchronize(w->s);
             ws_put(w);
-            set_last_hip_error(e, "pairing product", __FILE__, __LINE__);
-            return e == hipErrorOutOfMemory ? MG_ERR_OOM : MG_ERR_HIP;
+            return hip_status(e, "pairing product");
         }
         *handle = w;
         return MG_OK;
@@ -264,8 +259,7 @@ template <class K> class PairingEngineT : public PairingEngine {
         if (e == hipSuccess) std::memcpy(out_f12_host, w->h, P::F12W * 4);
         ws_put(w);
         if (e != hipSuccess) {
-            set_last_hip_error(e, "pairing product", __FILE__, __LINE__);
-            return e == hipErrorOutOfMemory ? MG_ERR_OOM : MG_ERR_HIP;
+            return hip_status(e, "pairing product");
         }
         return MG_OK;
     }

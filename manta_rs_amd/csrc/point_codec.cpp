@@ -7,17 +7,11 @@ namespace mg {
 namespace {
 
 int run(int curve, const PointCodecArgs &a) {
-    HeavyOp no_capture_meanwhile; // the staging buffers are allocated and freed inside the call
     if (curve == 0) return point_codec_bn254(a);
     if (curve == 1) return point_codec_bls381(a);
     return MG_ERR_ARG;
 }
 bool valid(int curve, int group) { return (curve == 0 || curve == 1) && (group == 1 || group == 2); }
-size_t count_bad(const uint8_t *st, size_t n) {
-    size_t b = 0;
-    for (size_t i = 0; i < n; ++i) b += st[i] != PT_OK;
-    return b;
-}
 size_t fq_bytes(int curve) { return curve == 0 ? 32 : 48; }
 
 } // namespace
@@ -27,10 +21,7 @@ int points_decode(int curve, int group, const uint8_t *bytes, size_t n, int comp
     if (!valid(curve, group) || (n && (!bytes || !out))) return MG_ERR_ARG;
     if (compressed && !checked) return MG_ERR_ARG; // arkworks has no unchecked compressed read: the root is the check
     std::vector<uint8_t> own;
-    if (!status) {
-        own.resize(n);
-        status = own.data();
-    }
+    status = status_or_own(status, n, own);
     const int rc = run(curve, PointCodecArgs{group, 0, compressed != 0, checked != 0, bytes, n, out, status});
     if (rc == MG_OK && n_bad) *n_bad = count_bad(status, n);
     return rc;
@@ -39,10 +30,7 @@ int points_decode(int curve, int group, const uint8_t *bytes, size_t n, int comp
 int points_check(int curve, int group, const u64 *affine, size_t n, uint8_t *status, size_t *n_bad) {
     if (!valid(curve, group) || (n && !affine)) return MG_ERR_ARG;
     std::vector<uint8_t> own;
-    if (!status) {
-        own.resize(n);
-        status = own.data();
-    }
+    status = status_or_own(status, n, own);
     const int rc = run(curve, PointCodecArgs{group, 1, 0, 1, affine, n, nullptr, status});
     if (rc == MG_OK && n_bad) *n_bad = count_bad(status, n);
     return rc;

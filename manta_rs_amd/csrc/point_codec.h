@@ -19,8 +19,8 @@
 // exceptional branches of the group law, taken by points of small order only).
 #pragma once
 #include "ec_dev.h"
-#include "engine.h"
 #include "params_gen.h"
+#include "staging.h"
 #include <cstring>
 #include <vector>
 
@@ -265,53 +265,11 @@ __global__ __launch_bounds__(256) void point_encode_kernel(const u32 *__restrict
 
 } // namespace codec
 
-// ---- host side: chunked through pinned staging buffers on the calling thread's setup stream ---------------------------
+// ---- host side: run_chunks (staging.h) through a pinned block on the calling thread's setup stream --------------------
 // At most POINT_CODEC_CHUNK points are on the device at a time: device memory and pinned host memory of a call are each
 // bounded by POINT_CODEC_CHUNK x (input + output record) -- < 26 MB for uncompressed BLS12-381 G2, the largest record.
 constexpr size_t POINT_CODEC_CHUNK = size_t(1) << 16;
-
-struct CodecStage { // one call's buffers, freed on every path
-    void *d = nullptr, *h = nullptr;
-    ~CodecStage() {
-        if (d) hipFree(d);
-        if (h) hipHostFree(h);
-    }
-};
-
-// in_bytes / out_bytes per point; `launch(d_in, d_out, d_status, count)` enqueues the kernel on the setup stream
-template <class Launch>
-int codec_run(const char *what, size_t n, size_t in_bytes, size_t out_bytes, bool with_status, const void *src, void *dst,
-              uint8_t *status, Launch launch) {
-    if (n == 0) return MG_OK;
-    hipStream_t s = setup_stream();
-    if (!s) return MG_ERR_OOM;
-    const size_t cap = n < POINT_CODEC_CHUNK ? n : POINT_CODEC_CHUNK;
-    const size_t st_bytes = with_status ? cap : 0;
-    const size_t total = cap * (in_bytes + out_bytes) + st_bytes;
-    CodecStage b;
-    hipError_t e = hipMalloc(&b.d, total);
-    if (e == hipSuccess) e = hipHostMalloc(&b.h, total, hipHostMallocDefault);
-    uint8_t *d_in = (uint8_t *)b.d, *d_out = d_in + cap * in_bytes, *d_st = d_out + cap * out_bytes;
-    uint8_t *h_in = (uint8_t *)b.h, *h_out = h_in + cap * in_bytes, *h_st = h_out + cap * out_bytes;
-    for (size_t off = 0; off < n && e == hipSuccess; off += cap) {
-        const size_t cnt = n - off < cap ? n - off : cap;
-        std::memcpy(h_in, (const uint8_t *)src + off * in_bytes, cnt * in_bytes);
-        e = hipMemcpyAsync(d_in, h_in, cnt * in_bytes, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) break;
-        launch(d_in, d_out, d_st, cnt, s);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        if (out_bytes && (e = hipMemcpyAsync(h_out, d_out, cnt * out_bytes, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        if (with_status && (e = hipMemcpyAsync(h_st, d_st, cnt, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) break;
-        if (out_bytes) std::memcpy((uint8_t *)dst + off * out_bytes, h_out, cnt * out_bytes);
-        if (with_status) std::memcpy(status + off, h_st, cnt);
-    }
-    if (e != hipSuccess) {
-        set_last_hip_error(e, what, __FILE__, __LINE__);
-        return e == hipErrorOutOfMemory ? MG_ERR_OOM : MG_ERR_HIP;
-    }
-    return MG_OK;
-}
+constexpr Staging POINT_CODEC_STAGING{POINT_CODEC_CHUNK, true};
 
 template <class Curve, int G> struct PointCodecT {
     typedef typename codec::Group<Curve, G>::F F;
@@ -319,26 +277,29 @@ template <class Curve, int G> struct PointCodecT {
     static unsigned blocks(size_t cnt) { return (unsigned)((cnt + 255) / 256); }
     static int decode(const uint8_t *bytes, size_t n, bool compressed, bool checked, u64 *out, uint8_t *status) {
         const int cf = compressed, ck = checked;
-        return codec_run("mg_points_decode", n, (compressed ? 1 : 2) * COORD, 2 * COORD, true, bytes, out, status,
-                         [&](uint8_t *di, uint8_t *dout, uint8_t *dst, size_t cnt, hipStream_t s) {
-                             hipLaunchKernelGGL((codec::point_decode_kernel<Curve, G>), dim3(blocks(cnt)), dim3(256), 0, s,
-                                                (const u32 *)di, cnt, cf, ck, (u32 *)dout, dst);
-                         });
+        return run_chunks(POINT_CODEC_STAGING, n, nullptr, 0,
+                          {Span::in(bytes, (compressed ? 1 : 2) * COORD), Span::out(out, 2 * COORD), Span::out(status, 1)}, 0,
+                          [&](const Chunk &c) {
+                              hipLaunchKernelGGL((codec::point_decode_kernel<Curve, G>), dim3(blocks(c.n)), dim3(256), 0, c.stream,
+                                                 (const u32 *)c.a[0], c.n, cf, ck, (u32 *)c.a[1], c.a[2]);
+                              return hipGetLastError();
+                          });
     }
     static int check(const u64 *aff, size_t n, uint8_t *status) {
-        return codec_run("mg_points_check", n, 2 * COORD, 0, true, aff, nullptr, status,
-                         [&](uint8_t *di, uint8_t *, uint8_t *dst, size_t cnt, hipStream_t s) {
-                             hipLaunchKernelGGL((codec::point_check_kernel<Curve, G>), dim3(blocks(cnt)), dim3(256), 0, s,
-                                                (const u32 *)di, cnt, dst);
-                         });
+        return run_chunks(POINT_CODEC_STAGING, n, nullptr, 0, {Span::in(aff, 2 * COORD), Span::out(status, 1)}, 0, [&](const Chunk &c) {
+            hipLaunchKernelGGL((codec::point_check_kernel<Curve, G>), dim3(blocks(c.n)), dim3(256), 0, c.stream, (const u32 *)c.a[0],
+                               c.n, c.a[1]);
+            return hipGetLastError();
+        });
     }
     static int encode(const u64 *aff, size_t n, bool compressed, uint8_t *out) {
         const int cf = compressed;
-        return codec_run("mg_points_encode", n, 2 * COORD, (compressed ? 1 : 2) * COORD, false, aff, out, nullptr,
-                         [&](uint8_t *di, uint8_t *dout, uint8_t *, size_t cnt, hipStream_t s) {
-                             hipLaunchKernelGGL((codec::point_encode_kernel<Curve, G>), dim3(blocks(cnt)), dim3(256), 0, s,
-                                                (const u32 *)di, cnt, cf, (u32 *)dout);
-                         });
+        return run_chunks(POINT_CODEC_STAGING, n, nullptr, 0, {Span::in(aff, 2 * COORD), Span::out(out, (compressed ? 1 : 2) * COORD)}, 0,
+                          [&](const Chunk &c) {
+                              hipLaunchKernelGGL((codec::point_encode_kernel<Curve, G>), dim3(blocks(c.n)), dim3(256), 0, c.stream,
+                                                 (const u32 *)c.a[0], c.n, cf, (u32 *)c.a[1]);
+                              return hipGetLastError();
+                          });
     }
 };
 

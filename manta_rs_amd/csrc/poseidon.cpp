@@ -1,7 +1,7 @@
 // Host layer of batched Poseidon and the Merkle-tree hashing (mantagpu.h mg_poseidon_* / mg_merkle_*): parameter decoding,
 // argument checks (all before any device work), chunking, the level schedule of trees and forests. Kernels in poseidon.h.
 #include "poseidon.h"
-#include "host_ec.h"
+#include "staging.h"
 #include <cstring>
 #include <vector>
 
@@ -16,19 +16,6 @@ constexpr size_t POSEIDON_CHUNK = size_t(1) << 19; // = MG_POSEIDON_CHUNK of man
 
 namespace {
 
-template <class C> bool decode_elements(const uint8_t *bytes, size_t count, std::vector<u64> &out) {
-    typedef host::HFp<C> H;
-    out.resize(count * 4);
-    for (size_t i = 0; i < count; ++i) {
-        H a;
-        std::memcpy(a.v, bytes + 32 * i, 32); // little-endian canonical (ark-ff deserialize): a value >= r is refused
-        if (H::geq_p(a.v)) return false;
-        const H m = H::to_mont(a);
-        std::memcpy(&out[4 * i], m.v, 32);
-    }
-    return true;
-}
-
 hipError_t launch(const mg_poseidon *h, PoseidonLaunch a) {
     a.width = h->width;
     a.half_full = h->full / 2;
@@ -36,44 +23,21 @@ hipError_t launch(const mg_poseidon *h, PoseidonLaunch a) {
     return h->curve == 0 ? poseidon_launch_bn254(a) : poseidon_launch_bls381(a);
 }
 
-struct DevMem { // one call's device memory, freed on every path
-    void *p = nullptr;
-    ~DevMem() {
-        if (p) hipFree(p);
-    }
-};
-
 size_t prm_bytes(const mg_poseidon *h) { return h->prm.size() * 8; }
 
-// PERMUTE (in place) or HASH over n items from host memory, POSEIDON_CHUNK at a time
-int run_chunks(const mg_poseidon *h, int op, const u64 *in, size_t n, u64 *out) {
-    if (n == 0) return MG_OK;
-    HeavyOp no_capture_meanwhile; // device memory is allocated and freed inside the call
-    hipStream_t s = setup_stream();
-    if (!s) return MG_ERR_OOM;
-    const size_t t = (size_t)h->width, in_w = op == PoseidonLaunch::PERMUTE ? t : t - 1;
-    const size_t out_w = op == PoseidonLaunch::PERMUTE ? t : 1;
-    const size_t cap = n < POSEIDON_CHUNK ? n : POSEIDON_CHUNK, pb = prm_bytes(h);
-    DevMem m;
-    MG_HIP(hipMalloc(&m.p, pb + cap * (in_w + (op == PoseidonLaunch::PERMUTE ? 0 : out_w)) * 32));
-    uint8_t *d_prm = (uint8_t *)m.p, *d_in = d_prm + pb;
-    uint8_t *d_out = op == PoseidonLaunch::PERMUTE ? d_in : d_in + cap * in_w * 32;
-    MG_HIP(hipMemcpyAsync(d_prm, h->prm.data(), pb, hipMemcpyHostToDevice, s));
-    for (size_t off = 0; off < n; off += cap) {
-        const size_t cnt = n - off < cap ? n - off : cap;
-        MG_HIP(hipMemcpyAsync(d_in, in + off * in_w * 4, cnt * in_w * 32, hipMemcpyHostToDevice, s));
+// PERMUTE (in place: one device array, 2^19 x 192 B at width 6) or HASH over n items from host memory, POSEIDON_CHUNK at a time,
+// pageable: copies go straight from and to the caller's arrays
+int run(const mg_poseidon *h, int op, const std::vector<Span> &arrays, size_t n) {
+    return run_chunks(Staging{POSEIDON_CHUNK, false}, n, h->prm.data(), prm_bytes(h), arrays, 0, [&](const Chunk &c) {
         PoseidonLaunch a{};
         a.op = op;
-        a.prm = (const u32 *)d_prm;
-        a.in = (const u32 *)d_in;
-        a.out = (u32 *)d_out;
-        a.n = cnt;
-        a.stream = s;
-        MG_HIP(launch(h, a));
-        MG_HIP(hipMemcpyAsync(out + off * out_w * 4, d_out, cnt * out_w * 32, hipMemcpyDeviceToHost, s));
-        MG_HIP(hipStreamSynchronize(s));
-    }
-    return MG_OK;
+        a.prm = (const u32 *)c.consts;
+        a.in = (const u32 *)c.a[0];
+        a.out = (u32 *)c.a.back();
+        a.n = c.n;
+        a.stream = c.stream;
+        return launch(h, a);
+    });
 }
 
 bool tree_args_ok(const mg_poseidon *h, unsigned height) { return h && h->width == 3 && height >= 2 && height <= 32; }
@@ -105,16 +69,14 @@ int merkle_run(const mg_poseidon *h, unsigned height, const u64 *leaves, const s
         base += acc;
         if (l0 < 0 && (mx <= (u64)MERKLE_TOP || l == H - 1)) l0 = (int)l;
     }
-    HeavyOp no_capture_meanwhile;
     hipStream_t s = setup_stream();
     if (!s) return MG_ERR_OOM;
     const size_t pb = prm_bytes(h), tb = off.size() * 8;
     const size_t lvl_bytes = keep ? base * 32 : (total[0] + (H > 1 ? total[1] : 0)) * 32;
     const size_t path_len = H - 1;
-    DevMem m;
-    MG_HIP(hipMalloc(&m.p, pb + tb + lvl_bytes + nt * 32 + k * 8 + k * path_len * 32));
-    uint8_t *d_prm = (uint8_t *)m.p, *d_off = d_prm + pb, *d_lv = d_off + tb, *d_roots = d_lv + lvl_bytes;
-    uint8_t *d_idx = d_roots + nt * 32, *d_paths = d_idx + k * 8;
+    DevBlock m; // parameters | offsets table | levels | roots | path indices | paths
+    if (const int rc = m.alloc({pb, tb, lvl_bytes, nt * 32, k * 8, k * path_len * 32}, "hipMalloc(merkle)")) return rc;
+    uint8_t *d_prm = m.dev(0), *d_off = m.dev(1), *d_lv = m.dev(2), *d_roots = m.dev(3), *d_idx = m.dev(4), *d_paths = m.dev(5);
     uint8_t *buf[2] = {d_lv, keep ? d_lv : d_lv + total[0] * 32}; // level l lives in buf[l & 1]
     MG_HIP(hipMemcpyAsync(d_prm, h->prm.data(), pb, hipMemcpyHostToDevice, s));
     MG_HIP(hipMemcpyAsync(d_off, off.data(), tb, hipMemcpyHostToDevice, s));
@@ -164,8 +126,9 @@ int poseidon_create(int curve, int width, int full_rounds, int partial_rounds, c
     if (full_rounds <= 0 || (full_rounds & 1) || partial_rounds < 0 || full_rounds + partial_rounds > 4096) return MG_ERR_ARG;
     const size_t count = (size_t)(full_rounds + partial_rounds) * width + (size_t)width * width + 1;
     if (len != count * 32) return MG_ERR_ARG;
-    std::vector<u64> prm;
-    const bool ok = curve == 0 ? decode_elements<Bn254FrCfg>(bytes, count, prm) : decode_elements<Bls381FrCfg>(bytes, count, prm);
+    std::vector<u64> prm(count * 4);
+    const bool ok = curve == 0 ? decode_canonical_elements<Bn254FrCfg>(bytes, count, prm.data())
+                               : decode_canonical_elements<Bls381FrCfg>(bytes, count, prm.data());
     if (!ok) return MG_ERR_ARG;
     *out = new mg_poseidon{curve, width, full_rounds, partial_rounds, std::move(prm)};
     return MG_OK;
@@ -175,26 +138,25 @@ void poseidon_destroy(mg_poseidon *h) { delete h; }
 
 int poseidon_permute(const mg_poseidon *h, u64 *states, size_t n) {
     if (!h || (n && !states)) return MG_ERR_ARG;
-    return run_chunks(h, PoseidonLaunch::PERMUTE, states, n, states);
+    return run(h, PoseidonLaunch::PERMUTE, {Span::inout(states, (size_t)h->width * 32)}, n);
 }
 
 int poseidon_hash(const mg_poseidon *h, const u64 *inputs, size_t n, u64 *out) {
     if (!h || (n && (!inputs || !out))) return MG_ERR_ARG;
-    return run_chunks(h, PoseidonLaunch::HASH, inputs, n, out);
+    return run(h, PoseidonLaunch::HASH, {Span::in(inputs, (size_t)(h->width - 1) * 32), Span::out(out, 32)}, n);
 }
 
 int poseidon_hash_device(const mg_poseidon *h, const u64 *d_in, size_t n, u64 *d_out) {
     if (!h || (n && (!d_in || !d_out))) return MG_ERR_ARG;
     if (n == 0) return MG_OK;
-    HeavyOp no_capture_meanwhile;
     hipStream_t s = setup_stream();
     if (!s) return MG_ERR_OOM;
-    DevMem m;
-    MG_HIP(hipMalloc(&m.p, prm_bytes(h)));
-    MG_HIP(hipMemcpyAsync(m.p, h->prm.data(), prm_bytes(h), hipMemcpyHostToDevice, s));
+    DevBlock m;
+    if (const int rc = m.alloc({prm_bytes(h)}, "hipMalloc(poseidon parameters)")) return rc;
+    MG_HIP(hipMemcpyAsync(m.dev(0), h->prm.data(), prm_bytes(h), hipMemcpyHostToDevice, s));
     PoseidonLaunch a{};
     a.op = PoseidonLaunch::HASH;
-    a.prm = (const u32 *)m.p;
+    a.prm = m.dev<const u32>(0);
     a.in = (const u32 *)d_in;
     a.out = (u32 *)d_out;
     a.n = n;

@@ -57,8 +57,7 @@ int DevBuf::reserve(size_t bytes) {
     hipError_t e = hipMalloc(&p, want);
     if (e != hipSuccess) {
         p = nullptr;
-        set_last_hip_error(e, "hipMalloc(DevBuf)", __FILE__, __LINE__);
-        return e == hipErrorOutOfMemory ? MG_ERR_OOM : MG_ERR_HIP;
+        return hip_status(e, "hipMalloc(DevBuf)");
     }
     cap = want;
     return MG_OK;

@@ -6,27 +6,22 @@
 // same key. Key conventions as readable in-repo at manta-trusted-setup/src/groth16/mpc.rs:251-431.
 // SURVEY.md section 8(f-3).
 #include "prover.h"
+#include "staging.h"
 #include <cstring>
 
 namespace mg {
 
 static int mul_all(GroupEngine *e, const u64 *gen, const std::vector<u64> &scalars, std::vector<u32> &out) {
     const size_t n = scalars.size() / 4, aw = (size_t)e->affine_words();
-    u32 *d_s = nullptr, *d_o = nullptr;
-    hipError_t er = hipMalloc((void **)&d_s, n * 32);
-    if (er == hipSuccess) er = hipMalloc((void **)&d_o, n * aw * 4);
-    if (er == hipSuccess) er = memcpy_sync(d_s, scalars.data(), n * 32, hipMemcpyHostToDevice);
+    DevBlock m; // scalars | points
+    if (const int rc = m.alloc({n * 32, n * aw * 4}, "groth16_setup")) return rc;
+    u32 *d_s = m.dev<u32>(0), *d_o = m.dev<u32>(1);
+    hipError_t er = memcpy_sync(d_s, scalars.data(), n * 32, hipMemcpyHostToDevice);
     int rc = MG_OK;
     if (er == hipSuccess) rc = e->fixed_base_mul((const u32 *)gen, d_s, n, d_o, nullptr);
     out.resize(n * aw);
     if (er == hipSuccess && !rc) er = memcpy_sync(out.data(), d_o, n * aw * 4, hipMemcpyDeviceToHost);
-    if (d_s) hipFree(d_s);
-    if (d_o) hipFree(d_o);
-    if (er != hipSuccess) {
-        set_last_hip_error(er, "groth16_setup", __FILE__, __LINE__);
-        return er == hipErrorOutOfMemory ? MG_ERR_OOM : MG_ERR_HIP;
-    }
-    return rc;
+    return er == hipSuccess ? rc : hip_status(er, "groth16_setup");
 }
 
 int groth16_setup(int curve, const mg_csr *a, const mg_csr *b, const mg_csr *c, u64 m, u64 V, u64 P, const u64 *toxic5,
