@@ -175,13 +175,14 @@ template <class F> struct XYZZ {
     // one asm statement per multiply-add LOST 7 %: the compiler pads every asm statement with an s_nop (~3 400 per loop
     // body). BN254's 9-limb kernel gains the same 3 % (1.55 against 1.60 ms per batched launch). MG_ACC_TWO_CHAINS restores
     // the C coding for re-measurement.
+#ifdef MG_ACC_TWO_CHAINS
+    static constexpr bool THROUGHPUT_CH = false;
+#else
+    static constexpr bool THROUGHPUT_CH = true;
+#endif
     MG_DEV void madd_throughput(const Affine<F> &q, bool neg) {
         if constexpr (!F::EXT && F::LAZY) {
-#ifdef MG_ACC_TWO_CHAINS
-            madd_lazy<false>(q, neg);
-#else
-            madd_lazy<true>(q, neg);
-#endif
+            madd_lazy<THROUGHPUT_CH>(q, neg);
             return;
         }
         madd(q, neg);
@@ -197,13 +198,20 @@ template <class F> struct XYZZ {
     //   U2, S2 < 2;  P = U2 + 9p - X1 < 11;  R = S2 + 5p - Y1 < 7;  PP = P^2: 121 <= LIM;  PPP = P PP: 22;  Q = X1 PP: 16;
     //   X3 = R^2 - PPP - 2Q: R^2 49 <= LIM, value < 2 + 6 = 8 (normalised: it is stored);  T = Q + 9p - X3 < 11;
     //   N = 3p - PPP <= 3;  Y3 = R T + Y1 N: 7*11 + 4*3 = 89 <= LIM, value < 2;  ZZ3, ZZZ3 < 2.
-    template <bool CH = false> MG_DEV void madd_lazy(const Affine<F> &q_in, bool negate) {
+    // The addition in two halves, for callers that want to put work between them (the accumulate kernels fetch the next base record
+    // there: msm_accumulate.h). madd_begin does everything that reads q -- the exceptional cases (q or the accumulator at
+    // infinity, doubling, cancellation: the accumulator is final when it returns false) and U2, S2, P, R, PP of the general case
+    // (returns true: madd_finish then completes X3, Y3, ZZ3, ZZZ3 from the accumulator and the three carried values alone).
+    struct MaddCarry {
+        F P, R, PP;
+    };
+    template <bool CH = false> MG_DEV bool madd_begin(const Affine<F> &q_in, bool negate, MaddCarry &c) {
         static_assert(!F::EXT && F::LAZY, "reduced-radix base field only");
         static_assert(F::BX == 8 && F::BY == 4 && F::BM == 2 && F::LIM >= 121, "bound analysis above");
         // LL: the column accumulators have room for lazy limbs (BLS12-381's 14 x 28 bits); otherwise (BN254's 9 x 29
         // bits) the differences are normalised as before and only the fused product and the cheap zero test remain
         constexpr bool LL = F::LAZY_LIMBS;
-        if (q_in.is_inf()) return;
+        if (q_in.is_inf()) return false;
         F qy = q_in.y;
         if (negate) {
             if constexpr (LL) qy = F::template negl<3>(q_in.y); // 3p - y with lazy limbs: feeds the product S2 only
@@ -214,31 +222,34 @@ template <class F> struct XYZZ {
             y = negate ? F::template neg<2>(q_in.y) : q_in.y; // stored coordinates are normalised
             zz = F::one();
             zzz = F::one();
-            return;
+            return false;
         }
         const F U2 = F::template mul_t<CH>(q_in.x, zz);
         const F S2 = F::template mul_t<CH>(qy, zzz);
-        F P, R;
         if constexpr (LL) {
-            P = F::template subl<9>(U2, x); // < 11p, lazy limbs
-            R = F::template subl<5>(S2, y); // < 7p
+            c.P = F::template subl<9>(U2, x); // < 11p, lazy limbs
+            c.R = F::template subl<5>(S2, y); // < 7p
         } else {
-            P = F::template sub<8>(U2, x); // < 10p
-            R = F::template sub<4>(S2, y); // < 6p
+            c.P = F::template sub<8>(U2, x); // < 10p
+            c.R = F::template sub<4>(S2, y); // < 6p
         }
-        const F PP = F::template sqr_t<CH>(P);
-        if (PP.template is_zero_mod<2>()) { // P = 0 (mod p): same x -- doubling or cancellation (rare; exact)
-            if ((LL ? F::normalize_u(R) : R).template is_zero_mod<7>()) {
+        c.PP = F::template sqr_t<CH>(c.P);
+        if (c.PP.template is_zero_mod<2>()) { // P = 0 (mod p): same x -- doubling or cancellation (rare; exact)
+            if ((LL ? F::normalize_u(c.R) : c.R).template is_zero_mod<7>()) {
                 Affine<F> q{q_in.x, negate ? F::template neg<2>(q_in.y) : q_in.y};
                 *this = dbl_affine(q);
             } else {
                 *this = inf();
             }
-            return;
+            return false;
         }
-        const F PPP = F::template mul_t<CH>(P, PP);
-        const F Q = F::template mul_t<CH>(x, PP);
-        const F X3 = F::template sub2<6>(F::template sqr_t<CH>(R), PPP, Q); // R^2 + 6p - PPP - 2Q < 8p, normalised
+        return true;
+    }
+    template <bool CH = false> MG_DEV void madd_finish(const MaddCarry &c) {
+        constexpr bool LL = F::LAZY_LIMBS;
+        const F PPP = F::template mul_t<CH>(c.P, c.PP);
+        const F Q = F::template mul_t<CH>(x, c.PP);
+        const F X3 = F::template sub2<6>(F::template sqr_t<CH>(c.R), PPP, Q); // R^2 + 6p - PPP - 2Q < 8p, normalised
         F T, N;
         if constexpr (LL) {
             T = F::template subl<9>(Q, X3); // < 11p
@@ -247,11 +258,15 @@ template <class F> struct XYZZ {
             T = F::template sub<8>(Q, X3); // < 10p
             N = F::template neg<2>(PPP);   // 2p - PPP
         }
-        const F Y3 = F::template mul_add_t<CH>(R, T, y, N);
-        zz = F::template mul_t<CH>(zz, PP);
+        const F Y3 = F::template mul_add_t<CH>(c.R, T, y, N);
+        zz = F::template mul_t<CH>(zz, c.PP);
         zzz = F::template mul_t<CH>(zzz, PPP);
         x = X3;
         y = Y3;
+    }
+    template <bool CH = false> MG_DEV void madd_lazy(const Affine<F> &q_in, bool negate) {
+        MaddCarry c;
+        if (madd_begin<CH>(q_in, negate, c)) madd_finish<CH>(c);
     }
     MG_DEV void madd_body(const Affine<F> &q_in, bool negate) {
         if constexpr (!F::EXT && F::LAZY) {

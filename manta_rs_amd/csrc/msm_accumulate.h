@@ -7,13 +7,49 @@ namespace mg {
 // --------------------------------------------------------------------------------------------
 // K7a: chunk accumulate
 // --------------------------------------------------------------------------------------------
-// (179 VGPRs for BLS12-381 G1 -> two wavefronts per SIMD, which already saturates the integer pipe; forcing
-// three through the launch bounds spills and is slower, software-prefetching the gather changes nothing; BN254 G1 needs 130
-// -> three per SIMD, and asking for four -- amdgpu_waves_per_eu(4, 4): 128 VGPRs, two spilled -- changes nothing either)
+// (BLS12-381 G1: 183 VGPRs with the straight loop, 199 with the rotated one, 228 with the fetch ahead, no scratch -> two wavefronts
+// per SIMD in each case, which already saturates the integer pipe; forcing three through the launch bounds spills and is
+// slower; a prefetch into a SECOND register set changed nothing in rounds 4 and 6. BN254 G1 holds 124 -> four per SIMD.)
 // PROBE = true is the measurement twin bench.py's roofline leg runs (kernel timing on): identical but for its first wavefront
 // bracketing its whole run with the shader clock counter (s_memtime) and the constant-rate wall clock -- ticks per wall-clock
 // second = the clock the kernel actually ran at. A template parameter, not a run-time test: the extra live values cost the
 // product kernel six VGPRs when they were an `if`.
+//
+// The loop is ROTATED around the two halves of the mixed addition (ec_dev.h madd_begin / madd_finish). Compile-time switches,
+// measurements in profiles/accumulate_loop_ab.txt and accumulate_loop_before.txt / _after.txt:
+//   MG_ACC_INPLACE (default 1)  the loop leaves through its bottom test only and the run that ends at an `invalid` key is
+//       closed behind the loop. With the early `break` of the straight loop (0) the compiler keeps the accumulator in two
+//       register sets -- a zeroed copy for the exit beside the one the addition works on -- and copies all 52 limbs across
+//       and back in every iteration (171 VALU instructions per addition by the counter). A headline gain only: the kernel is
+//       not shorter when it runs alone.
+//   MG_ACC_BLOCK (default 0: a loss, 219 VGPRs; needs INPLACE)  keys and vals are read four entries at a time (dwordx4) in blocks
+//       aligned on the absolute pair index; the 0-3 entries in front of a chunk's first aligned index and behind its last
+//       full block take the one-dword path.
+//   MG_ACC_AHEAD (default 0: a loss where it counts; needs INPLACE)  the base record of entry j + 1 is gathered BETWEEN the
+//       halves of addition j, into the registers addition j has just finished reading, and the pair of entry j + 2 with it:
+//       no load of an iteration depends on another load of the same iteration. With 0 the same fetches are issued behind
+//       madd_finish and waited for at once. Shorter alone, slower with three MSMs in flight; the suspected cause (not
+//       measured): at 228 VGPRs two resident wavefronts leave a SIMD 56 registers and no tail kernel of a neighbouring MSM
+//       fits beside them.
+//   MG_ACC_SINGLE_ROTATED (default 0: not measured)  the same rotated loop in accumulate_single.
+#ifndef MG_ACC_INPLACE
+#define MG_ACC_INPLACE 1
+#endif
+#ifndef MG_ACC_BLOCK
+#define MG_ACC_BLOCK 0
+#endif
+#ifndef MG_ACC_AHEAD
+#define MG_ACC_AHEAD 0
+#endif
+#ifndef MG_ACC_SINGLE_ROTATED
+#define MG_ACC_SINGLE_ROTATED 0
+#endif
+// accumulate_chunks rotates its loop for BLS12-381 G1 alone, by name: the choice rests on the register counts above. BN254 G1
+// would need 133 VGPRs (152 with the fetch ahead) and lose its fourth wavefront per SIMD, so it keeps the straight loop; a new
+// field gets the straight loop until its own counts are known.
+template <class F> struct AccChunksRotated : std::false_type {};
+template <> struct AccChunksRotated<FpR<Bls381FqCfg>> : std::integral_constant<bool, MG_ACC_INPLACE != 0> {};
+template <class F> constexpr bool acc_chunks_rotated() { return AccChunksRotated<F>::value; }
 #ifdef MG_ACC_WAVES // per translation unit: cap the accumulate kernel's registers for this many wavefronts per SIMD
 #define MG_ACC_ATTR __attribute__((amdgpu_waves_per_eu(MG_ACC_WAVES, MG_ACC_WAVES)))
 #else
@@ -52,23 +88,84 @@ __global__ __launch_bounds__(256) MG_ACC_ATTR void accumulate_chunks(const u32 *
     }
     XYZZ<F> acc = XYZZ<F>::inf();
     bool first = true;
-    for (size_t j = begin; j < end; ++j) {
-        const u32 k = keys[j];
-        if (k != cur) {
-            if (first) {
-                pkeys[2 * t] = cur;
-                acc.store(ppts + (size_t)(2 * t) * XYZZ<F>::WORDS);
-                first = false;
-            } else {
-                acc.store(buckets + (size_t)cur * XYZZ<F>::WORDS);
-            }
-            acc = XYZZ<F>::inf();
-            cur = k;
-            if (k == invalid) break;
+    // a run ends: its sum is the lane's first partial or, from the second run on, the bucket itself (no other lane has a part of it)
+    auto close_run = [&]() {
+        if (first) {
+            pkeys[2 * t] = cur;
+            acc.store(ppts + (size_t)(2 * t) * XYZZ<F>::WORDS);
+            first = false;
+        } else {
+            acc.store(buckets + (size_t)cur * XYZZ<F>::WORDS);
         }
-        const u32 v = vals[j];
-        const Affine<F> p = Affine<F>::load(bases + (size_t)(v & 0x7fffffffu) * astride);
-        acc.madd_throughput(p, (v >> 31) != 0);
+        acc = XYZZ<F>::inf();
+    };
+    if constexpr (acc_chunks_rotated<F>()) {
+        // entry j is (k, v, p); (kn, vn) is the pair of entry j + 1 while there is one. (vals is read for every entry below `end`,
+        // also behind an `invalid` key: in bounds, the sort leaves defined values there, and no record is gathered through them)
+        u32 kn = invalid, vn = 0;
+        [[maybe_unused]] uint4 kb, vb; // MG_ACC_BLOCK: the aligned four-entry block the next pair lies in
+        auto load_block = [&](size_t i) { // i aligned; loads it if the whole block lies inside the chunk
+            if (i + 4 <= end) {
+                kb = *reinterpret_cast<const uint4 *>(keys + i);
+                vb = *reinterpret_cast<const uint4 *>(vals + i);
+            }
+        };
+        auto next_pair = [&](size_t i) { // i < end
+            if constexpr (MG_ACC_BLOCK) {
+                const u32 q = (u32)i & 3u;
+                if (i - q >= begin && i - q + 4 <= end) { // inside a full block: fetched when its first entry is asked for
+                    if (q == 0) load_block(i);
+                    kn = q == 0 ? kb.x : (q == 1 ? kb.y : (q == 2 ? kb.z : kb.w));
+                    vn = q == 0 ? vb.x : (q == 1 ? vb.y : (q == 2 ? vb.z : vb.w));
+                    return;
+                }
+            }
+            kn = keys[i], vn = vals[i]; // head and tail of the chunk, and every entry without MG_ACC_BLOCK
+        };
+        size_t j = begin;
+        u32 k = cur, v = vals[j];
+        Affine<F> p = Affine<F>::load(bases + (size_t)(v & 0x7fffffffu) * astride);
+        if constexpr (MG_ACC_BLOCK)
+            if ((begin & 3) == 0) load_block(begin); // the chunk starts on a block: entries begin + 1 .. + 3 come from it
+        if (j + 1 < end) next_pair(j + 1);
+        bool more;
+        do {
+            if (k != cur) {
+                close_run();
+                cur = k;
+            }
+            typename XYZZ<F>::MaddCarry c;
+            const bool general = acc.template madd_begin<XYZZ<F>::THROUGHPUT_CH>(p, (v >> 31) != 0, c);
+            auto fetch = [&]() { // p is dead: entry j + 1 takes its place, the pair behind it follows
+                ++j;
+                more = j < end && kn != invalid;
+                k = kn;
+                v = vn;
+                if (more) {
+                    p = Affine<F>::load(bases + (size_t)(v & 0x7fffffffu) * astride);
+                    if (j + 1 < end) next_pair(j + 1);
+                }
+            };
+            if constexpr (MG_ACC_AHEAD) fetch();
+            if (general) acc.template madd_finish<XYZZ<F>::THROUGHPUT_CH>(c);
+            if constexpr (!MG_ACC_AHEAD) fetch();
+        } while (more);
+        if (j < end) { // stopped by an `invalid` key: the straight loop's last boundary
+            close_run();
+            cur = invalid;
+        }
+    } else {
+        for (size_t j = begin; j < end; ++j) {
+            const u32 k = keys[j];
+            if (k != cur) {
+                close_run();
+                cur = k;
+                if (k == invalid) break;
+            }
+            const u32 v = vals[j];
+            const Affine<F> p = Affine<F>::load(bases + (size_t)(v & 0x7fffffffu) * astride);
+            acc.madd_throughput(p, (v >> 31) != 0);
+        }
     }
     if (first) { // the whole chunk is one run
         pkeys[2 * t] = cur;
@@ -121,12 +218,37 @@ __global__ __launch_bounds__(256) MG_TAIL_ATTR void accumulate_single(const u32 
     const size_t begin = (size_t)t * L;
     size_t end = begin + L;
     if (end > M) end = M;
-    if (t < T)
+    if constexpr (MG_ACC_SINGLE_ROTATED && MG_ACC_INPLACE && !F::EXT && F::LAZY) { // the rotated loop of accumulate_chunks, without keys
+        if (t < T && begin < end) {
+            size_t j = begin;
+            u32 v = vals[j], vn = 0;
+            Affine<F> p = Affine<F>::load(bases + (size_t)(v & 0x7fffffffu) * astride);
+            if (j + 1 < end) vn = vals[j + 1];
+            bool more;
+            do {
+                typename XYZZ<F>::MaddCarry c;
+                const bool general = acc.template madd_begin<XYZZ<F>::THROUGHPUT_CH>(p, (v >> 31) != 0, c);
+                auto fetch = [&]() {
+                    ++j;
+                    more = j < end;
+                    v = vn;
+                    if (more) {
+                        p = Affine<F>::load(bases + (size_t)(v & 0x7fffffffu) * astride);
+                        if (j + 1 < end) vn = vals[j + 1];
+                    }
+                };
+                if constexpr (MG_ACC_AHEAD) fetch();
+                if (general) acc.template madd_finish<XYZZ<F>::THROUGHPUT_CH>(c);
+                if constexpr (!MG_ACC_AHEAD) fetch();
+            } while (more);
+        }
+    } else if (t < T) {
         for (size_t j = begin; j < end; ++j) {
             const u32 v = vals[j];
             const Affine<F> p = Affine<F>::load(bases + (size_t)(v & 0x7fffffffu) * astride);
             acc.madd_throughput(p, (v >> 31) != 0);
         }
+    }
     if ((size_t)blockIdx.x * blockDim.x * L >= M) { // (uniform) no pair reached this workgroup
         if (threadIdx.x == 0) pkeys[blockIdx.x] = invalid;
         return;
