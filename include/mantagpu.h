@@ -591,6 +591,66 @@ int mg_notes_decrypt(const mg_note_cipher *h, const uint64_t *viewing_key, const
                      const uint64_t *ciphertexts_mont, const uint64_t *tags_mont, size_t n, uint64_t *plaintext_out_mont,
                      uint8_t *ok, uint8_t *status);
 
+/* ---- manta-pay's UTXO statement, one UTXO or one key per GPU lane: commitments, accumulator items, nullifier commitments and
+ *      viewing keys. Replaces, in bulk, `utxo_reconstruct` / `utxo_check` (manta-accounting/src/transfer/utxo/protocol.rs:
+ *      1461-1499), `item_hash` (manta-pay/src/config/utxo.rs:1153-1167), the commitment, record and item of `derive_mint`
+ *      (protocol.rs:1152-1207), the nullifier commitment of `derive_spend` (protocol.rs:1291-1350) and
+ *      `ViewingKeyDerivationFunction::viewing_key` (utxo.rs:523-545). Only MG_BN254; MG_BLS12_381 is MG_ERROR_INVALID_ARGUMENT.
+ *      With H5, H4, H3, H2 the `Hasher`s of utxo-commitment-scheme.dat (width 6, 8 + 56 rounds), utxo-accumulator-item-hash.dat
+ *      (width 5, 8 + 56), nullifier-commitment-scheme.dat (width 4, 8 + 55) and viewing-key-derivation-function.dat (width 3,
+ *      8 + 55), hash = word 0 of the permutation of (tag, inputs):
+ *        UTXO record  = flag | public id | public value | commitment, four Montgomery elements; flag 0 opaque, 1 transparent
+ *        plaintext    = randomness | asset id | asset value, the three elements of the notes calls
+ *        secret asset = the asset when opaque, (0, 0) when transparent; public asset = the reverse (protocol.rs:93-114)
+ *        commitment   = H5 of randomness, secret id, secret value, rk.x, rk.y              (utxo.rs:367-393)
+ *        item         = H4 of flag, public id, public value, commitment                    (utxo.rs:1153-1167)
+ *        nullifier    = H3 of pak.x, pak.y, item                                           (utxo.rs:1465-1485)
+ *        viewing key  = H2 of pak.x, pak.y as an integer mod l (`rem_mod_prime`); receiving key = viewing key * G
+ *      Elements are Montgomery limbs of BN254 Fr, points affine x | y (8 x u64), embedded scalars 4 x u64 canonical below l, as
+ *      in the calls above. Per-lane status: MG_UTXO_BAD_ENCODING for a flag that is not 0 / 1 or an asset value or public value
+ *      word of 2^128 or more (`AssetValue` is a u128 and `is_transparent` a bool by type), else MG_UTXO_MISMATCH (open only);
+ *      a lane that is not MG_UTXO_OK returns zeros in every output of that lane. The nullifier commitments of items already at
+ *      hand need no call of their own: that is the hash call of a width-4 mg_poseidon handle over rows pak.x | pak.y | item.
+ *      Synchronous, thread-safe (a model is immutable host memory; the constants are uploaded per call), on the calling thread's
+ *      setup stream, MG_EDWARDS_CHUNK lanes at a time (device memory of a call < 32 MiB whatever n); n = 0 succeeds. ---------- */
+#define MG_UTXO_OK 0
+#define MG_UTXO_BAD_ENCODING 1
+#define MG_UTXO_MISMATCH 2 /* the rebuilt record differs from the ledger's in a public word or in the commitment */
+typedef struct mg_utxo_file {
+    const uint8_t *bytes;
+    size_t len;
+} mg_utxo_file;
+typedef struct mg_utxo_files { /* manta-parameters' files of the fields of `BaseParameters` (protocol.rs:530-570), each whole */
+    mg_utxo_file utxo_commitment_scheme;
+    mg_utxo_file utxo_accumulator_item_hash;
+    mg_utxo_file nullifier_commitment_scheme;
+    mg_utxo_file viewing_key_derivation_function;
+    mg_utxo_file group_generator; /* 32 bytes, the encoding mg_edwards_decode reads */
+} mg_utxo_files;
+typedef struct mg_utxo_model mg_utxo_model;
+/* Decodes these five files with the manta codec. Host only, no GPU needed: MG_ERROR_INVALID_ARGUMENT, with nothing allocated, for
+ * a length that is not exactly the file's, an element >= r, or a generator that does not decode, is the identity, is off the
+ * curve or outside the subgroup of order l. The fixed-base table of G is built here, once per model. */
+int mg_utxo_model_create(mg_curve_t curve, const mg_utxo_files *files, mg_utxo_model **out);
+void mg_utxo_model_destroy(mg_utxo_model *h);
+/* The sender's side of `derive_mint`: plaintexts hold the whole asset, flags[i] (a byte, 0 / 1) says which half is secret ->
+ * the records (n x 16 u64), their items (n x 4) and status[i] = MG_UTXO_OK / MG_UTXO_BAD_ENCODING. With mg_notes_encrypt this
+ * is `derive_mint` but for the AES light note and the address partition. Every array must be given. */
+int mg_utxos_mint(const mg_utxo_model *h, const uint64_t *recv_keys_affine_mont, const uint64_t *plaintexts_mont,
+                  const uint8_t *flags, size_t n, uint64_t *utxos_out_mont, uint64_t *items_out_mont, uint8_t *status);
+/* The receiver's side: `utxo_check` of n opened notes against the ledger's records for the address viewing_key * G (computed
+ * once per call), the identifier being (the record's flag, the plaintext's randomness); then `item_hash`, and -- when pak (one
+ * affine point on the curve) and nullifiers_out are both given; one without the other is an invalid argument -- the nullifier
+ * commitment. *n_ok (may be NULL) = the number of MG_UTXO_OK lanes. A viewing key >= l or a pak off the curve is
+ * MG_ERROR_INVALID_ARGUMENT before any device work. */
+int mg_utxos_open(const mg_utxo_model *h, const uint64_t *viewing_key, const uint64_t *pak_affine_mont,
+                  const uint64_t *plaintexts_mont, const uint64_t *utxos_mont, size_t n, uint8_t *status, uint64_t *items_out_mont,
+                  uint64_t *nullifiers_out_mont, size_t *n_ok);
+/* n proof authorization keys -> their viewing keys (canonical limbs below l) and, unless NULL, the receiving keys (affine
+ * Montgomery): the account table of a signer. The keys' coordinates must be reduced; they are hashed as given. */
+int mg_viewing_keys(const mg_utxo_model *h, const uint64_t *paks_affine_mont, size_t n, uint64_t *viewing_keys_out,
+                    uint64_t *recv_keys_out_affine_mont);
+
 #ifdef __cplusplus
 }
 #endif

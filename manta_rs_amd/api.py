@@ -76,6 +76,7 @@ EXPORTS = [
     "mg_merkle_tree", "mg_merkle_forest_roots",
     "mg_edwards_decode", "mg_edwards_encode", "mg_edwards_check", "mg_edwards_mul", "mg_edwards_add",
     "mg_note_cipher_create", "mg_note_cipher_destroy", "mg_notes_encrypt", "mg_notes_decrypt",
+    "mg_utxo_model_create", "mg_utxo_model_destroy", "mg_utxos_mint", "mg_utxos_open", "mg_viewing_keys",
 ]
 
 
@@ -1087,6 +1088,88 @@ class NoteCipher:
     def close(self):
         if self._h is not None and self._h.value:
             LIB.mg_note_cipher_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+UTXO_OK, UTXO_BAD_ENCODING, UTXO_MISMATCH = 0, 1, 2
+
+
+class _UtxoFile(ctypes.Structure):
+    _fields_ = [("bytes", ctypes.c_char_p), ("len", ctypes.c_size_t)]
+
+
+class _UtxoFiles(ctypes.Structure):
+    _fields_ = [(name, _UtxoFile) for name in ("utxo_commitment_scheme", "utxo_accumulator_item_hash",
+                                               "nullifier_commitment_scheme", "viewing_key_derivation_function",
+                                               "group_generator")]
+
+
+class UtxoModel:
+    """manta-pay's UTXO statement (manta-accounting/src/transfer/utxo/protocol.rs `derive_mint`, `utxo_check`, `item_hash`,
+    `derive_spend`; manta-pay/src/config/utxo.rs) decoded from manta-parameters' utxo-commitment-scheme.dat,
+    utxo-accumulator-item-hash.dat, nullifier-commitment-scheme.dat, viewing-key-derivation-function.dat and group-generator.dat
+    (the files' bytes). Decoding is host-only; `mint` / `open` / `viewing_keys` run on the GPU, one UTXO or key per lane.
+    Records are [n, 4, 4] (flag | public id | public value | commitment), plaintexts [n, 3, 4] (randomness | asset id | asset
+    value), Montgomery limbs."""
+
+    def __init__(self, utxo_commitment_scheme, utxo_accumulator_item_hash, nullifier_commitment_scheme,
+                 viewing_key_derivation_function, group_generator, curve=BN254):
+        self._h = _vp()
+        self._files = [bytes(b) for b in (utxo_commitment_scheme, utxo_accumulator_item_hash, nullifier_commitment_scheme,
+                                          viewing_key_derivation_function, group_generator)]
+        files = _UtxoFiles(*[_UtxoFile(b, len(b)) for b in self._files])
+        _chk(LIB.mg_utxo_model_create(curve, ctypes.byref(files), ctypes.byref(self._h)), "mg_utxo_model_create")
+
+    def mint(self, recv_keys, plaintexts, flags):
+        """n outputs: recv_keys [n, 8], plaintexts [n, 3, 4] holding the whole asset, flags [n] uint8 (1 = transparent) ->
+        (utxos [n, 4, 4], items [n, 4], status [n] uint8 UTXO_*; zeros where the status is not UTXO_OK) (`mg_utxos_mint`)"""
+        rk, pt = _ed_points(recv_keys), _u64(plaintexts).reshape(-1, 3, 4)
+        fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+        n = rk.shape[0]
+        if pt.shape[0] != n or fl.shape[0] != n:
+            raise ValueError("mint: one key, one plaintext and one flag per UTXO")
+        utxos, items, st = np.zeros((n, 4, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+        _chk(LIB.mg_utxos_mint(self._h, _p(rk), _p(pt), _p(fl), _sz(n), _p(utxos), _p(items), _p(st)), "mg_utxos_mint")
+        return utxos, items, st
+
+    def open(self, viewing_key, plaintexts, utxos, pak=None):
+        """`utxo_check` of n opened notes against the ledger's records for the address viewing_key * G, then the items and --
+        with pak, one affine point -- the nullifier commitments -> (status [n] uint8 UTXO_*, items [n, 4], nullifiers [n, 4] or
+        None, n_ok) (`mg_utxos_open`)"""
+        vk, pt, ut = _u64(viewing_key).reshape(-1), _u64(plaintexts).reshape(-1, 3, 4), _u64(utxos).reshape(-1, 4, 4)
+        n = pt.shape[0]
+        if vk.size != 4 or ut.shape[0] != n:
+            raise ValueError("open: one viewing key; one plaintext and one record per UTXO")
+        if pak is not None:
+            pak = _u64(pak).reshape(-1)
+            if pak.size != 8:
+                raise ValueError("pak: one affine point (8 x u64)")
+        st, items = np.zeros(n, dtype=np.uint8), np.zeros((n, 4), dtype=np.uint64)
+        nul = None if pak is None else np.zeros((n, 4), dtype=np.uint64)
+        n_ok = _sz(0)
+        _chk(LIB.mg_utxos_open(self._h, _p(vk), _p(pak), _p(pt), _p(ut), _sz(n), _p(st), _p(items), _p(nul), ctypes.byref(n_ok)),
+             "mg_utxos_open")
+        return st, items, nul, int(n_ok.value)
+
+    def viewing_keys(self, paks, recv_keys=True):
+        """n proof authorization keys [n, 8] -> (viewing keys [n, 4] canonical limbs below EDWARDS_ORDER, receiving keys [n, 8]
+        or None) (`mg_viewing_keys`)"""
+        pk = _ed_points(paks)
+        n = pk.shape[0]
+        vks = np.zeros((n, 4), dtype=np.uint64)
+        rks = np.zeros((n, 8), dtype=np.uint64) if recv_keys else None
+        _chk(LIB.mg_viewing_keys(self._h, _p(pk), _sz(n), _p(vks), _p(rks)), "mg_viewing_keys")
+        return vks, rks
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            LIB.mg_utxo_model_destroy(self._h)
         self._h = None
 
     def __del__(self):

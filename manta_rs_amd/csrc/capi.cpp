@@ -941,3 +941,47 @@ MG_API int mg_notes_decrypt(const mg_note_cipher *h, const uint64_t *viewing_key
     return notes_decrypt(h, viewing_key, epks_affine_mont, ciphertexts_mont, tags_mont, n, plaintext_out_mont, ok, status);
     MG_CATCH
 }
+
+namespace mg {
+int utxo_model_create(int curve, const uint8_t *const *bytes, const size_t *len, mg_utxo_model **out);
+void utxo_model_destroy(mg_utxo_model *h);
+int utxos_mint(const mg_utxo_model *h, const u64 *recv_keys, const u64 *plaintexts, const uint8_t *flags, size_t n, u64 *utxos_out,
+               u64 *items_out, uint8_t *status);
+int utxos_open(const mg_utxo_model *h, const u64 *viewing_key, const u64 *pak, const u64 *plaintexts, const u64 *utxos, size_t n,
+               uint8_t *status, u64 *items_out, u64 *nullifiers_out, size_t *n_ok);
+int viewing_keys(const mg_utxo_model *h, const u64 *paks, size_t n, u64 *viewing_keys_out, u64 *recv_keys_out);
+} // namespace mg
+MG_API int mg_utxo_model_create(mg_curve_t curve, const mg_utxo_files *files, mg_utxo_model **out) {
+    MG_TRY
+    if (out) *out = nullptr;
+    if (!files) return MG_ERR_ARG;
+    const mg_utxo_file *f[5] = {&files->utxo_commitment_scheme, &files->utxo_accumulator_item_hash,
+                                &files->nullifier_commitment_scheme, &files->viewing_key_derivation_function,
+                                &files->group_generator};
+    const uint8_t *bytes[5];
+    size_t len[5];
+    for (int i = 0; i < 5; ++i) bytes[i] = f[i]->bytes, len[i] = f[i]->len;
+    return utxo_model_create((int)curve, bytes, len, out);
+    MG_CATCH
+}
+MG_API void mg_utxo_model_destroy(mg_utxo_model *h) { utxo_model_destroy(h); }
+MG_API int mg_utxos_mint(const mg_utxo_model *h, const uint64_t *recv_keys_affine_mont, const uint64_t *plaintexts_mont,
+                         const uint8_t *flags, size_t n, uint64_t *utxos_out_mont, uint64_t *items_out_mont, uint8_t *status) {
+    MG_TRY
+    return utxos_mint(h, recv_keys_affine_mont, plaintexts_mont, flags, n, utxos_out_mont, items_out_mont, status);
+    MG_CATCH
+}
+MG_API int mg_utxos_open(const mg_utxo_model *h, const uint64_t *viewing_key, const uint64_t *pak_affine_mont,
+                         const uint64_t *plaintexts_mont, const uint64_t *utxos_mont, size_t n, uint8_t *status,
+                         uint64_t *items_out_mont, uint64_t *nullifiers_out_mont, size_t *n_ok) {
+    MG_TRY
+    return utxos_open(h, viewing_key, pak_affine_mont, plaintexts_mont, utxos_mont, n, status, items_out_mont, nullifiers_out_mont,
+                      n_ok);
+    MG_CATCH
+}
+MG_API int mg_viewing_keys(const mg_utxo_model *h, const uint64_t *paks_affine_mont, size_t n, uint64_t *viewing_keys_out,
+                           uint64_t *recv_keys_out_affine_mont) {
+    MG_TRY
+    return viewing_keys(h, paks_affine_mont, n, viewing_keys_out, recv_keys_out_affine_mont);
+    MG_CATCH
+}

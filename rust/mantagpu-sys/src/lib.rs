@@ -84,6 +84,30 @@ pub const MG_EDWARDS_MUL_PAIRWISE: c_int = 2;
 pub const MG_NOTE_OK: u8 = 0;
 pub const MG_NOTE_BAD_TAG: u8 = 1;
 pub const MG_NOTE_BAD_VALUE: u8 = 2;
+#[repr(C)]
+pub struct mg_utxo_model {
+    _private: [u8; 0],
+}
+/// One parameter file of manta-parameters, whole.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mg_utxo_file {
+    pub bytes: *const u8,
+    pub len: usize,
+}
+/// The five files of `mg_utxo_model_create`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mg_utxo_files {
+    pub utxo_commitment_scheme: mg_utxo_file,
+    pub utxo_accumulator_item_hash: mg_utxo_file,
+    pub nullifier_commitment_scheme: mg_utxo_file,
+    pub viewing_key_derivation_function: mg_utxo_file,
+    pub group_generator: mg_utxo_file,
+}
+pub const MG_UTXO_OK: u8 = 0;
+pub const MG_UTXO_BAD_ENCODING: u8 = 1;
+pub const MG_UTXO_MISMATCH: u8 = 2;
 
 /// `ark_groth16::ProvingKey<E>` as the library reads it (groth16.rs:216-245, field list :253-264).
 #[repr(C)]
@@ -502,5 +526,38 @@ extern "C" {
         plaintext_out_mont: *mut u64,
         ok: *mut u8,
         status: *mut u8,
+    ) -> c_int;
+
+    // ---- the UTXO statement: commitments, items, nullifier commitments, viewing keys (MG_EDWARDS_CHUNK lanes per device pass)
+    pub fn mg_utxo_model_create(curve: mg_curve_t, files: *const mg_utxo_files, out: *mut *mut mg_utxo_model) -> c_int;
+    pub fn mg_utxo_model_destroy(h: *mut mg_utxo_model);
+    pub fn mg_utxos_mint(
+        h: *const mg_utxo_model,
+        recv_keys_affine_mont: *const u64,
+        plaintexts_mont: *const u64,
+        flags: *const u8,
+        n: usize,
+        utxos_out_mont: *mut u64,
+        items_out_mont: *mut u64,
+        status: *mut u8,
+    ) -> c_int;
+    pub fn mg_utxos_open(
+        h: *const mg_utxo_model,
+        viewing_key: *const u64,
+        pak_affine_mont: *const u64,
+        plaintexts_mont: *const u64,
+        utxos_mont: *const u64,
+        n: usize,
+        status: *mut u8,
+        items_out_mont: *mut u64,
+        nullifiers_out_mont: *mut u64,
+        n_ok: *mut usize,
+    ) -> c_int;
+    pub fn mg_viewing_keys(
+        h: *const mg_utxo_model,
+        paks_affine_mont: *const u64,
+        n: usize,
+        viewing_keys_out: *mut u64,
+        recv_keys_out_affine_mont: *mut u64,
     ) -> c_int;
 }
