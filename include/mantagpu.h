@@ -392,6 +392,9 @@ int mg_ctx_create_from_bytes(mg_curve_t curve, const uint8_t *bytes, size_t len,
 int mg_ctx_create_from_bytes_checked(mg_curve_t curve, const uint8_t *bytes, size_t len, const uint8_t checksum[32],
                                      mg_ctx **out);
 int mg_blake3(const uint8_t *data, size_t len, uint8_t out32[32]);
+/* Blake2s-256 (RFC 7693; unkeyed, no salt, no personalisation -- the reference's `Blake2s256::new()`): host code, any length,
+ * compiled from the same source as the hash of the signature kernels below. */
+int mg_blake2s256(const uint8_t *data, size_t len, uint8_t out32[32]);
 /* Once per circuit shape: the matrices of `cs.to_matrices()` (identical for every proof of a shape). Validated
  * in full before anything changes (row_ptr monotone from 0 to nnz, column indices < V); a rejected call leaves
  * the context as it was. */
@@ -650,6 +653,48 @@ int mg_utxos_open(const mg_utxo_model *h, const uint64_t *viewing_key, const uin
  * Montgomery): the account table of a signer. The keys' coordinates must be reduced; they are hashed as given. */
 int mg_viewing_keys(const mg_utxo_model *h, const uint64_t *paks_affine_mont, size_t n, uint64_t *viewing_keys_out,
                     uint64_t *recv_keys_out_affine_mont);
+
+/* ---- Batched Schnorr authorization signatures of manta-pay: the `AuthorizationSignature` of every `TransferPost` that spends
+ *      (manta-crypto/src/signature/mod.rs `schnorr::{sign, verify}`, manta-pay/src/config/utxo.rs `SchnorrHashFunction`,
+ *      manta-accounting/src/transfer/utxo/protocol.rs `signature_scheme()` and `auth::VerifySignature::verify`). The generator
+ *      is `base.group_generator`, the G of the model above: the calls take its handle and need no parameter file of their own
+ *      (schnorr-hash-function.dat is empty). One signature per lane:
+ *        challenge  h = Blake2s-256("manta-pay/1.0.0/Schnorr-hash" | enc(pk) | enc(R) | message) as a little-endian integer,
+ *                   reduced mod l (`from_le_bytes_mod_order`); enc = the 32 bytes mg_edwards_encode writes
+ *        sign       R = k G, pk = sk G, s = k + sk h mod l; the signature is (s, R). Deterministic given the nonce k.
+ *        verify     the ledger's rule: s G == R is refused (MG_SIG_DEGENERATE; it happens exactly when sk h = 0 mod l, e.g.
+ *                   sk = 0), otherwise accepted iff s G == R + h pk
+ *      Points are affine x | y Montgomery (8 x u64), scalars and challenges 4 x u64 canonical below l, as in the calls above.
+ *      Messages cross as n rows of `stride` bytes, row i at messages + i * stride, with lengths[i] <= stride bytes of it the
+ *      message (the rest is never hashed); lengths = NULL: every message is `stride` bytes. stride is a multiple of 4, at
+ *      most MG_SIGNATURE_MAX_MESSAGE; stride = 0 is legal (empty messages; `messages` may then be NULL).
+ *      Per-lane status of a verification, in this order of precedence: MG_SIG_BAD_ENCODING for s >= l (it comes off the wire), a
+ *      coordinate >= p, or pk or R not on the curve -- the subgroup test stays with mg_edwards_decode, whose rejected lanes
+ *      arrive here as (0, 0) and are refused --, MG_SIG_DEGENERATE, MG_SIG_MISMATCH, MG_SIG_OK.
+ *      MG_ERROR_INVALID_ARGUMENT before any device work: a NULL required array, a stride that is not a multiple of 4 or above
+ *      the maximum, a lengths[i] > stride, and for signing a key or nonce >= l (the caller's own secrets). n = 0 succeeds.
+ *      Synchronous, thread-safe, on the calling thread's setup stream, nothing on the NULL stream; the model's table (94.5 KB)
+ *      is uploaded once per call. Lanes per device pass = min(2^16, max(64, 16 MiB / max(stride, 4))): a pass holds at most
+ *      16 MiB of message rows and 16.25 MiB of everything else, so the device memory of a call is < 33 MiB whatever n and
+ *      stride. ------------------------------------------------------------------------------------------------------------- */
+#define MG_SIGNATURE_MAX_MESSAGE (1u << 16)
+#define MG_SIG_OK 0
+#define MG_SIG_BAD_ENCODING 1
+#define MG_SIG_DEGENERATE 2 /* s G == R: refused by `VerifySignature::verify` before the equation is looked at */
+#define MG_SIG_MISMATCH 3
+/* The challenges alone (n x 4 u64). The points are encoded as given: reduced coordinates are the caller's business here. */
+int mg_schnorr_challenges(const mg_utxo_model *h, const uint64_t *pks_affine_mont, const uint64_t *nonce_points_affine_mont,
+                          const uint8_t *messages, size_t stride, const uint32_t *lengths, size_t n, uint64_t *challenges_out);
+/* n signatures (scalars[i], nonce_points[i]) of messages[i] under pks[i] -> status[i] (may be NULL) and *n_ok (may be NULL) =
+ * the number of MG_SIG_OK lanes. Beside mg_groth16_verify_batch a ledger chains mg_edwards_decode -> mg_signatures_verify. */
+int mg_signatures_verify(const mg_utxo_model *h, const uint64_t *pks_affine_mont, const uint64_t *nonce_points_affine_mont,
+                         const uint64_t *scalars, const uint8_t *messages, size_t stride, const uint32_t *lengths, size_t n,
+                         uint8_t *status, size_t *n_ok);
+/* n signatures with the caller's keys and nonces (both < l) -> scalars (n x 4), nonce points (n x 8) and, unless NULL, the
+ * verifying keys sk G (n x 8). */
+int mg_signatures_sign(const mg_utxo_model *h, const uint64_t *signing_keys, const uint64_t *nonces, const uint8_t *messages,
+                       size_t stride, const uint32_t *lengths, size_t n, uint64_t *scalars_out,
+                       uint64_t *nonce_points_out_affine_mont, uint64_t *pks_out_affine_mont);
 
 #ifdef __cplusplus
 }

@@ -77,6 +77,7 @@ EXPORTS = [
     "mg_edwards_decode", "mg_edwards_encode", "mg_edwards_check", "mg_edwards_mul", "mg_edwards_add",
     "mg_note_cipher_create", "mg_note_cipher_destroy", "mg_notes_encrypt", "mg_notes_decrypt",
     "mg_utxo_model_create", "mg_utxo_model_destroy", "mg_utxos_mint", "mg_utxos_open", "mg_viewing_keys",
+    "mg_blake2s256", "mg_schnorr_challenges", "mg_signatures_verify", "mg_signatures_sign",
 ]
 
 
@@ -355,6 +356,13 @@ def blake3(data: bytes) -> bytes:
     """`blake3::hash` (manta-parameters' checksum, lib.rs:173-177), computed by the library's host code"""
     out = ctypes.create_string_buffer(32)
     _chk(LIB.mg_blake3(bytes(data), _sz(len(data)), out), "mg_blake3")
+    return out.raw
+
+
+def blake2s(data: bytes) -> bytes:
+    """Blake2s-256 (RFC 7693, unkeyed), computed by the library's host code from the source the signature kernels compile"""
+    out = ctypes.create_string_buffer(32)
+    _chk(LIB.mg_blake2s256(bytes(data), _sz(len(data)), out), "mg_blake2s256")
     return out.raw
 
 
@@ -1098,6 +1106,20 @@ class NoteCipher:
 
 
 UTXO_OK, UTXO_BAD_ENCODING, UTXO_MISMATCH = 0, 1, 2
+SIGNATURE_MAX_MESSAGE = 1 << 16  # MG_SIGNATURE_MAX_MESSAGE: the largest stride of a message row
+SIG_OK, SIG_BAD_ENCODING, SIG_DEGENERATE, SIG_MISMATCH = 0, 1, 2, 3
+
+
+def _messages(messages, lengths, n):
+    """[n, stride] uint8 rows and optional lengths [n] -> (rows, stride, lengths as uint32 or None)"""
+    msg = np.ascontiguousarray(messages, dtype=np.uint8)
+    if msg.ndim != 2 or msg.shape[0] != n:
+        raise ValueError("messages: one row of `stride` bytes per signature")
+    if lengths is not None:
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32).reshape(-1)
+        if lengths.shape[0] != n:
+            raise ValueError("lengths: one per signature")
+    return msg, msg.shape[1], lengths
 
 
 class _UtxoFile(ctypes.Structure):
@@ -1166,6 +1188,47 @@ class UtxoModel:
         rks = np.zeros((n, 8), dtype=np.uint64) if recv_keys else None
         _chk(LIB.mg_viewing_keys(self._h, _p(pk), _sz(n), _p(vks), _p(rks)), "mg_viewing_keys")
         return vks, rks
+
+    def schnorr_challenges(self, pks, nonce_points, messages, lengths=None):
+        """h = Blake2s-256(tag | enc(pk) | enc(R) | message) mod l of n signatures: pks, nonce_points [n, 8], messages [n, stride]
+        uint8 with optional lengths [n] -> [n, 4] canonical limbs below EDWARDS_ORDER (`mg_schnorr_challenges`)"""
+        pk, rp = _ed_points(pks), _ed_points(nonce_points)
+        n = pk.shape[0]
+        if rp.shape[0] != n:
+            raise ValueError("schnorr_challenges: one key and one nonce point per signature")
+        msg, stride, lens = _messages(messages, lengths, n)
+        out = np.zeros((n, 4), dtype=np.uint64)
+        _chk(LIB.mg_schnorr_challenges(self._h, _p(pk), _p(rp), _p(msg), _sz(stride), _p(lens), _sz(n), _p(out)),
+             "mg_schnorr_challenges")
+        return out
+
+    def verify_signatures(self, pks, nonce_points, scalars, messages, lengths=None):
+        """the ledger's `VerifySignature::verify` of n signatures (scalars [n, 4], nonce_points [n, 8]) under pks [n, 8] ->
+        (status [n] uint8 SIG_*, n_ok) (`mg_signatures_verify`)"""
+        pk, rp, sc = _ed_points(pks), _ed_points(nonce_points), _u64(scalars).reshape(-1, 4)
+        n = pk.shape[0]
+        if rp.shape[0] != n or sc.shape[0] != n:
+            raise ValueError("verify_signatures: one key, one nonce point and one scalar per signature")
+        msg, stride, lens = _messages(messages, lengths, n)
+        st = np.zeros(n, dtype=np.uint8)
+        n_ok = _sz(0)
+        _chk(LIB.mg_signatures_verify(self._h, _p(pk), _p(rp), _p(sc), _p(msg), _sz(stride), _p(lens), _sz(n), _p(st),
+                                      ctypes.byref(n_ok)), "mg_signatures_verify")
+        return st, int(n_ok.value)
+
+    def sign(self, signing_keys, nonces, messages, lengths=None, pks=True):
+        """n signatures with the caller's keys and nonces ([n, 4] canonical limbs below EDWARDS_ORDER) -> (scalars [n, 4], nonce
+        points [n, 8], verifying keys [n, 8] or None) (`mg_signatures_sign`)"""
+        sk, k = _u64(signing_keys).reshape(-1, 4), _u64(nonces).reshape(-1, 4)
+        n = sk.shape[0]
+        if k.shape[0] != n:
+            raise ValueError("sign: one key and one nonce per signature")
+        msg, stride, lens = _messages(messages, lengths, n)
+        s, rp = np.zeros((n, 4), dtype=np.uint64), np.zeros((n, 8), dtype=np.uint64)
+        pk = np.zeros((n, 8), dtype=np.uint64) if pks else None
+        _chk(LIB.mg_signatures_sign(self._h, _p(sk), _p(k), _p(msg), _sz(stride), _p(lens), _sz(n), _p(s), _p(rp), _p(pk)),
+             "mg_signatures_sign")
+        return s, rp, pk
 
     def close(self):
         if self._h is not None and self._h.value:

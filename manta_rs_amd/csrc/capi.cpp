@@ -657,6 +657,17 @@ MG_API int mg_blake3(const uint8_t *data, size_t len, uint8_t out32[32]) {
     return MG_SUCCESS;
     MG_CATCH
 }
+namespace mg {
+void blake2s256(const uint8_t *data, size_t len, uint8_t out[32]);
+}
+MG_API int mg_blake2s256(const uint8_t *data, size_t len, uint8_t out32[32]) {
+    MG_TRY
+    if ((!data && len) || !out32) return MG_ERROR_INVALID_ARGUMENT;
+    static const uint8_t none = 0;
+    blake2s256(data ? data : &none, len, out32);
+    return MG_SUCCESS;
+    MG_CATCH
+}
 MG_API int mg_ctx_create_from_bytes(mg_curve_t curve, const uint8_t *bytes, size_t len, mg_ctx **out);
 MG_API int mg_ctx_create_from_bytes_checked(mg_curve_t curve, const uint8_t *bytes, size_t len, const uint8_t checksum[32],
                                             mg_ctx **out) {
@@ -983,5 +994,36 @@ MG_API int mg_viewing_keys(const mg_utxo_model *h, const uint64_t *paks_affine_m
                            uint64_t *recv_keys_out_affine_mont) {
     MG_TRY
     return viewing_keys(h, paks_affine_mont, n, viewing_keys_out, recv_keys_out_affine_mont);
+    MG_CATCH
+}
+
+namespace mg {
+int schnorr_challenges(const mg_utxo_model *h, const u64 *pks, const u64 *nonce_points, const uint8_t *messages, size_t stride,
+                       const uint32_t *lengths, size_t n, u64 *challenges_out);
+int signatures_verify(const mg_utxo_model *h, const u64 *pks, const u64 *nonce_points, const u64 *scalars, const uint8_t *messages,
+                      size_t stride, const uint32_t *lengths, size_t n, uint8_t *status, size_t *n_ok);
+int signatures_sign(const mg_utxo_model *h, const u64 *signing_keys, const u64 *nonces, const uint8_t *messages, size_t stride,
+                    const uint32_t *lengths, size_t n, u64 *scalars_out, u64 *nonce_points_out, u64 *pks_out);
+} // namespace mg
+MG_API int mg_schnorr_challenges(const mg_utxo_model *h, const uint64_t *pks_affine_mont, const uint64_t *nonce_points_affine_mont,
+                                 const uint8_t *messages, size_t stride, const uint32_t *lengths, size_t n,
+                                 uint64_t *challenges_out) {
+    MG_TRY
+    return schnorr_challenges(h, pks_affine_mont, nonce_points_affine_mont, messages, stride, lengths, n, challenges_out);
+    MG_CATCH
+}
+MG_API int mg_signatures_verify(const mg_utxo_model *h, const uint64_t *pks_affine_mont, const uint64_t *nonce_points_affine_mont,
+                                const uint64_t *scalars, const uint8_t *messages, size_t stride, const uint32_t *lengths, size_t n,
+                                uint8_t *status, size_t *n_ok) {
+    MG_TRY
+    return signatures_verify(h, pks_affine_mont, nonce_points_affine_mont, scalars, messages, stride, lengths, n, status, n_ok);
+    MG_CATCH
+}
+MG_API int mg_signatures_sign(const mg_utxo_model *h, const uint64_t *signing_keys, const uint64_t *nonces, const uint8_t *messages,
+                              size_t stride, const uint32_t *lengths, size_t n, uint64_t *scalars_out,
+                              uint64_t *nonce_points_out_affine_mont, uint64_t *pks_out_affine_mont) {
+    MG_TRY
+    return signatures_sign(h, signing_keys, nonces, messages, stride, lengths, n, scalars_out, nonce_points_out_affine_mont,
+                           pks_out_affine_mont);
     MG_CATCH
 }

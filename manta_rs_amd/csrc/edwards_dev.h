@@ -167,5 +167,19 @@ template <class E> MG_DEV bool fsqrt(const Fp<typename E::Fq> &a, Fp<typename E:
     return F::sqr(x) == a;
 }
 
+// v -= 2^S l where v >= 2^S l, on plain integers
+template <int S, class E = EdBn254> MG_DEV void sub_shifted_l_if_geq(u32 (&v)[8]) {
+    u32 t[8], bw = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const u32 m = (E::L[i] << S) | (S && i ? E::L[i ? i - 1 : 0] >> ((32 - S) & 31) : 0u);
+        const u64 d = (u64)v[i] - m - bw;
+        t[i] = (u32)d;
+        bw = (u32)(d >> 63);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = bw ? v[i] : t[i];
+}
+
 } // namespace ed
 } // namespace mg

@@ -121,6 +121,7 @@ int utxo_model_create(int curve, const uint8_t *const *bytes, const size_t *len,
 }
 
 void utxo_model_destroy(mg_utxo_model *h) { delete h; }
+const u32 *utxo_model_table(const mg_utxo_model *h) { return h->table.data(); }
 
 int utxos_mint(const mg_utxo_model *h, const u64 *recv_keys, const u64 *plaintexts, const uint8_t *flags, size_t n, u64 *utxos_out,
                u64 *items_out, uint8_t *status) {

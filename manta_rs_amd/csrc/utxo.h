@@ -40,3 +40,9 @@ struct UtxoLaunch {
 hipError_t utxo_launch_bn254(const UtxoLaunch &a);
 
 } // namespace mg
+
+struct mg_utxo_model;
+namespace mg {
+// the model's fixed-base table of the generator (edwards.h, ED_TABLE_WORDS words), for the modules that share the handle
+const u32 *utxo_model_table(const mg_utxo_model *h);
+} // namespace mg

@@ -91,20 +91,6 @@ __global__ __launch_bounds__(BLOCK) void open_kernel(const u32 *__restrict__ prm
     status[i] = st;
 }
 
-// v -= 2^S l where v >= 2^S l, on plain integers
-template <int S> MG_DEV void sub_shifted_l_if_geq(u32 (&v)[8]) {
-    u32 t[8], bw = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const u32 m = (E::L[i] << S) | (S && i ? E::L[i ? i - 1 : 0] >> ((32 - S) & 31) : 0u);
-        const u64 d = (u64)v[i] - m - bw;
-        t[i] = (u32)d;
-        bw = (u32)(d >> 63);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = bw ? v[i] : t[i];
-}
-
 // `ViewingKeyDerivationFunction::viewing_key` (utxo.rs:523-545): H2(pak.x, pak.y) as an integer, reduced mod l
 // (`rem_mod_prime`). r < 8 l, so the quotient's three bits are three conditional subtractions of 4 l, 2 l and l.
 __global__ __launch_bounds__(BLOCK) void viewing_keys_kernel(const u32 *__restrict__ prm, const u32 *__restrict__ paks, size_t n,
@@ -113,9 +99,9 @@ __global__ __launch_bounds__(BLOCK) void viewing_keys_kernel(const u32 *__restri
     if (i >= n) return;
     const F in2[2] = {F::load(paks + i * 16), F::load(paks + i * 16 + 8)};
     F v = F::from_mont(hash<3>(prm + UTXO_H2_OFF, UTXO_H2_PARTIAL, in2));
-    sub_shifted_l_if_geq<2>(v.v);
-    sub_shifted_l_if_geq<1>(v.v);
-    sub_shifted_l_if_geq<0>(v.v);
+    ed::sub_shifted_l_if_geq<2>(v.v);
+    ed::sub_shifted_l_if_geq<1>(v.v);
+    ed::sub_shifted_l_if_geq<0>(v.v);
     v.store(scalars + i * 8);
 }
 

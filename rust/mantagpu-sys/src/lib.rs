@@ -108,6 +108,11 @@ pub struct mg_utxo_files {
 pub const MG_UTXO_OK: u8 = 0;
 pub const MG_UTXO_BAD_ENCODING: u8 = 1;
 pub const MG_UTXO_MISMATCH: u8 = 2;
+pub const MG_SIGNATURE_MAX_MESSAGE: usize = 1 << 16;
+pub const MG_SIG_OK: u8 = 0;
+pub const MG_SIG_BAD_ENCODING: u8 = 1;
+pub const MG_SIG_DEGENERATE: u8 = 2;
+pub const MG_SIG_MISMATCH: u8 = 3;
 
 /// `ark_groth16::ProvingKey<E>` as the library reads it (groth16.rs:216-245, field list :253-264).
 #[repr(C)]
@@ -372,6 +377,7 @@ extern "C" {
         out: *mut *mut mg_ctx,
     ) -> c_int;
     pub fn mg_blake3(data: *const u8, len: usize, out32: *mut u8) -> c_int;
+    pub fn mg_blake2s256(data: *const u8, len: usize, out32: *mut u8) -> c_int;
     pub fn mg_ctx_create_from_bytes_sharded(
         curve: mg_curve_t,
         bytes: *const u8,
@@ -559,5 +565,41 @@ extern "C" {
         n: usize,
         viewing_keys_out: *mut u64,
         recv_keys_out_affine_mont: *mut u64,
+    ) -> c_int;
+
+    // ---- Schnorr authorization signatures over the model's generator: messages are n rows of `stride` bytes, lengths may be null
+    pub fn mg_schnorr_challenges(
+        h: *const mg_utxo_model,
+        pks_affine_mont: *const u64,
+        nonce_points_affine_mont: *const u64,
+        messages: *const u8,
+        stride: usize,
+        lengths: *const u32,
+        n: usize,
+        challenges_out: *mut u64,
+    ) -> c_int;
+    pub fn mg_signatures_verify(
+        h: *const mg_utxo_model,
+        pks_affine_mont: *const u64,
+        nonce_points_affine_mont: *const u64,
+        scalars: *const u64,
+        messages: *const u8,
+        stride: usize,
+        lengths: *const u32,
+        n: usize,
+        status: *mut u8,
+        n_ok: *mut usize,
+    ) -> c_int;
+    pub fn mg_signatures_sign(
+        h: *const mg_utxo_model,
+        signing_keys: *const u64,
+        nonces: *const u64,
+        messages: *const u8,
+        stride: usize,
+        lengths: *const u32,
+        n: usize,
+        scalars_out: *mut u64,
+        nonce_points_out_affine_mont: *mut u64,
+        pks_out_affine_mont: *mut u64,
     ) -> c_int;
 }
