@@ -6,6 +6,9 @@
 #include <cstddef>
 #include "prover.h"
 #include "verify.h"
+#include "edwards.h"
+#include "utxo.h"
+#include "schnorr.h"
 #include <cstring>
 #include <new>
 #include <vector>
@@ -657,9 +660,6 @@ MG_API int mg_blake3(const uint8_t *data, size_t len, uint8_t out32[32]) {
     return MG_SUCCESS;
     MG_CATCH
 }
-namespace mg {
-void blake2s256(const uint8_t *data, size_t len, uint8_t out[32]);
-}
 MG_API int mg_blake2s256(const uint8_t *data, size_t len, uint8_t out32[32]) {
     MG_TRY
     if ((!data && len) || !out32) return MG_ERROR_INVALID_ARGUMENT;
@@ -889,19 +889,6 @@ MG_API int mg_merkle_forest_roots(const mg_poseidon *h, unsigned height, const u
     MG_CATCH
 }
 
-namespace mg {
-int edwards_decode(int curve, const uint8_t *bytes, size_t n, int checked, u64 *out, uint8_t *status, size_t *n_bad);
-int edwards_check(int curve, const u64 *affine, size_t n, uint8_t *status, size_t *n_bad);
-int edwards_encode(int curve, const u64 *affine, size_t n, uint8_t *out);
-int edwards_mul(int curve, int mode, const u64 *points, size_t n_points, const u64 *scalars, size_t n_scalars, u64 *out);
-int edwards_add(int curve, const u64 *a_pts, const u64 *b_pts, size_t n, u64 *out);
-int note_cipher_create(int curve, const uint8_t *bytes, size_t len, const u64 *generator, mg_note_cipher **out);
-void note_cipher_destroy(mg_note_cipher *h);
-int notes_encrypt(const mg_note_cipher *h, const u64 *recv_keys, const u64 *randomness, const u64 *plaintexts, size_t n,
-                  u64 *epk_out, u64 *ciphertext_out, u64 *tag_out);
-int notes_decrypt(const mg_note_cipher *h, const u64 *viewing_key, const u64 *epks, const u64 *ciphertexts, const u64 *tags,
-                  size_t n, u64 *plaintext_out, uint8_t *ok, uint8_t *status);
-} // namespace mg
 MG_API int mg_edwards_decode(mg_curve_t curve, const uint8_t *bytes, size_t n, int checked, uint64_t *out_affine_mont,
                              uint8_t *status, size_t *n_bad) {
     MG_TRY
@@ -953,15 +940,6 @@ MG_API int mg_notes_decrypt(const mg_note_cipher *h, const uint64_t *viewing_key
     MG_CATCH
 }
 
-namespace mg {
-int utxo_model_create(int curve, const uint8_t *const *bytes, const size_t *len, mg_utxo_model **out);
-void utxo_model_destroy(mg_utxo_model *h);
-int utxos_mint(const mg_utxo_model *h, const u64 *recv_keys, const u64 *plaintexts, const uint8_t *flags, size_t n, u64 *utxos_out,
-               u64 *items_out, uint8_t *status);
-int utxos_open(const mg_utxo_model *h, const u64 *viewing_key, const u64 *pak, const u64 *plaintexts, const u64 *utxos, size_t n,
-               uint8_t *status, u64 *items_out, u64 *nullifiers_out, size_t *n_ok);
-int viewing_keys(const mg_utxo_model *h, const u64 *paks, size_t n, u64 *viewing_keys_out, u64 *recv_keys_out);
-} // namespace mg
 MG_API int mg_utxo_model_create(mg_curve_t curve, const mg_utxo_files *files, mg_utxo_model **out) {
     MG_TRY
     if (out) *out = nullptr;
@@ -997,14 +975,6 @@ MG_API int mg_viewing_keys(const mg_utxo_model *h, const uint64_t *paks_affine_m
     MG_CATCH
 }
 
-namespace mg {
-int schnorr_challenges(const mg_utxo_model *h, const u64 *pks, const u64 *nonce_points, const uint8_t *messages, size_t stride,
-                       const uint32_t *lengths, size_t n, u64 *challenges_out);
-int signatures_verify(const mg_utxo_model *h, const u64 *pks, const u64 *nonce_points, const u64 *scalars, const uint8_t *messages,
-                      size_t stride, const uint32_t *lengths, size_t n, uint8_t *status, size_t *n_ok);
-int signatures_sign(const mg_utxo_model *h, const u64 *signing_keys, const u64 *nonces, const uint8_t *messages, size_t stride,
-                    const uint32_t *lengths, size_t n, u64 *scalars_out, u64 *nonce_points_out, u64 *pks_out);
-} // namespace mg
 MG_API int mg_schnorr_challenges(const mg_utxo_model *h, const uint64_t *pks_affine_mont, const uint64_t *nonce_points_affine_mont,
                                  const uint8_t *messages, size_t stride, const uint32_t *lengths, size_t n,
                                  uint64_t *challenges_out) {

@@ -7,22 +7,6 @@
 #include <cstring>
 #include <vector>
 
-namespace mg {
-namespace {
-
-using namespace edh; // the host group law, the fixed-base table and the point / scalar checks, shared with utxo.cpp
-
-EdwardsLaunch on_chunk(int op, const Chunk &c) { // the launch of `op` over one chunk; the caller adds the arrays
-    EdwardsLaunch a{};
-    a.op = op;
-    a.n = c.n;
-    a.stream = c.stream;
-    return a;
-}
-
-} // namespace
-} // namespace mg
-
 struct mg_note_cipher {
     std::vector<mg::u32> prm;   // round keys | MDS | initial state, Montgomery words
     std::vector<mg::u32> table; // fixed-base table of the generator
@@ -30,18 +14,15 @@ struct mg_note_cipher {
 
 namespace mg {
 
+using namespace edh; // the host group law, the fixed-base table and the point / scalar checks, shared with utxo.cpp
+
 int edwards_decode(int curve, const uint8_t *bytes, size_t n, int checked, u64 *out, uint8_t *status, size_t *n_bad) {
     if (curve != 0 || (n && (!bytes || !out))) return MG_ERR_ARG;
     std::vector<uint8_t> own;
     status = status_or_own(status, n, own);
     const int rc = run_chunks(EDWARDS_STAGING, n, nullptr, 0, {Span::in(bytes, 32), Span::out(out, 64), Span::out(status, 1)}, 0,
                               [&](const Chunk &c) {
-                                  EdwardsLaunch a = on_chunk(EdwardsLaunch::DECODE, c);
-                                  a.checked = checked != 0;
-                                  a.a = (const u32 *)c.a[0];
-                                  a.out = (u32 *)c.a[1];
-                                  a.status = c.a[2];
-                                  return edwards_launch_bn254(a);
+                                  return ed_decode(c.stream, (const u32 *)c.a[0], c.n, checked != 0, (u32 *)c.a[1], c.a[2]);
                               });
     if (rc == MG_OK && n_bad) *n_bad = count_bad(status, n);
     return rc;
@@ -52,10 +33,7 @@ int edwards_check(int curve, const u64 *affine, size_t n, uint8_t *status, size_
     std::vector<uint8_t> own;
     status = status_or_own(status, n, own);
     const int rc = run_chunks(EDWARDS_STAGING, n, nullptr, 0, {Span::in(affine, 64), Span::out(status, 1)}, 0, [&](const Chunk &c) {
-        EdwardsLaunch a = on_chunk(EdwardsLaunch::CHECK, c);
-        a.a = (const u32 *)c.a[0];
-        a.status = c.a[1];
-        return edwards_launch_bn254(a);
+        return ed_check(c.stream, (const u32 *)c.a[0], c.n, c.a[1]);
     });
     if (rc == MG_OK && n_bad) *n_bad = count_bad(status, n);
     return rc;
@@ -64,10 +42,7 @@ int edwards_check(int curve, const u64 *affine, size_t n, uint8_t *status, size_
 int edwards_encode(int curve, const u64 *affine, size_t n, uint8_t *out) {
     if (curve != 0 || (n && (!affine || !out))) return MG_ERR_ARG;
     return run_chunks(EDWARDS_STAGING, n, nullptr, 0, {Span::in(affine, 64), Span::out(out, 32)}, 0, [&](const Chunk &c) {
-        EdwardsLaunch a = on_chunk(EdwardsLaunch::ENCODE, c);
-        a.a = (const u32 *)c.a[0];
-        a.out = (u32 *)c.a[1];
-        return edwards_launch_bn254(a);
+        return ed_encode(c.stream, (const u32 *)c.a[0], c.n, (u32 *)c.a[1]);
     });
 }
 
@@ -85,12 +60,7 @@ int edwards_mul(int curve, int mode, const u64 *points, size_t n_points, const u
     if (mode == 0) {
         const int top = top_bit(scalars);
         return run_chunks(EDWARDS_STAGING, n, scalars, 32, {Span::in(points, 64), Span::out(out, 64)}, 0, [&](const Chunk &c) {
-            EdwardsLaunch a = on_chunk(EdwardsLaunch::MUL_SHARED, c);
-            a.consts = (const u32 *)c.consts;
-            a.top = top;
-            a.a = (const u32 *)c.a[0];
-            a.out = (u32 *)c.a[1];
-            return edwards_launch_bn254(a);
+            return ed_mul_shared(c.stream, (const u32 *)c.a[0], c.n, (const u32 *)c.consts, top, (u32 *)c.a[1]);
         });
     }
     if (mode == 1) {
@@ -98,20 +68,12 @@ int edwards_mul(int curve, int mode, const u64 *points, size_t n_points, const u
         build_table(points, table);
         return run_chunks(EDWARDS_STAGING, n, table.data(), table.size() * 4, {Span::in(scalars, 32), Span::out(out, 64)}, 0,
                           [&](const Chunk &c) {
-                              EdwardsLaunch a = on_chunk(EdwardsLaunch::MUL_FIXED, c);
-                              a.consts = (const u32 *)c.consts;
-                              a.b = (const u32 *)c.a[0];
-                              a.out = (u32 *)c.a[1];
-                              return edwards_launch_bn254(a);
+                              return ed_mul_fixed(c.stream, (const u32 *)c.consts, (const u32 *)c.a[0], c.n, (u32 *)c.a[1]);
                           });
     }
     return run_chunks(EDWARDS_STAGING, n, nullptr, 0, {Span::in(points, 64), Span::in(scalars, 32), Span::out(out, 64)}, 0,
                       [&](const Chunk &c) {
-                          EdwardsLaunch a = on_chunk(EdwardsLaunch::MUL_PAIRWISE, c);
-                          a.a = (const u32 *)c.a[0];
-                          a.b = (const u32 *)c.a[1];
-                          a.out = (u32 *)c.a[2];
-                          return edwards_launch_bn254(a);
+                          return ed_mul_pairwise(c.stream, (const u32 *)c.a[0], (const u32 *)c.a[1], c.n, (u32 *)c.a[2]);
                       });
 }
 
@@ -119,11 +81,7 @@ int edwards_add(int curve, const u64 *a_pts, const u64 *b_pts, size_t n, u64 *ou
     if (curve != 0 || (n && (!a_pts || !b_pts || !out))) return MG_ERR_ARG;
     return run_chunks(EDWARDS_STAGING, n, nullptr, 0, {Span::in(a_pts, 64), Span::in(b_pts, 64), Span::out(out, 64)}, 0,
                       [&](const Chunk &c) {
-                          EdwardsLaunch a = on_chunk(EdwardsLaunch::ADD, c);
-                          a.a = (const u32 *)c.a[0];
-                          a.b = (const u32 *)c.a[1];
-                          a.out = (u32 *)c.a[2];
-                          return edwards_launch_bn254(a);
+                          return ed_add(c.stream, (const u32 *)c.a[0], (const u32 *)c.a[1], c.n, (u32 *)c.a[2]);
                       });
 }
 
@@ -167,23 +125,13 @@ int notes_encrypt(const mg_note_cipher *h, const u64 *recv_keys, const u64 *rand
                       {Span::in(recv_keys, 64), Span::in(randomness, 32), Span::in(plaintexts, 96), Span::out(epk_out, 64),
                        Span::out(ciphertext_out, 96), Span::out(tag_out, 32)},
                       64, [&](const Chunk &c) {
-                          EdwardsLaunch a = on_chunk(EdwardsLaunch::MUL_FIXED, c); // epk = G * randomness
-                          a.consts = (const u32 *)c.consts + prm_words;
-                          a.b = (const u32 *)c.a[1];
-                          a.out = (u32 *)c.a[3];
-                          hipError_t e = edwards_launch_bn254(a);
+                          const u32 *prm = (const u32 *)c.consts, *table = prm + prm_words, *rand = (const u32 *)c.a[1];
+                          u32 *key = (u32 *)c.scratch;
+                          hipError_t e = ed_mul_fixed(c.stream, table, rand, c.n, (u32 *)c.a[3]); // epk = G * randomness
                           if (e != hipSuccess) return e;
-                          a.op = EdwardsLaunch::MUL_PAIRWISE; // key = recv_key * randomness
-                          a.a = (const u32 *)c.a[0];
-                          a.out = (u32 *)c.scratch;
-                          if ((e = edwards_launch_bn254(a)) != hipSuccess) return e;
-                          a.op = EdwardsLaunch::ENCRYPT;
-                          a.consts = (const u32 *)c.consts;
-                          a.a = (const u32 *)c.scratch;
-                          a.b = (const u32 *)c.a[2];
-                          a.out = (u32 *)c.a[4];
-                          a.out2 = (u32 *)c.a[5];
-                          return edwards_launch_bn254(a);
+                          e = ed_mul_pairwise(c.stream, (const u32 *)c.a[0], rand, c.n, key); // key = recv_key * randomness
+                          if (e != hipSuccess) return e;
+                          return ed_encrypt(c.stream, prm, key, (const u32 *)c.a[2], c.n, (u32 *)c.a[4], (u32 *)c.a[5]);
                       });
 }
 
@@ -202,21 +150,12 @@ int notes_decrypt(const mg_note_cipher *h, const u64 *viewing_key, const u64 *ep
                               {Span::in(epks, 64), Span::in(ciphertexts, 96), Span::in(tags, 32), Span::out(plaintext_out, 96),
                                Span::out(status, 1)},
                               64, [&](const Chunk &c) {
-                                  EdwardsLaunch a = on_chunk(EdwardsLaunch::MUL_SHARED, c); // key = epk * viewing key
-                                  a.consts = (const u32 *)c.consts + prm_words;
-                                  a.top = top;
-                                  a.a = (const u32 *)c.a[0];
-                                  a.out = (u32 *)c.scratch;
-                                  const hipError_t e = edwards_launch_bn254(a);
+                                  const u32 *prm = (const u32 *)c.consts;
+                                  u32 *key = (u32 *)c.scratch; // key = epk * viewing key
+                                  const hipError_t e = ed_mul_shared(c.stream, (const u32 *)c.a[0], c.n, prm + prm_words, top, key);
                                   if (e != hipSuccess) return e;
-                                  a.op = EdwardsLaunch::DECRYPT;
-                                  a.consts = (const u32 *)c.consts;
-                                  a.a = (const u32 *)c.scratch;
-                                  a.b = (const u32 *)c.a[1];
-                                  a.c = (const u32 *)c.a[2];
-                                  a.out = (u32 *)c.a[3];
-                                  a.status = c.a[4];
-                                  return edwards_launch_bn254(a);
+                                  return ed_decrypt(c.stream, prm, key, (const u32 *)c.a[1], (const u32 *)c.a[2], c.n,
+                                                    (u32 *)c.a[3], c.a[4]);
                               });
     if (rc == MG_OK)
         for (size_t i = 0; i < n; ++i) ok[i] = status[i] == NOTE_OK;

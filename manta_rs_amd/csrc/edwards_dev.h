@@ -10,11 +10,28 @@
 // included, needs a branch, and the group law has no data-dependent control flow at all. Doubling is "dbl-2008-hwcd" (4 products
 // and 4 squarings, T of the input unused); a general addition is 9 products and one by d, an addition of an affine point with
 // d x y precomputed (AffineNiels) 8.
+//
+// Below the group law: the per-lane pieces that more than one kernel file runs (encoder, the two per-lane scalar products, the
+// point and value predicates), and the launch shape all of these kernels share.
 #pragma once
 #include "fp_dev.h"
 #include "params_gen.h"
+#include "point_codec.h"
 
 namespace mg {
+
+// fixed-base table: entry [j][m] = m 16^j B as x | y | d x y (affine, Montgomery), j < 63, m < 16: a scalar below 2^252 is 63
+// four-bit digits, its product 63 additions of gathered entries and no doubling
+constexpr int ED_WINDOW_BITS = 4, ED_WINDOWS = 63, ED_TABLE_ENTRIES = ED_WINDOWS << ED_WINDOW_BITS;
+constexpr int ED_TABLE_WORDS = ED_TABLE_ENTRIES * 24;
+
+// One point, note, UTXO or signature per lane: n lanes in blocks of LANE_BLOCK. Nothing is launched for n == 0.
+constexpr int LANE_BLOCK = 256;
+template <class Kernel, class... Args> hipError_t launch_lanes(Kernel kernel, hipStream_t stream, size_t n, Args... args) {
+    if (n == 0) return hipSuccess;
+    kernel<<<dim3((unsigned)((n + LANE_BLOCK - 1) / LANE_BLOCK)), dim3(LANE_BLOCK), 0, stream>>>(args...);
+    return hipGetLastError();
+}
 
 struct EdBn254 {
     typedef Bn254FrCfg Fq; // the base field of the embedded curve = the scalar field of BN254
@@ -123,6 +140,49 @@ template <class E> MG_DEV bool on_curve(const Aff<Fp<typename E::Fq>> &p) {
     return F::add(x2, y2) == F::add(F::one(), F::mul(Curve<E>::d(), F::mul(x2, y2)));
 }
 
+// PT_OK for a point with both coordinates canonical and on the curve, else the PT_* of the first of the two that fails
+template <class E> MG_DEV uint8_t point_status(const Aff<Fp<typename E::Fq>> &p) {
+    const bool bad = codec::geq_p<typename E::Fq>(p.x) || codec::geq_p<typename E::Fq>(p.y);
+    const bool on = on_curve<E>(p);
+    return bad ? PT_BAD_ENCODING : !on ? PT_NOT_ON_CURVE : PT_OK;
+}
+
+// ark-ec 0.3 `GroupAffine: CanonicalSerialize`: the identity (0, 1) is 32 zero bytes; any other point is x, canonical, with
+// bit 255 = (y > -y)
+template <class E> MG_DEV Fp<typename E::Fq> encode(const Aff<Fp<typename E::Fq>> &p) {
+    typedef Fp<typename E::Fq> F;
+    const bool ident = p.x.is_zero() && p.y == F::one();
+    F x = F::from_mont(p.x);
+    if (!ident && codec::is_high<typename E::Fq>(p.y)) x.v[7] |= 0x80000000u;
+    return x;
+}
+
+// k B for k < 2^252 from the table of B (layout above): 63 gathered additions, no doubling
+template <class E> MG_DEV Ext<E> mul_fixed(const u32 *table, const u32 (&k)[8]) {
+    Ext<E> acc = Ext<E>::identity();
+#pragma unroll 1
+    for (int w = 0; w < ED_WINDOWS; ++w) {
+        u32 word = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j == (w >> 3)) word = k[j];
+        const u32 m = (word >> ((w & 7) * 4)) & 15u;
+        acc = Ext<E>::madd(acc, Niels<Fp<typename E::Fq>>::load(table + (size_t)(w * 16 + m) * 24));
+    }
+    return acc;
+}
+
+// k q for k < 2^L_BITS, k different in every lane: double, add always, keep the sum where the lane's bit is set
+template <class E> MG_DEV Ext<E> mul_select(const u32 (&k)[8], const Niels<Fp<typename E::Fq>> &q) {
+    Ext<E> acc = Ext<E>::identity();
+#pragma unroll 1
+    for (int b = E::L_BITS - 1; b >= 0; --b) {
+        acc = Ext<E>::dbl(acc);
+        acc = Ext<E>::select(bit_of(k, b) != 0, Ext<E>::madd(acc, q), acc);
+    }
+    return acc;
+}
+
 // a^SQRT_EXP: a fixed exponent, square-and-multiply from the top
 template <class E> MG_DEV Fp<typename E::Fq> pow_sqrt_exp(const Fp<typename E::Fq> &a) {
     typedef Fp<typename E::Fq> F;
@@ -165,6 +225,13 @@ template <class E> MG_DEV bool fsqrt(const Fp<typename E::Fq> &a, Fp<typename E:
     }
     r = x;
     return F::sqr(x) == a;
+}
+
+// manta-pay's `AssetValue` is a u128 (`try_into_u128`, config/utxo.rs:716-731): a value word (Montgomery) whose integer is
+// 2^128 or more is no asset value
+template <class F> MG_DEV bool fits_u128(const F &mont) {
+    const F v = F::from_mont(mont);
+    return (v.v[4] | v.v[5] | v.v[6] | v.v[7]) == 0;
 }
 
 // v -= 2^S l where v >= 2^S l, on plain integers

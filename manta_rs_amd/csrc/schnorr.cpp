@@ -28,20 +28,12 @@ struct MessageSpans {
         if (stride) rows = (int)arrays.size(), arrays.push_back(Span::in(messages, stride));
         if (lens) lengths = (int)arrays.size(), arrays.push_back(Span::in(lens, 4));
     }
-    void set(SchnorrLaunch &a, const Chunk &c, size_t stride) const {
-        a.messages = rows < 0 ? nullptr : (const u32 *)c.a[rows];
-        a.lengths = lengths < 0 ? nullptr : (const u32 *)c.a[lengths];
-        a.stride = (u32)stride;
+    // the challenges of a chunk: its message rows hashed behind `pks` and `nonce_pts`
+    hipError_t challenge(const Chunk &c, const u32 *pks, const u32 *nonce_pts, size_t stride, u32 *out) const {
+        return schnorr_challenge(c.stream, pks, nonce_pts, rows < 0 ? nullptr : (const u32 *)c.a[rows],
+                                 lengths < 0 ? nullptr : (const u32 *)c.a[lengths], (u32)stride, c.n, out);
     }
 };
-
-SchnorrLaunch on_chunk(int op, const Chunk &c) {
-    SchnorrLaunch a{};
-    a.op = op;
-    a.n = c.n;
-    a.stream = c.stream;
-    return a;
-}
 
 } // namespace
 
@@ -54,12 +46,7 @@ int schnorr_challenges(const mg_utxo_model *h, const u64 *pks, const u64 *nonce_
     MessageSpans ms;
     ms.add(arrays, messages, stride, lengths);
     return run_chunks(Staging{schnorr_lanes_per_pass(stride), false}, n, nullptr, 0, arrays, 0, [&](const Chunk &c) {
-        SchnorrLaunch a = on_chunk(SchnorrLaunch::CHALLENGE, c);
-        a.pks = (const u32 *)c.a[0];
-        a.nonce_pts = (const u32 *)c.a[1];
-        a.challenges = (u32 *)c.a[2];
-        ms.set(a, c, stride);
-        return schnorr_launch_bn254(a);
+        return ms.challenge(c, (const u32 *)c.a[0], (const u32 *)c.a[1], stride, (u32 *)c.a[2]);
     });
 }
 
@@ -75,18 +62,12 @@ int signatures_verify(const mg_utxo_model *h, const u64 *pks, const u64 *nonce_p
     ms.add(arrays, messages, stride, lengths);
     const int rc = run_chunks(Staging{schnorr_lanes_per_pass(stride), false}, n, utxo_model_table(h), (size_t)ED_TABLE_WORDS * 4,
                               arrays, 32, [&](const Chunk &c) {
-                                  SchnorrLaunch a = on_chunk(SchnorrLaunch::CHALLENGE, c);
-                                  a.pks = (const u32 *)c.a[0];
-                                  a.nonce_pts = (const u32 *)c.a[1];
-                                  a.challenges = (u32 *)c.scratch;
-                                  ms.set(a, c, stride);
-                                  const hipError_t e = schnorr_launch_bn254(a);
+                                  const u32 *pks = (const u32 *)c.a[0], *nonce_pts = (const u32 *)c.a[1];
+                                  u32 *challenges = (u32 *)c.scratch;
+                                  const hipError_t e = ms.challenge(c, pks, nonce_pts, stride, challenges);
                                   if (e != hipSuccess) return e;
-                                  a.op = SchnorrLaunch::VERIFY;
-                                  a.table = (const u32 *)c.consts;
-                                  a.scalars = (const u32 *)c.a[2];
-                                  a.status = c.a[3];
-                                  return schnorr_launch_bn254(a);
+                                  return schnorr_verify(c.stream, (const u32 *)c.consts, pks, nonce_pts, (const u32 *)c.a[2],
+                                                        challenges, c.n, c.a[3]);
                               });
     if (rc == MG_OK && n_ok) *n_ok = n - count_bad(status, n);
     return rc;
@@ -106,30 +87,14 @@ int signatures_sign(const mg_utxo_model *h, const u64 *signing_keys, const u64 *
     ms.add(arrays, messages, stride, lengths);
     return run_chunks(Staging{schnorr_lanes_per_pass(stride), false}, n, utxo_model_table(h), (size_t)ED_TABLE_WORDS * 4, arrays,
                       pks_out ? 32 : 96, [&](const Chunk &c) {
+                          const u32 *table = (const u32 *)c.consts, *sk = (const u32 *)c.a[0], *k = (const u32 *)c.a[1];
+                          u32 *nonce_pts = (u32 *)c.a[3], *challenges = (u32 *)c.scratch;
                           u32 *pk = pk_at < 0 ? (u32 *)(c.scratch + c.n * 32) : (u32 *)c.a[pk_at];
-                          EdwardsLaunch m{}; // R = k G, pk = sk G
-                          m.op = EdwardsLaunch::MUL_FIXED;
-                          m.consts = (const u32 *)c.consts;
-                          m.n = c.n;
-                          m.stream = c.stream;
-                          m.b = (const u32 *)c.a[1];
-                          m.out = (u32 *)c.a[3];
-                          hipError_t e = edwards_launch_bn254(m);
+                          hipError_t e = ed_mul_fixed(c.stream, table, k, c.n, nonce_pts); // R = k G
                           if (e != hipSuccess) return e;
-                          m.b = (const u32 *)c.a[0];
-                          m.out = pk;
-                          if ((e = edwards_launch_bn254(m)) != hipSuccess) return e;
-                          SchnorrLaunch a = on_chunk(SchnorrLaunch::CHALLENGE, c);
-                          a.pks = pk;
-                          a.nonce_pts = (const u32 *)c.a[3];
-                          a.challenges = (u32 *)c.scratch;
-                          ms.set(a, c, stride);
-                          if ((e = schnorr_launch_bn254(a)) != hipSuccess) return e;
-                          a.op = SchnorrLaunch::SIGN_FINISH;
-                          a.keys = (const u32 *)c.a[0];
-                          a.scalars = (const u32 *)c.a[1];
-                          a.out = (u32 *)c.a[2];
-                          return schnorr_launch_bn254(a);
+                          if ((e = ed_mul_fixed(c.stream, table, sk, c.n, pk)) != hipSuccess) return e; // pk = sk G
+                          if ((e = ms.challenge(c, pk, nonce_pts, stride, challenges)) != hipSuccess) return e;
+                          return schnorr_sign_finish(c.stream, sk, k, challenges, c.n, (u32 *)c.a[2]);
                       });
 }
 

@@ -1,10 +1,12 @@
 // Batched Schnorr authorization signatures of manta-pay (manta-crypto/src/signature/mod.rs `schnorr`, manta-pay/src/config/
-// utxo.rs `SchnorrHashFunction`, manta-accounting/src/transfer/utxo/protocol.rs `auth::VerifySignature`): the launch interface
-// between the host layer (schnorr.cpp, the C ABI mg_schnorr_challenges / mg_signatures_verify / mg_signatures_sign) and the
-// kernels (schnorr_bn254.hip). One signature per lane.
+// utxo.rs `SchnorrHashFunction`, manta-accounting/src/transfer/utxo/protocol.rs `auth::VerifySignature`): the host layer behind
+// the C ABI mg_schnorr_challenges / mg_signatures_verify / mg_signatures_sign / mg_blake2s256 (schnorr.cpp) and one launch function
+// per kernel (schnorr_bn254.hip). One signature per lane.
 #pragma once
 #include "engine.h"
 #include "fp_dev.h"
+
+struct mg_utxo_model;
 
 namespace mg {
 
@@ -25,23 +27,25 @@ constexpr bool schnorr_sizes_ok(size_t n, size_t stride) {
     return stride % 4 == 0 && stride <= SIGNATURE_MAX_MESSAGE && n <= SIZE_MAX / (stride < 64 ? 64 : stride);
 }
 
-struct SchnorrLaunch {
-    enum Op { CHALLENGE, VERIFY, SIGN_FINISH };
-    int op;
-    const u32 *table;    // VERIFY: the fixed-base table of the generator (edwards.h)
-    const u32 *pks;      // CHALLENGE / VERIFY: verifying keys, affine Montgomery (16 words each)
-    const u32 *nonce_pts; // CHALLENGE / VERIFY: nonce points R
-    const u32 *scalars;  // VERIFY: s; SIGN_FINISH: the nonces k (8 words each, canonical)
-    const u32 *keys;     // SIGN_FINISH: the signing keys
-    const u32 *messages; // CHALLENGE: rows of `stride` bytes (stride a multiple of 4; null when stride is 0)
-    const u32 *lengths;  // CHALLENGE: bytes of each row that are the message, or null: all of `stride`
-    u32 stride;
-    u32 *challenges;     // CHALLENGE: out; VERIFY / SIGN_FINISH: in (8 words each, canonical, below l)
-    u32 *out;            // SIGN_FINISH: s
-    uint8_t *status;     // VERIFY: SIG_*
-    size_t n;
-    hipStream_t stream;
-};
-hipError_t schnorr_launch_bn254(const SchnorrLaunch &a);
+// ---- the kernels: device pointers, n lanes on `s`. Points are affine Montgomery (16 words each); scalars and challenges are 8
+// canonical words each, below l
+// messages: rows of `stride` bytes (stride a multiple of 4; null when stride is 0); lengths: the bytes of each row that are the
+// message, or null: all of `stride`
+hipError_t schnorr_challenge(hipStream_t s, const u32 *pks, const u32 *nonce_pts, const u32 *messages, const u32 *lengths,
+                             u32 stride, size_t n, u32 *challenges);
+// table: the fixed-base table of the generator (edwards_dev.h); scalars: s; status: SIG_*
+hipError_t schnorr_verify(hipStream_t s, const u32 *table, const u32 *pks, const u32 *nonce_pts, const u32 *scalars,
+                          const u32 *challenges, size_t n, uint8_t *status);
+hipError_t schnorr_sign_finish(hipStream_t s, const u32 *signing_keys, const u32 *nonces, const u32 *challenges, size_t n,
+                               u32 *scalars_out);
+
+// ---- the host layer (schnorr.cpp): arrays in the caller's memory, the library's status
+void blake2s256(const uint8_t *data, size_t len, uint8_t out[32]);
+int schnorr_challenges(const mg_utxo_model *h, const u64 *pks, const u64 *nonce_points, const uint8_t *messages, size_t stride,
+                       const uint32_t *lengths, size_t n, u64 *challenges_out);
+int signatures_verify(const mg_utxo_model *h, const u64 *pks, const u64 *nonce_points, const u64 *scalars, const uint8_t *messages,
+                      size_t stride, const uint32_t *lengths, size_t n, uint8_t *status, size_t *n_ok);
+int signatures_sign(const mg_utxo_model *h, const u64 *signing_keys, const u64 *nonces, const uint8_t *messages, size_t stride,
+                    const uint32_t *lengths, size_t n, u64 *scalars_out, u64 *nonce_points_out, u64 *pks_out);
 
 } // namespace mg

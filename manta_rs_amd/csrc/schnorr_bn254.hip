@@ -2,12 +2,11 @@
 // Fp<Bn254FrCfg>. The challenge is h = Blake2s-256("manta-pay/1.0.0/Schnorr-hash" | enc(pk) | enc(R) | message) as a
 // little-endian integer mod l (`SchnorrHashFunction::hash`, `from_le_bytes_mod_order`); verification is the ledger's
 // `auth::VerifySignature::verify` (protocol.rs:1102-1125): s G == R is refused, then s G == R + h pk decides; signing is
-// s = k + sk h mod l (`Schnorr::sign`). Group law: edwards_dev.h; hash: blake2s.h; field helpers of the encoder: point_codec.h.
+// s = k + sk h mod l (`Schnorr::sign`). Group law, encoder and the two scalar products: edwards_dev.h; hash: blake2s.h. Behind
+// each kernel, its launch function (schnorr.h).
 #include "schnorr.h"
 #include "blake2s.h"
-#include "edwards.h"
 #include "edwards_dev.h"
-#include "point_codec.h"
 
 namespace mg {
 namespace schnorr {
@@ -18,21 +17,11 @@ typedef Fp<C> F;
 typedef Fp<EdBn254ScalarCfg> S; // integers mod l
 typedef ed::Ext<E> P;
 typedef ed::Aff<F> A;
-typedef ed::Niels<F> Q;
-constexpr int BLOCK = 256;
 
 // "manta-pay/1.0.0/Schnorr-hash" as little-endian words: 28 bytes, so enc(pk) starts at word 7, enc(R) at word 15, the message
 // at word 23, and the first block ends after the first word of enc(R)
 constexpr int TAG_WORDS = 7, HEAD_WORDS = TAG_WORDS + 16;
 constexpr u32 TAG[TAG_WORDS] = {0x746e616du, 0x61702d61u, 0x2e312f79u, 0x2f302e30u, 0x6e686353u, 0x2d72726fu, 0x68736168u};
-
-// `CanonicalSerialize` of edwards_bn254.hip encode_kernel, in registers
-MG_DEV F encode(const A &p) {
-    const bool ident = p.x.is_zero() && p.y == F::one();
-    F x = F::from_mont(p.x);
-    if (!ident && codec::is_high<C>(p.y)) x.v[7] |= 0x80000000u;
-    return x;
-}
 
 // The stream of one lane for blake2s::digest: the 23 words of tag | enc(pk) | enc(R), then the lane's message row. Word J of
 // block b is a head word in blocks 0 and 1 only, picked by selects over compile-time indices; a message word is loaded only if
@@ -67,13 +56,13 @@ MG_DEV void reduce_mod_l(u32 (&v)[8]) {
     ed::sub_shifted_l_if_geq<0>(v);
 }
 
-__global__ __launch_bounds__(BLOCK) void challenge_kernel(const u32 *__restrict__ pks, const u32 *__restrict__ nonce_pts,
-                                                          const u32 *__restrict__ messages, const u32 *__restrict__ lengths,
-                                                          u32 stride, size_t n, u32 *__restrict__ out) {
+__global__ __launch_bounds__(LANE_BLOCK) void challenge_kernel(const u32 *__restrict__ pks, const u32 *__restrict__ nonce_pts,
+                                                               const u32 *__restrict__ messages, const u32 *__restrict__ lengths,
+                                                               u32 stride, size_t n, u32 *__restrict__ out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Stream s;
-    const F epk = encode(A::load(pks + i * 16)), er = encode(A::load(nonce_pts + i * 16));
+    const F epk = ed::encode<E>(A::load(pks + i * 16)), er = ed::encode<E>(A::load(nonce_pts + i * 16));
 #pragma unroll
     for (int j = 0; j < TAG_WORDS; ++j) s.head[j] = TAG[j];
 #pragma unroll
@@ -101,42 +90,26 @@ MG_DEV bool geq_l(const u32 (&v)[8]) {
 // a == (x : y) of an affine point, a projective: X = x Z and Y = y Z (Z != 0 for whatever the complete law made of curve points)
 MG_DEV bool same_point(const P &a, const F &x, const F &y) { return a.X == F::mul(x, a.Z) && a.Y == F::mul(y, a.Z); }
 
-// A = s G by the 63 gathered additions of mul_fixed_kernel, B = h pk by the double / add-always / select ladder of
-// mul_pairwise_kernel, C = B + R; both comparisons projective, no inversion and no data-dependent branch: a lane that is
-// already refused computes on and is masked where the status is chosen.
-__global__ __launch_bounds__(BLOCK) void verify_kernel(const u32 *__restrict__ table, const u32 *__restrict__ pks,
-                                                       const u32 *__restrict__ nonce_pts, const u32 *__restrict__ scalars,
-                                                       const u32 *__restrict__ challenges, size_t n,
-                                                       uint8_t *__restrict__ status) {
+// A = s G from the generator's table, B = h pk by the select ladder, C = B + R; both comparisons projective, no inversion and no
+// data-dependent branch: a lane that is already refused computes on and is masked where the status is chosen.
+__global__ __launch_bounds__(LANE_BLOCK) void verify_kernel(const u32 *__restrict__ table, const u32 *__restrict__ pks,
+                                                            const u32 *__restrict__ nonce_pts, const u32 *__restrict__ scalars,
+                                                            const u32 *__restrict__ challenges, size_t n,
+                                                            uint8_t *__restrict__ status) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     u32 k[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) k[j] = scalars[i * 8 + j];
     bool bad = geq_l(k);
-    P a = P::identity();
-#pragma unroll 1
-    for (int w = 0; w < ED_WINDOWS; ++w) {
-        u32 word = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (j == (w >> 3)) word = k[j];
-        const u32 m = (word >> ((w & 7) * 4)) & 15u;
-        a = P::madd(a, Q::load(table + (size_t)(w * 16 + m) * 24));
-    }
+    const P a = ed::mul_fixed<E>(table, k);
     const A pk = A::load(pks + i * 16);
-    bad = bad || codec::geq_p<C>(pk.x) || codec::geq_p<C>(pk.y) || !ed::on_curve<E>(pk);
+    bad = bad || ed::point_status<E>(pk) != PT_OK;
 #pragma unroll
     for (int j = 0; j < 8; ++j) k[j] = challenges[i * 8 + j];
-    const Q q = P::niels(pk);
-    P b = P::identity();
-#pragma unroll 1
-    for (int t = E::L_BITS - 1; t >= 0; --t) {
-        b = P::dbl(b);
-        b = P::select(ed::bit_of(k, t) != 0, P::madd(b, q), b);
-    }
+    const P b = ed::mul_select<E>(k, P::niels(pk));
     const A r = A::load(nonce_pts + i * 16);
-    bad = bad || codec::geq_p<C>(r.x) || codec::geq_p<C>(r.y) || !ed::on_curve<E>(r);
+    bad = bad || ed::point_status<E>(r) != PT_OK;
     const P c = P::madd(b, P::niels(r));
     const bool degenerate = same_point(a, r.x, r.y);
     const bool equal = F::mul(a.X, c.Z) == F::mul(c.X, a.Z) && F::mul(a.Y, c.Z) == F::mul(c.Y, a.Z);
@@ -144,8 +117,9 @@ __global__ __launch_bounds__(BLOCK) void verify_kernel(const u32 *__restrict__ t
 }
 
 // s = k + sk h mod l: sk to Montgomery form mod l, one Montgomery product with the plain h, one modular addition
-__global__ __launch_bounds__(BLOCK) void sign_finish_kernel(const u32 *__restrict__ keys, const u32 *__restrict__ nonces,
-                                                            const u32 *__restrict__ challenges, size_t n, u32 *__restrict__ out) {
+__global__ __launch_bounds__(LANE_BLOCK) void sign_finish_kernel(const u32 *__restrict__ keys, const u32 *__restrict__ nonces,
+                                                                 const u32 *__restrict__ challenges, size_t n,
+                                                                 u32 *__restrict__ out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const S skh = S::mul(S::to_mont(S::load(keys + i * 8)), S::load(challenges + i * 8));
@@ -154,25 +128,17 @@ __global__ __launch_bounds__(BLOCK) void sign_finish_kernel(const u32 *__restric
 
 } // namespace schnorr
 
-hipError_t schnorr_launch_bn254(const SchnorrLaunch &a) {
-    if (a.n == 0) return hipSuccess;
-    const dim3 grid((unsigned)((a.n + schnorr::BLOCK - 1) / schnorr::BLOCK)), blk(schnorr::BLOCK);
-    switch (a.op) {
-    case SchnorrLaunch::CHALLENGE:
-        hipLaunchKernelGGL(schnorr::challenge_kernel, grid, blk, 0, a.stream, a.pks, a.nonce_pts, a.messages, a.lengths, a.stride,
-                           a.n, a.challenges);
-        break;
-    case SchnorrLaunch::VERIFY:
-        hipLaunchKernelGGL(schnorr::verify_kernel, grid, blk, 0, a.stream, a.table, a.pks, a.nonce_pts, a.scalars,
-                           (const u32 *)a.challenges, a.n, a.status);
-        break;
-    case SchnorrLaunch::SIGN_FINISH:
-        hipLaunchKernelGGL(schnorr::sign_finish_kernel, grid, blk, 0, a.stream, a.keys, a.scalars, (const u32 *)a.challenges, a.n,
-                           a.out);
-        break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+hipError_t schnorr_challenge(hipStream_t s, const u32 *pks, const u32 *nonce_pts, const u32 *messages, const u32 *lengths,
+                             u32 stride, size_t n, u32 *challenges) {
+    return launch_lanes(schnorr::challenge_kernel, s, n, pks, nonce_pts, messages, lengths, stride, n, challenges);
+}
+hipError_t schnorr_verify(hipStream_t s, const u32 *table, const u32 *pks, const u32 *nonce_pts, const u32 *scalars,
+                          const u32 *challenges, size_t n, uint8_t *status) {
+    return launch_lanes(schnorr::verify_kernel, s, n, table, pks, nonce_pts, scalars, challenges, n, status);
+}
+hipError_t schnorr_sign_finish(hipStream_t s, const u32 *signing_keys, const u32 *nonces, const u32 *challenges, size_t n,
+                               u32 *scalars_out) {
+    return launch_lanes(schnorr::sign_finish_kernel, s, n, signing_keys, nonces, challenges, n, scalars_out);
 }
 
 } // namespace mg

@@ -88,15 +88,6 @@ void fixed_base_mul(const std::vector<u32> &table, const u64 *k, u32 *out) {
     H::mul(acc.Y, zi).store_words(out + 8);
 }
 
-UtxoLaunch on_chunk(int op, const Chunk &c) {
-    UtxoLaunch a{};
-    a.op = op;
-    a.prm = (const u32 *)c.consts;
-    a.n = c.n;
-    a.stream = c.stream;
-    return a;
-}
-
 } // namespace
 
 // spans = the four `Hasher` files in the order of utxo.h, then the generator
@@ -130,14 +121,8 @@ int utxos_mint(const mg_utxo_model *h, const u64 *recv_keys, const u64 *plaintex
                       {Span::in(recv_keys, 64), Span::in(plaintexts, 96), Span::in(flags, 1), Span::out(utxos_out, 128),
                        Span::out(items_out, 32), Span::out(status, 1)},
                       0, [&](const Chunk &c) {
-                          UtxoLaunch a = on_chunk(UtxoLaunch::MINT, c);
-                          a.keys = (const u32 *)c.a[0];
-                          a.plain = (const u32 *)c.a[1];
-                          a.flags = c.a[2];
-                          a.utxos_out = (u32 *)c.a[3];
-                          a.items = (u32 *)c.a[4];
-                          a.status = c.a[5];
-                          return utxo_launch_bn254(a);
+                          return utxo_mint(c.stream, (const u32 *)c.consts, (const u32 *)c.a[0], (const u32 *)c.a[1], c.a[2], c.n,
+                                           (u32 *)c.a[3], (u32 *)c.a[4], c.a[5]);
                       });
 }
 
@@ -156,14 +141,9 @@ int utxos_open(const mg_utxo_model *h, const u64 *viewing_key, const u64 *pak, c
     std::vector<Span> arrays = {Span::in(plaintexts, 96), Span::in(utxos, 128), Span::out(status, 1), Span::out(items_out, 32)};
     if (pak) arrays.push_back(Span::out(nullifiers_out, 32));
     const int rc = run_chunks(EDWARDS_STAGING, n, consts.data(), consts.size() * 4, arrays, 0, [&](const Chunk &c) {
-        UtxoLaunch a = on_chunk(UtxoLaunch::OPEN, c);
-        a.shared = (const u32 *)c.consts + UTXO_PRM_WORDS;
-        a.plain = (const u32 *)c.a[0];
-        a.utxos_in = (const u32 *)c.a[1];
-        a.status = c.a[2];
-        a.items = (u32 *)c.a[3];
-        a.nullifiers = pak ? (u32 *)c.a[4] : nullptr;
-        return utxo_launch_bn254(a);
+        const u32 *prm = (const u32 *)c.consts;
+        return utxo_open(c.stream, prm, prm + UTXO_PRM_WORDS, (const u32 *)c.a[0], (const u32 *)c.a[1], c.n, (u32 *)c.a[3],
+                         pak ? (u32 *)c.a[4] : nullptr, c.a[2]);
     });
     if (rc == MG_OK && n_ok) *n_ok = n - count_bad(status, n);
     return rc;
@@ -178,19 +158,12 @@ int viewing_keys(const mg_utxo_model *h, const u64 *paks, size_t n, u64 *viewing
     std::vector<Span> arrays = {Span::in(paks, 64), Span::out(viewing_keys_out, 32)};
     if (recv_keys_out) arrays.push_back(Span::out(recv_keys_out, 64));
     return run_chunks(EDWARDS_STAGING, n, consts.data(), consts.size() * 4, arrays, 0, [&](const Chunk &c) {
-        UtxoLaunch a = on_chunk(UtxoLaunch::VIEWING_KEYS, c);
-        a.keys = (const u32 *)c.a[0];
-        a.scalars = (u32 *)c.a[1];
-        const hipError_t e = utxo_launch_bn254(a);
+        const u32 *prm = (const u32 *)c.consts;
+        u32 *scalars = (u32 *)c.a[1];
+        const hipError_t e = utxo_viewing_keys(c.stream, prm, (const u32 *)c.a[0], c.n, scalars);
         if (e != hipSuccess || !recv_keys_out) return e;
-        EdwardsLaunch m{}; // receiving key = G * viewing key, from the scalars the kernel above left on the device
-        m.op = EdwardsLaunch::MUL_FIXED;
-        m.consts = (const u32 *)c.consts + UTXO_PRM_WORDS;
-        m.b = (const u32 *)c.a[1];
-        m.out = (u32 *)c.a[2];
-        m.n = c.n;
-        m.stream = c.stream;
-        return edwards_launch_bn254(m);
+        // receiving key = G * viewing key, from the scalars the kernel above left on the device
+        return ed_mul_fixed(c.stream, prm + UTXO_PRM_WORDS, scalars, c.n, (u32 *)c.a[2]);
     });
 }
 

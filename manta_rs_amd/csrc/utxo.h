@@ -1,9 +1,11 @@
-// Batched UTXO derivation of manta-pay (commitments, accumulator items, nullifier commitments, viewing keys): the launch
-// interface between the host layer (utxo.cpp, the C ABI mg_utxo_model_* / mg_utxos_* / mg_viewing_keys) and the kernels
+// Batched UTXO derivation of manta-pay (commitments, accumulator items, nullifier commitments, viewing keys): the host layer
+// behind the C ABI mg_utxo_model_* / mg_utxos_* / mg_viewing_keys (utxo.cpp) and one launch function per kernel
 // (utxo_bn254.hip). One UTXO or one key per lane.
 #pragma once
 #include "engine.h"
 #include "fp_dev.h"
+
+struct mg_utxo_model;
 
 namespace mg {
 
@@ -20,29 +22,26 @@ constexpr int UTXO_H3_OFF = UTXO_H4_OFF + utxo_prm_words(5, UTXO_H4_PARTIAL);
 constexpr int UTXO_H2_OFF = UTXO_H3_OFF + utxo_prm_words(4, UTXO_H3_PARTIAL);
 constexpr int UTXO_PRM_WORDS = UTXO_H2_OFF + utxo_prm_words(3, UTXO_H2_PARTIAL);
 
-struct UtxoLaunch {
-    enum Op { MINT, OPEN, VIEWING_KEYS };
-    int op;
-    const u32 *prm;       // the four hashers
-    const u32 *shared;    // OPEN: the address's receiving key x | y, then (with nullifiers) the authorization key x | y
-    const u32 *keys;      // MINT: receiving keys; VIEWING_KEYS: proof authorization keys (affine, 16 words each)
-    const u32 *plain;     // MINT / OPEN: plaintext blocks randomness | asset id | asset value (24 words each)
-    const uint8_t *flags; // MINT: 0 opaque, 1 transparent
-    const u32 *utxos_in;  // OPEN: the ledger's records flag | public id | public value | commitment (32 words each)
-    u32 *utxos_out;       // MINT: the records
-    u32 *items;           // MINT / OPEN: accumulator items
-    u32 *nullifiers;      // OPEN: nullifier commitments, or null
-    u32 *scalars;         // VIEWING_KEYS: canonical limbs below l (8 words each)
-    uint8_t *status;      // MINT / OPEN: UTXO_*
-    size_t n;
-    hipStream_t stream;
-};
-hipError_t utxo_launch_bn254(const UtxoLaunch &a);
+// ---- the kernels: device pointers, n lanes on `s`. prm: the four hashers; plain: blocks randomness | asset id | asset value
+// (24 words each); a record is flag | public id | public value | commitment (32 words); status: UTXO_*
+// flags: 0 opaque, 1 transparent
+hipError_t utxo_mint(hipStream_t s, const u32 *prm, const u32 *recv_keys, const u32 *plain, const uint8_t *flags, size_t n,
+                     u32 *utxos_out, u32 *items, uint8_t *status);
+// shared: the address's receiving key x | y, then (with nullifiers) the authorization key x | y
+hipError_t utxo_open(hipStream_t s, const u32 *prm, const u32 *shared, const u32 *plain, const u32 *utxos, size_t n, u32 *items,
+                     u32 *nullifiers /* or null */, uint8_t *status);
+// paks: proof authorization keys (affine, 16 words each); scalars: canonical limbs below l (8 words each)
+hipError_t utxo_viewing_keys(hipStream_t s, const u32 *prm, const u32 *paks, size_t n, u32 *scalars);
 
-} // namespace mg
-
-struct mg_utxo_model;
-namespace mg {
-// the model's fixed-base table of the generator (edwards.h, ED_TABLE_WORDS words), for the modules that share the handle
+// ---- the host layer (utxo.cpp): arrays in the caller's memory, the library's status
+int utxo_model_create(int curve, const uint8_t *const *bytes, const size_t *len, mg_utxo_model **out);
+void utxo_model_destroy(mg_utxo_model *h);
+// the model's fixed-base table of the generator (edwards_dev.h, ED_TABLE_WORDS words), for the modules that share the handle
 const u32 *utxo_model_table(const mg_utxo_model *h);
+int utxos_mint(const mg_utxo_model *h, const u64 *recv_keys, const u64 *plaintexts, const uint8_t *flags, size_t n, u64 *utxos_out,
+               u64 *items_out, uint8_t *status);
+int utxos_open(const mg_utxo_model *h, const u64 *viewing_key, const u64 *pak, const u64 *plaintexts, const u64 *utxos, size_t n,
+               uint8_t *status, u64 *items_out, u64 *nullifiers_out, size_t *n_ok);
+int viewing_keys(const mg_utxo_model *h, const u64 *paks, size_t n, u64 *viewing_keys_out, u64 *recv_keys_out);
+
 } // namespace mg
