@@ -60,13 +60,13 @@ __global__ __launch_bounds__(256) void powers_kernel(u32 *__restrict__ out, cons
 // back and written in the arkworks format. Both null inside the witness map, which stays in the work form throughout.
 // the butterfly's product: the single-chain coding of fpr_dev.h (mad_chain_*: every multiply-add of a column in one dependent
 // chain, no 64-bit joins) -- 112 instead of 131 VGPRs in the register kernel (four wavefronts per SIMD) and -10 % on the 2^20
-// transform (profiles/r04_ntt_register_stages.txt); MG_NTT_TWO_CHAINS restores the compiler's coding for re-measurement
+// transform (profiles/r04_ntt_register_stages.txt; the stage-per-round-trip kernel: 82 -> 64 VGPRs, DIF passes -4 %);
+// MG_NTT_TWO_CHAINS restores the compiler's coding for re-measurement
 #ifdef MG_NTT_TWO_CHAINS
 #define MG_NTT_MUL(x, y) R::mul(x, y)
 #else
 #define MG_NTT_MUL(x, y) R::template mul_t<true>(x, y)
 #endif
-#define MG_NTT_MUL_RR(x, y) MG_NTT_MUL(x, y) // (the stage-per-round-trip kernel: 82 -> 64 VGPRs, DIF passes -4 %)
 // The witness map is the head of the chain that bounds a single proof (witness map -> h MSM) and runs beside the accumulate kernels
 // of the other MSMs: its wavefronts ask for issue priority 2 -- above the accumulate kernels (0), below the MSMs' tail kernels (3).
 // Sequential PrivateTransfer proofs, sparse / W / dense, library variants alternating on one box (profiles/r05_single_proof_ab.txt):
@@ -88,134 +88,177 @@ struct NttIo {
     // the work vector between two passes of the public transform (a scratch vector, not the caller's) in the packed 32 B form
     // (FpR::store_packed): bit 0 = this pass reads it, bit 1 = this pass writes it. A strided pass moves two adjacent elements
     // per butterfly column: 64 B = one aligned sector instead of 72 B across two (2^20: passes 77.6 + 101 -> 75 + 97 us)
+    // bit 2 = the tile's twiddles are staged in LDS behind it (ntt_stage_twiddles)
     u32 packed;
 };
+
+// the 48-byte record at index i of a twiddle table: 12 words per entry (three 16-byte loads), nine limbs of them used
+template <class FrC> MG_DEV FpR<FrC> ntt_load_tw(const u32 *__restrict__ tw, size_t i) {
+    static_assert(FpR<FrC>::K == 9, "a twiddle record holds nine limbs");
+    const uint4 *q = reinterpret_cast<const uint4 *>(tw + i * 12);
+    const uint4 q0 = q[0], q1 = q[1], q2 = q[2];
+    FpR<FrC> w;
+    w.v[0] = q0.x, w.v[1] = q0.y, w.v[2] = q0.z, w.v[3] = q0.w, w.v[4] = q1.x, w.v[5] = q1.y, w.v[6] = q1.z, w.v[7] = q1.w, w.v[8] = q2.x;
+    return w;
+}
+// Round 5, single-column tiles (cb = 0: the passes of ONE proof's witness map, a chain of six launches with ~1.5 wavefronts per
+// SIMD): the tile's 2^ns - 1 twiddles -- entry 2^(tl-1) - 1 + jl for local stage tl -- are fetched ONCE, next to the tile, into
+// LDS behind it (limb-major, stride E). Before, every stage waited for its own 48 B gather from a table that the accumulate kernels'
+// GB of table traffic keep out of the L2: eight dependent memory latencies per pass (io.packed bit 2; MANTA_NTT_TWL=0 turns it off).
+template <class FrC>
+MG_DEV void ntt_stage_twiddles(u32 *__restrict__ stw, u32 E, const u32 *__restrict__ tw, unsigned lg, unsigned s0, u32 lo_bits,
+                               u32 lo_base) {
+    for (u32 x = threadIdx.x + 1; x < E; x += blockDim.x) {
+        const unsigned tl = 32u - (unsigned)__clz(x);
+        const unsigned s = s0 + tl - 1;
+        if (s > 1) {
+            const size_t j = ((size_t)(x - (1u << (tl - 1))) << lo_bits) | lo_base;
+            ntt_load_tw<FrC>(tw, j << (lg - s)).store_strided(stw + (x - 1), (int)E);
+        }
+    }
+}
+// One radix-2 butterfly on (a, b) in place, and what a stage of them does to the bound B of the header comment (every value of the
+// tile < B p): the only copy of either, for the LDS stage loop and the register kernel alike. DIT adds 2 (the first stage, w = 1:
+// b < 4p, b' = a + 5p - b: adds 5); DIF doubles B and reduces the sum below 2p whenever 2B would exceed 8 (`red`, uniform per stage).
+// The overflow argument of the header comment rests on these two functions agreeing, which is why there is one of each.
+// lazy (DIT, the register kernel only): the sums a + t and a + 3p - t are left with unnormalised limbs (< 2^31) -- legal wherever
+// they only feed the next stage's product and its normalising additions: 9 x 2^31 x 2^29 + 9 x 2^58 < 2^64 -- which saves the two
+// carry passes (54 of ~330 VALU instructions per butterfly); the subtraction then adds 3p (fpr_dev.h `subl`), one p more than the
+// normalised form: B + 3.
+// (a and b are updated in place, the difference first: returned as a pair of values the compiler merges the w = 1 branch into the
+// general one with selected constants, and ntt_pass_reg<DIT, 2> goes from 116 to 131 VGPRs -- three waves per SIMD instead of four)
+template <bool DIF> MG_DEV bool ntt_stage_reduces(int B) { return DIF && 2 * B > 8; }
+template <bool DIF> MG_DEV int ntt_bound_step(int B, bool has_w, bool lazy) {
+    if (DIF) return ntt_stage_reduces<DIF>(B) ? 2 : 2 * B;
+    return has_w ? B + (lazy ? 3 : 2) : B + 5;
+}
+template <class FrC, bool DIF> MG_DEV void ntt_butterfly(FpR<FrC> &a, FpR<FrC> &b, const FpR<FrC> &w, bool has_w, bool red, bool lazy) {
+    typedef FpR<FrC> R;
+    static_assert(R::LIM >= 64, "bound analysis above: any B <= 27 in the only product");
+    if (DIF) {
+        R x = R::add(a, b);                  // < 2B p
+        R y = R::template sub<9>(a, b);      // a + 9p - b (b < 8p) < (B + 9) p
+        if (has_w) y = MG_NTT_MUL(y, w);     // < 2p
+        else y = R::template reduce<17>(y);  // last DIF stage (w = 1)
+        if (red) x = R::template reduce<16>(x);
+        a = x, b = y;
+    } else if (has_w) {
+        const R t = MG_NTT_MUL(b, w); // < 2p
+        if (lazy) {
+            b = R::template subl<3>(a, t);
+#pragma unroll
+            for (int l = 0; l < R::K; ++l) a.v[l] += t.v[l];
+        } else {
+            b = R::template sub<2>(a, t);
+            a = R::add(a, t);
+        }
+    } else { // first DIT stage (w = 1): b < 4p
+        const R t = b;
+        b = R::template sub<5>(a, t);
+        a = R::add(a, t);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The tile of a pass kernel's workgroup: the E = 2^ns elements that differ only in index bits [lo_bits, lo_bits + ns) for 2^cb
+// adjacent values of the low bits, TOT = E 2^cb elements; element t of the tile is element gi(t) of the vector.
+struct NttTile {
+    u32 E, TOT, lo_bits, lo_base;
+    unsigned cb;
+    size_t base;
+    MG_DEV NttTile(unsigned s0, unsigned ns, unsigned cb_) : E(1u << ns), TOT(E << cb_), lo_bits(s0 - 1), cb(cb_) {
+        const u32 nlo = (1u << lo_bits) >> cb;
+        lo_base = (blockIdx.x % nlo) << cb;
+        base = ((size_t)(blockIdx.x / nlo) << (lo_bits + ns)) + lo_base;
+    }
+    MG_DEV size_t gi(u32 t) const { return base + ((size_t)(t >> cb) << lo_bits) + (t & ((1u << cb) - 1)); }
+};
+// where tile element t lives in LDS (limb-major): at t with stride TOT, or -- the register kernel -- with one pad word per 32
+template <bool PAD> MG_DEV u32 ntt_lds_at(u32 t) { return PAD ? t + (t >> 5) : t; }
+// HBM -> LDS, every input option: the arkworks-format input gathered at the bit-reversed index, the packed form, the work form
+template <class FrC, bool PAD>
+MG_DEV void ntt_tile_fill(u32 *__restrict__ sm, u32 stride, const NttTile &T, const u32 *__restrict__ data, unsigned lg, const NttIo &io) {
+    typedef FpR<FrC> R;
+    for (u32 t = threadIdx.x; t < T.TOT; t += blockDim.x) {
+        const size_t gi = T.gi(t);
+        R r;
+        if (io.in_std) { // arkworks format at the bit-reversed index -> work form (< 2p)
+            const u32 j = __brev((u32)gi) >> (32 - lg);
+            r = R::from_std_shift(Fp<FrC>::load(io.in_std + (size_t)j * 8));
+            if (io.pre_rr) r = R::mul(r, R::load(io.pre_rr + (size_t)j * R::K));
+        } else if (io.packed & 1u) {
+            r = R::load_packed(data + gi * 8);
+        } else {
+            r = R::load(data + gi * R::K);
+        }
+        r.store_strided(sm + ntt_lds_at<PAD>(t), (int)stride);
+    }
+}
+// LDS -> HBM, every output option: times post[i], or the pass's final reduce; then the arkworks format, the packed form, the work form
+template <class FrC, bool DIF, bool PAD>
+MG_DEV void ntt_tile_drain(const u32 *__restrict__ sm, u32 stride, const NttTile &T, u32 *__restrict__ data, const u32 *__restrict__ post,
+                           const NttIo &io, int B) {
+    typedef FpR<FrC> R;
+    for (u32 t = threadIdx.x; t < T.TOT; t += blockDim.x) {
+        const size_t gi = T.gi(t);
+        R v = R::load_strided(sm + ntt_lds_at<PAD>(t), (int)stride);
+        if (post) v = R::mul(v, R::load(post + gi * R::K)); // any B <= 27 times a canonical table entry: < 2p
+        else if (DIF ? B > 4 : true) v = R::template reduce<32>(v);
+        if (io.out_std) { // work form (< 4p) -> arkworks format, times the constant of the plain inverse transform first
+            if (io.scale_rr) v = R::mul(v, R::load(io.scale_rr));
+            v.to_std().store(io.out_std + gi * 8);
+        } else if (io.packed & 2u) { // (v < 2p and normalised: a product or a reduce made it)
+            v.store_packed(data + gi * 8);
+        } else {
+            v.store(data + gi * R::K);
+        }
+    }
+}
+// the stages of a pass, one LDS round trip and one barrier each, over a tile already in LDS (limb-major, stride E 2^cb): local stages
+// 1 .. ns = global stages s0 .. s0 + ns - 1, ascending (DIT) or descending (DIF). stw: the tile's twiddles in LDS (ntt_stage_twiddles)
+// or null: each butterfly gathers its own from the table.
+template <class FrC, bool DIF>
+MG_DEV void ntt_tile_stages(u32 *__restrict__ sm, u32 E, unsigned ns, unsigned s0, unsigned lg, u32 lo_bits, u32 lo_base, unsigned cb,
+                            const u32 *__restrict__ tw, const u32 *__restrict__ stw, int &B, u32 tid, u32 nthr) {
+    typedef FpR<FrC> R;
+    const u32 TOT = E << cb, CM = (1u << cb) - 1;
+    for (unsigned st = 0; st < ns; ++st) {
+        const unsigned tl = DIF ? ns - st : st + 1; // local stage 1..ns
+        const unsigned s = s0 + tl - 1;             // global stage
+        const u32 half = 1u << (tl - 1);
+        const bool has_w = s > 1;
+        const bool red = ntt_stage_reduces<DIF>(B); // uniform
+        for (u32 k = tid; k < TOT / 2; k += nthr) {
+            const u32 c = k & CM, kk = k >> cb;
+            const u32 jl = kk & (half - 1), g = kk >> (tl - 1);
+            const u32 i0 = (((g << tl) | jl) << cb) + c, i1 = i0 + (half << cb);
+            R a = R::load_strided(sm + i0, (int)TOT), b = R::load_strided(sm + i1, (int)TOT);
+            R w;
+            if (has_w && stw) w = R::load_strided(stw + (half - 1 + jl), (int)E);
+            else if (has_w) w = ntt_load_tw<FrC>(tw, (((size_t)jl << lo_bits) | (lo_base + c)) << (lg - s));
+            ntt_butterfly<FrC, DIF>(a, b, w, has_w, red, false);
+            a.store_strided(sm + i0, (int)TOT), b.store_strided(sm + i1, (int)TOT);
+        }
+        B = ntt_bound_step<DIF>(B, has_w, false);
+        __syncthreads();
+    }
+}
 template <class FrC, bool DIF>
 __global__ __launch_bounds__(1024) void ntt_pass_rr(u32 *__restrict__ d0, u32 *__restrict__ d1, u32 *__restrict__ d2,
                                                    const u32 *__restrict__ tw, unsigned lg, unsigned s0, unsigned ns,
                                                    unsigned cb, const u32 *__restrict__ post, NttIo io) {
     MG_PRIO_WM();
     extern __shared__ __attribute__((aligned(16))) u32 sm[];
-    typedef FpR<FrC> R;
-    constexpr int K = R::K;
-    static_assert(K == 9 && R::LIM >= 64, "bound analysis above");
+    constexpr int K = FpR<FrC>::K;
     u32 *__restrict__ data = (blockIdx.y == 0 ? d0 : (blockIdx.y == 1 ? d1 : d2)) + ((size_t)blockIdx.z << lg) * K;
-    const u32 E = 1u << ns, TOT = E << cb, CM = (1u << cb) - 1;
-    const u32 lo_bits = s0 - 1;
-    const u32 nlo = (1u << lo_bits) >> cb;
-    const u32 lo_base = (blockIdx.x % nlo) << cb, hi = blockIdx.x / nlo;
-    const size_t base = ((size_t)hi << (lo_bits + ns)) + lo_base;
-    // Round 5, single-column tiles (cb = 0: the passes of ONE proof's witness map, a chain of six launches with ~1.5 wavefronts per
-    // SIMD): the tile's 2^ns - 1 twiddles -- entry 2^(tl-1) - 1 + jl for local stage tl -- are fetched ONCE, next to the tile, into
-    // LDS behind it. Before, every stage waited for its own 48 B gather from a table that the accumulate kernels' GB of table
-    // traffic keep out of the L2: eight dependent memory latencies per pass (io.packed bit 2; MANTA_NTT_TWL=0 turns it off).
-    const bool twl = (io.packed & 4u) != 0;
-    u32 *__restrict__ stw = sm + (size_t)K * TOT;
-    if (twl) {
-        for (u32 x = threadIdx.x + 1; x < E; x += blockDim.x) {
-            const unsigned tl = 32u - (unsigned)__clz(x);
-            const unsigned s = s0 + tl - 1;
-            if (s > 1) {
-                const size_t j = ((size_t)(x - (1u << (tl - 1))) << lo_bits) | lo_base;
-                const uint4 *q = reinterpret_cast<const uint4 *>(tw + (j << (lg - s)) * 12);
-                const uint4 q0 = q[0], q1 = q[1], q2 = q[2];
-                u32 *o = stw + (x - 1);
-                o[0 * E] = q0.x, o[1 * E] = q0.y, o[2 * E] = q0.z, o[3 * E] = q0.w, o[4 * E] = q1.x, o[5 * E] = q1.y, o[6 * E] = q1.z,
-                o[7 * E] = q1.w, o[8 * E] = q2.x;
-            }
-        }
-    }
-    for (u32 t = threadIdx.x; t < TOT; t += blockDim.x) {
-        const size_t gi = base + ((size_t)(t >> cb) << lo_bits) + (t & CM);
-        if (io.in_std) { // arkworks format at the bit-reversed index -> work form (< 2p)
-            const u32 j = __brev((u32)gi) >> (32 - lg);
-            R r = R::from_std_shift(Fp<FrC>::load(io.in_std + (size_t)j * 8));
-            if (io.pre_rr) r = R::mul(r, R::load(io.pre_rr + (size_t)j * K));
-#pragma unroll
-            for (int l = 0; l < K; ++l) sm[l * TOT + t] = r.v[l];
-            continue;
-        }
-        if (io.packed & 1u) {
-            const R r = R::load_packed(data + gi * 8);
-#pragma unroll
-            for (int l = 0; l < K; ++l) sm[l * TOT + t] = r.v[l];
-            continue;
-        }
-        const u32 *p = data + gi * K;
-#pragma unroll
-        for (int l = 0; l < K; ++l) sm[l * TOT + t] = p[l];
-    }
+    const NttTile T(s0, ns, cb);
+    u32 *__restrict__ stw = (io.packed & 4u) ? sm + (size_t)K * T.TOT : nullptr;
+    if (stw) ntt_stage_twiddles<FrC>(stw, T.E, tw, lg, s0, T.lo_bits, T.lo_base);
+    ntt_tile_fill<FrC, false>(sm, T.TOT, T, data, lg, io);
     __syncthreads();
     int B = 4; // every value in the tile is < B*p
-    for (unsigned st = 0; st < ns; ++st) {
-        const unsigned tl = DIF ? ns - st : st + 1; // local stage 1..ns
-        const unsigned s = s0 + tl - 1;             // global stage
-        const u32 half = 1u << (tl - 1);
-        const bool has_w = s > 1;
-        const bool red = DIF && 2 * B > 8; // uniform
-        for (u32 k = threadIdx.x; k < TOT / 2; k += blockDim.x) {
-            const u32 c = k & CM, kk = k >> cb;
-            const u32 jl = kk & (half - 1), g = kk >> (tl - 1);
-            const u32 i0 = ((((g << tl) | jl)) << cb) + c, i1 = i0 + (half << cb);
-            R a, b;
-#pragma unroll
-            for (int l = 0; l < K; ++l) a.v[l] = sm[l * TOT + i0], b.v[l] = sm[l * TOT + i1];
-            R w;
-            if (has_w && twl) {
-                const u32 *o = stw + (half - 1 + jl);
-#pragma unroll
-                for (int l = 0; l < K; ++l) w.v[l] = o[l * E];
-            } else if (has_w) {
-                const size_t j = ((size_t)jl << lo_bits) | (lo_base + c);
-                const uint4 *q = reinterpret_cast<const uint4 *>(tw + (j << (lg - s)) * 12); // 48 B records
-                const uint4 q0 = q[0], q1 = q[1], q2 = q[2];
-                w.v[0] = q0.x, w.v[1] = q0.y, w.v[2] = q0.z, w.v[3] = q0.w, w.v[4] = q1.x, w.v[5] = q1.y, w.v[6] = q1.z,
-                w.v[7] = q1.w, w.v[8] = q2.x;
-            }
-            R x, y;
-            if (DIF) {
-                x = R::add(a, b);                    // < 2B p
-                y = R::template sub<9>(a, b);        // a + 9p - b (b < 8p) < (B + 9) p
-                if (has_w) y = MG_NTT_MUL_RR(y, w);  // < 2p
-                else y = R::template reduce<17>(y);  // last DIF stage (w = 1)
-                if (red) x = R::template reduce<16>(x);
-            } else {
-                if (has_w) {
-                    b = MG_NTT_MUL_RR(b, w); // < 2p
-                    x = R::add(a, b);
-                    y = R::template sub<2>(a, b);
-                } else { // first DIT stage (w = 1): b < 4p
-                    x = R::add(a, b);
-                    y = R::template sub<5>(a, b);
-                }
-            }
-#pragma unroll
-            for (int l = 0; l < K; ++l) sm[l * TOT + i0] = x.v[l], sm[l * TOT + i1] = y.v[l];
-        }
-        if (DIF) B = red ? 2 : 2 * B;
-        else B = has_w ? B + 2 : B + 5;
-        __syncthreads();
-    }
-    for (u32 t = threadIdx.x; t < TOT; t += blockDim.x) {
-        const size_t gi = base + ((size_t)(t >> cb) << lo_bits) + (t & CM);
-        R v;
-#pragma unroll
-        for (int l = 0; l < K; ++l) v.v[l] = sm[l * TOT + t];
-        if (post) v = R::mul(v, R::load(post + gi * K)); // any B <= 27 times a canonical table entry: < 2p
-        else if (DIF ? B > 4 : true) v = R::template reduce<32>(v);
-        if (io.out_std) { // work form (< 4p) -> arkworks format, times the constant of the plain inverse transform first
-            if (io.scale_rr) v = R::mul(v, R::load(io.scale_rr));
-            v.to_std().store(io.out_std + gi * 8);
-            continue;
-        }
-        if (io.packed & 2u) { // (v < 2p and normalised: a product or a reduce made it)
-            v.store_packed(data + gi * 8);
-            continue;
-        }
-        u32 *p = data + gi * K;
-#pragma unroll
-        for (int l = 0; l < K; ++l) p[l] = v.v[l];
-    }
+    ntt_tile_stages<FrC, DIF>(sm, T.E, ns, s0, lg, T.lo_bits, T.lo_base, cb, tw, stw, B, threadIdx.x, blockDim.x);
+    ntt_tile_drain<FrC, DIF, false>(sm, T.TOT, T, data, post, io, B);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -223,58 +266,7 @@ __global__ __launch_bounds__(1024) void ntt_pass_rr(u32 *__restrict__ d0, u32 *_
 // transform and the low pass of the forward coset transform that follows it work on the SAME contiguous tile, and so do the high pass
 // of the forward transform, the pointwise step and the high pass of the last inverse transform on the same strided tile: 7 launches
 // (2 + 2 + pointwise + 2) become 4, three LDS fill / drain pairs and three trips through HBM of a | b | c go away -- on a chain whose
-// every launch is latency (six launches of 30-45 us at ~1.5 wavefronts per SIMD).
-// ntt_tile_stages = the stage loop of ntt_pass_rr at cb = 0 over one tile already in LDS (limb-major, stride E).
-template <class FrC, bool DIF>
-MG_DEV void ntt_tile_stages(u32 *__restrict__ sm, u32 E, unsigned ns, unsigned s0, unsigned lg, u32 lo_bits, u32 lo_base,
-                            const u32 *__restrict__ tw, int &B, u32 tid, u32 nthr) {
-    typedef FpR<FrC> R;
-    constexpr int K = R::K;
-    for (unsigned st = 0; st < ns; ++st) {
-        const unsigned tl = DIF ? ns - st : st + 1; // local stage 1..ns
-        const unsigned s = s0 + tl - 1;             // global stage
-        const u32 half = 1u << (tl - 1);
-        const bool has_w = s > 1;
-        const bool red = DIF && 2 * B > 8; // uniform
-        for (u32 k = tid; k < E / 2; k += nthr) {
-            const u32 jl = k & (half - 1), g = k >> (tl - 1);
-            const u32 i0 = (g << tl) | jl, i1 = i0 + half;
-            R a, b;
-#pragma unroll
-            for (int l = 0; l < K; ++l) a.v[l] = sm[l * E + i0], b.v[l] = sm[l * E + i1];
-            R w;
-            if (has_w) {
-                const size_t j = ((size_t)jl << lo_bits) | lo_base;
-                const uint4 *q = reinterpret_cast<const uint4 *>(tw + (j << (lg - s)) * 12); // 48 B records
-                const uint4 q0 = q[0], q1 = q[1], q2 = q[2];
-                w.v[0] = q0.x, w.v[1] = q0.y, w.v[2] = q0.z, w.v[3] = q0.w, w.v[4] = q1.x, w.v[5] = q1.y, w.v[6] = q1.z,
-                w.v[7] = q1.w, w.v[8] = q2.x;
-            }
-            R x, y;
-            if (DIF) {
-                x = R::add(a, b);                    // < 2B p
-                y = R::template sub<9>(a, b);        // a + 9p - b (b < 8p)
-                if (has_w) y = MG_NTT_MUL_RR(y, w);  // < 2p
-                else y = R::template reduce<17>(y);  // last DIF stage (w = 1)
-                if (red) x = R::template reduce<16>(x);
-            } else {
-                if (has_w) {
-                    b = MG_NTT_MUL_RR(b, w); // < 2p
-                    x = R::add(a, b);
-                    y = R::template sub<2>(a, b);
-                } else { // first DIT stage (w = 1): b < 4p
-                    x = R::add(a, b);
-                    y = R::template sub<5>(a, b);
-                }
-            }
-#pragma unroll
-            for (int l = 0; l < K; ++l) sm[l * E + i0] = x.v[l], sm[l * E + i1] = y.v[l];
-        }
-        if (DIF) B = red ? 2 : 2 * B;
-        else B = has_w ? B + 2 : B + 5;
-        __syncthreads();
-    }
-}
+// every launch is latency (six launches of 30-45 us at ~1.5 wavefronts per SIMD). Both run ntt_tile_stages at cb = 0, twiddles gathered.
 // low pass of the inverse transform (DIF stages ns .. 1, then the table `post`) + low pass of the forward transform (DIT stages 1 .. ns)
 // on one contiguous tile of 2^ns elements; grid (n >> ns, vectors, batch), E / 2 threads
 template <class FrC>
@@ -285,38 +277,20 @@ __global__ __launch_bounds__(512) void ntt_fused_low(u32 *__restrict__ d0, u32 *
     extern __shared__ __attribute__((aligned(16))) u32 sm[];
     typedef FpR<FrC> R;
     constexpr int K = R::K;
-    static_assert(K == 9 && R::LIM >= 64, "bound analysis of ntt_pass_rr");
     u32 *__restrict__ data = (blockIdx.y == 0 ? d0 : (blockIdx.y == 1 ? d1 : d2)) + ((size_t)blockIdx.z << lg) * K;
     const u32 E = 1u << ns;
     const size_t base = (size_t)blockIdx.x << ns;
-    for (u32 t = threadIdx.x; t < E; t += blockDim.x) {
-        const u32 *p = data + (base + t) * K;
-#pragma unroll
-        for (int l = 0; l < K; ++l) sm[l * E + t] = p[l];
-    }
+    for (u32 t = threadIdx.x; t < E; t += blockDim.x) R::load(data + (base + t) * K).store_strided(sm + t, (int)E);
     __syncthreads();
     int B = 4; // every value of the tile is < B p (the high pass left < 4p)
-    ntt_tile_stages<FrC, true>(sm, E, ns, 1, lg, 0, 0, tw_inv, B, threadIdx.x, blockDim.x);
-    for (u32 t = threadIdx.x; t < E; t += blockDim.x) { // n^-1 g^bitrev(i): any B <= 27 times a canonical entry -> < 2p
-        R v;
-#pragma unroll
-        for (int l = 0; l < K; ++l) v.v[l] = sm[l * E + t];
-        v = R::mul(v, R::load(post + (base + t) * K));
-#pragma unroll
-        for (int l = 0; l < K; ++l) sm[l * E + t] = v.v[l];
-    }
+    ntt_tile_stages<FrC, true>(sm, E, ns, 1, lg, 0, 0, 0, tw_inv, nullptr, B, threadIdx.x, blockDim.x);
+    for (u32 t = threadIdx.x; t < E; t += blockDim.x) // n^-1 g^bitrev(i): any B <= 27 times a canonical entry -> < 2p
+        R::mul(R::load_strided(sm + t, (int)E), R::load(post + (base + t) * K)).store_strided(sm + t, (int)E);
     __syncthreads();
     B = 2;
-    ntt_tile_stages<FrC, false>(sm, E, ns, 1, lg, 0, 0, tw_fwd, B, threadIdx.x, blockDim.x);
-    for (u32 t = threadIdx.x; t < E; t += blockDim.x) {
-        R v;
-#pragma unroll
-        for (int l = 0; l < K; ++l) v.v[l] = sm[l * E + t];
-        v = R::template reduce<32>(v);
-        u32 *p = data + (base + t) * K;
-#pragma unroll
-        for (int l = 0; l < K; ++l) p[l] = v.v[l];
-    }
+    ntt_tile_stages<FrC, false>(sm, E, ns, 1, lg, 0, 0, 0, tw_fwd, nullptr, B, threadIdx.x, blockDim.x);
+    for (u32 t = threadIdx.x; t < E; t += blockDim.x)
+        R::template reduce<32>(R::load_strided(sm + t, (int)E)).store(data + (base + t) * K);
 }
 // high pass of the forward transform on a, b, c (DIT stages lo + 1 .. lg; a third of the workgroup each) + (a b - c) / Z + high pass of
 // the inverse transform on the result (DIF stages lg .. lo + 1), one strided tile (column blockIdx.x) of 2^ns elements per vector;
@@ -333,39 +307,25 @@ __global__ __launch_bounds__(1024) void ntt_fused_high_pw(u32 *__restrict__ a, u
     const u32 per = blockDim.x / 3, vec = threadIdx.x / per, tid = threadIdx.x - vec * per;
     u32 *__restrict__ data = (vec == 0 ? a : (vec == 1 ? b : c)) + ((size_t)blockIdx.z << lg) * K;
     u32 *__restrict__ tile = sm + (size_t)vec * K * E;
-    for (u32 t = tid; t < E; t += per) {
-        const u32 *p = data + ((size_t)lo_base + ((size_t)t << lo_bits)) * K;
-#pragma unroll
-        for (int l = 0; l < K; ++l) tile[l * E + t] = p[l];
-    }
+    for (u32 t = tid; t < E; t += per) R::load(data + ((size_t)lo_base + ((size_t)t << lo_bits)) * K).store_strided(tile + t, (int)E);
     __syncthreads();
     int B = 4;
-    ntt_tile_stages<FrC, false>(tile, E, ns, s0, lg, lo_bits, lo_base, tw_fwd, B, tid, per);
+    ntt_tile_stages<FrC, false>(tile, E, ns, s0, lg, lo_bits, lo_base, 0, tw_fwd, nullptr, B, tid, per);
     const R zinv = R::load(zinv_rr);
     u32 *ta = sm, *tb = sm + (size_t)K * E, *tc = sm + (size_t)2 * K * E;
     for (u32 t = threadIdx.x; t < E; t += blockDim.x) { // h = (a b - c) (g^D - 1)^-1 on the coset, < 2p
-        R x, y, z;
-#pragma unroll
-        for (int l = 0; l < K; ++l) x.v[l] = ta[l * E + t], y.v[l] = tb[l * E + t], z.v[l] = tc[l * E + t];
-        x = R::template reduce<32>(x), y = R::template reduce<32>(y), z = R::template reduce<32>(z);
-        R ab = R::mul(x, y);
-        ab = R::template sub<5>(ab, z);
-        ab = R::mul(ab, zinv);
-#pragma unroll
-        for (int l = 0; l < K; ++l) ta[l * E + t] = ab.v[l];
+        const R x = R::template reduce<32>(R::load_strided(ta + t, (int)E)), y = R::template reduce<32>(R::load_strided(tb + t, (int)E)),
+                z = R::template reduce<32>(R::load_strided(tc + t, (int)E));
+        R::mul(R::template sub<5>(R::mul(x, y), z), zinv).store_strided(ta + t, (int)E);
     }
     __syncthreads();
     B = 2;
-    ntt_tile_stages<FrC, true>(ta, E, ns, s0, lg, lo_bits, lo_base, tw_inv, B, threadIdx.x, blockDim.x);
+    ntt_tile_stages<FrC, true>(ta, E, ns, s0, lg, lo_bits, lo_base, 0, tw_inv, nullptr, B, threadIdx.x, blockDim.x);
     u32 *__restrict__ out = a + ((size_t)blockIdx.z << lg) * K;
     for (u32 t = threadIdx.x; t < E; t += blockDim.x) {
-        R v;
-#pragma unroll
-        for (int l = 0; l < K; ++l) v.v[l] = ta[l * E + t];
+        R v = R::load_strided(ta + t, (int)E);
         if (B > 4) v = R::template reduce<32>(v);
-        u32 *p = out + ((size_t)lo_base + ((size_t)t << lo_bits)) * K;
-#pragma unroll
-        for (int l = 0; l < K; ++l) p[l] = v.v[l];
+        v.store(out + ((size_t)lo_base + ((size_t)t << lo_bits)) * K);
     }
 }
 
@@ -380,12 +340,8 @@ __global__ __launch_bounds__(1024) void ntt_fused_high_pw(u32 *__restrict__ a, u
 // ns. The tile is stored with one pad word per 32 (address t + t / 32): the strided accesses of the low groups -- 8 elements per
 // lane, lane-to-lane stride 8 -- and the unit-stride ones of the high groups are both conflict-free.
 // Same arguments, same bounds bookkeeping and same I/O options as ntt_pass_rr; tiles of at least 64 * 2^LR elements.
-// one butterfly stage on the 2^LR elements a lane holds in registers: pairs the owned bit Q; 2^Q distinct twiddles (the owned
-// bits below Q), each shared by the 2^(LR-1-Q) butterflies that differ in the owned bits above Q
-// lazy (DIT only): the sums a + t and a + 3p - t are left with unnormalised limbs (< 2^31) -- legal wherever they only feed the
-// next stage's product and its normalising additions: 9 x 2^31 x 2^29 + 9 x 2^58 < 2^64 -- which saves the two carry passes
-// (54 of ~330 VALU instructions per butterfly); the subtraction then adds 3p (fpr_dev.h `subl`), one p more than the normalised form
-// only the FIRST of two consecutive in-register DIT stages of a two-bit group: its lazy outputs (limbs < 2^29 + 2^30) meet one
+// A stage may leave its outputs lazy (ntt_butterfly)
+// only as the FIRST of two consecutive in-register DIT stages of a two-bit group: its lazy outputs (limbs < 2^29 + 2^30) meet one
 // normalising stage before they are stored; groups of three would stack two lazy stages (limbs up to 2^29 + 2 x 2^30: too wide)
 template <bool DIF> MG_DEV bool ntt_lazy_stage(int q, int lr, unsigned bit, unsigned first_bit, unsigned gs, unsigned s) {
 #ifdef MG_NTT_NO_LAZY
@@ -394,52 +350,23 @@ template <bool DIF> MG_DEV bool ntt_lazy_stage(int q, int lr, unsigned bit, unsi
     return !DIF && lr == 2 && q == 0 && gs == 2 && bit == first_bit && s > 1;
 #endif
 }
+// one butterfly stage on the 2^LR elements a lane holds in registers: pairs the owned bit Q; 2^Q distinct twiddles (the owned
+// bits below Q), each shared by the 2^(LR-1-Q) butterflies that differ in the owned bits above Q
 template <class FrC, bool DIF, int LR, int Q>
 MG_DEV void ntt_reg_stage(FpR<FrC> (&v)[1 << LR], const u32 *__restrict__ tw, bool has_w, bool red, unsigned b0, u32 e_lo,
-                          u32 lo_bits, u32 col, unsigned tw_shift, bool lazy = false, const u32 *__restrict__ stw = nullptr, u32 ntw = 0) {
+                          u32 lo_bits, u32 col, unsigned tw_shift, bool lazy, const u32 *__restrict__ stw, u32 ntw) {
     typedef FpR<FrC> R;
 #pragma unroll
     for (int u = 0; u < (1 << Q); ++u) {
+        const u32 jl = ((u32)u << b0) | e_lo; // the stage bits below the paired one
         R w;
-        if (has_w && stw) { // the tile's twiddles staged in LDS (single-column tiles): entry 2^bit - 1 + jl, bit = b0 + Q
-            const u32 *o = stw + ((1u << (b0 + (unsigned)Q)) - 1u + (((u32)u << b0) | e_lo));
-#pragma unroll
-            for (int l = 0; l < R::K; ++l) w.v[l] = o[l * ntw];
-        } else if (has_w) {
-            const u32 jl = ((u32)u << b0) | e_lo; // the stage bits below the paired one
-            const size_t j = ((size_t)jl << lo_bits) | col;
-            const uint4 *qp = reinterpret_cast<const uint4 *>(tw + (j << tw_shift) * 12); // 48 B records
-            const uint4 q0 = qp[0], q1 = qp[1], q2 = qp[2];
-            w.v[0] = q0.x, w.v[1] = q0.y, w.v[2] = q0.z, w.v[3] = q0.w, w.v[4] = q1.x, w.v[5] = q1.y, w.v[6] = q1.z, w.v[7] = q1.w,
-            w.v[8] = q2.x;
-        }
+        // the tile's twiddles staged in LDS (single-column tiles): entry 2^bit - 1 + jl, bit = b0 + Q
+        if (has_w && stw) w = R::load_strided(stw + ((1u << (b0 + (unsigned)Q)) - 1u + jl), (int)ntw);
+        else if (has_w) w = ntt_load_tw<FrC>(tw, (((size_t)jl << lo_bits) | col) << tw_shift);
 #pragma unroll
         for (int h = 0; h < (1 << (LR - 1 - Q)); ++h) {
-            constexpr int dummy = 0;
-            (void)dummy;
             const int i0 = (h << (Q + 1)) | u, i1 = i0 | (1 << Q);
-            const R a = v[i0], b = v[i1];
-            if (DIF) {
-                R x = R::add(a, b);                   // < 2B p
-                R y = R::template sub<9>(a, b);       // a + 9p - b (b < 8p) < (B + 9) p
-                if (has_w) y = MG_NTT_MUL(y, w);      // < 2p
-                else y = R::template reduce<17>(y);   // last DIF stage (w = 1)
-                if (red) x = R::template reduce<16>(x);
-                v[i0] = x, v[i1] = y;
-            } else if (has_w) {
-                const R t = MG_NTT_MUL(b, w); // < 2p
-                if (lazy) {
-#pragma unroll
-                    for (int l = 0; l < R::K; ++l) v[i0].v[l] = a.v[l] + t.v[l];
-                    v[i1] = R::template subl<3>(a, t);
-                } else {
-                    v[i0] = R::add(a, t);
-                    v[i1] = R::template sub<2>(a, t);
-                }
-            } else { // first DIT stage (w = 1): b < 4p
-                v[i0] = R::add(a, b);
-                v[i1] = R::template sub<5>(a, b);
-            }
+            ntt_butterfly<FrC, DIF>(v[i0], v[i1], w, has_w, red, lazy);
         }
     }
 }
@@ -455,49 +382,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MG_NTT_REG_
     extern __shared__ __attribute__((aligned(16))) u32 sm[];
     typedef FpR<FrC> R;
     constexpr int K = R::K, NE = 1 << LR;
-    static_assert(K == 9 && R::LIM >= 64, "bound analysis of ntt_pass_rr");
     u32 *__restrict__ data = (blockIdx.y == 0 ? d0 : (blockIdx.y == 1 ? d1 : d2)) + ((size_t)blockIdx.z << lg) * K;
-    const u32 E = 1u << ns, TOT = E << cb, CM = (1u << cb) - 1, TOTP = TOT + (TOT >> 5);
-    const u32 lo_bits = s0 - 1;
-    const u32 nlo = (1u << lo_bits) >> cb;
-    const u32 lo_base = (blockIdx.x % nlo) << cb, hi_blk = blockIdx.x / nlo;
-    const size_t base = ((size_t)hi_blk << (lo_bits + ns)) + lo_base;
-    auto pad = [](u32 t) { return t + (t >> 5); };
-    const bool twl = (io.packed & 4u) != 0; // single-column tiles: the tile's 2^ns - 1 twiddles in LDS behind it (see ntt_pass_rr)
-    u32 *__restrict__ stw = sm + (size_t)K * TOTP;
-    if (twl) {
-        for (u32 x = threadIdx.x + 1; x < E; x += blockDim.x) {
-            const unsigned tl = 32u - (unsigned)__clz(x);
-            const unsigned s = s0 + tl - 1;
-            if (s > 1) {
-                const size_t j = ((size_t)(x - (1u << (tl - 1))) << lo_bits) | lo_base;
-                const uint4 *q = reinterpret_cast<const uint4 *>(tw + (j << (lg - s)) * 12);
-                const uint4 q0 = q[0], q1 = q[1], q2 = q[2];
-                u32 *o = stw + (x - 1);
-                o[0 * E] = q0.x, o[1 * E] = q0.y, o[2 * E] = q0.z, o[3 * E] = q0.w, o[4 * E] = q1.x, o[5 * E] = q1.y, o[6 * E] = q1.z,
-                o[7 * E] = q1.w, o[8 * E] = q2.x;
-            }
-        }
-    }
-    for (u32 t = threadIdx.x; t < TOT; t += blockDim.x) {
-        const size_t gi = base + ((size_t)(t >> cb) << lo_bits) + (t & CM);
-        const u32 o = pad(t);
-        R r;
-        if (io.in_std) { // arkworks format at the bit-reversed index -> work form (< 2p)
-            const u32 j = __brev((u32)gi) >> (32 - lg);
-            r = R::from_std_shift(Fp<FrC>::load(io.in_std + (size_t)j * 8));
-            if (io.pre_rr) r = R::mul(r, R::load(io.pre_rr + (size_t)j * K));
-        } else if (io.packed & 1u) {
-            r = R::load_packed(data + gi * 8);
-        } else {
-            r = R::load(data + gi * K);
-        }
-#pragma unroll
-        for (int l = 0; l < K; ++l) sm[l * TOTP + o] = r.v[l];
-    }
+    const NttTile T(s0, ns, cb);
+    const u32 TOTP = T.TOT + (T.TOT >> 5);
+    u32 *__restrict__ stw = (io.packed & 4u) ? sm + (size_t)K * TOTP : nullptr;
+    if (stw) ntt_stage_twiddles<FrC>(stw, T.E, tw, lg, s0, T.lo_bits, T.lo_base);
+    ntt_tile_fill<FrC, true>(sm, TOTP, T, data, lg, io);
     __syncthreads();
     int B = 4; // every value in the tile is < B*p
-    const u32 nthr = TOT >> LR;
+    const u32 nthr = T.TOT >> LR;
     for (unsigned done = 0; done < ns;) {
         const unsigned gs = ns - done < (unsigned)LR ? ns - done : (unsigned)LR;
         // the LR stage bits this group's threads own: [b0, b0 + LR), the gs unprocessed ones among them are bits
@@ -506,32 +399,32 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MG_NTT_REG_
         unsigned b0 = first_bit + gs >= (unsigned)LR ? (DIF ? first_bit : (first_bit + LR <= ns ? first_bit : ns - LR)) : 0;
         if (b0 + LR > ns) b0 = ns >= (unsigned)LR ? ns - LR : 0;
         const unsigned p0 = cb + b0;
-        const int B_in = B;
+        // per owned bit Q, in the order the stages run: is it one of this group's stages, is its sum reduced, may its outputs stay
+        // lazy (DIT: a stage whose outputs are consumed by another stage of this group, not stored) -- and the bound after the
+        // group. Uniform: once per group, the same for every thread, also for those without elements.
+        bool on[LR], red[LR], lazy[LR];
+#pragma unroll
+        for (int k = 0; k < LR; ++k) {
+            const int q = DIF ? LR - 1 - k : k;
+            const unsigned bit = b0 + (unsigned)q, s = s0 + bit; // local stage bit (local stage number tl = bit + 1); global stage
+            on[q] = bit >= first_bit && bit < first_bit + gs;
+            lazy[q] = on[q] && ntt_lazy_stage<DIF>(q, LR, bit, first_bit, gs, s);
+            red[q] = on[q] && ntt_stage_reduces<DIF>(B);
+            if (on[q]) B = ntt_bound_step<DIF>(B, s > 1, lazy[q]);
+        }
         for (u32 vt = threadIdx.x; vt < nthr; vt += blockDim.x) { // (one trip when the workgroup has a thread per 2^LR elements)
-            B = B_in;
             const u32 lo = vt & ((1u << p0) - 1), hi = vt >> p0;
             const u32 tb = (hi << (p0 + LR)) | lo;
-            const u32 c = lo & CM, e_lo = lo >> cb; // column; the stage bits below b0
+            const u32 c = lo & ((1u << cb) - 1), e_lo = lo >> cb; // column; the stage bits below b0
             R v[NE];
 #pragma unroll
-            for (int j = 0; j < NE; ++j) {
-                const u32 o = pad(tb + ((u32)j << p0));
-#pragma unroll
-                for (int l = 0; l < K; ++l) v[j].v[l] = sm[l * TOTP + o];
-            }
+            for (int j = 0; j < NE; ++j) v[j] = R::load_strided(sm + ntt_lds_at<true>(tb + ((u32)j << p0)), (int)TOTP);
             // the stages of this group, one call per owned bit with the bit as a template constant (every register index static)
             auto run = [&](auto qc) {
                 constexpr int Q = decltype(qc)::value;
-                const unsigned bit = b0 + (unsigned)Q; // local stage bit; local stage number tl = bit + 1
-                if (bit < first_bit || bit >= first_bit + gs) return; // (uniform) not one of this group's stages
-                const unsigned s = s0 + bit;               // global stage
-                // DIT: a stage whose outputs are consumed by another stage of this group (not stored) may leave them lazy
-                const bool lazy = ntt_lazy_stage<DIF>(Q, LR, bit, first_bit, gs, s);
-                ntt_reg_stage<FrC, DIF, LR, Q>(v, tw, s > 1, DIF && 2 * B > 8, b0, e_lo, lo_bits, lo_base + c, lg - s, lazy,
-                                               twl ? stw : (const u32 *)nullptr, E);
-                const bool red = DIF && 2 * B > 8;
-                if (DIF) B = red ? 2 : 2 * B;
-                else B = s > 1 ? B + (lazy ? 3 : 2) : B + 5;
+                if (!on[Q]) return; // (uniform) not one of this group's stages
+                const unsigned s = s0 + b0 + (unsigned)Q; // global stage
+                ntt_reg_stage<FrC, DIF, LR, Q>(v, tw, s > 1, red[Q], b0, e_lo, T.lo_bits, T.lo_base + c, lg - s, lazy[Q], stw, T.E);
             };
             if constexpr (DIF) {
                 if constexpr (LR > 2) run(std::integral_constant<int, 2>());
@@ -543,44 +436,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MG_NTT_REG_
                 if constexpr (LR > 2) run(std::integral_constant<int, 2>());
             }
 #pragma unroll
-            for (int j = 0; j < NE; ++j) {
-                const u32 o = pad(tb + ((u32)j << p0));
-#pragma unroll
-                for (int l = 0; l < K; ++l) sm[l * TOTP + o] = v[j].v[l];
-            }
-        }
-        { // the bound after this group's stages, the same for every thread (also for those without elements)
-            B = B_in;
-            for (unsigned k = 0; k < gs; ++k) {
-                const unsigned bit = DIF ? first_bit + gs - 1 - k : first_bit + k;
-                const bool has_w = s0 + bit > 1, red = DIF && 2 * B > 8;
-                const bool lazy = ntt_lazy_stage<DIF>((int)(bit - b0), LR, bit, first_bit, gs, s0 + bit);
-                if (DIF) B = red ? 2 : 2 * B;
-                else B = has_w ? B + (lazy ? 3 : 2) : B + 5;
-            }
+            for (int j = 0; j < NE; ++j) v[j].store_strided(sm + ntt_lds_at<true>(tb + ((u32)j << p0)), (int)TOTP);
         }
         __syncthreads();
         done += gs;
     }
-    for (u32 t = threadIdx.x; t < TOT; t += blockDim.x) {
-        const size_t gi = base + ((size_t)(t >> cb) << lo_bits) + (t & CM);
-        const u32 o = pad(t);
-        R v;
-#pragma unroll
-        for (int l = 0; l < K; ++l) v.v[l] = sm[l * TOTP + o];
-        if (post) v = R::mul(v, R::load(post + gi * K)); // any B <= 27 times a canonical table entry: < 2p
-        else if (DIF ? B > 4 : true) v = R::template reduce<32>(v);
-        if (io.out_std) { // work form (< 4p) -> arkworks format, times the constant of the plain inverse transform first
-            if (io.scale_rr) v = R::mul(v, R::load(io.scale_rr));
-            v.to_std().store(io.out_std + gi * 8);
-            continue;
-        }
-        if (io.packed & 2u) { // (v < 2p and normalised: a product or a reduce made it)
-            v.store_packed(data + gi * 8);
-            continue;
-        }
-        v.store(data + gi * K);
-    }
+    ntt_tile_drain<FrC, DIF, true>(sm, TOTP, T, data, post, io, B);
 }
 
 // arkworks-format table (Montgomery, 8 words) -> canonical reduced-radix table with `stride` words per entry
@@ -831,7 +692,7 @@ template <class FrC> class FrEngineT : public FrEngine {
     // all stages of one transform over up to 3 reduced-radix vectors as LDS-fused passes of <= 10 stages
     template <bool DIF>
     static void run_passes(u32 *d0, u32 *d1, u32 *d2, int nvec, const u32 *tw_rr, unsigned lg, const u32 *post_rr, hipStream_t s,
-                           u32 batch = 1, NttIo io = NttIo{nullptr, nullptr, nullptr, nullptr, 0u}) {
+                           u32 batch = 1, NttIo io = NttIo{}) {
         if (lg == 0) return;
         static const bool attr_set = [] { // tiles of 2048 elements x 36 B = 72 KB: above the 64 KB default of dynamic LDS
             hipFuncSetAttribute(reinterpret_cast<const void *>(&ntt_pass_rr<FrC, DIF>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -886,17 +747,25 @@ template <class FrC> class FrEngineT : public FrEngine {
             if (lr && tot >= (64u << lr) && ns >= (unsigned)lr) {
                 const size_t lds_p = (size_t)(4 * RK) * (tot + (tot >> 5)) + twl_bytes;
                 const u32 th = std::min<u32>(512u, tot >> lr);
-                if (lr == 3)
-                    hipLaunchKernelGGL((ntt_pass_reg<FrC, DIF, 3>), dim3(blocks, nvec, batch), dim3(th), lds_p, s, d0, d1, d2, tw_rr, lg, s0,
-                                       ns, cb, last ? post_rr : (const u32 *)nullptr, pio);
-                else
-                    hipLaunchKernelGGL((ntt_pass_reg<FrC, DIF, 2>), dim3(blocks, nvec, batch), dim3(th), lds_p, s, d0, d1, d2, tw_rr, lg, s0,
-                                       ns, cb, last ? post_rr : (const u32 *)nullptr, pio);
+                const auto reg = lr == 3 ? &ntt_pass_reg<FrC, DIF, 3> : &ntt_pass_reg<FrC, DIF, 2>;
+                hipLaunchKernelGGL(reg, dim3(blocks, nvec, batch), dim3(th), lds_p, s, d0, d1, d2, tw_rr, lg, s0, ns, cb,
+                                   last ? post_rr : (const u32 *)nullptr, pio);
             } else
-            hipLaunchKernelGGL((ntt_pass_rr<FrC, DIF>), dim3(blocks, nvec, batch), dim3(threads), lds + twl_bytes, s, d0, d1, d2, tw_rr, lg, s0,
-                               ns, cb, last ? post_rr : (const u32 *)nullptr, pio);
+                hipLaunchKernelGGL((ntt_pass_rr<FrC, DIF>), dim3(blocks, nvec, batch), dim3(threads), lds + twl_bytes, s, d0, d1, d2, tw_rr,
+                                   lg, s0, ns, cb, last ? post_rr : (const u32 *)nullptr, pio);
             done += ns;
         }
+    }
+
+    // single-column tiles of 2^ns elements (one proof's witness map): a butterfly per thread, 36 B of LDS per element
+    static u32 tile_threads(unsigned ns) { return std::max(64u, (1u << ns) / 2); }
+    static size_t tile_lds(unsigned ns) { return (size_t)(4 * RK) << ns; }
+    // one ntt_pass_rr pass over such tiles: stages s0 .. s0 + ns - 1 of the 2^lg transform of `nvec` vectors, plain work form in and out
+    template <bool DIF>
+    static void rr_pass(u32 *d0, u32 *d1, u32 *d2, int nvec, const u32 *tw_rr, unsigned lg, unsigned s0, unsigned ns, const u32 *post_rr,
+                        hipStream_t s, u32 batch) {
+        hipLaunchKernelGGL((ntt_pass_rr<FrC, DIF>), dim3((1u << lg) >> ns, nvec, batch), dim3(tile_threads(ns)), tile_lds(ns), s, d0, d1, d2,
+                           tw_rr, lg, s0, ns, 0u, post_rr, NttIo{});
     }
 
     // Radix2EvaluationDomain::{fft, ifft, coset_fft, coset_ifft}_in_place on 2^log_n arkworks-format elements in HBM:
@@ -982,34 +851,27 @@ template <class FrC> class FrEngineT : public FrEngine {
                 return true;
             }();
             (void)attr_set;
-            const NttIo none{nullptr, nullptr, nullptr, nullptr, 0u};
             // inverse transform, high stages lg .. L + 1 (strided tiles of 2^H), a | b | c
-            hipLaunchKernelGGL((ntt_pass_rr<FrC, true>), dim3(n >> H, 3, batch), dim3(std::max(64u, (1u << H) / 2)), (size_t)(4 * RK) << H, s, a, b, c,
-                               d->tw_inv_rr, lg, L + 1, H, 0u, (const u32 *)nullptr, none);
+            rr_pass<true>(a, b, c, 3, d->tw_inv_rr, lg, L + 1, H, nullptr, s, batch);
             // its low stages + n^-1 g^i + the forward coset transform's low stages (contiguous tiles of 2^L)
             if (fuse_on & 1) {
-                hipLaunchKernelGGL((ntt_fused_low<FrC>), dim3(n >> L, 3, batch), dim3(std::max(64u, (1u << L) / 2)), (size_t)(4 * RK) << L, s, a, b, c,
-                                   d->tw_inv_rr, d->tw_fwd_rr, lg, L, d->t1_br_rr);
+                hipLaunchKernelGGL((ntt_fused_low<FrC>), dim3(n >> L, 3, batch), dim3(tile_threads(L)), tile_lds(L), s, a, b, c, d->tw_inv_rr,
+                                   d->tw_fwd_rr, lg, L, d->t1_br_rr);
             } else {
-                hipLaunchKernelGGL((ntt_pass_rr<FrC, true>), dim3(n >> L, 3, batch), dim3(std::max(64u, (1u << L) / 2)), (size_t)(4 * RK) << L, s, a, b, c,
-                                   d->tw_inv_rr, lg, 1u, L, 0u, d->t1_br_rr, none);
-                hipLaunchKernelGGL((ntt_pass_rr<FrC, false>), dim3(n >> L, 3, batch), dim3(std::max(64u, (1u << L) / 2)), (size_t)(4 * RK) << L, s, a, b, c,
-                                   d->tw_fwd_rr, lg, 1u, L, 0u, (const u32 *)nullptr, none);
+                rr_pass<true>(a, b, c, 3, d->tw_inv_rr, lg, 1u, L, d->t1_br_rr, s, batch);
+                rr_pass<false>(a, b, c, 3, d->tw_fwd_rr, lg, 1u, L, nullptr, s, batch);
             }
             // forward high stages on a, b, c + (a b - c) / Z + the last inverse transform's high stages
             if (fuse_on & 2) {
-                hipLaunchKernelGGL((ntt_fused_high_pw<FrC>), dim3(n >> H, 1, batch), dim3(3 * std::max(64u, (1u << H) / 2)), (size_t)(3 * 4 * RK) << H, s,
-                                   a, b, c, d->tw_fwd_rr, d->tw_inv_rr, lg, H, d->consts_rr + RK);
+                hipLaunchKernelGGL((ntt_fused_high_pw<FrC>), dim3(n >> H, 1, batch), dim3(3 * tile_threads(H)), 3 * tile_lds(H), s, a, b, c,
+                                   d->tw_fwd_rr, d->tw_inv_rr, lg, H, d->consts_rr + RK);
             } else {
-                hipLaunchKernelGGL((ntt_pass_rr<FrC, false>), dim3(n >> H, 3, batch), dim3(std::max(64u, (1u << H) / 2)), (size_t)(4 * RK) << H, s, a, b, c,
-                                   d->tw_fwd_rr, lg, L + 1, H, 0u, (const u32 *)nullptr, none);
+                rr_pass<false>(a, b, c, 3, d->tw_fwd_rr, lg, L + 1, H, nullptr, s, batch);
                 hipLaunchKernelGGL((qap_pointwise_kernel<FrC>), dim3((n + 255) / 256, batch), dim3(256), 0, s, a, b, c, d->consts_rr + RK, n);
-                hipLaunchKernelGGL((ntt_pass_rr<FrC, true>), dim3(n >> H, 1, batch), dim3(std::max(64u, (1u << H) / 2)), (size_t)(4 * RK) << H, s, a, a, a,
-                                   d->tw_inv_rr, lg, L + 1, H, 0u, (const u32 *)nullptr, none);
+                rr_pass<true>(a, a, a, 1, d->tw_inv_rr, lg, L + 1, H, nullptr, s, batch);
             }
             // its low stages + n^-1 g^-i
-            hipLaunchKernelGGL((ntt_pass_rr<FrC, true>), dim3(n >> L, 1, batch), dim3(std::max(64u, (1u << L) / 2)), (size_t)(4 * RK) << L, s, a, a, a,
-                               d->tw_inv_rr, lg, 1u, L, 0u, d->t2_br_rr, none);
+            rr_pass<true>(a, a, a, 1, d->tw_inv_rr, lg, 1u, L, d->t2_br_rr, s, batch);
             MG_HIP(hipGetLastError());
             return MG_OK;
         }

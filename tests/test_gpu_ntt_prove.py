@@ -780,6 +780,87 @@ def test_witness_map_matches_oracle_across_domain_sizes(gpu, curve):
         ctx.close()
 
 
+_NTT_SIZES = (9, 10, 11, 13, 14)
+_WM_SIZES = (9, 10, 13)
+_NTT_VARIANTS_SCRIPT = '''
+import hashlib, os, sys
+sys.path.insert(0, r"{root}"); sys.path.insert(0, os.path.join(r"{root}", "tests"))
+import numpy as np
+import helpers as H
+import oracle_lib as O
+from manta_rs_amd import api as gpu, synth
+gpu.init(0)
+digest = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+for curve in (0, 1):
+    for lg in {ntt_sizes}:
+        x = H.rand_fr_mont(curve, 1 << lg, seed=lg + 1)
+        dom = gpu.Radix2EvaluationDomain(curve, 1 << lg)
+        for inverse in (False, True):
+            for coset in (False, True):
+                print("NTT", curve, lg, int(inverse), int(coset), digest(dom._run(x, inverse, coset)), flush=True)
+    g1, g2 = O.generator(curve, 1), O.generator(curve, 2)
+    for lg in {wm_sizes}:
+        D, P = 1 << lg, 5
+        c = synth.make_circuit(curve, D - P, max(D // 2, 40), P, seed=lg, profile="W")
+        class K:
+            pass
+        k = K()
+        k.V, k.P = c.V, c.P
+        for name, n, g in (("alpha_g1", 1, g1), ("beta_g1", 1, g1), ("delta_g1", 1, g1), ("beta_g2", 1, g2), ("delta_g2", 1, g2),
+                           ("a_query", c.V, g1), ("b_g1_query", c.V, g1), ("b_g2_query", c.V, g2), ("h_query", D - 1, g1),
+                           ("l_query", c.V - c.P, g1)):
+            setattr(k, name, np.tile(np.asarray(g, dtype=np.uint64).reshape(1, -1), (n, 1)))
+        ctx = gpu.ProvingContext(curve, k, full_table_bytes=0)
+        ctx.set_r1cs(gpu.R1CS.from_circuit(c))
+        print("WM", curve, lg, digest(ctx.witness_map(c.z)), flush=True)
+        ctx.close()
+'''
+
+
+def test_ntt_kernel_variants_match_oracle(gpu):
+    """The pass kernels that only MANTA_NTT_R reaches -- the register kernel in DIF, with three stages per round trip (LR = 3), with a
+    remainder group, and both pass kernels with column groups (cb > 0) on small tiles -- against the oracle, bit-exact, on both curves.
+    Every child runs the unfused witness map (MANTA_NTT_FUSE=0) and keeps the widest column groups (MANTA_NTT_MIN_WGS=1):
+      2^9   one pass, twiddles in LDS; LR = 2 ends on a remainder group of one stage, LR = 3 is three whole groups on its smallest tile
+      2^10  one pass, twiddles in LDS; LR = 3 ends on a remainder group
+      2^11  two passes (packed hand-over), the second with cb = 3 on a 256-element tile: register kernel at LR = 2, LDS kernel at LR = 3
+      2^13  two passes, 512-element tiles with cb = 3: the register kernel for both LR
+      2^14  two passes, 1024-element tiles with cb = 3: the register kernel for both LR, LR = 3 with a remainder group
+    The witness map (DIF passes with `post` tables over three vectors, then DIT, then DIF over one) at 2^9, 2^10 and 2^13 (cb = 3).
+    Knobs are read once per process, hence the children; each prints one digest per case."""
+    import hashlib
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def digest(a):
+        return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+    O.set_threads(O.usable_cpus())
+    want = []
+    for curve in (0, 1):
+        for lg in _NTT_SIZES:
+            x = H.rand_fr_mont(curve, 1 << lg, seed=lg + 1)
+            for inverse in (False, True):
+                for coset in (False, True):
+                    want.append("NTT %d %d %d %d %s" % (curve, lg, inverse, coset, digest(O.ntt(curve, x, inverse=inverse, coset=coset))))
+        for lg in _WM_SIZES:
+            D, P = 1 << lg, 5
+            c = synth.make_circuit(curve, D - P, max(D // 2, 40), P, seed=lg, profile="W")
+            want.append("WM %d %d %s" % (curve, lg, digest(O.witness_map(c))))
+    script = _NTT_VARIANTS_SCRIPT.format(root=root, ntt_sizes=repr(_NTT_SIZES), wm_sizes=repr(_WM_SIZES))
+    for r in ({"MANTA_NTT_R": "0"}, {"MANTA_NTT_R": "2"}, {"MANTA_NTT_R": "3"}, {"MANTA_NTT_R": "3", "MANTA_NTT_TWL": "0"}):
+        knobs = dict(r, MANTA_NTT_FUSE="0", MANTA_NTT_MIN_WGS="1")
+        env = H.knob_env(knobs, strip_prefix="MANTA_")  # (A/B switches: the diagnosis twin)
+        assert env["MANTA_LIB"].endswith("libmantagpu_diag.so"), env["MANTA_LIB"]
+        out = subprocess.run([sys.executable, "-c", script], env=env, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, (knobs, out.stdout[-2000:] + out.stderr[-2000:])
+        got = [ln for ln in out.stdout.split("\n") if ln.startswith(("NTT ", "WM "))]
+        assert len(got) == len(want), (knobs, len(got), len(want))
+        wrong = [g.rsplit(" ", 1)[0] for g, w in zip(got, want) if g != w]
+        assert not wrong, (knobs, wrong)
+
+
 def test_hardware_queues_are_probed_and_slots_get_their_own(gpu):
     """Round 5: the library measures which of its streams share a hardware queue (csrc/queues.hip: a kernel on one stream waits,
     bounded, for a word a kernel on the other writes) and gives every single-proof slot three streams on three different queues.
