@@ -190,6 +190,32 @@ int mg_ec_elementwise(mg_curve_t curve, int group, int op, const uint64_t *a_aff
 #define MG_FIELD_INV 7
 int mg_field_op(int field, int op, int repr, int lazy_a, int lazy_b, const uint64_t *a, const uint64_t *b, size_t n,
                 uint64_t *out);
+/* The first two stages of the MSM pipeline, each alone over host arrays: parity-test surfaces for the kernels that
+ * mg_msm_launch runs (the same digit kernel, the same radix sort), not needed by the shim. Synchronous; one device
+ * block per call. The OUTPUT arrays are uploaded from the caller's buffers before the launch, so whatever the kernels
+ * do not write comes back as the caller left it.
+ *
+ * mg_msm_digits: scalars [batch][n_scalars][4] u64 (canonical integers of any size below 2^256, or Montgomery words
+ *   with MG_SCALARS_MONT) -> signed window digits -> (bucket key, base index | sign << 31) pairs for a set of n stored
+ *   bases that is described, not supplied: table_mode 0 = plain bases, 1 = a table per window, 2 = full tables
+ *   (window_bits 2..12); map = NULL or n indices (stored base i takes scalar map[i]); the set is the concatenation of
+ *   n_sets queries of set_len entries (n_sets = 1: set_len = its logical length; n = n_sets * set_len without a map,
+ *   n_scalars <= set_len for n_sets > 1). Stored bases without a scalar (index >= n_scalars) have the scalar 0.
+ *   layout = {W = ceil(scalar bits / window_bits), B = 2^(window_bits - 1), bucket keys per (vector, query), the key
+ *   of a zero digit}. keys, vals: batch * W * n u32 each. compact = 0: digit (vector q, window w, base i) at
+ *   (q W + w) n + i, zero digits as (invalid key, 0). compact = 1: the pairs of the non-zero digits only, in an
+ *   unspecified order at the front of the arrays, their number in *count.
+ *   MG_ERROR_INVALID_ARGUMENT for what an MSM launch refuses: 2^31 pairs, a key space of 2^24 (batch * n_sets *
+ *   bucket keys), a base index of 2^31, index ranges that contradict each other.
+ * mg_sort_pairs: n (key, value) pairs, keys below 2^end_bit (1 <= end_bit <= 32; the caller's duty), sorted stably by
+ *   key. count != NULL: only the first *count <= n pairs exist (the number is read on the device) and the outputs from
+ *   *count on are not written. (lowmask, inv_from) = (0xffffffff, 0xffffffff): the key itself; otherwise the order is
+ *   that of key >= inv_from ? lowmask + 1 : key & lowmask, which must be below 2^end_bit. */
+int mg_msm_digits(mg_curve_t curve, const uint64_t *scalars, size_t batch, size_t n_scalars, int scalar_flags, int window_bits,
+                  int table_mode, size_t n, const uint32_t *map, size_t n_sets, size_t set_len, int compact, uint32_t *keys,
+                  uint32_t *vals, uint32_t *count, uint32_t layout[4]);
+int mg_sort_pairs(const uint32_t *keys, const uint32_t *vals, size_t n, int end_bit, const uint32_t *count, uint32_t lowmask,
+                  uint32_t inv_from, uint32_t *keys_out, uint32_t *vals_out);
 /* Radix-2 (inverse) NTT over a vector of 2^log_n GROUP elements, natural order in and out: ark-poly
  * `Radix2EvaluationDomain::{fft, ifft}` applied to points -- how `mpc::initialize` turns the powers of tau into the
  * Lagrange basis (manta-trusted-setup/src/groth16/mpc.rs:378-381). Host arrays of affine Montgomery points. */

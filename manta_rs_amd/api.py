@@ -61,6 +61,7 @@ EXPORTS = [
     "mg_init", "mg_strerror", "mg_last_error", "mg_device_count", "mg_malloc", "mg_free", "mg_memcpy_h2d",
     "mg_memcpy_d2h", "mg_device_synchronize", "mg_host_alloc", "mg_host_free", "mg_set_kernel_timing", "mg_last_accumulate_ms", "mg_bases_create", "mg_bases_destroy", "mg_bases_device_bytes",
     "mg_msm", "mg_msm_launch", "mg_msm_finish", "mg_points_sum", "mg_fixed_base_mul", "mg_ec_elementwise", "mg_point_serialize", "mg_ntt",
+    "mg_msm_digits", "mg_sort_pairs",
     "mg_ntt_device", "mg_groth16_setup", "mg_ctx_create", "mg_ctx_create_from_bytes", "mg_ctx_set_r1cs", "mg_groth16_prove", "mg_groth16_prove_batch", "mg_witness_map", "mg_ctx_domain_size", "mg_ctx_table_bytes",
     "mg_ctx_destroy", "mg_bases_create_sharded", "mg_bases_num_shards", "mg_bases_shard", "mg_msm_launch_sharded",
     "mg_ctx_create_sharded", "mg_ctx_create_from_bytes_sharded", "mg_ctx_num_variables", "mg_ctx_num_inputs",
@@ -433,6 +434,53 @@ def field_op(field, op, a, b=None, repr=0, lazy_a=0, lazy_b=0) -> np.ndarray:
     _chk(LIB.mg_field_op(FIELD_IDS[field], FIELD_OPS[op], int(repr), int(lazy_a), int(lazy_b), _p(a), _p(bb), _sz(a.shape[0]),
                          _p(out)), "mg_field_op")
     return out
+
+
+def _u32_buffer(a, n, name):
+    """the caller's [n] uint32 buffer as a fresh contiguous copy (the library works in place on it), or zeros"""
+    out = np.zeros(n, dtype=np.uint32) if a is None else np.array(a, dtype=np.uint32).reshape(-1)
+    assert out.shape == (n,), "%s: %d elements, expected %d" % (name, out.size, n)
+    return out
+
+
+def msm_digits(curve, scalars, c, n, mont=False, table_mode=0, map=None, n_sets=1, set_len=None, compact=False, keys=None, vals=None):
+    """The MSM's digit kernel alone (`mg_msm_digits`): scalars = [batch, n_scalars, 4] (or [n_scalars, 4]) uint64 against a
+    described set of n stored bases -> dict(W, B, seg_keys, invalid, keys, vals, count). keys / vals (batch * W * n uint32,
+    default zeros) are what the device arrays hold before the launch; count is None in the fixed layout."""
+    sc = _u64(scalars)
+    if sc.ndim == 2:
+        sc = sc[None]
+    assert sc.ndim == 3 and sc.shape[2] == 4, sc.shape
+    batch, n_scalars = sc.shape[0], sc.shape[1]
+    bits = 254 if curve == BN254 else 255
+    W = (bits + c - 1) // c if c > 0 else 0
+    size = batch * W * n
+    k, v = _u32_buffer(keys, size, "keys"), _u32_buffer(vals, size, "vals")
+    mp = None if map is None else np.ascontiguousarray(map, dtype=np.uint32)
+    assert mp is None or mp.shape == (n,), mp.shape
+    count = ctypes.c_uint32(0)
+    layout = (ctypes.c_uint32 * 4)()
+    _chk(LIB.mg_msm_digits(curve, _p(sc), _sz(batch), _sz(n_scalars), int(bool(mont)), int(c), int(table_mode), _sz(n), _p(mp), _sz(n_sets),
+                           _sz(n if set_len is None else set_len), int(bool(compact)), _p(k), _p(v), ctypes.byref(count) if compact else None,
+                           layout), "mg_msm_digits")
+    assert layout[0] == W
+    return dict(W=int(layout[0]), B=int(layout[1]), seg_keys=int(layout[2]), invalid=int(layout[3]), keys=k, vals=v,
+                count=int(count.value) if compact else None)
+
+
+def sort_pairs(keys, vals, end_bit, count=None, lowmask=0xFFFFFFFF, inv_from=0xFFFFFFFF, keys_out=None, vals_out=None):
+    """The MSM's radix sort alone (`mg_sort_pairs`): [n] uint32 keys below 2^end_bit and their values -> (keys, vals) sorted stably
+    by key (by `key >= inv_from ? lowmask + 1 : key & lowmask` when masked). count: only that many pairs exist, read on the device.
+    keys_out / vals_out: what the output arrays hold before the launch (default zeros)."""
+    k = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+    v = np.ascontiguousarray(vals, dtype=np.uint32).reshape(-1)
+    n = k.shape[0]
+    assert v.shape == (n,)
+    ko, vo = _u32_buffer(keys_out, n, "keys_out"), _u32_buffer(vals_out, n, "vals_out")
+    cnt = None if count is None else ctypes.byref(ctypes.c_uint32(count))
+    _chk(LIB.mg_sort_pairs(_p(k), _p(v), _sz(n), int(end_bit), cnt, ctypes.c_uint32(lowmask), ctypes.c_uint32(inv_from), _p(ko), _p(vo)),
+         "mg_sort_pairs")
+    return ko, vo
 
 
 def point_serialize(curve, group, point, compressed=True):

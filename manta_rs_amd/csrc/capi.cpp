@@ -434,6 +434,47 @@ MG_API int mg_field_op(int field, int op, int repr, int lazy_a, int lazy_b, cons
     MG_CATCH
 }
 
+// The MSM front end stage by stage (parity-test surfaces, as mg_field_op is for the field arithmetic): the digit kernel and the
+// radix sort msm_launch runs, each alone over host arrays.
+MG_API int mg_msm_digits(mg_curve_t curve, const uint64_t *scalars, size_t batch, size_t n_scalars, int scalar_flags, int window_bits,
+                         int table_mode, size_t n, const uint32_t *map, size_t n_sets, size_t set_len, int compact, uint32_t *keys,
+                         uint32_t *vals, uint32_t *count, uint32_t layout[4]) {
+    MG_TRY
+    GroupEngine *e = get_engine((int)curve, 1); // (the digit kernel depends on the scalar field alone)
+    const size_t lim = (size_t)1 << 31;
+    if (!e || batch >= lim || n_scalars >= lim || n >= lim || n_sets >= lim || set_len >= lim || (scalar_flags & ~MG_SCALARS_MONT))
+        return MG_ERROR_INVALID_ARGUMENT;
+    const MsmDigitsCall c{(const u32 *)scalars, (u32)batch, (u32)n_scalars, (scalar_flags & MG_SCALARS_MONT) ? SCALARS_MONT : SCALARS_CANONICAL,
+                          window_bits, table_mode, (u32)n, map, (u32)n_sets, (u32)set_len, compact != 0, keys, vals, count, layout};
+    return e->msm_digits(c);
+    MG_CATCH
+}
+MG_API int mg_sort_pairs(const uint32_t *keys, const uint32_t *vals, size_t n, int end_bit, const uint32_t *count, uint32_t lowmask,
+                         uint32_t inv_from, uint32_t *keys_out, uint32_t *vals_out) {
+    MG_TRY
+    if (!keys || !vals || !keys_out || !vals_out || end_bit < 1 || end_bit > 32 || n >= ((size_t)1 << 32) || (count && *count > n))
+        return MG_ERROR_INVALID_ARGUMENT;
+    if (n == 0) return MG_SUCCESS;
+    hipStream_t s = setup_stream();
+    if (!s) return MG_ERROR_OUT_OF_MEMORY;
+    const size_t pb = n * 4, tb = sort_pairs_temp_bytes(n);
+    DevBlock m; // keys | values | sorted keys | sorted values | the sort's scratch | element count
+    if (const int rc = m.alloc({pb, pb, pb, pb, tb, count ? 4u : 0u}, "mg_sort_pairs")) return rc;
+    const void *const src[5] = {keys, vals, keys_out, vals_out, count};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 5 && e == hipSuccess; ++i)
+        if (src[i]) e = hipMemcpyAsync(m.dev(i < 4 ? i : 5), src[i], i < 4 ? pb : 4, hipMemcpyHostToDevice, s);
+    int rc = MG_OK;
+    if (e == hipSuccess)
+        rc = sort_pairs(m.dev<u32>(0), m.dev<u32>(2), m.dev<u32>(1), m.dev<u32>(3), n, end_bit, m.dev(4), tb, s, m.dev<u32>(5), lowmask, inv_from);
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(keys_out, m.dev(2), pb, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(vals_out, m.dev(3), pb, hipMemcpyDeviceToHost, s);
+    const hipError_t e2 = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = e2;
+    return rc ? rc : e == hipSuccess ? MG_SUCCESS : hip_status(e, "mg_sort_pairs");
+    MG_CATCH
+}
+
 // ---------------------------------------------------------------------------------------------- NTT
 MG_API int mg_ntt_device(mg_curve_t curve, uint64_t *d_data, unsigned log_n, int inverse, int coset) {
     MG_TRY

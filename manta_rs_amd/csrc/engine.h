@@ -268,6 +268,20 @@ inline hipStream_t msm_stream_of(const MsmWorkspace *ws) {
     return ws->run_on ? ws->run_on : (ws->use_solo && ws->solo ? ws->solo : ws->stream);
 }
 
+// mg_msm_digits (mantagpu.h): the digit kernel of msm_launch alone, host arrays in and out
+struct MsmDigitsCall {
+    const u32 *scalars; // [batch][n_scalars][8]
+    u32 batch, n_scalars;
+    int scalar_mode, c, table_mode; // table_mode: 0 plain bases, 1 per-window tables, 2 full tables
+    u32 n;                          // stored bases = lanes
+    const u32 *map;                 // [n] or nullptr
+    u32 n_sets, set_len;
+    bool compact;
+    u32 *keys, *vals; // [batch W n] each, uploaded before the launch and fetched after it
+    u32 *count;       // compact: the device's pair count
+    u32 *layout;      // out: W, B, seg_keys, invalid
+};
+
 // Opaque host point (XYZZ, 64-bit limbs) big enough for G2/BLS12-381.
 struct HostPoint {
     u64 w[4 * 12];
@@ -316,6 +330,9 @@ class GroupEngine {
     virtual int msm_fold_device(MsmWorkspace *ws, u32 *d_out, size_t out_stride_words, hipStream_t on = nullptr) = 0;
     // an MSM whose result was taken on the device: wait for its stream, clear `pending`
     virtual int msm_discard(MsmWorkspace *ws) = 0;
+    // The first stage of msm_launch on its own -- the plan, the key layout and the digit-kernel launch of a set of c.n stored bases,
+    // no points involved -- as a parity-test surface (tests/test_gpu_msm_frontend.py)
+    virtual int msm_digits(const MsmDigitsCall &c) = 0;
 
     // host-point helpers (type-erased)
     virtual void hp_set_inf(HostPoint *p) const = 0;

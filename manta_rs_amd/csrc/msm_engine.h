@@ -190,14 +190,7 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         bs->n_orig = n_in;
         bs->n_sets = n_sets;
         bs->set_len = n_in / n_sets;
-        if (n_sets > 1 && n_sets <= BaseSet::MAX_SETS) { // where every query starts among the stored points
-            for (u32 q = 0; q <= n_sets; ++q) {
-                const size_t first = (size_t)q * bs->set_len; // original index
-                bs->set_first[q] = map.empty() ? (u32)(first < n ? first : n)
-                                               : (u32)(std::lower_bound(map.begin(), map.end(), (u32)first) - map.begin());
-            }
-            bs->set_first[n_sets] = (u32)n;
-        }
+        set_query_ranges(bs, map.data(), map.size());
         if (!map.empty()) {
             if (hipMalloc((void **)&bs->d_map, map.size() * 4) != hipSuccess ||
                 memcpy_sync(bs->d_map, map.data(), map.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
@@ -209,7 +202,7 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         if (full) pre_c = -pre_c;
         int W = 1;
         if (pre_c > 0) {
-            W = (FrC::BITS + pre_c - 1) / pre_c; // digits_kernel: |k| < 2^(BITS - 1)
+            W = windows_of(pre_c);
             bs->pre_c = pre_c;
             bs->pre_W = W;
             bs->full = full;
@@ -230,6 +223,18 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         *out = bs;
         return MG_OK;
     }
+    // where every query of a concatenated set starts among the n stored points (map: ascending, or none)
+    static void set_query_ranges(BaseSet *bs, const u32 *map, size_t map_len) {
+        const size_t n = bs->n;
+        const u32 n_sets = bs->n_sets;
+        if (n_sets <= 1 || n_sets > BaseSet::MAX_SETS) return;
+        for (u32 q = 0; q <= n_sets; ++q) {
+            const size_t first = (size_t)q * bs->set_len; // original index
+            bs->set_first[q] = !map_len ? (u32)(first < n ? first : n) : (u32)(std::lower_bound(map, map + map_len, (u32)first) - map);
+        }
+        bs->set_first[n_sets] = (u32)n;
+    }
+    static int windows_of(int c) { return (FrC::BITS + c - 1) / c; } // digits_kernel: |k| < 2^(BITS - 1)
     static int hip_failure(hipError_t e, const char *what, int rc) { set_last_hip_error(e, what, __FILE__, __LINE__); return rc; }
     // drop_infinity: the points other than infinity go to `compact`, map[i] = the original index of stored point i; one infinity
     // entry is kept if nothing else is left, so that the set is never empty. false: there is nothing to drop.
@@ -325,7 +330,7 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
             // bucket reduce, which 16 windows of 32 768 buckets need: profiles/r03_plain_bases_sweep.txt)
             int c = c_override > 0 ? c_override : (lg <= 8 ? 5 : lg <= 12 ? 8 : lg <= 15 ? 10 : lg <= 18 ? 12 : lg <= 19 ? 14 : 16);
             p.c = c;
-            p.W = (FrC::BITS + c - 1) / c;
+            p.W = windows_of(c);
             p.Wb = p.W;
         }
         p.B = 1u << (p.c - 1);
@@ -565,6 +570,56 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         return MG_OK;
     }
 
+    // ---------------------------------------------------------------- the digit stage alone (parity-test surface)
+    // What msm_launch does up to and including the digit kernel, for a base set that exists as a description only (the kernel
+    // reads no point): the plan of plan_for, the key layout and refusals of launch_reserve, the launch of launch_digits. The pair
+    // arrays start as the caller's, so what the kernel leaves alone comes back untouched. Which layout runs is the caller's choice
+    // here (c.compact), where launch_reserve decides it.
+    int msm_digits(const MsmDigitsCall &c) override {
+        if (!c.scalars || !c.keys || !c.vals || !c.layout || (c.compact && !c.count) || c.n == 0 || c.n_scalars == 0 || c.batch == 0 ||
+            c.batch > 65535 || (c.scalar_mode != SCALARS_CANONICAL && c.scalar_mode != SCALARS_MONT) || c.table_mode < 0 ||
+            c.table_mode > 2 || c.c < 1 || c.c > 24 || (c.table_mode == 2 && (c.c < 2 || c.c > 12)) || c.n_sets == 0 || c.set_len == 0)
+            return MG_ERR_ARG;
+        BaseSet bs; // as bases_create leaves it, without the points
+        bs.curve = CURVE_ID, bs.group = GROUP, bs.device = current_device();
+        bs.n = c.n, bs.n_orig = (size_t)c.n_sets * c.set_len, bs.n_sets = c.n_sets, bs.set_len = c.set_len;
+        if (c.table_mode) bs.pre_c = c.c, bs.pre_W = windows_of(c.c), bs.full = c.table_mode == 2;
+        // the index ranges: stored bases beyond the logical length, scalars beyond a query (msm_launch), a map entry beyond the set
+        if (bs.n > bs.n_orig || (!c.map && bs.n != bs.n_orig) || c.n_scalars > bs.n_orig || (c.n_sets > 1 && c.n_scalars > c.set_len))
+            return MG_ERR_ARG;
+        for (size_t i = 0; c.map && i < c.n; ++i)
+            if (c.map[i] >= bs.n_orig) return MG_ERR_ARG;
+        // (a map in any order is legal for the kernel; the per-query launches need the ascending one bases_create builds)
+        if (!c.map || std::is_sorted(c.map, c.map + c.n)) set_query_ranges(&bs, c.map, c.map ? c.n : 0);
+        Launch r{&bs, nullptr, nullptr, nullptr, nullptr, c.n, c.n_scalars, (size_t)c.n_scalars * 8, c.scalar_mode, c.batch, c.n_sets, c.batch > 1,
+                 c.compact, plan_for(&bs, c.n, c.c, c.batch)};
+        if (const int rc = key_layout(r)) return rc;
+        c.layout[0] = (u32)r.pl.W, c.layout[1] = r.pl.B, c.layout[2] = r.seg_keys, c.layout[3] = r.invalid;
+        hipStream_t s = r.s = setup_stream();
+        if (!s) return MG_ERR_OOM;
+        const size_t sb = (size_t)c.batch * c.n_scalars * 32, pb = r.M * 4;
+        DevBlock m; // scalars | map | keys | vals | pair count
+        if (const int rc = m.alloc({sb, c.map ? (size_t)c.n * 4 : 0, pb, pb, c.compact ? 4u : 0u}, "mg_msm_digits")) return rc;
+        u32 *const d_keys = m.dev<u32>(2), *const d_vals = m.dev<u32>(3);
+        r.d_scalars = m.dev<u32>(0), bs.d_map = m.dev<u32>(1), r.d_count = m.dev<u32>(4);
+        const u32 zero = 0;
+        hipError_t e = hipMemcpyAsync(m.dev(0), c.scalars, sb, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && c.map) e = hipMemcpyAsync(bs.d_map, c.map, (size_t)c.n * 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_keys, c.keys, pb, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_vals, c.vals, pb, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && c.compact) e = hipMemcpyAsync(r.d_count, &zero, 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) {
+            enqueue_digits(r, d_keys, d_vals);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(c.keys, d_keys, pb, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(c.vals, d_vals, pb, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && c.compact) e = hipMemcpyAsync(c.count, r.d_count, 4, hipMemcpyDeviceToHost, s);
+        const hipError_t e2 = hipStreamSynchronize(s);
+        bs.d_map = nullptr; // the block's
+        return e != hipSuccess ? hip_status(e, "mg_msm_digits") : e2 != hipSuccess ? hip_status(e2, "mg_msm_digits") : MG_OK;
+    }
+
     // ---------------------------------------------------------------- fixed-base batch mul
     int fixed_base_mul(const u32 *base_affine_host, const u32 *d_scalars, size_t n, u32 *d_out_affine,
                        hipStream_t s) override {
@@ -760,18 +815,30 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         MsmTail tail;
     };
 
+    // The pair count and the layout of the bucket keys of a launch (r.M, KB, seg_keys, nb, invalid), or MG_ERR_ARG for what the
+    // 32-bit pairs cannot hold: 2^31 pairs, a key space of 2^24, a base index of 2^31.
+    static int key_layout(Launch &r) {
+        const MsmPlan &pl = r.pl;
+        r.M = r.n * (size_t)pl.W * r.batch;
+        // full tables: a digit addresses its summand, every pair of a scalar vector carries the same key and the "bucket" is the result
+        r.KB = pl.full ? 1u : pl.B; // bucket keys per bucket window
+        if (r.M >= (1ull << 31) || (size_t)r.batch * r.nsets * pl.Wb * r.KB >= (1ull << 24)) return MG_ERR_ARG;
+        // with precomputed tables the base index is w*stride + i: table w starts bs->n points after w-1
+        if ((size_t)pl.W * r.bs->n * (pl.full ? pl.B : 1u) >= (1ull << 31)) return MG_ERR_ARG;
+        r.seg_keys = (u32)pl.Wb * r.KB;            // bucket keys per (scalar vector, query)
+        r.nb = r.batch * r.nsets * r.seg_keys;     // real buckets; key nb = INVALID
+        r.invalid = r.nb;
+        return MG_OK;
+    }
+
     // the sizes of the launch, the reservations of everything up to the merge levels, the layout of the keys
     int launch_reserve(Launch &r) {
         MsmWorkspace *const ws = r.ws; const MsmPlan &pl = r.pl;
-        const size_t M = r.M = r.n * (size_t)pl.W * r.batch;
-        // full tables: a digit addresses its summand, every pair of a scalar vector carries the same key and the "bucket" is the result
-        r.KB = pl.full ? 1u : pl.B; // bucket keys per bucket window
-        if (M >= (1ull << 31) || (size_t)r.batch * r.nsets * pl.Wb * r.KB >= (1ull << 24)) return MG_ERR_ARG;
-        if (pl.full) r.sparse = true; // compacting digit kernel: no invalid keys, so a single MSM needs no sort at all
-        const u32 seg_keys = r.seg_keys = (u32)pl.Wb * r.KB; // bucket keys per (scalar vector, query)
-        const u32 nb = r.nb = r.batch * r.nsets * seg_keys;   // real buckets; key nb = INVALID
-        const u32 invalid = r.invalid = nb;
         int rc;
+        if ((rc = key_layout(r))) return rc;
+        const size_t M = r.M;
+        if (pl.full) r.sparse = true; // compacting digit kernel: no invalid keys, so a single MSM needs no sort at all
+        const u32 seg_keys = r.seg_keys, nb = r.nb, invalid = r.invalid;
         if ((rc = ws->keys_in.reserve(M * 4)) || (rc = ws->keys_out.reserve(M * 4)) ||
             (rc = ws->vals_in.reserve(M * 4)) || (rc = ws->vals_out.reserve(M * 4)))
             return rc;
@@ -784,8 +851,6 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
             (rc = ws->ppts[1].reserve((size_t)2 * waves1 * XW * 4)))
             return rc;
 
-        // with precomputed tables the base index is w*stride + i: table w starts bs->n points after w-1
-        if ((size_t)pl.W * r.bs->n * (pl.full ? pl.B : 1u) >= (1ull << 31)) return MG_ERR_ARG;
         int end_bit = 1;
         while ((1u << end_bit) <= invalid) ++end_bit;
         // the fixed layout marks a zero digit with the key `invalid` = one past the last bucket; where that key alone would cost
@@ -827,7 +892,7 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
 
     // the zero-fills, then the digit kernel: (key, value) pairs
     void launch_digits(Launch &r) {
-        MsmWorkspace *const ws = r.ws; const MsmPlan &pl = r.pl; const BaseSet *const bs = r.bs; hipStream_t s = r.s;
+        MsmWorkspace *const ws = r.ws; hipStream_t s = r.s;
         // every zero-fill of this launch, up front (none of the targets is touched by the digit kernel or the sort)
         ZeroRanges zr{};
         zr.p[0] = r.d_count, zr.n[0] = r.d_count ? 1u : 0u;
@@ -837,6 +902,12 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         zr.p[2] = ws->timed ? (u32 *)ws->h_clk : nullptr, zr.n[2] = ws->timed ? 4u : 0u;
         const u32 most = zr.n[1] > 4u ? zr.n[1] : 4u;
         hipLaunchKernelGGL((zero_ranges<F>), dim3(most > 256u * 1024u ? 1024u : cdiv(most, 256)), dim3(256), 0, s, zr);
+        enqueue_digits(r, ws->keys_in.as<u32>(), ws->vals_in.as<u32>());
+        r.batch *= r.nsets; // from here on every (vector, query) pair is a vector of its own: its keys, its window sums, its result
+    }
+    // the digit kernel of a launch, writing its pairs to (keys, vals); sets r.per_query
+    static void enqueue_digits(Launch &r, u32 *keys, u32 *vals) {
+        const MsmPlan &pl = r.pl; const BaseSet *const bs = r.bs; hipStream_t s = r.s;
         // compacting path: fewer, larger workgroups = fewer atomics on the counter
         const u32 dthreads = r.d_count ? msm_knobs().digits_threads : 256u;
         // Concatenated queries on full tables, ONE scalar vector (the a | b_g1 | l MSM of a single proof): every pair's key is its
@@ -851,16 +922,15 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
                 const u32 lo = bs->set_first[q], hi = bs->set_first[q + 1];
                 if (hi <= lo) continue;
                 hipLaunchKernelGGL((digits_kernel<FrC>), dim3(cdiv(hi - lo, dthreads), 1), dim3(dthreads), 0, s, r.d_scalars, hi, pl.c,
-                                   pl.W, pl.B, 2, (u32)bs->n, r.scalar_mode, r.invalid, ws->keys_in.as<u32>(), ws->vals_in.as<u32>(),
+                                   pl.W, pl.B, 2, (u32)bs->n, r.scalar_mode, r.invalid, keys, vals,
                                    (const u32 *)bs->d_map, (u32)r.n_scalars, r.scalar_stride_words, r.seg_keys, r.d_count, nsets,
                                    (u32)bs->set_len, lo);
             }
         } else
             hipLaunchKernelGGL((digits_kernel<FrC>), dim3(cdiv(r.n, dthreads), r.batch), dim3(dthreads), 0, s, r.d_scalars, (u32)r.n,
                                pl.c, pl.W, pl.B, pl.full ? 2 : (pl.precomp ? 1 : 0), (u32)bs->n, r.scalar_mode, r.invalid,
-                               ws->keys_in.as<u32>(), ws->vals_in.as<u32>(), (const u32 *)bs->d_map, (u32)r.n_scalars,
+                               keys, vals, (const u32 *)bs->d_map, (u32)r.n_scalars,
                                r.scalar_stride_words, r.seg_keys, r.d_count, nsets, (u32)bs->set_len);
-        r.batch *= nsets; // from here on every (vector, query) pair is a vector of its own: its keys, its window sums, its result
     }
 
     int launch_sort(Launch &r) {

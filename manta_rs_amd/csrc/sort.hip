@@ -26,8 +26,11 @@ static constexpr int SORT_ITEMS = 16;
 // vector q + 1's) with key = q * seg + bucket, seg a power of two: a STABLE sort by the bucket bits alone leaves every (q, bucket)
 // run contiguous -- order (bucket, q) instead of (q, bucket), which the run-detecting consumers do not care about -- and saves the
 // passes over the vector bits (the dense h MSM of 32 proofs: 14 bits = two passes instead of 19 = three over 40 M pairs). Keys
-// from `inv_from` up (the invalid key of zero digits) sort behind every bucket. lowmask = inv_from = ~0: the identity.
-__device__ __forceinline__ u32 sort_key(u32 k, u32 lowmask, u32 inv_from) { return k >= inv_from ? lowmask + 1u : (k & lowmask); }
+// from `inv_from` up (the invalid key of zero digits) sort behind every bucket. lowmask = ~0: the identity -- there is no value
+// behind the masked keys then, and lowmask + 1 would send the key ~0 to the FRONT of a 32-bit sort.
+__device__ __forceinline__ u32 sort_key(u32 k, u32 lowmask, u32 inv_from) {
+    return (k >= inv_from && lowmask != 0xffffffffu) ? lowmask + 1u : (k & lowmask);
+}
 
 // (`count`: when non-null the number of elements is read from the device -- the MSM's digit kernel compacts
 // away zero digits and only it knows how many pairs are left; the grid is sized for the maximum and tiles

@@ -297,6 +297,35 @@ extern "C" {
         n: usize,
         out: *mut u64,
     ) -> c_int;
+    pub fn mg_msm_digits(
+        curve: mg_curve_t,
+        scalars: *const u64,
+        batch: usize,
+        n_scalars: usize,
+        scalar_flags: c_int,
+        window_bits: c_int,
+        table_mode: c_int,
+        n: usize,
+        map: *const u32,
+        n_sets: usize,
+        set_len: usize,
+        compact: c_int,
+        keys: *mut u32,
+        vals: *mut u32,
+        count: *mut u32,
+        layout: *mut u32,
+    ) -> c_int;
+    pub fn mg_sort_pairs(
+        keys: *const u32,
+        vals: *const u32,
+        n: usize,
+        end_bit: c_int,
+        count: *const u32,
+        lowmask: u32,
+        inv_from: u32,
+        keys_out: *mut u32,
+        vals_out: *mut u32,
+    ) -> c_int;
     pub fn mg_group_ntt(
         curve: mg_curve_t,
         group: c_int,

@@ -194,6 +194,56 @@ def test_proof_decode_rejects_what_ark_serialize_rejects():
             api.proof_decode(curve, bytes(c0_big))
 
 
+def test_msm_frontend_entry_points_reject_bad_arguments_before_any_device_work():
+    """mg_msm_digits refuses what an MSM launch refuses (2^31 pairs, a key space of 2^24, a base index of 2^31, index ranges that
+    contradict each other) and mg_sort_pairs what the sort does (end_bit outside 1..32, a count above n): MG_ERROR_INVALID_ARGUMENT
+    from the argument checks, which run before the first allocation (this test has no GPU)."""
+    import ctypes
+    from manta_rs_amd import api
+    sz, u32 = ctypes.c_size_t, ctypes.c_uint32
+    sc = np.ones((2, 4), dtype=np.uint64)
+    buf = np.zeros(64, dtype=np.uint32)
+    layout, cnt = (u32 * 4)(), u32(0)
+
+    def digits(curve=0, scalars=sc, batch=1, n_scalars=2, flags=0, c=8, table=0, n=2, map=None, n_sets=1, set_len=2, compact=0, keys=buf,
+               vals=buf, count=None, lay=layout):
+        return api.LIB.mg_msm_digits(curve, api._p(scalars), sz(batch), sz(n_scalars), flags, c, table, sz(n), api._p(map), sz(n_sets),
+                                     sz(set_len), compact, api._p(keys), api._p(vals), ctypes.byref(count) if count is not None else None, lay)
+
+    bad_map = np.array([0, 4], dtype=np.uint32)
+    refused = dict(
+        curve=digits(curve=2), no_scalars=digits(scalars=None), no_keys=digits(keys=None), no_vals=digits(vals=None), no_layout=digits(lay=None),
+        compact_without_count=digits(compact=1), flags=digits(flags=2), c0=digits(c=0), c25=digits(c=25), table3=digits(table=3),
+        full_c13=digits(table=2, c=13), full_c1=digits(table=2, c=1), batch0=digits(batch=0), batch_65536=digits(batch=65536), n0=digits(n=0, set_len=0),
+        no_scalar=digits(n_scalars=0), sets0=digits(n_sets=0),
+        # index ranges
+        n_is_not_the_set=digits(n=2, set_len=3), scalars_beyond_the_set=digits(n_scalars=3), scalars_beyond_a_query=digits(n=4, n_sets=2, n_scalars=3),
+        map_entry_beyond_the_set=digits(map=bad_map, n_sets=2), more_stored_than_entries=digits(n=2, set_len=1, map=np.zeros(2, dtype=np.uint32)),
+        # BLS12-381, c = 17, plain bases: 15 x 65 536 keys per vector, 18 vectors >= 2^24
+        key_space=digits(curve=1, c=17, batch=18, scalars=np.ones((36, 4), dtype=np.uint64)),
+        # c = 2: 127 windows x 2^24 bases x 2 vectors = 2^32 pairs
+        pairs=digits(c=2, n=1 << 24, set_len=1 << 24, n_scalars=1, batch=2),
+        # full tables, c = 12: 22 windows x 50 000 bases x 2 048 multiples >= 2^31 table entries
+        base_index=digits(table=2, c=12, n=50000, set_len=50000),
+    )
+    assert refused == {k: 1 for k in refused}, refused
+
+    def sort(keys=buf, vals=buf, n=64, end_bit=8, count=None, ko=buf, vo=buf):
+        return api.LIB.mg_sort_pairs(api._p(keys), api._p(vals), sz(n), end_bit, ctypes.byref(u32(count)) if count is not None else None,
+                                     u32(0xFFFFFFFF), u32(0xFFFFFFFF), api._p(ko), api._p(vo))
+
+    refused = dict(no_keys=sort(keys=None), no_vals=sort(vals=None), no_keys_out=sort(ko=None), no_vals_out=sort(vo=None), end_bit0=sort(end_bit=0),
+                   end_bit33=sort(end_bit=33), count_above_n=sort(count=65), n_2_32=sort(n=1 << 32))
+    assert refused == {k: 1 for k in refused}, refused
+    assert sort(n=0) == 0  # nothing to sort, nothing allocated
+    try:
+        gpus = api.device_count()
+    except api.MantaGpuError:
+        gpus = 0
+    if gpus == 0:  # well-formed calls reach the device and report ITS refusal: there is no host path behind either entry point
+        assert digits(count=cnt, compact=1) in (2, 3) and digits() in (2, 3) and sort() in (2, 3)
+
+
 def test_rust_patch_has_no_panic_on_upload_failure():
     """mantagpu.h promises status codes ("no exceptions, no abort") and the reference's `ProvingContext::new` cannot fail:
     the patch to groth16.rs must not `.expect(...)` the upload -- it defers it to the first `prove`, whose `Result` carries
