@@ -421,6 +421,15 @@ int mg_blake3(const uint8_t *data, size_t len, uint8_t out32[32]);
 /* Blake2s-256 (RFC 7693; unkeyed, no salt, no personalisation -- the reference's `Blake2s256::new()`): host code, any length,
  * compiled from the same source as the hash of the signature kernels below. */
 int mg_blake2s256(const uint8_t *data, size_t len, uint8_t out32[32]);
+/* The same hash with a digest of out_len bytes, 1..32 (`Blake2sVar::new(out_len)`; the length is part of the parameter word, so
+ * this is no prefix of the 32-byte digest; out_len = 32 is mg_blake2s256), and AES-256-GCM with a 12-byte nonce, no associated
+ * data and a 16-byte tag (the `aes-gcm` crate's `Aead`): host code, any length, compiled from the same sources as the note
+ * kernels at the end of this header. decrypt = 0: `in` is len bytes of plaintext, `out` gets len + 16 (ciphertext | tag).
+ * decrypt != 0: `in` is ciphertext | tag (len >= 16), `out` gets len - 16 bytes, *ok = the tag verified; where it did not, the
+ * output is zeros. `ok` may be NULL when encrypting. */
+int mg_blake2s(const uint8_t *data, size_t len, size_t out_len, uint8_t *out);
+int mg_aes256_gcm(const uint8_t key[32], const uint8_t nonce[12], const uint8_t *in, size_t len, int decrypt, uint8_t *out,
+                  int *ok);
 /* Once per circuit shape: the matrices of `cs.to_matrices()` (identical for every proof of a shape). Validated
  * in full before anything changes (row_ptr monotone from 0 to nnz, column indices < V); a rejected call leaves
  * the context as it was. */
@@ -614,8 +623,9 @@ int mg_notes_encrypt(const mg_note_cipher *h, const uint64_t *recv_keys_affine_m
 #define MG_NOTE_OK 0
 #define MG_NOTE_BAD_TAG 1   /* the recomputed tag differs: not this key's note, or altered */
 #define MG_NOTE_BAD_VALUE 2 /* the tag matches but the asset value word is 2^128 or more (`try_into_u128`, utxo.rs:716-731) */
-/* `NoteOpen::open` of n notes against one viewing key: the sponge is keyed by epks[i] * viewing_key; ok[i] = 1 iff the note
- * opens (status[i] = MG_NOTE_OK; status may be NULL), and the plaintext of a note that does not is zeros. */
+/* Decryption of n Poseidon notes against one viewing key: the sponge is keyed by epks[i] * viewing_key; ok[i] = 1 iff the note
+ * opens (status[i] = MG_NOTE_OK; status may be NULL), and the plaintext of a note that does not is zeros. (The scan a wallet
+ * runs, `NoteOpen::open`, reads the light note and not this one: mg_light_notes_open below.) */
 int mg_notes_decrypt(const mg_note_cipher *h, const uint64_t *viewing_key, const uint64_t *epks_affine_mont,
                      const uint64_t *ciphertexts_mont, const uint64_t *tags_mont, size_t n, uint64_t *plaintext_out_mont,
                      uint8_t *ok, uint8_t *status);
@@ -663,8 +673,8 @@ typedef struct mg_utxo_model mg_utxo_model;
 int mg_utxo_model_create(mg_curve_t curve, const mg_utxo_files *files, mg_utxo_model **out);
 void mg_utxo_model_destroy(mg_utxo_model *h);
 /* The sender's side of `derive_mint`: plaintexts hold the whole asset, flags[i] (a byte, 0 / 1) says which half is secret ->
- * the records (n x 16 u64), their items (n x 4) and status[i] = MG_UTXO_OK / MG_UTXO_BAD_ENCODING. With mg_notes_encrypt this
- * is `derive_mint` but for the AES light note and the address partition. Every array must be given. */
+ * the records (n x 16 u64), their items (n x 4) and status[i] = MG_UTXO_OK / MG_UTXO_BAD_ENCODING. With mg_notes_encrypt,
+ * mg_light_notes_encrypt and mg_address_partitions this is the whole of `derive_mint`. Every array must be given. */
 int mg_utxos_mint(const mg_utxo_model *h, const uint64_t *recv_keys_affine_mont, const uint64_t *plaintexts_mont,
                   const uint8_t *flags, size_t n, uint64_t *utxos_out_mont, uint64_t *items_out_mont, uint8_t *status);
 /* The receiver's side: `utxo_check` of n opened notes against the ledger's records for the address viewing_key * G (computed
@@ -721,6 +731,63 @@ int mg_signatures_verify(const mg_utxo_model *h, const uint64_t *pks_affine_mont
 int mg_signatures_sign(const mg_utxo_model *h, const uint64_t *signing_keys, const uint64_t *nonces, const uint8_t *messages,
                        size_t stride, const uint32_t *lengths, size_t n, uint64_t *scalars_out,
                        uint64_t *nonce_points_out_affine_mont, uint64_t *pks_out_affine_mont);
+
+/* ---- manta-pay's AES-GCM notes, its address partition and its Merkle shard index, one note, key or leaf per GPU lane. What
+ *      `NoteOpen::open` (manta-accounting/src/transfer/utxo/protocol.rs:1396-1434), `NullifierOpen::open` (1371-1394) and the
+ *      note halves of `derive_mint` / `derive_spend` (1330-1340) run: `IncomingBaseAES` and `OutgoingBaseAES`
+ *      (manta-pay/src/config/utxo.rs:760-1031, 1511-1777; manta-pay/src/crypto/encryption/aes.rs), `AddressPartitionFunction`
+ *      (utxo.rs:1810-1831) and the shard function of the UTXO Merkle forest (utxo.rs:1319-1337). Only MG_BN254. The handle is
+ *      the UTXO model above: the calls use its generator table and need no parameter file of their own.
+ *        key        = Blake2s-256(enc(K)), K the agreed point: recv_key * randomness when encrypting, epk * viewing_key when
+ *                     opening; enc = the 32 bytes mg_edwards_encode writes. Keys and agreed points never leave the device.
+ *        cipher     = AES-256-GCM, nonce "random nonce" (12 bytes), no associated data; a note crosses as ciphertext | tag
+ *        light note = randomness | asset id (32 bytes little-endian canonical each) | asset value (u128, 16 bytes little-endian):
+ *                     80 -> MG_LIGHT_NOTE_BYTES; across this ABI the plaintext is the three Montgomery elements of the Poseidon
+ *                     note calls, and the ephemeral key is that note's (`light_incoming_randomness()` clones the randomness)
+ *        outgoing   = asset id | asset value: 48 -> MG_OUTGOING_NOTE_BYTES; two Montgomery elements per note; it is sealed to
+ *                     the spender's own receiving key, one per call
+ *        partition  = Blake2s with a ONE-byte digest over "manta-v1.0.0/address-partition-function" | x | y of the receiving
+ *                     key, 32 bytes little-endian canonical each (`serialize_unchecked` of the affine point). That this is plain
+ *                     x | y with no flag bits, the identity (0, 1) included, restates ark-ec 0.3 from memory and is not
+ *                     confirmed by any file of the reference.
+ *        shard      = the same hash over "manta-v1.0.0/merkle-tree-shard-function" | leaf: the byte a caller needs per leaf
+ *                     to build the `offsets` of mg_merkle_forest_roots
+ *      Per-lane status: the MG_NOTE_* above and MG_NOTE_OTHER_PARTITION. MG_NOTE_BAD_VALUE when encrypting is a value word of
+ *      2^128 or more; when opening it is a verified tag over randomness or id bytes that are not below r (the reference
+ *      `.expect()`s there). A lane that is not MG_NOTE_OK returns zeros in every output of that lane.
+ *      MG_ERROR_INVALID_ARGUMENT before any device work: a NULL required array or model, a randomness or viewing key >= l, the
+ *      outgoing receiving key off the curve or unreduced, an n whose arrays would wrap a size_t. Coordinates of the other
+ *      points must be reduced; points off the curve give meaningless notes (mg_edwards_check tells). n = 0 succeeds.
+ *      Synchronous, thread-safe, on the calling thread's setup stream, nothing on the NULL stream, MG_EDWARDS_CHUNK lanes at a
+ *      time (device memory of a call < 32 MiB whatever n). ------------------------------------------------------------------ */
+#define MG_NOTE_OTHER_PARTITION 3 /* mg_light_notes_open with partitions: the note carries another address's byte; not tried */
+#define MG_LIGHT_NOTE_BYTES 96
+#define MG_OUTGOING_NOTE_BYTES 64
+/* n receiving keys (n x 8 u64) -> n bytes; n leaves (n x 4 u64 Montgomery) -> n bytes */
+int mg_address_partitions(const mg_utxo_model *h, const uint64_t *recv_keys_affine_mont, size_t n, uint8_t *out);
+int mg_merkle_shard_indices(mg_curve_t curve, const uint64_t *leaves_mont, size_t n, uint8_t *out);
+/* The light note of `derive_mint`: n notes (n x MG_LIGHT_NOTE_BYTES) and status[i] = MG_NOTE_OK / MG_NOTE_BAD_VALUE; the
+ * ephemeral keys G * randomness[i], unless NULL, equal those of mg_notes_encrypt for the same randomness. Every other array
+ * must be given. */
+int mg_light_notes_encrypt(const mg_utxo_model *h, const uint64_t *recv_keys_affine_mont, const uint64_t *randomness,
+                           const uint64_t *plaintexts_mont, size_t n, uint64_t *epk_out_affine_mont /* may be NULL */,
+                           uint8_t *ciphertexts_out, uint8_t *status);
+/* `NoteOpen::open` of n ledger notes against one viewing key. With `partitions` (the notes' partition bytes) the call computes
+ * its own byte once on the host (viewing_key * G from the model's table, then the hash), and only the lanes that carry it go
+ * through a key agreement and the cipher: they are gathered before the device passes. Every other lane is
+ * MG_NOTE_OTHER_PARTITION whatever its ciphertext holds. partitions = NULL tries every lane. ok[i] = 1 iff status[i] =
+ * MG_NOTE_OK (status may be NULL); *n_tried (may be NULL) = the lanes that went through a key agreement. */
+int mg_light_notes_open(const mg_utxo_model *h, const uint64_t *viewing_key, const uint64_t *epks_affine_mont,
+                        const uint8_t *ciphertexts, const uint8_t *partitions /* may be NULL */, size_t n,
+                        uint64_t *plaintext_out_mont, uint8_t *ok, uint8_t *status, size_t *n_tried /* may be NULL */);
+/* The outgoing note of `derive_spend`, sealed to ONE receiving key (the spender's own): its fixed-base table is built on the
+ * host for the call, so both products of a lane are table products. Every array must be given. */
+int mg_outgoing_notes_encrypt(const mg_utxo_model *h, const uint64_t *recv_key_affine_mont /* one */, const uint64_t *randomness,
+                              const uint64_t *assets_mont, size_t n, uint64_t *epk_out_affine_mont, uint8_t *ciphertexts_out,
+                              uint8_t *status);
+/* `NullifierOpen::open`: n outgoing notes against one viewing key -> the assets (n x 8 u64); status may be NULL */
+int mg_outgoing_notes_open(const mg_utxo_model *h, const uint64_t *viewing_key, const uint64_t *epks_affine_mont,
+                           const uint8_t *ciphertexts, size_t n, uint64_t *assets_out_mont, uint8_t *ok, uint8_t *status);
 
 #ifdef __cplusplus
 }

@@ -79,6 +79,8 @@ EXPORTS = [
     "mg_note_cipher_create", "mg_note_cipher_destroy", "mg_notes_encrypt", "mg_notes_decrypt",
     "mg_utxo_model_create", "mg_utxo_model_destroy", "mg_utxos_mint", "mg_utxos_open", "mg_viewing_keys",
     "mg_blake2s256", "mg_schnorr_challenges", "mg_signatures_verify", "mg_signatures_sign",
+    "mg_blake2s", "mg_aes256_gcm", "mg_address_partitions", "mg_merkle_shard_indices",
+    "mg_light_notes_encrypt", "mg_light_notes_open", "mg_outgoing_notes_encrypt", "mg_outgoing_notes_open",
 ]
 
 
@@ -360,11 +362,38 @@ def blake3(data: bytes) -> bytes:
     return out.raw
 
 
-def blake2s(data: bytes) -> bytes:
-    """Blake2s-256 (RFC 7693, unkeyed), computed by the library's host code from the source the signature kernels compile"""
+def blake2s(data: bytes, digest_size=None) -> bytes:
+    """Blake2s-256 (RFC 7693, unkeyed), computed by the library's host code from the source the signature kernels compile; with
+    digest_size (1..32) the same hash with a digest of that length (`mg_blake2s`), which is no prefix of the 32-byte one"""
+    if digest_size is None:
+        out = ctypes.create_string_buffer(32)
+        _chk(LIB.mg_blake2s256(bytes(data), _sz(len(data)), out), "mg_blake2s256")
+        return out.raw
     out = ctypes.create_string_buffer(32)
-    _chk(LIB.mg_blake2s256(bytes(data), _sz(len(data)), out), "mg_blake2s256")
+    _chk(LIB.mg_blake2s(bytes(data), _sz(len(data)), _sz(int(digest_size)), out), "mg_blake2s")
+    return out.raw[:int(digest_size)]
+
+
+def aes256_gcm_encrypt(key: bytes, nonce: bytes, plaintext: bytes) -> bytes:
+    """AES-256-GCM, 12-byte nonce, no associated data -> ciphertext | 16-byte tag; the library's host code, compiled from the
+    source the note kernels compile (`mg_aes256_gcm`)"""
+    key, nonce, plaintext = bytes(key), bytes(nonce), bytes(plaintext)
+    if len(key) != 32 or len(nonce) != 12:
+        raise ValueError("aes256_gcm: a 32-byte key and a 12-byte nonce")
+    out = ctypes.create_string_buffer(len(plaintext) + 16)
+    _chk(LIB.mg_aes256_gcm(key, nonce, plaintext, _sz(len(plaintext)), 0, out, None), "mg_aes256_gcm")
     return out.raw
+
+
+def aes256_gcm_decrypt(key: bytes, nonce: bytes, sealed: bytes):
+    """ciphertext | tag -> (plaintext, ok); the plaintext is zeros where the tag does not verify (`mg_aes256_gcm`)"""
+    key, nonce, sealed = bytes(key), bytes(nonce), bytes(sealed)
+    if len(key) != 32 or len(nonce) != 12 or len(sealed) < 16:
+        raise ValueError("aes256_gcm: a 32-byte key, a 12-byte nonce and at least the 16 bytes of a tag")
+    out = ctypes.create_string_buffer(max(1, len(sealed) - 16))
+    ok = ctypes.c_int(0)
+    _chk(LIB.mg_aes256_gcm(key, nonce, sealed, _sz(len(sealed)), 1, out, ctypes.byref(ok)), "mg_aes256_gcm")
+    return out.raw[:len(sealed) - 16], bool(ok.value)
 
 
 def xyzz_limbs(curve, group) -> int:
@@ -1042,7 +1071,8 @@ def merkle_forest_roots(hasher: PoseidonHasher, height, leaves, offsets) -> np.n
 EDWARDS_CHUNK = 1 << 16  # MG_EDWARDS_CHUNK: lanes per device pass
 EDWARDS_ORDER = 2736030358979909402780800718157159386076813972158567259200215660948447373041  # l, the subgroup order
 EDWARDS_MUL_SHARED_SCALAR, EDWARDS_MUL_FIXED_BASE, EDWARDS_MUL_PAIRWISE = 0, 1, 2
-NOTE_OK, NOTE_BAD_TAG, NOTE_BAD_VALUE = 0, 1, 2
+NOTE_OK, NOTE_BAD_TAG, NOTE_BAD_VALUE, NOTE_OTHER_PARTITION = 0, 1, 2, 3
+LIGHT_NOTE_BYTES, OUTGOING_NOTE_BYTES = 96, 64  # MG_LIGHT_NOTE_BYTES, MG_OUTGOING_NOTE_BYTES: ciphertext | tag
 
 
 def _ed_points(points):
@@ -1278,6 +1308,72 @@ class UtxoModel:
              "mg_signatures_sign")
         return s, rp, pk
 
+    def address_partitions(self, recv_keys) -> np.ndarray:
+        """`AddressPartitionFunction::partition` of n receiving keys [n, 8] -> [n] uint8 (`mg_address_partitions`)"""
+        rk = _ed_points(recv_keys)
+        out = np.zeros(rk.shape[0], dtype=np.uint8)
+        _chk(LIB.mg_address_partitions(self._h, _p(rk), _sz(rk.shape[0]), _p(out)), "mg_address_partitions")
+        return out
+
+    def light_encrypt(self, recv_keys, randomness, plaintexts, epks=True):
+        """the AES-GCM light notes of n outputs: recv_keys [n, 8], randomness [n, 4] scalars, plaintexts [n, 3, 4] Montgomery ->
+        (epk [n, 8] or None, notes [n, LIGHT_NOTE_BYTES] uint8 ciphertext | tag, status [n] uint8 NOTE_*; zeros where the
+        status is not NOTE_OK) (`mg_light_notes_encrypt`)"""
+        rk, rnd, pt = _ed_points(recv_keys), _u64(randomness).reshape(-1, 4), _u64(plaintexts).reshape(-1, 3, 4)
+        n = rk.shape[0]
+        if rnd.shape[0] != n or pt.shape[0] != n:
+            raise ValueError("light_encrypt: one key, one randomness and one plaintext per note")
+        epk = np.zeros((n, 8), dtype=np.uint64) if epks else None
+        ct, st = np.zeros((n, LIGHT_NOTE_BYTES), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        _chk(LIB.mg_light_notes_encrypt(self._h, _p(rk), _p(rnd), _p(pt), _sz(n), _p(epk), _p(ct), _p(st)), "mg_light_notes_encrypt")
+        return epk, ct, st
+
+    def light_open(self, viewing_key, epks, notes, partitions=None):
+        """`NoteOpen::open` of n light notes [n, LIGHT_NOTE_BYTES] against one viewing key ([4] scalar); with partitions [n] uint8
+        only the notes that carry the byte of viewing_key * G are tried -> (plaintext [n, 3, 4], zeros where the note does not
+        open; ok [n] bool; status [n] uint8 NOTE_*; n_tried) (`mg_light_notes_open`)"""
+        vk, ep = _u64(viewing_key).reshape(-1), _ed_points(epks)
+        ct = np.ascontiguousarray(notes, dtype=np.uint8).reshape(-1, LIGHT_NOTE_BYTES)
+        n = ep.shape[0]
+        if vk.size != 4 or ct.shape[0] != n:
+            raise ValueError("light_open: one viewing key; one epk and one note per lane")
+        if partitions is not None:
+            partitions = np.ascontiguousarray(partitions, dtype=np.uint8).reshape(-1)
+            if partitions.shape[0] != n:
+                raise ValueError("partitions: one byte per note")
+        pt = np.zeros((n, 3, 4), dtype=np.uint64)
+        ok, st = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        tried = _sz(0)
+        _chk(LIB.mg_light_notes_open(self._h, _p(vk), _p(ep), _p(ct), _p(partitions), _sz(n), _p(pt), _p(ok), _p(st),
+                                     ctypes.byref(tried)), "mg_light_notes_open")
+        return pt, ok.astype(bool), st, int(tried.value)
+
+    def outgoing_encrypt(self, recv_key, randomness, assets):
+        """the outgoing notes of n spends, sealed to the spender's own receiving key ([8], one): randomness [n, 4] scalars,
+        assets [n, 2, 4] Montgomery (id | value) -> (epk [n, 8], notes [n, OUTGOING_NOTE_BYTES] uint8, status [n] uint8 NOTE_*)
+        (`mg_outgoing_notes_encrypt`)"""
+        rk, rnd, a = _u64(recv_key).reshape(-1), _u64(randomness).reshape(-1, 4), _u64(assets).reshape(-1, 2, 4)
+        n = rnd.shape[0]
+        if rk.size != 8 or a.shape[0] != n:
+            raise ValueError("outgoing_encrypt: one receiving key; one randomness and one asset per note")
+        epk, ct, st = np.zeros((n, 8), dtype=np.uint64), np.zeros((n, OUTGOING_NOTE_BYTES), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        _chk(LIB.mg_outgoing_notes_encrypt(self._h, _p(rk), _p(rnd), _p(a), _sz(n), _p(epk), _p(ct), _p(st)),
+             "mg_outgoing_notes_encrypt")
+        return epk, ct, st
+
+    def outgoing_open(self, viewing_key, epks, notes):
+        """`NullifierOpen::open` of n outgoing notes [n, OUTGOING_NOTE_BYTES] against one viewing key -> (assets [n, 2, 4], zeros
+        where the note does not open; ok [n] bool; status [n] uint8 NOTE_*) (`mg_outgoing_notes_open`)"""
+        vk, ep = _u64(viewing_key).reshape(-1), _ed_points(epks)
+        ct = np.ascontiguousarray(notes, dtype=np.uint8).reshape(-1, OUTGOING_NOTE_BYTES)
+        n = ep.shape[0]
+        if vk.size != 4 or ct.shape[0] != n:
+            raise ValueError("outgoing_open: one viewing key; one epk and one note per lane")
+        a = np.zeros((n, 2, 4), dtype=np.uint64)
+        ok, st = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        _chk(LIB.mg_outgoing_notes_open(self._h, _p(vk), _p(ep), _p(ct), _sz(n), _p(a), _p(ok), _p(st)), "mg_outgoing_notes_open")
+        return a, ok.astype(bool), st
+
     def close(self):
         if self._h is not None and self._h.value:
             LIB.mg_utxo_model_destroy(self._h)
@@ -1288,6 +1384,15 @@ class UtxoModel:
             self.close()
         except Exception:
             pass
+
+
+def merkle_shard_indices(leaves, curve=BN254) -> np.ndarray:
+    """the shard of the UTXO Merkle forest each of n leaves [n, 4] (Montgomery) belongs to -> [n] uint8: what a caller sorts the
+    leaves by to build the `offsets` of merkle_forest_roots (`mg_merkle_shard_indices`)"""
+    lv = _u64(leaves).reshape(-1, 4)
+    out = np.zeros(lv.shape[0], dtype=np.uint8)
+    _chk(LIB.mg_merkle_shard_indices(curve, _p(lv), _sz(lv.shape[0]), _p(out)), "mg_merkle_shard_indices")
+    return out
 
 
 class VerifyingContext:

@@ -1,6 +1,9 @@
-// Blake2s-256 (RFC 7693), unkeyed, no salt, no personalisation: the hash of manta-pay's Schnorr challenge
-// (manta-pay/src/config/utxo.rs `SchnorrHashFunction`: `Blake2s256::new()`, updates, `finalize`). One source for the kernel
-// (schnorr_bn254.hip) and for host code (mg_blake2s256): plain C++, no HIP header needed on the host.
+// Blake2s (RFC 7693), unkeyed, no salt, no personalisation: with the 32-byte digest the hash of manta-pay's Schnorr challenge
+// (manta-pay/src/config/utxo.rs `SchnorrHashFunction`: `Blake2s256::new()`, updates, `finalize`) and of its AES note keys, with a
+// one-byte digest (`Blake2sVar::new(1)`) its address partition and Merkle shard functions. The digest length is part of the
+// parameter word, so a shorter digest is another hash and not a prefix of the longer one. One source for the kernels
+// (schnorr_bn254.hip, light_note_bn254.hip) and for host code (mg_blake2s256, mg_blake2s): plain C++, no HIP header needed on the
+// host.
 //
 // The stream is presented as 32-bit little-endian words: a source `W` answers `w.template word<J>(b)` = word J of block b,
 // with the bytes past the end of the stream zero. J is a template argument, so the sixteen message words of a block are
@@ -21,7 +24,7 @@
 namespace mg {
 namespace blake2s {
 
-// h0 of the unkeyed 32-byte digest = IV[0] ^ 0x01010020 (fanout 1, depth 1, digest length 32)
+// h0 of an unkeyed digest of k bytes = IV[0] ^ 0x01010000 ^ k (fanout 1, depth 1, no key, digest length k)
 constexpr uint32_t IV[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
 constexpr int SIGMA[10][16] = {
     {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3},
@@ -54,8 +57,8 @@ template <int R> MG_B2S_FN void round(uint32_t (&v)[16], const uint32_t (&m)[16]
     g(v[3], v[4], v[9], v[14], m[SIGMA[R][14]], m[SIGMA[R][15]]);
 }
 
-MG_B2S_FN void init(uint32_t (&h)[8]) {
-    h[0] = IV[0] ^ 0x01010020u;
+MG_B2S_FN void init(uint32_t (&h)[8], uint32_t out_len = 32) {
+    h[0] = IV[0] ^ 0x01010000u ^ out_len;
     h[1] = IV[1], h[2] = IV[2], h[3] = IV[3], h[4] = IV[4], h[5] = IV[5], h[6] = IV[6], h[7] = IV[7];
 }
 
@@ -73,11 +76,12 @@ template <class W, int... J> MG_B2S_FN void fill(uint32_t (&m)[16], const W &w, 
     ((m[J] = w.template word<J>(b)), ...);
 }
 
-// The digest of a stream of `total` bytes as eight words (byte 4 i of the digest = the low byte of out[i]). The final block is
+// The digest of a stream of `total` bytes as eight words (byte 4 i of the digest = the low byte of out[i]; a digest of
+// out_len < 32 bytes is the first out_len of these). The final block is
 // the last one that holds a byte of the stream -- a stream of a non-zero multiple of 64 bytes finalises its last full block,
 // there is no extra empty one -- and the empty stream is one zero block with t = 0.
-template <class W> MG_B2S_FN void digest(uint64_t total, const W &w, uint32_t (&out)[8]) {
-    init(out);
+template <class W> MG_B2S_FN void digest(uint64_t total, const W &w, uint32_t (&out)[8], uint32_t out_len = 32) {
+    init(out, out_len);
     const uint64_t blocks = total ? (total + 63) / 64 : 1;
     for (uint64_t b = 0; b < blocks; ++b) {
         uint32_t m[16];
@@ -99,10 +103,10 @@ struct Bytes {
     }
 };
 
-inline void hash(const uint8_t *data, size_t len, uint8_t out[32]) {
+inline void hash(const uint8_t *data, size_t len, uint8_t *out, size_t out_len = 32) { // out_len in 1..32
     uint32_t h[8];
-    digest(len, Bytes{data, len}, h);
-    for (int i = 0; i < 32; ++i) out[i] = (uint8_t)(h[i >> 2] >> (8 * (i & 3)));
+    digest(len, Bytes{data, len}, h, (uint32_t)out_len);
+    for (size_t i = 0; i < out_len; ++i) out[i] = (uint8_t)(h[i >> 2] >> (8 * (i & 3)));
 }
 
 } // namespace blake2s

@@ -9,6 +9,7 @@
 #include "edwards.h"
 #include "utxo.h"
 #include "schnorr.h"
+#include "light_note.h"
 #include <cstring>
 #include <new>
 #include <vector>
@@ -1013,6 +1014,55 @@ MG_API int mg_viewing_keys(const mg_utxo_model *h, const uint64_t *paks_affine_m
                            uint64_t *recv_keys_out_affine_mont) {
     MG_TRY
     return viewing_keys(h, paks_affine_mont, n, viewing_keys_out, recv_keys_out_affine_mont);
+    MG_CATCH
+}
+
+MG_API int mg_blake2s(const uint8_t *data, size_t len, size_t out_len, uint8_t *out) {
+    MG_TRY
+    return blake2s_var(data, len, out_len, out);
+    MG_CATCH
+}
+MG_API int mg_aes256_gcm(const uint8_t key[32], const uint8_t nonce[12], const uint8_t *in, size_t len, int decrypt, uint8_t *out,
+                         int *ok) {
+    MG_TRY
+    return aes256_gcm(key, nonce, in, len, decrypt, out, ok);
+    MG_CATCH
+}
+MG_API int mg_address_partitions(const mg_utxo_model *h, const uint64_t *recv_keys_affine_mont, size_t n, uint8_t *out) {
+    MG_TRY
+    return address_partitions(h, recv_keys_affine_mont, n, out);
+    MG_CATCH
+}
+MG_API int mg_merkle_shard_indices(mg_curve_t curve, const uint64_t *leaves_mont, size_t n, uint8_t *out) {
+    MG_TRY
+    return merkle_shard_indices((int)curve, leaves_mont, n, out);
+    MG_CATCH
+}
+MG_API int mg_light_notes_encrypt(const mg_utxo_model *h, const uint64_t *recv_keys_affine_mont, const uint64_t *randomness,
+                                  const uint64_t *plaintexts_mont, size_t n, uint64_t *epk_out_affine_mont,
+                                  uint8_t *ciphertexts_out, uint8_t *status) {
+    MG_TRY
+    return light_notes_encrypt(h, recv_keys_affine_mont, randomness, plaintexts_mont, n, epk_out_affine_mont, ciphertexts_out, status);
+    MG_CATCH
+}
+MG_API int mg_light_notes_open(const mg_utxo_model *h, const uint64_t *viewing_key, const uint64_t *epks_affine_mont,
+                               const uint8_t *ciphertexts, const uint8_t *partitions, size_t n, uint64_t *plaintext_out_mont,
+                               uint8_t *ok, uint8_t *status, size_t *n_tried) {
+    MG_TRY
+    return light_notes_open(h, viewing_key, epks_affine_mont, ciphertexts, partitions, n, plaintext_out_mont, ok, status, n_tried);
+    MG_CATCH
+}
+MG_API int mg_outgoing_notes_encrypt(const mg_utxo_model *h, const uint64_t *recv_key_affine_mont, const uint64_t *randomness,
+                                     const uint64_t *assets_mont, size_t n, uint64_t *epk_out_affine_mont,
+                                     uint8_t *ciphertexts_out, uint8_t *status) {
+    MG_TRY
+    return outgoing_notes_encrypt(h, recv_key_affine_mont, randomness, assets_mont, n, epk_out_affine_mont, ciphertexts_out, status);
+    MG_CATCH
+}
+MG_API int mg_outgoing_notes_open(const mg_utxo_model *h, const uint64_t *viewing_key, const uint64_t *epks_affine_mont,
+                                  const uint8_t *ciphertexts, size_t n, uint64_t *assets_out_mont, uint8_t *ok, uint8_t *status) {
+    MG_TRY
+    return outgoing_notes_open(h, viewing_key, epks_affine_mont, ciphertexts, n, assets_out_mont, ok, status);
     MG_CATCH
 }
 

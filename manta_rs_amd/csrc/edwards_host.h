@@ -86,6 +86,19 @@ inline void build_table(const u64 *base, std::vector<u32> &out) {
     }
 }
 
+// k B for k < 2^252 from the table of B (63 entries, one per digit), affine Montgomery x | y
+inline void fixed_base_mul(const u32 *table, const u64 *k, u32 *out) {
+    HExt acc = HExt::identity();
+    for (int w = 0; w < ED_WINDOWS; ++w) {
+        const u32 m = (u32)(k[w >> 4] >> ((w & 15) * 4)) & 15u;
+        const u32 *e = &table[(size_t)(w * 16 + m) * 24];
+        acc = HExt::add(acc, HExt::from_affine(h_const(e), h_const(e + 8)));
+    }
+    const H zi = H::inv(acc.Z);
+    H::mul(acc.X, zi).store_words(out);
+    H::mul(acc.Y, zi).store_words(out + 8);
+}
+
 inline bool scalar_ok(const u64 *k) { // < l
     for (int i = 3; i >= 0; --i) {
         const u64 li = (u64)EdBn254::L[2 * i] | ((u64)EdBn254::L[2 * i + 1] << 32);

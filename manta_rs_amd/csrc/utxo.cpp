@@ -75,19 +75,6 @@ bool decode_generator(const uint8_t *bytes, u64 *out) {
     return true;
 }
 
-// k G from the model's table (63 entries, one per digit), affine Montgomery x | y
-void fixed_base_mul(const std::vector<u32> &table, const u64 *k, u32 *out) {
-    HExt acc = HExt::identity();
-    for (int w = 0; w < ED_WINDOWS; ++w) {
-        const u32 m = (u32)(k[w >> 4] >> ((w & 15) * 4)) & 15u;
-        const u32 *e = &table[(size_t)(w * 16 + m) * 24];
-        acc = HExt::add(acc, HExt::from_affine(h_const(e), h_const(e + 8)));
-    }
-    const H zi = H::inv(acc.Z);
-    H::mul(acc.X, zi).store_words(out);
-    H::mul(acc.Y, zi).store_words(out + 8);
-}
-
 } // namespace
 
 // spans = the four `Hasher` files in the order of utxo.h, then the generator
@@ -136,7 +123,7 @@ int utxos_open(const mg_utxo_model *h, const u64 *viewing_key, const u64 *pak, c
     if (n == 0) return MG_OK;
     std::vector<u32> consts(h->prm);
     consts.resize(UTXO_PRM_WORDS + 32);
-    fixed_base_mul(h->table, viewing_key, &consts[UTXO_PRM_WORDS]); // `derive_address`, once per call
+    fixed_base_mul(h->table.data(), viewing_key, &consts[UTXO_PRM_WORDS]); // `derive_address`, once per call
     if (pak) std::memcpy(&consts[UTXO_PRM_WORDS + 16], pak, 64);
     std::vector<Span> arrays = {Span::in(plaintexts, 96), Span::in(utxos, 128), Span::out(status, 1), Span::out(items_out, 32)};
     if (pak) arrays.push_back(Span::out(nullifiers_out, 32));

@@ -84,6 +84,9 @@ pub const MG_EDWARDS_MUL_PAIRWISE: c_int = 2;
 pub const MG_NOTE_OK: u8 = 0;
 pub const MG_NOTE_BAD_TAG: u8 = 1;
 pub const MG_NOTE_BAD_VALUE: u8 = 2;
+pub const MG_NOTE_OTHER_PARTITION: u8 = 3;
+pub const MG_LIGHT_NOTE_BYTES: usize = 96;
+pub const MG_OUTGOING_NOTE_BYTES: usize = 64;
 #[repr(C)]
 pub struct mg_utxo_model {
     _private: [u8; 0],
@@ -407,6 +410,16 @@ extern "C" {
     ) -> c_int;
     pub fn mg_blake3(data: *const u8, len: usize, out32: *mut u8) -> c_int;
     pub fn mg_blake2s256(data: *const u8, len: usize, out32: *mut u8) -> c_int;
+    pub fn mg_blake2s(data: *const u8, len: usize, out_len: usize, out: *mut u8) -> c_int;
+    pub fn mg_aes256_gcm(
+        key: *const u8,
+        nonce: *const u8,
+        input: *const u8,
+        len: usize,
+        decrypt: c_int,
+        out: *mut u8,
+        ok: *mut c_int,
+    ) -> c_int;
     pub fn mg_ctx_create_from_bytes_sharded(
         curve: mg_curve_t,
         bytes: *const u8,
@@ -630,5 +643,56 @@ extern "C" {
         scalars_out: *mut u64,
         nonce_points_out_affine_mont: *mut u64,
         pks_out_affine_mont: *mut u64,
+    ) -> c_int;
+
+    // ---- the AES-GCM notes, the address partition and the Merkle shard index (MG_EDWARDS_CHUNK lanes per device pass)
+    pub fn mg_address_partitions(
+        h: *const mg_utxo_model,
+        recv_keys_affine_mont: *const u64,
+        n: usize,
+        out: *mut u8,
+    ) -> c_int;
+    pub fn mg_merkle_shard_indices(curve: mg_curve_t, leaves_mont: *const u64, n: usize, out: *mut u8) -> c_int;
+    pub fn mg_light_notes_encrypt(
+        h: *const mg_utxo_model,
+        recv_keys_affine_mont: *const u64,
+        randomness: *const u64,
+        plaintexts_mont: *const u64,
+        n: usize,
+        epk_out_affine_mont: *mut u64,
+        ciphertexts_out: *mut u8,
+        status: *mut u8,
+    ) -> c_int;
+    pub fn mg_light_notes_open(
+        h: *const mg_utxo_model,
+        viewing_key: *const u64,
+        epks_affine_mont: *const u64,
+        ciphertexts: *const u8,
+        partitions: *const u8,
+        n: usize,
+        plaintext_out_mont: *mut u64,
+        ok: *mut u8,
+        status: *mut u8,
+        n_tried: *mut usize,
+    ) -> c_int;
+    pub fn mg_outgoing_notes_encrypt(
+        h: *const mg_utxo_model,
+        recv_key_affine_mont: *const u64,
+        randomness: *const u64,
+        assets_mont: *const u64,
+        n: usize,
+        epk_out_affine_mont: *mut u64,
+        ciphertexts_out: *mut u8,
+        status: *mut u8,
+    ) -> c_int;
+    pub fn mg_outgoing_notes_open(
+        h: *const mg_utxo_model,
+        viewing_key: *const u64,
+        epks_affine_mont: *const u64,
+        ciphertexts: *const u8,
+        n: usize,
+        assets_out_mont: *mut u64,
+        ok: *mut u8,
+        status: *mut u8,
     ) -> c_int;
 }
