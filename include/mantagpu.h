@@ -269,6 +269,46 @@ int mg_groth16_setup(mg_curve_t curve, const mg_csr *a, const mg_csr *b, const m
                      uint64_t n_vars, uint64_t n_inputs, const uint64_t *toxic_mont /* 5 x 4: alpha beta gamma delta tau */,
                      const uint64_t *g1_generator, const uint64_t *g2_generator, const mg_pk_out *out);
 
+/* ---- phase-2 key initialisation of the trusted setup: `mpc::initialize` (manta-trusted-setup/src/groth16/mpc.rs:353-431),
+ *      which `groth16_phase2_prepare` runs once per circuit on a powers-of-tau accumulator. Synchronous; all device work on
+ *      the calling thread's setup stream. --------------------------------------------------------------------------- */
+/* out[j] = sum over terms t and stored entries (i, j) of M_t of [M_t[i][j]] * bases[t][i]  (n_cols affine points).
+ * Parity-test surface of mg_mpc_initialize and a primitive of its own (`specialize_to_phase_2`, mpc.rs:251-294).
+ * bases_affine[t]: m affine Montgomery points (zeros = infinity, honoured); mats[t]: m rows, n_cols columns, Montgomery
+ * coefficients (the multiplier is `coeff.into_repr()`; a stored zero contributes nothing, repeated (row, column) entries
+ * each count). group: 1 or 2. entries_per_lane: sorted entries per lane of the segmented sum, 0 = the library's choice;
+ * no result depends on it. One sort, one multiplication kernel, one segmented sum and its merge levels, one batched
+ * normalisation for the whole call: the number of launches and copies does not depend on n_cols.
+ * MG_ERROR_INVALID_ARGUMENT before any device work, with out_affine untouched: n_terms = 0, m = 0, n_cols = 0, a NULL
+ * basis or matrix, a row_ptr that does not rise from 0 to nnz, a column >= n_cols, 2^31 stored entries or more in all, more columns than the
+ * 32-bit word index of the sums holds (2^32 / words of an XYZZ point: 119 M for BN254 G1, 38 M for BLS12-381 G2). */
+int mg_qap_columns(mg_curve_t curve, int group, size_t n_terms, const uint64_t *const *bases_affine,
+                   const mg_csr *const *mats, uint64_t m, uint64_t n_cols, uint32_t entries_per_lane,
+                   uint64_t *out_affine);
+
+typedef struct {
+    uint64_t n_g1, n_g2; /* tau_powers_g1[n_g1]; tau_powers_g2, alpha_tau_powers_g1, beta_tau_powers_g1: [n_g2] */
+    const uint64_t *tau_powers_g1, *tau_powers_g2, *alpha_tau_powers_g1, *beta_tau_powers_g1, *beta_g2;
+} mg_kzg_view;
+
+/* `mpc::initialize` (mpc.rs:353-431) after synthesis: the phase-2 key of a circuit from a KZG accumulator,
+ * gamma = delta = 1. Output arrays as for mg_groth16_setup, h_query[h_len].
+ * D = next_pow2(num_constraints + n_inputs); beyond the field's two-adicity: MG_ERROR_DOMAIN_TOO_LARGE (the reference's
+ * `TooManyConstraints`; decided before the matrices are read). h_len = D - 1 (what ark-groth16 keys carry) or D (what the reference's loop :372-377 produces).
+ * h_query[i] = tau^(i+D) G - tau^i G; four inverse group NTTs of the first D powers; `add_dummy_constraints` (:299-312);
+ * a_query = A^T tauL, b_g1_query = B^T tauL, b_g2_query = B^T tauL2, ext = A^T betaL + B^T alphaL + C^T tauL,
+ * gamma_abc_g1 = ext[..n_inputs], l_query = ext[n_inputs..]; alpha_g1, beta_g1, beta_g2 from the accumulator; delta_g1,
+ * gamma_g2, delta_g2 = the generators passed in. Each power vector is uploaded once, the Lagrange bases stay in device
+ * memory between the NTTs and the column sums, only the key comes back.
+ * MG_ERROR_INVALID_ARGUMENT before anything is allocated, with `out` untouched (as after every failure): a NULL argument,
+ * n_inputs = 0 or >= n_vars, a malformed matrix (as for mg_ctx_set_r1cs), another h_len, n_g1 < D + h_len, n_g2 < D, a
+ * domain above 2^26 that the field would still allow (the group NTT's own limit, as for mg_group_ntt), 2^31 column-sum
+ * entries (2 nnz(A) + 2 nnz(B) + nnz(C) + 2 n_inputs) or more, more columns (3 n_vars) than the 32-bit word index of the sums
+ * holds (about 39 M variables on BN254, 25 M on BLS12-381). */
+int mg_mpc_initialize(mg_curve_t curve, const mg_kzg_view *powers, const mg_csr *a, const mg_csr *b, const mg_csr *c,
+                      uint64_t num_constraints, uint64_t n_vars, uint64_t n_inputs, uint64_t h_len,
+                      const uint64_t *g1_generator, const uint64_t *g2_generator, const mg_pk_out *out);
+
 /* Uploads and re-lays the proving key once (lifetime = the Rust ProvingContext). */
 int mg_ctx_create(mg_curve_t curve, const mg_pk_view *pk, mg_ctx **out);
 /* The same with everything a deployment decides per context in ONE struct (the entry points below are shorthands for it):

@@ -81,6 +81,7 @@ EXPORTS = [
     "mg_blake2s256", "mg_schnorr_challenges", "mg_signatures_verify", "mg_signatures_sign",
     "mg_blake2s", "mg_aes256_gcm", "mg_address_partitions", "mg_merkle_shard_indices",
     "mg_light_notes_encrypt", "mg_light_notes_open", "mg_outgoing_notes_encrypt", "mg_outgoing_notes_open",
+    "mg_qap_columns", "mg_mpc_initialize",
 ]
 
 
@@ -612,6 +613,71 @@ def groth16_setup(r1cs: "R1CS", n_vars, toxic_mont, g1_generator, g2_generator) 
     _chk(LIB.mg_groth16_setup(curve, ctypes.byref(ms[0][3]), ctypes.byref(ms[1][3]), ctypes.byref(ms[2][3]),
                               ctypes.c_uint64(m), ctypes.c_uint64(V), ctypes.c_uint64(P), _p(tox), _p(_u64(g1_generator)),
                               _p(_u64(g2_generator)), ctypes.byref(out)), "mg_groth16_setup")
+    return pk
+
+
+def _csr(M):
+    """a matrix with row_ptr / col / val arrays -> (the arrays kept alive, the mg_csr over them)"""
+    rp = np.ascontiguousarray(M.row_ptr, dtype=np.uint32)
+    col = np.ascontiguousarray(M.col, dtype=np.uint32)
+    val = _u64(M.val)
+    return (rp, col, val), _Csr(_p(rp), _p(col), _p(val), len(col))
+
+
+def qap_columns(curve, group, bases, mats, n_cols, entries_per_lane=0) -> np.ndarray:
+    """Column sums of scaled group elements (`mg_qap_columns`; `specialize_to_phase_2`, mpc.rs:251-294):
+    out[j] = sum over t and the stored entries (i, j) of mats[t] of [mats[t][i][j]] bases[t][i]. bases: a list of [m, limbs]
+    uint64 affine point arrays, mats: as many CSR matrices (row_ptr[m + 1], col, val Montgomery Fr) of m rows and n_cols
+    columns. Returns [n_cols, limbs] affine points. entries_per_lane places the chunk boundaries of the segmented sum (0: the
+    library's choice); no result depends on it."""
+    bases = [_u64(b) for b in bases]
+    if len(bases) != len(mats):
+        raise ValueError("qap_columns: one basis per matrix")
+    m = len(mats[0].row_ptr) - 1 if mats else 0
+    for b, M in zip(bases, mats):
+        if b.ndim != 2 or b.shape != (m, affine_limbs(curve, group)) or len(M.row_ptr) != m + 1:
+            raise ValueError("qap_columns: every basis is [m, limbs] and every matrix has m rows")
+    keep = [_csr(M) for M in mats]
+    bp = (ctypes.c_void_p * max(len(bases), 1))(*[b.ctypes.data for b in bases])
+    mp = (ctypes.POINTER(_Csr) * max(len(mats), 1))(*[ctypes.pointer(k[1]) for k in keep])
+    out = np.zeros((int(n_cols), affine_limbs(curve, group)), dtype=np.uint64)
+    _chk(LIB.mg_qap_columns(curve, group, _sz(len(bases)), bp, mp, ctypes.c_uint64(m), ctypes.c_uint64(int(n_cols)),
+                            ctypes.c_uint32(int(entries_per_lane)), _p(out)), "mg_qap_columns")
+    return out
+
+
+class _KzgView(ctypes.Structure):
+    _fields_ = [("n_g1", ctypes.c_uint64), ("n_g2", ctypes.c_uint64)] + [
+        (k, _vp) for k in ("tau_powers_g1", "tau_powers_g2", "alpha_tau_powers_g1", "beta_tau_powers_g1", "beta_g2")]
+
+
+def mpc_initialize(curve, tau_powers_g1, tau_powers_g2, alpha_tau_powers_g1, beta_tau_powers_g1, beta_g2, r1cs: "R1CS", n_vars,
+                   h_len, g1_generator, g2_generator) -> ProvingKey:
+    """`mpc::initialize` (manta-trusted-setup/src/groth16/mpc.rs:353-431; `mg_mpc_initialize`): the phase-2 proving key of a
+    circuit from the vectors of a KZG accumulator, gamma = delta = 1 (the generators passed in). h_len = D - 1 (the length
+    ark-groth16 keys carry) or D (the reference's loop). The Lagrange bases and the QAP column sums are computed on the GPU;
+    only the key comes back."""
+    m, P, V = r1cs.num_constraints, r1cs.num_instance, int(n_vars)
+    D = 1
+    while D < m + P:
+        D <<= 1
+    h_len = int(h_len)
+    w1, w2 = affine_limbs(curve, 1), affine_limbs(curve, 2)
+    vecs = [_u64(v) for v in (tau_powers_g1, tau_powers_g2, alpha_tau_powers_g1, beta_tau_powers_g1, beta_g2)]
+    view = _KzgView(vecs[0].shape[0], min(v.shape[0] for v in vecs[1:4]), *[_p(v) for v in vecs])
+    pk = ProvingKey()
+    pk.curve, pk.V, pk.P, pk.D, pk.h_len = curve, V, P, D, h_len
+    shapes = {"alpha_g1": (1, w1), "beta_g1": (1, w1), "delta_g1": (1, w1), "beta_g2": (1, w2), "gamma_g2": (1, w2),
+              "delta_g2": (1, w2), "gamma_abc_g1": (P, w1), "a_query": (V, w1), "b_g1_query": (V, w1),
+              "b_g2_query": (V, w2), "h_query": (max(h_len, 0), w1), "l_query": (max(V - P, 0), w1)}
+    for k, sh in shapes.items():
+        setattr(pk, k, np.zeros(sh, dtype=np.uint64))
+    out = _PkOut(*[_p(getattr(pk, k)) for k, _ in _PkOut._fields_])
+    keep = [_csr(M) for M in (r1cs.A, r1cs.B, r1cs.C)]
+    _chk(LIB.mg_mpc_initialize(curve, ctypes.byref(view), ctypes.byref(keep[0][1]), ctypes.byref(keep[1][1]),
+                               ctypes.byref(keep[2][1]), ctypes.c_uint64(m), ctypes.c_uint64(V), ctypes.c_uint64(P),
+                               ctypes.c_uint64(h_len), _p(_u64(g1_generator)), _p(_u64(g2_generator)), ctypes.byref(out)),
+         "mg_mpc_initialize")
     return pk
 
 

@@ -5,7 +5,7 @@ manta-trusted-setup's hot loops, every group operation through the C ABI (`mg_ec
     batch_mul_pointwise         util.rs:447-455                           point i times scalar i
     contribute                  groth16/mpc.rs:451-468                    l_query, h_query *= 1/delta; delta_g1, delta_g2 *= delta
     accumulator_update          groth16/kzg.rs:444-468                    powers of tau times tau^i (and alpha, beta)
-    lagrange_basis / initialize groth16/mpc.rs:355-431                    group-domain IFFTs of the powers, then the QAP sums
+    lagrange_basis / initialize groth16/mpc.rs:355-431                    group-domain IFFTs of the powers, then the QAP sums (`mg_mpc_initialize`)
     merge_pairs_affine          util.rs:314-332                           one random linear combination of two point vectors (2 MSMs)
     same_ratio                  manta-crypto/src/arkworks/pairing.rs:88-109   e(a0, b1) == e(a1, b0) as one pairing product (`mg_pairing_check`)
     check_transform             groth16/mpc.rs:487-508                    the verifier's consistency checks of one contribution
@@ -239,10 +239,21 @@ def lagrange_basis(curve, group, powers, D) -> np.ndarray:
     return api.group_ntt(curve, group, np.ascontiguousarray(powers[:D]), inverse=True)
 
 
-def initialize(acc: Accumulator, c: synth.Circuit):
+def initialize(acc: Accumulator, c: synth.Circuit, h_len=None):
     """mpc.rs:355-431 `initialize`: the phase-2 proving key of circuit `c` from a powers-of-tau accumulator, gamma = delta =
-    1 (the generators). Lagrange bases by group IFFTs on the GPU; the sparse QAP sums (specialize_to_phase_2, :251-294) as
-    element-wise scalar multiplications on the GPU followed by per-variable sums."""
+    1 (the generators) -- one call of `mg_mpc_initialize`: the Lagrange bases by group IFFTs and the sparse QAP sums
+    (specialize_to_phase_2, :251-294) as column sums on the GPU, the bases staying in device memory in between. h_len: D - 1
+    (the default: the key ark-groth16 and `initialize_by_composition` carry) or D (the reference's loop :372-377)."""
+    from . import keygen
+    return api.mpc_initialize(acc.curve, acc.tau_powers_g1, acc.tau_powers_g2, acc.alpha_tau_powers_g1, acc.beta_tau_powers_g1,
+                              acc.beta_g2, api.R1CS.from_circuit(c), c.V, c.D - 1 if h_len is None else h_len,
+                              keygen.generator(acc.curve, 1), keygen.generator(acc.curve, 2))
+
+
+def initialize_by_composition(acc: Accumulator, c: synth.Circuit):
+    """The same key composed from the element-wise entry points, as `initialize` was before `mg_mpc_initialize`: group IFFTs
+    on the GPU, one GPU scalar multiplication per non-zero, then one host sum per variable. Kept as the cross-check of
+    `initialize` (tests) and as the other side of tools/qap_columns_bench.py."""
     curve, D, m, P, V = acc.curve, c.D, c.m, c.P, c.V
     r = synth.FR_MODULUS[curve]
     w1, w2 = api.affine_limbs(curve, 1), api.affine_limbs(curve, 2)

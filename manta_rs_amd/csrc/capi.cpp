@@ -745,6 +745,19 @@ MG_API int mg_groth16_setup(mg_curve_t curve, const mg_csr *a, const mg_csr *b, 
     return groth16_setup((int)curve, a, b, c, m, n_vars, n_inputs, toxic, g1_gen, g2_gen, out);
     MG_CATCH
 }
+MG_API int mg_qap_columns(mg_curve_t curve, int group, size_t n_terms, const uint64_t *const *bases_affine, const mg_csr *const *mats,
+                          uint64_t m, uint64_t n_cols, uint32_t entries_per_lane, uint64_t *out_affine) {
+    MG_TRY
+    return qap_columns((int)curve, group, n_terms, bases_affine, mats, m, n_cols, entries_per_lane, out_affine);
+    MG_CATCH
+}
+MG_API int mg_mpc_initialize(mg_curve_t curve, const mg_kzg_view *powers, const mg_csr *a, const mg_csr *b, const mg_csr *c, uint64_t m,
+                             uint64_t n_vars, uint64_t n_inputs, uint64_t h_len, const uint64_t *g1_gen, const uint64_t *g2_gen,
+                             const mg_pk_out *out) {
+    MG_TRY
+    return mpc_initialize((int)curve, powers, a, b, c, m, n_vars, n_inputs, h_len, g1_gen, g2_gen, out);
+    MG_CATCH
+}
 MG_API int mg_groth16_prove(const mg_ctx *ctx, const uint64_t *z, const uint64_t r[4], const uint64_t s[4],
                             uint8_t *proof_out) {
     MG_TRY

@@ -282,6 +282,14 @@ struct MsmDigitsCall {
     u32 *layout;      // out: W, B, seg_keys, invalid
 };
 
+// the stored entries of a call of GroupEngine::qap_columns, host arrays of n elements each
+struct QapEntries {
+    const u32 *col; // column of the entry = index of the sum it belongs to
+    const u32 *src; // index of the basis point it multiplies
+    const u64 *val; // its coefficient, 4 x u64 Montgomery Fr
+    size_t n;
+};
+
 // Opaque host point (XYZZ, 64-bit limbs) big enough for G2/BLS12-381.
 struct HostPoint {
     u64 w[4 * 12];
@@ -374,6 +382,20 @@ class GroupEngine {
     // domain's omega^k table on the device, n_inv_canonical != nullptr scales by n^-1 (inverse transform)
     virtual int group_ntt(const u32 *in_affine_host, unsigned lg, const u32 *d_twiddles_mont, const u32 *n_inv_canonical,
                           u32 *out_affine_host) = 0;
+    // the same transform between two device arrays of affine points (arkworks format); n_inv_canonical is a HOST pointer. Enqueued
+    // on the calling thread's setup stream and waited for.
+    virtual int group_ntt_device(const u32 *d_in_affine, unsigned lg, const u32 *d_twiddles_mont, const u32 *n_inv_canonical,
+                                 u32 *d_out_affine) = 0;
+    // out[i] = a[i] - b[i] over device arrays of affine points (the h_query of `mpc::initialize`); enqueued and waited for likewise
+    virtual int sub_device(const u32 *d_a_affine, const u32 *d_b_affine, size_t n, u32 *d_out_affine) = 0;
+    // Column sums of scaled group elements (qap_columns.h): out[j] = sum over the entries e with col[e] = j of
+    // [canonical(val[e])] bases[src[e]], j < n_cols. The bases are n_bases affine points in DEVICE memory (arkworks format, zeros =
+    // infinity), the entries HOST arrays, out n_cols affine points in host memory, written only if the call succeeds.
+    // entries_per_lane: sorted entries per lane of the segmented sum, 0 = the engine's choice; no result depends on it.
+    virtual int qap_columns(const u32 *d_bases_affine, size_t n_bases, const QapEntries &entries, u64 n_cols, u32 entries_per_lane,
+                            u32 *out_affine_host) = 0;
+    virtual void scalar_one_mont(u64 out[4]) const = 0; // 1 in Fr, Montgomery form
+    virtual u64 qap_max_columns() const = 0;            // the most columns qap_columns takes: its sums are indexed in 32-bit words
     // sum of affine points (device) -> host point
     virtual int sum_affine(const u32 *d_pts, size_t n, HostPoint *out) = 0;
 

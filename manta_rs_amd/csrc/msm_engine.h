@@ -7,6 +7,7 @@
 #include "msm_accumulate.h"
 #include "msm_reduce.h"
 #include "msm_tables.h"
+#include "qap_columns.h"
 
 namespace mg {
 
@@ -757,21 +758,129 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
                   u32 *out_affine_host) override {
         if (!in_affine_host || !out_affine_host || lg > 26 || (lg > 0 && !d_twiddles_mont)) return MG_ERR_ARG;
         const size_t n = (size_t)1 << lg, ab = n * AW_IO * 4;
-        DevBlock m; // affine in | working XYZZ | arkworks-format XYZZ | affine out | n^-1 (inverse transform only)
-        if (const int rc = m.alloc({ab, n * XW * 4, n * XW_IO * 4, ab, n_inv_canonical ? 32u : 0u}, "group_ntt")) return rc;
-        u32 *d_in = m.dev<u32>(0), *d_pts = m.dev<u32>(1), *d_std = m.dev<u32>(2), *d_out = m.dev<u32>(3), *d_sc = m.dev<u32>(4);
-        hipError_t e = memcpy_sync(d_in, in_affine_host, ab, hipMemcpyHostToDevice);
-        if (e == hipSuccess && n_inv_canonical) e = memcpy_sync(d_sc, n_inv_canonical, 32, hipMemcpyHostToDevice);
+        DevBlock m; // affine in | affine out
+        if (const int rc = m.alloc({ab, ab}, "group_ntt")) return rc;
+        hipError_t e = memcpy_sync(m.dev(0), in_affine_host, ab, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_status(e, "group_ntt");
+        if (const int rc = group_ntt_device(m.dev<u32>(0), lg, d_twiddles_mont, n_inv_canonical, m.dev<u32>(1))) return rc;
+        e = memcpy_sync(out_affine_host, m.dev(1), ab, hipMemcpyDeviceToHost);
+        return e == hipSuccess ? MG_OK : hip_status(e, "group_ntt");
+    }
+    // the transform itself, device array to device array (`mpc::initialize`: the Lagrange bases never leave HBM)
+    int group_ntt_device(const u32 *d_in, unsigned lg, const u32 *d_twiddles_mont, const u32 *n_inv_canonical, u32 *d_out) override {
+        if (!d_in || !d_out || lg > 26 || (lg > 0 && !d_twiddles_mont)) return MG_ERR_ARG;
+        hipStream_t st = setup_stream();
+        if (!st) return MG_ERR_OOM;
+        const size_t n = (size_t)1 << lg;
+        DevBlock m; // working XYZZ | arkworks-format XYZZ | n^-1 (inverse transform only)
+        if (const int rc = m.alloc({n * XW * 4, n * XW_IO * 4, n_inv_canonical ? 32u : 0u}, "group_ntt")) return rc;
+        u32 *d_pts = m.dev<u32>(0), *d_std = m.dev<u32>(1), *d_sc = m.dev<u32>(2);
+        hipError_t e = n_inv_canonical ? memcpy_sync(d_sc, n_inv_canonical, 32, hipMemcpyHostToDevice) : hipSuccess;
         if (e == hipSuccess) {
-            hipLaunchKernelGGL((group_ntt_load_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, setup_stream(), d_in, lg, d_pts);
+            hipLaunchKernelGGL((group_ntt_load_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, d_in, lg, d_pts);
             for (unsigned s = 1; s <= lg; ++s)
-                hipLaunchKernelGGL((group_ntt_stage_kernel<F, FrC>), dim3(cdiv(n / 2, 256)), dim3(256), 0, setup_stream(), d_pts, d_twiddles_mont, lg, s);
-            hipLaunchKernelGGL((group_scale_store_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, setup_stream(), d_pts, (const u32 *)d_sc, n, d_std);
+                hipLaunchKernelGGL((group_ntt_stage_kernel<F, FrC>), dim3(cdiv(n / 2, 256)), dim3(256), 0, st, d_pts, d_twiddles_mont, lg, s);
+            hipLaunchKernelGGL((group_scale_store_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, d_pts, (const u32 *)d_sc, n, d_std);
             constexpr int KB = 16;
-            hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(n, KB), 256)), dim3(256), 0, setup_stream(), d_std, n, d_out, (u32)AW_IO);
-            e = memcpy_sync(out_affine_host, d_out, ab, hipMemcpyDeviceToHost);
+            hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(n, KB), 256)), dim3(256), 0, st, d_std, n, d_out, (u32)AW_IO);
+            e = hipGetLastError();
+            const hipError_t e2 = hipStreamSynchronize(st);
+            if (e == hipSuccess) e = e2;
         }
         return e == hipSuccess ? MG_OK : hip_status(e, "group_ntt");
+    }
+    int sub_device(const u32 *d_a, const u32 *d_b, size_t n, u32 *d_out) override {
+        if (!d_a || !d_b || !d_out || n == 0) return MG_ERR_ARG;
+        hipStream_t st = setup_stream();
+        if (!st) return MG_ERR_OOM;
+        DevBlock m; // XYZZ results
+        if (const int rc = m.alloc({n * XW_IO * 4}, "sub_device")) return rc;
+        constexpr int KB = 16;
+        hipLaunchKernelGGL((ec_elementwise_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, 4, d_a, d_b, n, m.dev<u32>(0));
+        hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(n, KB), 256)), dim3(256), 0, st, m.dev<u32>(0), n, d_out, (u32)AW_IO);
+        hipError_t e = hipGetLastError();
+        const hipError_t e2 = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = e2;
+        return e == hipSuccess ? MG_OK : hip_status(e, "sub_device");
+    }
+
+    // ---------------------------------------------------------------- QAP column sums (qap_columns.h)
+    void scalar_one_mont(u64 out[4]) const override {
+        const host::HFp<FrC> one = host::HFp<FrC>::one();
+        std::memcpy(out, one.v, 32);
+    }
+    u64 qap_max_columns() const override { return ((u64)1 << 32) / XWM - 2; } // (columns + 1) XW words stay below 2^32
+    // sorted entries per lane of the segmented sum when the caller leaves it open: two wavefronts per SIMD of lanes (256 CUs) before
+    // the chunks grow, never fewer than 4 entries (below that the partials outnumber the entries) nor more than 64 (a chain of 64
+    // dependent general additions is already the longest stage of the call)
+    static u32 qap_entries_per_lane(size_t N) {
+        const size_t l = N / (128 * 1024);
+        return (u32)(l < 4 ? 4 : l > 64 ? 64 : l);
+    }
+    int qap_columns(const u32 *d_bases, size_t n_bases, const QapEntries &en, u64 n_cols, u32 entries_per_lane,
+                    u32 *out_affine_host) override {
+        const size_t N = en.n;
+        // what the 32-bit pairs and word counts cannot hold: 2^31 entries (the sort), 2^32 words of column sums (the zero-fill)
+        if (!out_affine_host || n_cols == 0 || n_cols > qap_max_columns() || N >= ((size_t)1 << 31) ||
+            (N && (!d_bases || !n_bases || !en.col || !en.src || !en.val)))
+            return MG_ERR_ARG;
+        for (size_t e = 0; e < N; ++e)
+            if (en.col[e] >= n_cols || en.src[e] >= n_bases) return MG_ERR_ARG;
+        const size_t out_bytes = (size_t)n_cols * AW_IO * 4;
+        if (N == 0) {
+            std::memset(out_affine_host, 0, out_bytes);
+            return MG_OK;
+        }
+        hipStream_t st = setup_stream();
+        if (!st) return MG_ERR_OOM;
+        const u32 L = entries_per_lane ? entries_per_lane : qap_entries_per_lane(N);
+        const u32 T = cdiv(N, L), waves1 = cdiv((size_t)2 * T, 64), invalid = (u32)n_cols;
+        int end_bit = 1;
+        while (end_bit < 32 && ((u64)1 << end_bit) < n_cols) ++end_bit; // keys are below n_cols
+        std::vector<u32> ids(N);
+        for (size_t e = 0; e < N; ++e) ids[e] = (u32)e;
+        const size_t sort_bytes = sort_pairs_temp_bytes(N);
+        enum { SRC, VAL, KEYS, IDS, SKEYS, SIDS, SORT, PROD, PK0, PP0, PK1, PP1, SUMS, STD, AFF };
+        DevBlock m;
+        if (const int rc = m.alloc({N * 4, N * 32, N * 4, N * 4, N * 4, N * 4, sort_bytes, N * XW * 4, (size_t)2 * T * 4,
+                                    (size_t)2 * T * XW * 4, (size_t)2 * waves1 * 4, (size_t)2 * waves1 * XW * 4,
+                                    (size_t)(n_cols + 1) * XW * 4, (size_t)n_cols * XW_IO * 4, out_bytes},
+                                   "qap_columns"))
+            return rc;
+        std::vector<u32> stage((size_t)n_cols * AW_IO);
+        hipError_t e = hipMemcpyAsync(m.dev(SRC), en.src, N * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(m.dev(VAL), en.val, N * 32, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(m.dev(KEYS), en.col, N * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(m.dev(IDS), ids.data(), N * 4, hipMemcpyHostToDevice, st);
+        int rc = MG_OK;
+        if (e == hipSuccess) {
+            u32 *const sums = m.dev<u32>(SUMS);
+            ZeroRanges zr{};
+            zr.p[0] = sums, zr.n[0] = (u32)((size_t)(n_cols + 1) * XW);
+            hipLaunchKernelGGL((zero_ranges<F>), dim3(zr.n[0] > 256u * 1024u ? 1024u : cdiv(zr.n[0], 256)), dim3(256), 0, st, zr);
+            rc = sort_pairs(m.dev<u32>(KEYS), m.dev<u32>(SKEYS), m.dev<u32>(IDS), m.dev<u32>(SIDS), N, end_bit, m.dev(SORT), sort_bytes, st);
+            if (!rc) {
+                hipLaunchKernelGGL((qap_entry_kernel<F, FrC>), dim3(cdiv(N, 256)), dim3(256), 0, st, m.dev<u32>(SIDS), (u32)N, m.dev<u32>(SRC),
+                                   m.dev<u32>(VAL), d_bases, m.dev<u32>(PROD));
+                hipLaunchKernelGGL((qap_segsum_kernel<F>), dim3(cdiv(T, 256)), dim3(256), 0, st, m.dev<u32>(SKEYS), m.dev<u32>(PROD), (u32)N, L,
+                                   invalid, sums, m.dev<u32>(PK0), m.dev<u32>(PP0), T);
+                u32 *pk[2] = {m.dev<u32>(PK0), m.dev<u32>(PK1)}, *pp[2] = {m.dev<u32>(PP0), m.dev<u32>(PP1)};
+                merge_levels(st, pk, pp, 2 * T, merge_g1(N), invalid, sums, (u32 *)nullptr);
+                constexpr int KB = 16;
+                hipLaunchKernelGGL((group_scale_store_kernel<F>), dim3(cdiv(n_cols, 256)), dim3(256), 0, st, sums, (const u32 *)nullptr,
+                                   (size_t)n_cols, m.dev<u32>(STD));
+                hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(n_cols, KB), 256)), dim3(256), 0, st, m.dev<u32>(STD),
+                                   (size_t)n_cols, m.dev<u32>(AFF), (u32)AW_IO);
+                e = hipGetLastError();
+                if (e == hipSuccess) e = hipMemcpyAsync(stage.data(), m.dev(AFF), out_bytes, hipMemcpyDeviceToHost, st);
+            }
+        }
+        const hipError_t e2 = hipStreamSynchronize(st); // (before the block goes, whatever failed)
+        if (rc) return rc;
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) return hip_status(e, "qap_columns");
+        std::memcpy(out_affine_host, stage.data(), out_bytes);
+        return MG_OK;
     }
 
     int sum_affine(const u32 *d_pts, size_t n, HostPoint *out) override {
@@ -1001,18 +1110,23 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
     // merge levels: the partials -> the bucket array (direct: the result, in redS)
     void launch_merge(Launch &r) {
         MsmWorkspace *const ws = r.ws;
-        u32 *const std_final = r.direct ? ws->redS.as<u32>() : (u32 *)nullptr;
-        u32 cnt = r.parts;
+        u32 *pk[2] = {ws->pkeys[0].as<u32>(), ws->pkeys[1].as<u32>()}, *pp[2] = {ws->ppts[0].as<u32>(), ws->ppts[1].as<u32>()};
+        merge_levels(r.s, pk, pp, r.parts, r.acc_single ? 2u : merge_g1(r.M), r.invalid, ws->buckets.as<u32>(),
+                     r.direct ? ws->redS.as<u32>() : (u32 *)nullptr);
+    }
+    // The merge levels over `cnt` partials in (pkeys[0], ppts[0]), ping-ponging with (pkeys[1], ppts[1]) until one wave is left:
+    // 64 G -> 2 entries per wave and level, complete runs to `buckets` (the last level: std_final, if given). G0 = entries
+    // folded serially per lane in the first level, which is throughput-bound (as many entries as accumulate lanes x 2); later
+    // levels are pure latency (G = 2); <= 512 entries finish in one wave. Shared by msm_launch and qap_columns.
+    static void merge_levels(hipStream_t st, u32 *const pkeys[2], u32 *const ppts[2], u32 cnt, u32 G0, u32 invalid, u32 *buckets,
+                             u32 *std_final) {
         int src = 0;
         for (int level = 0;; ++level) {
-            // entries folded serially per lane: the first level is throughput-bound (as many entries as
-            // accumulate lanes x 2), later ones are pure latency; <= 512 entries finish in one wave
-            u32 G = level == 0 && !r.acc_single ? merge_g1(r.M) : 2;
+            u32 G = level == 0 ? G0 : 2;
             if (cnt <= 512) G = cnt <= 64 ? 1 : cdiv(cnt, 64);
             const u32 waves = cdiv(cdiv(cnt, G), 64);
             const int fin = waves == 1;
-            merge_partials_launch(r.s, waves, ws->pkeys[src].as<u32>(), ws->ppts[src].as<u32>(), cnt, G, r.invalid, fin,
-                                  ws->buckets.as<u32>(), ws->pkeys[1 - src].as<u32>(), ws->ppts[1 - src].as<u32>(), std_final);
+            merge_partials_launch(st, waves, pkeys[src], ppts[src], cnt, G, invalid, fin, buckets, pkeys[1 - src], ppts[1 - src], std_final);
             if (fin) break;
             cnt = 2 * waves;
             src ^= 1;

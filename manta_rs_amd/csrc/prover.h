@@ -13,6 +13,20 @@ struct DevCsr {
     u64 nnz = 0;
 };
 
+// Structural checks of one matrix of m rows and n_cols columns as it arrives over the ABI (O(m + nnz) on the host): the device
+// kernels loop k = row_ptr[i] .. row_ptr[i+1] and gather by col[k] without further checks, so nothing malformed may pass here.
+// Shared by mg_ctx_set_r1cs, mg_qap_columns and mg_mpc_initialize.
+inline int validate_csr(const mg_csr *src, u64 m, u64 n_cols) {
+    if (!src || !src->row_ptr || (src->nnz && (!src->col || !src->val))) return MG_ERR_ARG;
+    if (src->nnz >= ((u64)1 << 32)) return MG_ERR_ARG;
+    if (src->row_ptr[0] != 0 || src->row_ptr[m] != src->nnz) return MG_ERR_ARG;
+    for (u64 i = 0; i < m; ++i)
+        if (src->row_ptr[i] > src->row_ptr[i + 1]) return MG_ERR_ARG; // monotone => every entry <= row_ptr[m] = nnz
+    for (u64 k = 0; k < src->nnz; ++k)
+        if (src->col[k] >= n_cols) return MG_ERR_ARG;
+    return MG_OK;
+}
+
 class FrEngine {
   public:
     virtual ~FrEngine() {}
@@ -96,5 +110,10 @@ int prover_create_from_bytes_ex(int curve, const uint8_t *bytes, size_t len, con
 // Groth16 key generation from explicit toxic waste and group generators (setup.cpp)
 int groth16_setup(int curve, const mg_csr *a, const mg_csr *b, const mg_csr *c, u64 m, u64 n_vars, u64 n_inputs,
                   const u64 *toxic5, const u64 *g1_gen, const u64 *g2_gen, const mg_pk_out *out);
+// the phase-2 key of a circuit from a KZG accumulator, and its sparse half alone (mpc.cpp)
+int qap_columns(int curve, int group, size_t n_terms, const u64 *const *bases_affine, const mg_csr *const *mats, u64 m, u64 n_cols,
+                u32 entries_per_lane, u64 *out_affine);
+int mpc_initialize(int curve, const mg_kzg_view *powers, const mg_csr *a, const mg_csr *b, const mg_csr *c, u64 m, u64 n_vars,
+                   u64 n_inputs, u64 h_len, const u64 *g1_gen, const u64 *g2_gen, const mg_pk_out *out);
 
 } // namespace mg

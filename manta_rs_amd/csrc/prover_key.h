@@ -334,18 +334,6 @@ class ProverKey : public Prover {
         return MG_OK;
     }
 
-    // Structural checks of one matrix as it arrives over the ABI (O(m + nnz) on the host): the device kernels loop
-    // k = row_ptr[i] .. row_ptr[i+1] and gather z[col[k]] without further checks, so nothing malformed may pass here.
-    static int validate_csr(const mg_csr *src, u64 m, u64 n_vars) {
-        if (!src || !src->row_ptr || (src->nnz && (!src->col || !src->val))) return MG_ERR_ARG;
-        if (src->nnz >= ((u64)1 << 32)) return MG_ERR_ARG;
-        if (src->row_ptr[0] != 0 || src->row_ptr[m] != src->nnz) return MG_ERR_ARG;
-        for (u64 i = 0; i < m; ++i)
-            if (src->row_ptr[i] > src->row_ptr[i + 1]) return MG_ERR_ARG; // monotone => every entry <= row_ptr[m] = nnz
-        for (u64 k = 0; k < src->nnz; ++k)
-            if (src->col[k] >= n_vars) return MG_ERR_ARG;
-        return MG_OK;
-    }
     static int upload_csr(const mg_csr *src, u64 m, DevCsr &dst) { // dst is empty on entry; freed by the caller on failure
         dst.nnz = src->nnz;
         MG_HIP(hipMalloc((void **)&dst.row_ptr, (m + 1) * 4));

@@ -10,6 +10,7 @@
 //! | k calls of the above from a signer / ledger simulation             | [`GpuProvingContext::prove_many`]      |
 //! | `VerifyingContext::new(&vk)` / `decode` `:305-517`                 | [`GpuVerifyingContext`]                |
 //! | `ArkGroth16::verify_with_processed_vk` `:603-609`                  | [`GpuVerifyingContext::verify`]        |
+//! | `mpc::initialize` (manta-trusted-setup `groth16/mpc.rs:353-431`)   | [`mpc_initialize`]                     |
 //!
 //! Source only: the build image of this repository has no Rust toolchain, so this file has never been compiled.
 
@@ -576,6 +577,119 @@ pub fn same<E: Mi355xCurve>(lhs: (E::G1Affine, E::G2Affine), rhs: (E::G1Affine, 
 /// `PairingEngineExt::same_ratio` (`pairing.rs:101-109`): `e(lhs.0, rhs.1) == e(lhs.1, rhs.0)`.
 pub fn same_ratio<E: Mi355xCurve>(lhs: (E::G1Affine, E::G1Affine), rhs: (E::G2Affine, E::G2Affine)) -> Result<bool, Error> {
     same::<E>((lhs.0, rhs.1), (lhs.1, rhs.0))
+}
+
+/// The phase-2 proving key `mg_mpc_initialize` returns, as flat limb vectors in the C ABI's point format (`x || y`
+/// Montgomery limbs, infinity = zeros): the layout [`flatten_g1`] / [`flatten_g2`] produce and `mg_ctx_create` consumes.
+pub struct Phase2Key {
+    pub n_vars: usize,
+    pub n_inputs: usize,
+    pub h_len: usize,
+    pub alpha_g1: Vec<u64>,
+    pub beta_g1: Vec<u64>,
+    pub delta_g1: Vec<u64>,
+    pub beta_g2: Vec<u64>,
+    pub gamma_g2: Vec<u64>,
+    pub delta_g2: Vec<u64>,
+    pub gamma_abc_g1: Vec<u64>,
+    pub a_query: Vec<u64>,
+    pub b_g1_query: Vec<u64>,
+    pub b_g2_query: Vec<u64>,
+    pub h_query: Vec<u64>,
+    pub l_query: Vec<u64>,
+}
+
+/// `mpc::initialize` (`manta-trusted-setup/src/groth16/mpc.rs:353-431`) after synthesis, on the GPU (`mg_mpc_initialize`):
+/// the phase-2 key of the circuit `matrices` from the vectors of a `kzg::Accumulator`, gamma = delta = 1. A ceremony
+/// preparer calls this once per circuit where `coordinator::prepare` calls `mpc::initialize`. `h_len` is `D - 1` (the
+/// length ark-groth16 keys carry) or `D` (what the reference's loop produces), `D = (m + n_inputs).next_power_of_two()`.
+#[allow(clippy::too_many_arguments)]
+pub fn mpc_initialize<E: Mi355xCurve>(
+    tau_powers_g1: &[E::G1Affine],
+    tau_powers_g2: &[E::G2Affine],
+    alpha_tau_powers_g1: &[E::G1Affine],
+    beta_tau_powers_g1: &[E::G1Affine],
+    beta_g2: E::G2Affine,
+    matrices: &ConstraintMatrices<E::Fr>,
+    h_len: usize,
+) -> Result<Phase2Key, Error> {
+    let (n_inputs, n_vars) = (matrices.num_instance_variables, matrices.num_instance_variables + matrices.num_witness_variables);
+    if n_inputs == 0 || n_inputs >= n_vars {
+        return Err(Error);
+    }
+    let n_g2 = tau_powers_g2.len().min(alpha_tau_powers_g1.len()).min(beta_tau_powers_g1.len());
+    let vecs = (
+        flatten_g1::<E>(tau_powers_g1),
+        flatten_g2::<E>(&tau_powers_g2[..n_g2]),
+        flatten_g1::<E>(&alpha_tau_powers_g1[..n_g2]),
+        flatten_g1::<E>(&beta_tau_powers_g1[..n_g2]),
+        flatten_g2::<E>(&[beta_g2]),
+    );
+    let view = sys::mg_kzg_view {
+        n_g1: tau_powers_g1.len() as u64,
+        n_g2: n_g2 as u64,
+        tau_powers_g1: vecs.0.as_ptr(),
+        tau_powers_g2: vecs.1.as_ptr(),
+        alpha_tau_powers_g1: vecs.2.as_ptr(),
+        beta_tau_powers_g1: vecs.3.as_ptr(),
+        beta_g2: vecs.4.as_ptr(),
+    };
+    let (a, b, c) = (Csr::new::<E>(&matrices.a), Csr::new::<E>(&matrices.b), Csr::new::<E>(&matrices.c));
+    let (g1, g2) = (
+        flatten_g1::<E>(&[E::G1Affine::prime_subgroup_generator()]),
+        flatten_g2::<E>(&[E::G2Affine::prime_subgroup_generator()]),
+    );
+    let (w1, w2) = (E::G1_LIMBS, E::G2_LIMBS);
+    let mut key = Phase2Key {
+        n_vars,
+        n_inputs,
+        h_len,
+        alpha_g1: vec![0; w1],
+        beta_g1: vec![0; w1],
+        delta_g1: vec![0; w1],
+        beta_g2: vec![0; w2],
+        gamma_g2: vec![0; w2],
+        delta_g2: vec![0; w2],
+        gamma_abc_g1: vec![0; n_inputs * w1],
+        a_query: vec![0; n_vars * w1],
+        b_g1_query: vec![0; n_vars * w1],
+        b_g2_query: vec![0; n_vars * w2],
+        h_query: vec![0; h_len * w1],
+        l_query: vec![0; (n_vars - n_inputs) * w1],
+    };
+    let out = sys::mg_pk_out {
+        alpha_g1: key.alpha_g1.as_mut_ptr(),
+        beta_g1: key.beta_g1.as_mut_ptr(),
+        delta_g1: key.delta_g1.as_mut_ptr(),
+        beta_g2: key.beta_g2.as_mut_ptr(),
+        gamma_g2: key.gamma_g2.as_mut_ptr(),
+        delta_g2: key.delta_g2.as_mut_ptr(),
+        gamma_abc_g1: key.gamma_abc_g1.as_mut_ptr(),
+        a_query: key.a_query.as_mut_ptr(),
+        b_g1_query: key.b_g1_query.as_mut_ptr(),
+        b_g2_query: key.b_g2_query.as_mut_ptr(),
+        h_query: key.h_query.as_mut_ptr(),
+        l_query: key.l_query.as_mut_ptr(),
+    };
+    // SAFETY: every input array has the length the view and the matrices declare; every output array has the length the
+    // header states for (n_vars, n_inputs, h_len), and the library checks h_len against the domain before it writes
+    check(unsafe {
+        sys::mg_mpc_initialize(
+            E::CURVE,
+            &view,
+            &a.view(),
+            &b.view(),
+            &c.view(),
+            matrices.num_constraints as u64,
+            n_vars as u64,
+            n_inputs as u64,
+            h_len as u64,
+            g1.as_ptr(),
+            g2.as_ptr(),
+            &out,
+        )
+    })?;
+    Ok(key)
 }
 
 /// `mg_init(device)`: bind the calling thread (and contexts created from it) to one GPU. One process per GPU is the

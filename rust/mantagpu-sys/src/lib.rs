@@ -189,6 +189,18 @@ pub struct mg_csr {
     pub nnz: u64,
 }
 
+/// The vectors of a `kzg::Accumulator` (manta-trusted-setup/src/groth16/kzg.rs:425-440) as `mg_mpc_initialize` reads them.
+#[repr(C)]
+pub struct mg_kzg_view {
+    pub n_g1: u64,
+    pub n_g2: u64,
+    pub tau_powers_g1: *const u64,
+    pub tau_powers_g2: *const u64,
+    pub alpha_tau_powers_g1: *const u64,
+    pub beta_tau_powers_g1: *const u64,
+    pub beta_g2: *const u64,
+}
+
 #[repr(C)]
 pub struct mg_pk_out {
     pub alpha_g1: *mut u64,
@@ -353,6 +365,32 @@ extern "C" {
         n_vars: u64,
         n_inputs: u64,
         toxic_mont: *const u64,
+        g1_generator: *const u64,
+        g2_generator: *const u64,
+        out: *const mg_pk_out,
+    ) -> c_int;
+    // ---- phase-2 key initialisation of the trusted setup (`mpc::initialize`, manta-trusted-setup/src/groth16/mpc.rs:353-431)
+    pub fn mg_qap_columns(
+        curve: mg_curve_t,
+        group: c_int,
+        n_terms: usize,
+        bases_affine: *const *const u64,
+        mats: *const *const mg_csr,
+        m: u64,
+        n_cols: u64,
+        entries_per_lane: u32,
+        out_affine: *mut u64,
+    ) -> c_int;
+    pub fn mg_mpc_initialize(
+        curve: mg_curve_t,
+        powers: *const mg_kzg_view,
+        a: *const mg_csr,
+        b: *const mg_csr,
+        c: *const mg_csr,
+        num_constraints: u64,
+        n_vars: u64,
+        n_inputs: u64,
+        h_len: u64,
         g1_generator: *const u64,
         g2_generator: *const u64,
         out: *const mg_pk_out,
