@@ -606,6 +606,36 @@ int mg_merkle_tree(const mg_poseidon *h, unsigned height, const uint64_t *leaves
  * at most 2^(height - 1) each) -> roots_out[i]. Routing leaves to trees stays with the caller (utxo.rs:1319-1337). */
 int mg_merkle_forest_roots(const mg_poseidon *h, unsigned height, const uint64_t *leaves_mont, const uint64_t *offsets,
                            size_t n_trees, uint64_t *roots_out);
+/* Appending to trees that are known only by their current path, as `merkle_tree::single_path::SinglePath` (the ledger's
+ * forest) and `Partial::from_leaves_and_path` (the signer's) keep them; replaces the hashing of `Tree::extend_digests` /
+ * `batch_push` (tree.rs:351-406) and `CurrentInnerPath::update` (path.rs:416), 19 dependent hashes per leaf there.
+ * The state of tree i: counts[i] = its leaves so far (n_old) and, for n_old > 0, leaf n_old - 1 and that leaf's `Path`
+ * exactly as mg_merkle_tree(..., indices = [n_old - 1]) returns it (`CurrentPath` with its sentinels written out: an entry
+ * on a level where bit l of n_old - 1 is 0 is a right sibling and must be 0). For n_old = 0 both are ignored. */
+typedef struct mg_merkle_state { /* n_trees trees, a struct of arrays */
+    uint64_t *counts;            /* [n_trees] */
+    uint64_t *last_leaves;       /* [n_trees][4] */
+    uint64_t *current_paths;     /* [n_trees][height - 1][4] */
+} mg_merkle_state;
+/* Tree i gets leaves offsets[i] .. offsets[i + 1] - 1 appended (offsets as for mg_merkle_forest_roots; b = 0 is allowed,
+ * n_old + b <= 2^(height - 1)). roots_out[i] and new_state (the state of leaf n_new - 1; unchanged for b = 0; new_state may
+ * be old_state, its arrays are the caller's) equal what mg_merkle_tree gives over all n_new leaves, bit for bit, and so do
+ *   paths_out [k][height - 1][4]: the `Path` in the new tree of new leaf path_indices[q] (n_old <= index < n_new) of tree
+ *     path_trees[q];
+ *   refresh_paths_inout [m][height - 1][4]: on entry the `Path` of older leaf refresh_indices[q] (< n_old) of tree
+ *     refresh_trees[q] in the old tree, on return its `Path` in the new one: only the entries whose sibling was recomputed
+ *     are overwritten.
+ * Only the nodes n_old >> l .. ceil(n_new / 2^l) - 1 of each level l are computed. Device memory of a call follows the
+ * appended work, not the trees' sizes: about (2 B + n_trees x height) x 32 B for B appended leaves in all, plus the states
+ * (n_trees x (height + 1) x 32 B) and the requests ((k + m) x height x 32 B).
+ * h must have width 3, height 2..32. MG_ERROR_INVALID_ARGUMENT, before any device work and with nothing written: a null array
+ * with a non-zero count, offsets not from 0 or decreasing, a tree over capacity, a request's tree >= n_trees or index outside
+ * its range, a non-zero right sibling in a current path. n_trees = 0 succeeds. */
+int mg_merkle_forest_append(const mg_poseidon *h, unsigned height, size_t n_trees, const mg_merkle_state *old_state,
+                            const uint64_t *leaves_mont, const uint64_t *offsets, uint64_t *roots_out,
+                            mg_merkle_state *new_state, const uint64_t *path_trees, const uint64_t *path_indices, size_t k,
+                            uint64_t *paths_out, const uint64_t *refresh_trees, const uint64_t *refresh_indices, size_t m,
+                            uint64_t *refresh_paths_inout);
 
 /* ---- manta-pay's embedded curve and its Poseidon note encryption, one point / note per GPU lane. The curve is
  *      `ed_on_bn254` (`Group = ed_on_bn254::EdwardsProjective`, manta-pay/src/config/mod.rs): a x^2 + y^2 = 1 + d x^2 y^2 over

@@ -74,7 +74,7 @@ EXPORTS = [
     "mg_tuning_init", "mg_get_tuning", "mg_set_tuning", "mg_tuning_env_names",
     "mg_points_decode", "mg_points_check", "mg_points_encode", "mg_proofs_decode",
     "mg_poseidon_create", "mg_poseidon_destroy", "mg_poseidon_permute", "mg_poseidon_hash", "mg_poseidon_hash_device",
-    "mg_merkle_tree", "mg_merkle_forest_roots",
+    "mg_merkle_tree", "mg_merkle_forest_roots", "mg_merkle_forest_append",
     "mg_edwards_decode", "mg_edwards_encode", "mg_edwards_check", "mg_edwards_mul", "mg_edwards_add",
     "mg_note_cipher_create", "mg_note_cipher_destroy", "mg_notes_encrypt", "mg_notes_decrypt",
     "mg_utxo_model_create", "mg_utxo_model_destroy", "mg_utxos_mint", "mg_utxos_open", "mg_viewing_keys",
@@ -1131,6 +1131,97 @@ def merkle_forest_roots(hasher: PoseidonHasher, height, leaves, offsets) -> np.n
     _chk(LIB.mg_merkle_forest_roots(hasher._h, ctypes.c_uint(int(height)), _p(lv), _p(off), _sz(nt), _p(roots)),
          "mg_merkle_forest_roots")
     return roots
+
+
+class _MerkleStateC(ctypes.Structure):  # mg_merkle_state
+    _fields_ = [("counts", _vp), ("last_leaves", _vp), ("current_paths", _vp)]
+
+
+class MerkleState:
+    """what `mg_merkle_forest_append` knows a forest by (mg_merkle_state): per tree its leaf count, its last leaf and that
+    leaf's `Path` -- `SinglePath` / `Partial::from_leaves_and_path` of the reference, the `CurrentPath`'s sentinels written
+    out as zeros. counts [n_trees] uint64, last_leaves [n_trees, 4], current_paths [n_trees, height - 1, 4] (Montgomery)."""
+
+    def __init__(self, counts, last_leaves, current_paths):
+        self.counts = np.array(_u64(counts).reshape(-1))
+        nt = self.counts.shape[0]
+        self.last_leaves = np.array(_u64(last_leaves).reshape(nt, 4))
+        cp = _u64(current_paths)
+        self.current_paths = np.array(cp if cp.ndim == 3 and cp.shape[0] == nt else cp.reshape(nt, -1, 4))
+
+    @classmethod
+    def empty(cls, n_trees, height):
+        """n_trees trees without leaves"""
+        n_trees, height = int(n_trees), int(height)
+        return cls(np.zeros(n_trees, dtype=np.uint64), np.zeros((n_trees, 4), dtype=np.uint64),
+                   np.zeros((n_trees, max(0, height - 1), 4), dtype=np.uint64))
+
+    @classmethod
+    def from_tree(cls, leaves, path):
+        """one tree from what `merkle_tree(hasher, height, leaves, indices=[n - 1])` was given and returned: its leaves (only
+        their number and the last one are kept) and the paths array [1, height - 1, 4] (n = 0: any [0 or 1, height - 1, 4])"""
+        lv = _u64(leaves).reshape(-1, 4)
+        n, path = lv.shape[0], _u64(path)
+        st = cls.empty(1, path.shape[-2] + 1)
+        st.counts[0] = n
+        if n:
+            st.last_leaves[0], st.current_paths[0] = lv[-1], path.reshape(-1, 4)
+        return st
+
+    @classmethod
+    def concat(cls, states):
+        """the forest made of the trees of several states, in order"""
+        states = list(states)
+        return cls(np.concatenate([s.counts for s in states]), np.concatenate([s.last_leaves for s in states]),
+                   np.concatenate([s.current_paths for s in states]))
+
+    def __len__(self):
+        return self.counts.shape[0]
+
+    def _c(self):
+        return _MerkleStateC(_p(self.counts), _p(self.last_leaves), _p(self.current_paths))
+
+
+def merkle_forest_append(hasher: PoseidonHasher, height, state: MerkleState, leaves, offsets, path_requests=(), refresh=(),
+                         in_place=False):
+    """appends leaves[offsets[i]:offsets[i + 1]] to tree i of the forest `state` describes (mg_merkle_forest_append), without the
+    older leaves. path_requests = (trees, indices) of new leaves whose `Path` in the new trees is wanted; refresh = (trees,
+    indices, paths [m, height - 1, 4]) of older leaves whose `Path` in the old trees is brought up to date. Returns (roots
+    [n_trees, 4], new state, paths [k, height - 1, 4], refreshed paths [m, height - 1, 4]). in_place: the new state is written
+    over `state` (which is also returned)."""
+    height = int(height)
+    lv = _u64(leaves).reshape(-1, 4)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    nt, plen = len(state), max(0, height - 1)
+    if off.shape[0] != nt + 1 or state.current_paths.shape[1] != plen:
+        raise ValueError("offsets must have one entry more than the state has trees, and the state's paths height - 1 entries")
+    pt, pi = (_u64(x).reshape(-1) for x in path_requests) if len(path_requests) else (np.zeros(0, dtype=np.uint64),) * 2
+    if len(refresh):
+        rt, ri = _u64(refresh[0]).reshape(-1), _u64(refresh[1]).reshape(-1)
+        rp = np.array(_u64(refresh[2]).reshape(rt.shape[0], plen, 4))
+    else:
+        rt = ri = np.zeros(0, dtype=np.uint64)
+        rp = np.zeros((0, plen, 4), dtype=np.uint64)
+    if pt.shape != pi.shape or rt.shape != ri.shape:
+        raise ValueError("a request is a (tree, index) pair")
+    new = state if in_place else MerkleState.empty(nt, height)
+    roots = np.zeros((nt, 4), dtype=np.uint64)
+    paths = np.zeros((pt.shape[0], plen, 4), dtype=np.uint64)
+    old_c, new_c = state._c(), new._c()
+    _chk(LIB.mg_merkle_forest_append(hasher._h, ctypes.c_uint(height), _sz(nt), ctypes.byref(old_c), _p(lv), _p(off), _p(roots),
+                                     ctypes.byref(new_c), _p(pt), _p(pi), _sz(pt.shape[0]), _p(paths), _p(rt), _p(ri),
+                                     _sz(rt.shape[0]), _p(rp)), "mg_merkle_forest_append")
+    return roots, new, paths, rp
+
+
+def merkle_append(hasher: PoseidonHasher, height, state: MerkleState, leaves, path_indices=(), refresh=()):
+    """merkle_forest_append for one tree: refresh = (indices, paths). Returns (root [4], new state, paths, refreshed paths)."""
+    lv = _u64(leaves).reshape(-1, 4)
+    pi = _u64(path_indices).reshape(-1)
+    req = (np.zeros_like(pi), pi) if pi.shape[0] else ()
+    ref = (np.zeros(len(refresh[0]), dtype=np.uint64), refresh[0], refresh[1]) if len(refresh) else ()
+    roots, new, paths, rp = merkle_forest_append(hasher, height, state, lv, [0, lv.shape[0]], req, ref)
+    return roots[0], new, paths, rp
 
 
 # ---- manta-pay's embedded curve (ed_on_bn254) and its Poseidon note encryption -------------------------------------------

@@ -908,6 +908,10 @@ int merkle_tree(const mg_poseidon *h, unsigned height, const u64 *leaves, size_t
                 u64 *paths_out);
 int merkle_forest_roots(const mg_poseidon *h, unsigned height, const u64 *leaves, const u64 *offsets, size_t n_trees,
                         u64 *roots_out);
+int merkle_forest_append(const mg_poseidon *h, unsigned height, size_t n_trees, const u64 *old_counts, const u64 *old_last,
+                         const u64 *old_paths, const u64 *leaves, const u64 *offsets, u64 *roots_out, u64 *new_counts,
+                         u64 *new_last, u64 *new_paths, const u64 *path_trees, const u64 *path_indices, size_t k, u64 *paths_out,
+                         const u64 *refresh_trees, const u64 *refresh_indices, size_t m, u64 *refresh_paths);
 } // namespace mg
 MG_API int mg_poseidon_create(mg_curve_t curve, int width, int full_rounds, int partial_rounds, const uint8_t *bytes, size_t len,
                               mg_poseidon **out) {
@@ -941,6 +945,19 @@ MG_API int mg_merkle_forest_roots(const mg_poseidon *h, unsigned height, const u
                                   size_t n_trees, uint64_t *roots_out) {
     MG_TRY
     return merkle_forest_roots(h, height, leaves_mont, offsets, n_trees, roots_out);
+    MG_CATCH
+}
+MG_API int mg_merkle_forest_append(const mg_poseidon *h, unsigned height, size_t n_trees, const mg_merkle_state *old_state,
+                                   const uint64_t *leaves_mont, const uint64_t *offsets, uint64_t *roots_out,
+                                   mg_merkle_state *new_state, const uint64_t *path_trees, const uint64_t *path_indices, size_t k,
+                                   uint64_t *paths_out, const uint64_t *refresh_trees, const uint64_t *refresh_indices, size_t m,
+                                   uint64_t *refresh_paths_inout) {
+    MG_TRY
+    if (n_trees && (!old_state || !new_state)) return MG_ERR_ARG;
+    const mg_merkle_state none{nullptr, nullptr, nullptr}, &o = old_state ? *old_state : none, &n = new_state ? *new_state : none;
+    return merkle_forest_append(h, height, n_trees, o.counts, o.last_leaves, o.current_paths, leaves_mont, offsets, roots_out,
+                                n.counts, n.last_leaves, n.current_paths, path_trees, path_indices, k, paths_out, refresh_trees,
+                                refresh_indices, m, refresh_paths_inout);
     MG_CATCH
 }
 

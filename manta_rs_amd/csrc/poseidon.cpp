@@ -179,6 +179,115 @@ int merkle_tree(const mg_poseidon *h, unsigned height, const u64 *leaves, size_t
     return merkle_run(h, height, leaves, std::vector<u64>{n}, true, root_out, indices, k, paths_out);
 }
 
+// Appends leaves offsets[i] .. offsets[i + 1] - 1 to tree i of a forest known by its state (count, last leaf, current path per
+// tree), gathers the k requested Paths of new leaves and refreshes the m Paths of older ones. Device memory follows the work:
+// the recomputed nodes (level 0 = the new leaves; at most 2 B + n_trees x height for B leaves), the states and the requests.
+// Levels below l0 -- the first with at most MERKLE_TOP recomputed nodes per tree, usually 0 -- take one launch each, the top
+// kernel finishes every tree, one gather launch writes paths, current paths and last leaves.
+int merkle_forest_append(const mg_poseidon *h, unsigned height, size_t n_trees, const u64 *old_counts, const u64 *old_last,
+                         const u64 *old_paths, const u64 *leaves, const u64 *offsets, u64 *roots_out, u64 *new_counts,
+                         u64 *new_last, u64 *new_paths, const u64 *path_trees, const u64 *path_indices, size_t k, u64 *paths_out,
+                         const u64 *refresh_trees, const u64 *refresh_indices, size_t m, u64 *refresh_paths) {
+    if (!tree_args_ok(h, height)) return MG_ERR_ARG;
+    if (n_trees && (!old_counts || !old_last || !old_paths || !offsets || !roots_out || !new_counts || !new_last || !new_paths))
+        return MG_ERR_ARG;
+    if ((k && (!path_trees || !path_indices || !paths_out)) || (m && (!refresh_trees || !refresh_indices || !refresh_paths)))
+        return MG_ERR_ARG;
+    if (n_trees && offsets[0] != 0) return MG_ERR_ARG;
+    const size_t nt = n_trees, T1 = nt + 1, H = height, len = H - 1;
+    const u64 cap = u64(1) << len;
+    std::vector<u64> n_new(nt);
+    for (size_t i = 0; i < nt; ++i) {
+        const u64 n_old = old_counts[i];
+        if (offsets[i + 1] < offsets[i] || n_old > cap || offsets[i + 1] - offsets[i] > cap - n_old) return MG_ERR_ARG;
+        n_new[i] = n_old + (offsets[i + 1] - offsets[i]);
+        if (n_old == 0) continue;
+        const u64 *path = old_paths + i * len * 4; // a current path has no right siblings (InnerPath::is_current)
+        for (size_t l = 0; l < len; ++l)
+            if (!(((n_old - 1) >> l) & 1) && (path[4 * l] | path[4 * l + 1] | path[4 * l + 2] | path[4 * l + 3])) return MG_ERR_ARG;
+    }
+    if (nt && offsets[nt] && !leaves) return MG_ERR_ARG;
+    for (size_t q = 0; q < k; ++q)
+        if (path_trees[q] >= nt || path_indices[q] < old_counts[path_trees[q]] || path_indices[q] >= n_new[path_trees[q]])
+            return MG_ERR_ARG;
+    for (size_t q = 0; q < m; ++q)
+        if (refresh_trees[q] >= nt || refresh_indices[q] >= old_counts[refresh_trees[q]]) return MG_ERR_ARG;
+    if (nt == 0) return MG_OK;
+    // the table of the recomputed ranges: level l of tree i holds nodes n_old >> l .. ceil(n_new / 2^l) - 1
+    std::vector<u64> off(H * T1), total(H);
+    u64 base = 0;
+    int l0 = -1;
+    for (size_t l = 0; l < H; ++l) {
+        u64 mx = 0;
+        for (size_t i = 0; i < nt; ++i) {
+            const u64 c = ((n_new[i] + (u64(1) << l) - 1) >> l) - (old_counts[i] >> l);
+            off[l * T1 + i] = base;
+            base += c;
+            mx = c > mx ? c : mx;
+        }
+        off[l * T1 + nt] = base;
+        total[l] = base - off[l * T1];
+        if (l0 < 0 && (mx <= (u64)MERKLE_TOP || l == H - 1)) l0 = (int)l;
+    }
+    hipStream_t s = setup_stream();
+    if (!s) return MG_ERR_OOM;
+    const size_t pb = prm_bytes(h), n_req = k + m, path_bytes = len * 32;
+    DevBlock d; // parameters | table | counts old, new | last leaves | current paths | chain | nodes | roots | requests | paths | new last
+    if (const int rc = d.alloc({pb, off.size() * 8, nt * 8, nt * 8, nt * 32, nt * path_bytes, nt * 32, base * 32, nt * 32, n_req * 8,
+                                n_req * 8, (n_req + nt) * path_bytes, nt * 32},
+                               "hipMalloc(merkle append)"))
+        return rc;
+    const auto up = [&](size_t i, const void *src, size_t bytes, size_t at = 0) {
+        return bytes ? hipMemcpyAsync(d.dev(i) + at, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    };
+    MG_HIP(up(0, h->prm.data(), pb));
+    MG_HIP(up(1, off.data(), off.size() * 8));
+    MG_HIP(up(2, old_counts, nt * 8));
+    MG_HIP(up(3, n_new.data(), nt * 8));
+    MG_HIP(up(4, old_last, nt * 32));
+    MG_HIP(up(5, old_paths, nt * path_bytes));
+    MG_HIP(hipMemcpyAsync(d.dev(6), d.dev(4), nt * 32, hipMemcpyDeviceToDevice, s)); // the chain starts at the last leaf
+    MG_HIP(up(7, leaves, total[0] * 32));
+    MG_HIP(up(9, path_trees, k * 8));
+    MG_HIP(up(9, refresh_trees, m * 8, k * 8));
+    MG_HIP(up(10, path_indices, k * 8));
+    MG_HIP(up(10, refresh_indices, m * 8, k * 8));
+    MG_HIP(up(11, refresh_paths, m * path_bytes, k * path_bytes)); // refreshed in place
+    PoseidonLaunch a{};
+    a.prm = d.dev<const u32>(0);
+    a.app = MerkleAppend{d.dev<const u64>(2), d.dev<const u64>(3), d.dev<const u32>(4), d.dev<const u32>(5), d.dev<u32>(6),
+                         d.dev<u32>(7),       d.dev<const u64>(1), (int)nt,             (int)H};
+    a.stream = s;
+    for (int l = 0; l < l0; ++l) {
+        a.op = PoseidonLaunch::APPEND_LEVEL;
+        a.level = l;
+        a.n = total[l + 1];
+        MG_HIP(launch(h, a));
+    }
+    a.op = PoseidonLaunch::APPEND_TOP;
+    a.level = l0;
+    a.roots = d.dev<u32>(8);
+    MG_HIP(launch(h, a));
+    a.op = PoseidonLaunch::APPEND_GATHER;
+    a.n = n_req;
+    a.req_trees = d.dev<const u64>(9);
+    a.indices = d.dev<const u64>(10);
+    a.out = d.dev<u32>(11);
+    a.roots = d.dev<u32>(12);
+    MG_HIP(launch(h, a));
+    const auto down = [&](void *dst, size_t i, size_t bytes, size_t at = 0) {
+        return bytes ? hipMemcpyAsync(dst, d.dev(i) + at, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    MG_HIP(down(roots_out, 8, nt * 32));
+    MG_HIP(down(paths_out, 11, k * path_bytes));
+    MG_HIP(down(refresh_paths, 11, m * path_bytes, k * path_bytes));
+    MG_HIP(down(new_paths, 11, nt * path_bytes, n_req * path_bytes));
+    MG_HIP(down(new_last, 12, nt * 32));
+    MG_HIP(hipStreamSynchronize(s));
+    std::memcpy(new_counts, n_new.data(), nt * 8); // last: new_state may be old_state
+    return MG_OK;
+}
+
 int merkle_forest_roots(const mg_poseidon *h, unsigned height, const u64 *leaves, const u64 *offsets, size_t n_trees,
                         u64 *roots_out) {
     if (!tree_args_ok(h, height) || (n_trees && (!offsets || !roots_out))) return MG_ERR_ARG;

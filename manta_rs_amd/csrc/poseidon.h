@@ -16,6 +16,13 @@
 // hash(node 2j, node 2j + 1) with an absent right child taken as 0; level l holds ceil(n / 2^l) nodes, the rest are the
 // sentinel 0. A forest is a table of per-tree segment offsets per level (off[l (n_trees + 1) + k]): tree k's nodes of level l
 // are entries off[l][k] .. off[l][k + 1] of that level's buffer.
+//
+// Appending (merkle_tree/{single_path,partial}.rs, tree.rs:351-406, path.rs:416): a tree is known by its leaf count n_old, its
+// last leaf and that leaf's Path. Appending b leaves (n_new = n_old + b) recomputes on level l the nodes s_l = n_old >> l ..
+// ceil(n_new / 2^l) - 1; only those are stored (the table's segments hold them, segment entry i = node s_l + i). The one older
+// node that work reads is node(l, s_l - 1) for odd s_l, the level's seed: the old path's entry l when n_old mod 2^l != 0, else
+// (l = ctz(n_old)) the last leaf's ancestor a_l, a_0 = last leaf, a_{j+1} = hash(path[j], a_j). That chain is one extra lane
+// per tree in each level pass (pass l -> l + 1 computes a_{l+1} while l < ctz(n_old)), never a fold of its own.
 #pragma once
 #include "engine.h"
 #include "fp_dev.h"
@@ -23,9 +30,19 @@
 
 namespace mg {
 
+// the device side of one append to a forest (APPEND_*): the old state, the kept recomputed nodes and their table
+struct MerkleAppend {
+    const u64 *n_old, *n_new; // [n_trees] leaf counts before and after
+    const u32 *last, *cur;    // the old state: last leaves [n_trees], current paths [n_trees][height - 1]
+    u32 *anc;                 // [n_trees] the ancestor chain: starts as a copy of `last`, ends as a_ctz(n_old)
+    u32 *nodes;               // every recomputed node, level after level
+    const u64 *off;           // [height][n_trees + 1] absolute segment offsets into `nodes`
+    int n_trees, height;
+};
+
 // keys | mds | tag in Montgomery words of 8 x u32 per element
 struct PoseidonLaunch {
-    enum Op { PERMUTE = 0, HASH = 1, LEVEL = 2, TOP = 3, PATHS = 4 };
+    enum Op { PERMUTE = 0, HASH = 1, LEVEL = 2, TOP = 3, PATHS = 4, APPEND_LEVEL = 5, APPEND_TOP = 6, APPEND_GATHER = 7 };
     int op, width, half_full, partial;
     const u32 *prm;      // device parameters
     const u32 *in;       // PERMUTE: n states (in place, = out); HASH: n x (t - 1) inputs; LEVEL / TOP: the source level
@@ -36,7 +53,12 @@ struct PoseidonLaunch {
     int n_trees, level, height;
     u32 *keep;           // TOP: where the levels above `level` are written (the table's absolute offsets), or null
     u32 *roots;          // TOP: n_trees roots
-    const u64 *indices;  // PATHS: leaf indices
+    const u64 *indices;  // PATHS: leaf indices; APPEND_GATHER: the requests' leaf indices
+    // APPEND_LEVEL: level -> level + 1 over n parents and the chain lanes; APPEND_TOP: finishes from `level`, roots; APPEND_GATHER:
+    // n requests (trees `req_trees`, leaves `indices`) then one per tree for its new current path -> out [n + n_trees] paths,
+    // and the new last leaves -> roots
+    MerkleAppend app;
+    const u64 *req_trees;
     hipStream_t stream;
 };
 hipError_t poseidon_launch_bn254(const PoseidonLaunch &a);
@@ -216,6 +238,132 @@ __global__ __launch_bounds__(POSEIDON_BLOCK) void paths_kernel(const u32 *__rest
     (s < c ? Fp<C>::load(levels + (lo + s) * 8) : Fp<C>::zero()).store(out + g * 8);
 }
 
+// ---- appending: the same three steps over the recomputed ranges only ------------------------------------------------------
+MG_DEV u64 nodes_end(u64 n, int l) { return (n + ((u64)1 << l) - 1) >> l; } // ceil(n / 2^l)
+// does pass l -> l + 1 advance tree's ancestor chain: l < ctz(n_old)
+MG_DEV bool chain_runs(u64 n_old, int l) { return n_old && !(n_old & (((u64)2 << l) - 1)); }
+// node(l, s_l - 1) of tree k for odd s_l; `anc` is where the chain stands (t.anc, or the top kernel's copy in LDS)
+template <class C> MG_DEV Fp<C> seed_of(const MerkleAppend &t, int k, int l, u64 n_old, const u32 *anc) {
+    return Fp<C>::load(n_old & (((u64)1 << l) - 1) ? t.cur + ((size_t)k * (t.height - 1) + l) * 8 : anc);
+}
+
+// level l -> l + 1 of every tree's recomputed range, one lane per parent: a left child one below the segment start is the
+// level's seed; after the parents one lane per tree hashes the next link of its chain
+template <class C>
+__global__ __launch_bounds__(POSEIDON_BLOCK) void append_level_kernel(const u32 *__restrict__ prm, int hf, int partial,
+                                                                      MerkleAppend t, int l, size_t n_parents) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_parents + t.n_trees) return;
+    Fp<C> a, b;
+    u32 *dst;
+    if (i < n_parents) {
+        const u64 *src_off = t.off + (size_t)l * (t.n_trees + 1), *dst_off = src_off + t.n_trees + 1;
+        const u64 e = dst_off[0] + i;
+        const int k = tree_of(dst_off, t.n_trees, e);
+        const u64 n_old = t.n_old[k], s = n_old >> l, c = src_off[k + 1] - src_off[k];
+        const u64 j = (n_old >> (l + 1)) + (e - dst_off[k]);
+        const u64 r = 2 * j + 1 - s; // the right child's place in the segment; the left child is one before it, or the seed
+        const u32 *ch = t.nodes + (src_off[k] + r) * 8;
+        a = r ? Fp<C>::load(ch - 8) : seed_of<C>(t, k, l, n_old, t.anc + (size_t)k * 8);
+        b = r < c ? Fp<C>::load(ch) : Fp<C>::zero();
+        dst = t.nodes + e * 8;
+    } else {
+        const size_t k = i - n_parents;
+        if (!chain_runs(t.n_old[k], l)) return;
+        dst = t.anc + k * 8;
+        a = Fp<C>::load(t.cur + (k * (t.height - 1) + l) * 8);
+        b = Fp<C>::load(dst);
+    }
+    hash2<C>(a, b, prm, hf, partial).store(dst);
+}
+
+// the finish of each tree in LDS, one block per tree, from level `l0` (at most MERKLE_TOP recomputed nodes per tree): levels
+// alternate between two LDS buffers, every level is also written to its segment (the gather reads it), and the chain is one
+// more item of a level while it runs
+constexpr int APPEND_LDS_B = MERKLE_TOP, APPEND_LDS_ANC = MERKLE_TOP + MERKLE_TOP / 2 + 8; // a level above l0 has <= TOP / 2 + 1
+template <class C>
+__global__ __launch_bounds__(POSEIDON_BLOCK) void append_top_kernel(const u32 *__restrict__ prm, int hf, int partial,
+                                                                    MerkleAppend t, int l0, u32 *__restrict__ roots) {
+    __shared__ u32 lds[(APPEND_LDS_ANC + 1) * 8];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const size_t stride = (size_t)t.n_trees + 1;
+    const u64 n_old = t.n_old[k], n_new = t.n_new[k];
+    u32 *const anc = lds + APPEND_LDS_ANC * 8;
+    u32 src = 0, dst = APPEND_LDS_B * 8; // word offsets of the level read and the level written
+    const u64 base = t.off[l0 * stride + k];
+    u32 c = (u32)(t.off[l0 * stride + k + 1] - base);
+#pragma unroll 1
+    for (u32 j = tid; j < c; j += POSEIDON_BLOCK) Fp<C>::load(t.nodes + (base + j) * 8).store(lds + j * 8);
+    if (tid == 0) Fp<C>::load(t.anc + (size_t)k * 8).store(anc);
+    __syncthreads();
+#pragma unroll 1
+    for (int l = l0; l < t.height - 1; ++l) {
+        const u64 s = n_old >> l, sp = n_old >> (l + 1), up = t.off[(l + 1) * stride + k];
+        const u32 cp = (u32)(nodes_end(n_new, l + 1) - sp), items = cp + (chain_runs(n_old, l) ? 1 : 0);
+#pragma unroll 1
+        for (u32 it = tid; it < items; it += POSEIDON_BLOCK) {
+            Fp<C> a, b;
+            if (it < cp) {
+                const u64 j = sp + it;
+                const u32 r = (u32)(2 * j + 1 - s); // the right child's place in the level; the left child is one before it
+                const u32 *ch = lds + src + r * 8;
+                a = r ? Fp<C>::load(ch - 8) : seed_of<C>(t, k, l, n_old, anc);
+                b = r < c ? Fp<C>::load(ch) : Fp<C>::zero();
+            } else {
+                a = Fp<C>::load(t.cur + ((size_t)k * (t.height - 1) + l) * 8);
+                b = Fp<C>::load(anc);
+            }
+            const Fp<C> hsh = hash2<C>(a, b, prm, hf, partial);
+            if (it < cp) {
+                hsh.store(lds + dst + it * 8);
+                hsh.store(t.nodes + (up + it) * 8);
+            } else
+                hsh.store(anc); // read above by this lane only: a level reads the chain as its seed only once it has ended
+        }
+        __syncthreads();
+        const u32 x = src;
+        src = dst, dst = x, c = cp;
+    }
+    if (tid == 0) { // a full tree appends nothing and recomputes nothing: its root is the end of the chain
+        (n_new == 0 ? Fp<C>::zero() : Fp<C>::load(c ? lds + src : anc)).store(roots + (size_t)k * 8);
+        Fp<C>::load(anc).store(t.anc + (size_t)k * 8);
+    }
+}
+
+// one lane per (request, level): entry l of the Path of leaf idx in the new tree is 0 past the level's last node, a recomputed
+// node from s_l on, the level's seed for a new leaf, and otherwise -- an older leaf's older sibling -- left as it is in `out`.
+// Requests n_req .. n_req + n_trees - 1 are the trees' new current paths (the old one when nothing was appended); the last
+// n_trees lanes write the new last leaves.
+template <class C>
+__global__ __launch_bounds__(POSEIDON_BLOCK) void append_gather_kernel(MerkleAppend t, const u64 *__restrict__ req_trees,
+                                                                       const u64 *__restrict__ req_idx, size_t n_req,
+                                                                       u32 *__restrict__ out, u32 *__restrict__ new_last) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int len = t.height - 1;
+    const size_t entries = (n_req + t.n_trees) * (size_t)len;
+    if (g >= entries + t.n_trees) return;
+    if (g >= entries) {
+        const size_t k = g - entries;
+        const u64 b = t.n_new[k] - t.n_old[k];
+        Fp<C>::load(b ? t.nodes + (t.off[k] + b - 1) * 8 : t.last + k * 8).store(new_last + k * 8);
+        return;
+    }
+    const size_t q = g / len;
+    const int l = (int)(g % len);
+    const int k = (int)(q < n_req ? req_trees[q] : q - n_req);
+    const u64 n_old = t.n_old[k], n_new = t.n_new[k];
+    u64 idx;
+    if (q < n_req) idx = req_idx[q];
+    else if (n_new == n_old) {
+        Fp<C>::load(t.cur + ((size_t)k * len + l) * 8).store(out + g * 8);
+        return;
+    } else idx = n_new - 1;
+    const u64 s = n_old >> l, sib = (idx >> l) ^ 1;
+    if (sib >= nodes_end(n_new, l)) Fp<C>::zero().store(out + g * 8);
+    else if (sib >= s) Fp<C>::load(t.nodes + (t.off[(size_t)l * (t.n_trees + 1) + k] + sib - s) * 8).store(out + g * 8);
+    else if (idx >= n_old) seed_of<C>(t, k, l, n_old, t.anc + (size_t)k * 8).store(out + g * 8);
+}
+
 } // namespace pos
 
 template <class C> hipError_t poseidon_launch(const PoseidonLaunch &a) {
@@ -258,6 +406,18 @@ template <class C> hipError_t poseidon_launch(const PoseidonLaunch &a) {
         if (a.n == 0) return hipSuccess;
         hipLaunchKernelGGL((pos::paths_kernel<C>), grid(a.n * (size_t)(a.height - 1)), blk, 0, a.stream, a.in, a.src_off,
                            a.height, a.indices, a.n, a.out);
+        break;
+    case PoseidonLaunch::APPEND_LEVEL:
+        hipLaunchKernelGGL((pos::append_level_kernel<C>), grid(a.n + a.app.n_trees), blk, 0, a.stream, a.prm, a.half_full, a.partial,
+                           a.app, a.level, a.n);
+        break;
+    case PoseidonLaunch::APPEND_TOP:
+        hipLaunchKernelGGL((pos::append_top_kernel<C>), dim3((unsigned)a.app.n_trees), blk, 0, a.stream, a.prm, a.half_full,
+                           a.partial, a.app, a.level, a.roots);
+        break;
+    case PoseidonLaunch::APPEND_GATHER:
+        hipLaunchKernelGGL((pos::append_gather_kernel<C>), grid((a.n + a.app.n_trees) * (size_t)a.app.height), blk, 0, a.stream,
+                           a.app, a.req_trees, a.indices, a.n, a.out, a.roots);
         break;
     default: return hipErrorInvalidValue;
     }

@@ -73,6 +73,13 @@ pub struct mg_poseidon {
     _private: [u8; 0],
 }
 pub const MG_POSEIDON_CHUNK: usize = 1 << 19;
+/// The per-tree state `mg_merkle_forest_append` reads and writes: leaf count, last leaf and its `Path` (arrays over the trees).
+#[repr(C)]
+pub struct mg_merkle_state {
+    pub counts: *mut u64,
+    pub last_leaves: *mut u64,
+    pub current_paths: *mut u64,
+}
 #[repr(C)]
 pub struct mg_note_cipher {
     _private: [u8; 0],
@@ -560,6 +567,24 @@ extern "C" {
         offsets: *const u64,
         n_trees: usize,
         roots_out: *mut u64,
+    ) -> c_int;
+    pub fn mg_merkle_forest_append(
+        h: *const mg_poseidon,
+        height: c_uint,
+        n_trees: usize,
+        old_state: *const mg_merkle_state,
+        leaves_mont: *const u64,
+        offsets: *const u64,
+        roots_out: *mut u64,
+        new_state: *mut mg_merkle_state,
+        path_trees: *const u64,
+        path_indices: *const u64,
+        k: usize,
+        paths_out: *mut u64,
+        refresh_trees: *const u64,
+        refresh_indices: *const u64,
+        m: usize,
+        refresh_paths_inout: *mut u64,
     ) -> c_int;
 
     // ---- the embedded curve (ed_on_bn254) and the Poseidon note cipher (MG_EDWARDS_CHUNK lanes per device pass)
