@@ -190,6 +190,29 @@ int mg_ec_elementwise(mg_curve_t curve, int group, int op, const uint64_t *a_aff
 #define MG_FIELD_INV 7
 int mg_field_op(int field, int op, int repr, int lazy_a, int lazy_b, const uint64_t *a, const uint64_t *b, size_t n,
                 uint64_t *out);
+/* The reduced-radix routines of the MSM kernels on RAW limb vectors: a, b, c, d and out are [n][K] uint32 limbs of LB bits
+ * (K x LB = 9 x 29 for the three 256-bit fields, 13 x 30 for BLS12-381 Fq), used as they are -- no conversion before or after.
+ *   op 0: a b R'^-1   1: a^2 R'^-1   2: (a b + c d) R'^-1   (almost-Montgomery, R' = 2^(K LB): the exact integer
+ *         (t + (t (-p^-1) mod R') p) / R' of t = a b [+ c d], K - 1 masked limbs and the unmasked top limb)
+ *      3: a + 6 p - b - 2 c   4: a + 12 p - b - 2 c   (limbs normalised; need b + 2 c < 6 p, 12 p)
+ *   coding 0: the plain routines (mul, sqr, mul_add, sub2); 1: what the accumulate kernel calls (mul_t / sqr_t / mul_add_t<true>,
+ *   sub2n). For the 29-bit fields coding 1 is the single-chain coding of the products. For BLS12-381 Fq the shipped library
+ *   builds those three as the plain routines (the single-chain coding of the flushed field is compiled only with
+ *   -DMG_CHAIN_FLUSHED: an A/B twin, on which the raw tests have to be run again), so there only sub2n differs from coding 0.
+ * Operands an op does not take are ignored (may be NULL). n <= 2^24. */
+#define MG_FPR_MUL 0
+#define MG_FPR_SQR 1
+#define MG_FPR_MUL_ADD 2
+#define MG_FPR_SUB2_6 3
+#define MG_FPR_SUB2_12 4
+int mg_fpr_raw_op(int field, int op, int coding, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d,
+                  size_t n, uint32_t *out);
+/* Where those products move a column accumulator's upper part aside ("flush") so that it cannot pass 2^64 -- the compile-time
+ * plan of the kernels, readable without a GPU. kind = MG_FPR_MUL / MG_FPR_SQR / MG_FPR_MUL_ADD. flush[k], k < 2 K - 1:
+ * bit 0 / 1 / 2 = flush before the a b / c d / m p products of column k; peak[k] = the planner's worst-case accumulator value
+ * of the column. *cols = 2 K - 1 (flush and peak hold at least 25 entries), *limb_bits = LB, *flushed_routines = 1 when the
+ * field's products run the group-by-group routines that consult the plan at all. Any output may be NULL. */
+int mg_fpr_column_plan(int field, int kind, uint32_t *flush, uint64_t *peak, int *cols, int *limb_bits, int *flushed_routines);
 /* The first two stages of the MSM pipeline, each alone over host arrays: parity-test surfaces for the kernels that
  * mg_msm_launch runs (the same digit kernel, the same radix sort), not needed by the shim. Synchronous; one device
  * block per call. The OUTPUT arrays are uploaded from the caller's buffers before the launch, so whatever the kernels

@@ -81,7 +81,7 @@ EXPORTS = [
     "mg_blake2s256", "mg_schnorr_challenges", "mg_signatures_verify", "mg_signatures_sign",
     "mg_blake2s", "mg_aes256_gcm", "mg_address_partitions", "mg_merkle_shard_indices",
     "mg_light_notes_encrypt", "mg_light_notes_open", "mg_outgoing_notes_encrypt", "mg_outgoing_notes_open",
-    "mg_qap_columns", "mg_mpc_initialize",
+    "mg_qap_columns", "mg_mpc_initialize", "mg_fpr_raw_op", "mg_fpr_column_plan",
 ]
 
 
@@ -464,6 +464,38 @@ def field_op(field, op, a, b=None, repr=0, lazy_a=0, lazy_b=0) -> np.ndarray:
     _chk(LIB.mg_field_op(FIELD_IDS[field], FIELD_OPS[op], int(repr), int(lazy_a), int(lazy_b), _p(a), _p(bb), _sz(a.shape[0]),
                          _p(out)), "mg_field_op")
     return out
+
+
+FPR_OPS = {"mul": 0, "sqr": 1, "mul_add": 2, "sub2_6": 3, "sub2_12": 4}
+FPR_LIMBS = {"bn254_fr": (9, 29), "bn254_fq": (9, 29), "bls381_fr": (9, 29), "bls381_fq": (13, 30)}  # (K, LB)
+
+
+def fpr_raw_op(field, op, a, b=None, c=None, d=None, chain=False) -> np.ndarray:
+    """One reduced-radix routine of the MSM kernels over RAW limb vectors (`mg_fpr_raw_op`): a, b, c, d = [n, K] uint32
+    limbs, no conversion on the way in or out. op = "mul" | "sqr" | "mul_add" | "sub2_6" | "sub2_12" (a + 6p / 12p - b - 2c).
+    chain selects what the accumulate kernel calls: mul_t / sqr_t / mul_add_t<true> and sub2n. For BLS12-381 Fq the shipped
+    library builds those products as the plain routines (single chain only with -DMG_CHAIN_FLUSHED), so only sub2n differs."""
+    K = FPR_LIMBS[field][0]
+    arrs = [None if x is None else np.ascontiguousarray(x, dtype=np.uint32) for x in (a, b, c, d)]
+    need = {"sqr": 1, "mul": 2, "sub2_6": 3, "sub2_12": 3, "mul_add": 4}[op]
+    for x in arrs[:need]:
+        assert x is not None and x.ndim == 2 and x.shape == arrs[0].shape and x.shape[1] == K, (op, None if x is None else x.shape)
+    out = np.zeros_like(arrs[0])
+    _chk(LIB.mg_fpr_raw_op(FIELD_IDS[field], FPR_OPS[op], int(bool(chain)), _p(arrs[0]), _p(arrs[1]), _p(arrs[2]), _p(arrs[3]),
+                           _sz(arrs[0].shape[0]), _p(out)), "mg_fpr_raw_op")
+    return out
+
+
+def fpr_column_plan(field, kind) -> dict:
+    """Where the reduced-radix products of `field` flush a column accumulator (`mg_fpr_column_plan`; no GPU needed):
+    kind = "mul" | "sqr" | "mul_add" -> dict(flush=[per column: bit 0 / 1 / 2 = before the a b / c d / m p group], peak=[per
+    column: worst-case accumulator value], limb_bits, flushed_routines)."""
+    flush, peak = np.zeros(25, dtype=np.uint32), np.zeros(25, dtype=np.uint64)
+    cols, lb, fr = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    _chk(LIB.mg_fpr_column_plan(FIELD_IDS[field], FPR_OPS[kind], _p(flush), _p(peak), ctypes.byref(cols), ctypes.byref(lb),
+                                ctypes.byref(fr)), "mg_fpr_column_plan")
+    return dict(flush=[int(x) for x in flush[:cols.value]], peak=[int(x) for x in peak[:cols.value]], limb_bits=lb.value,
+                flushed_routines=bool(fr.value))
 
 
 def _u32_buffer(a, n, name):

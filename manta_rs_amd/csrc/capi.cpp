@@ -435,6 +435,23 @@ MG_API int mg_field_op(int field, int op, int repr, int lazy_a, int lazy_b, cons
     MG_CATCH
 }
 
+// the reduced-radix routines on raw limb vectors, and where their products flush a column (field_ops.hip)
+namespace mg {
+int fpr_raw_op(int field, int op, int coding, const u32 *a, const u32 *b, const u32 *c, const u32 *d, size_t n, u32 *out);
+int fpr_column_plan_host(int field, int kind, u32 *flush, u64 *peak, int *cols, int *limb_bits, int *flushed_routines);
+}
+MG_API int mg_fpr_raw_op(int field, int op, int coding, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d, size_t n,
+                         uint32_t *out) {
+    MG_TRY
+    return fpr_raw_op(field, op, coding, a, b, c, d, n, out);
+    MG_CATCH
+}
+MG_API int mg_fpr_column_plan(int field, int kind, uint32_t *flush, uint64_t *peak, int *cols, int *limb_bits, int *flushed_routines) {
+    MG_TRY
+    return fpr_column_plan_host(field, kind, flush, peak, cols, limb_bits, flushed_routines);
+    MG_CATCH
+}
+
 // The MSM front end stage by stage (parity-test surfaces, as mg_field_op is for the field arithmetic): the digit kernel and the
 // radix sort msm_launch runs, each alone over host arrays.
 MG_API int mg_msm_digits(mg_curve_t curve, const uint64_t *scalars, size_t batch, size_t n_scalars, int scalar_flags, int window_bits,

@@ -249,7 +249,7 @@ template <class F> struct XYZZ {
         constexpr bool LL = F::LAZY_LIMBS;
         const F PPP = F::template mul_t<CH>(c.P, c.PP);
         const F Q = F::template mul_t<CH>(x, c.PP);
-        const F X3 = F::template sub2<6>(F::template sqr_t<CH>(c.R), PPP, Q); // R^2 + 6p - PPP - 2Q < 8p, normalised
+        const F X3 = F::template sub2n<6>(F::template sqr_t<CH>(c.R), PPP, Q); // R^2 + 6p - PPP - 2Q < 8p, normalised
         F T, N;
         if constexpr (LL) {
             T = F::template subl<9>(Q, X3); // < 11p

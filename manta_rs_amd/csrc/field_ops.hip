@@ -110,6 +110,89 @@ int field_op(int field, int op, int repr, int lazy_a, int lazy_b, const u32 *a, 
     return MG_ERR_ARG;
 }
 
+// ---- the reduced-radix routines on RAW limb vectors (`mg_fpr_raw_op`): operands and result are K words of LB-bit limbs as the
+// MSM kernels hold them, with no from_std / to_std around the operation -- mg_field_op above only ever feeds canonical values
+// plus k p, which never puts a large value into every limb, the case the column accumulators of the products are sized for.
+// coding 0 = FpR::mul / sqr / mul_add / sub2, 1 = the accumulate kernel's mul_t<true> / sqr_t<true> / mul_add_t<true> / sub2n.
+enum { ROP_MUL = 0, ROP_SQR = 1, ROP_MUL_ADD = 2, ROP_SUB2_6 = 3, ROP_SUB2_12 = 4 };
+
+template <class C>
+__global__ __launch_bounds__(256) void fpr_raw_op_kernel(int op, int coding, const u32 *__restrict__ a, const u32 *__restrict__ b,
+                                                         const u32 *__restrict__ c, const u32 *__restrict__ d, u32 *__restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    typedef FpR<C> R;
+    const R x = R::load(a + i * R::K);
+    const R y = b ? R::load(b + i * R::K) : R::zero(), z = c ? R::load(c + i * R::K) : R::zero(), w = d ? R::load(d + i * R::K) : R::zero();
+    R r = R::zero();
+    switch (op) {
+    case ROP_MUL: r = coding ? R::template mul_t<true>(x, y) : R::mul(x, y); break;
+    case ROP_SQR: r = coding ? R::template sqr_t<true>(x) : R::sqr(x); break;
+    case ROP_MUL_ADD: r = coding ? R::template mul_add_t<true>(x, y, z, w) : R::mul_add(x, y, z, w); break;
+    case ROP_SUB2_6: r = coding ? R::template sub2n<6>(x, y, z) : R::template sub2<6>(x, y, z); break;
+    case ROP_SUB2_12: r = coding ? R::template sub2n<12>(x, y, z) : R::template sub2<12>(x, y, z); break; // (the Fp2 additions' multiple)
+    }
+    r.store(out + i * R::K);
+}
+
+template <class C> static int run_raw(int op, int coding, const u32 *const (&in)[4], size_t n, u32 *out) {
+    const size_t bytes = n * FpR<C>::K * 4;
+    DevBlock m; // out | a | b | c | d (absent operands take no room)
+    if (const int rc = m.alloc({bytes, bytes, in[1] ? bytes : 0, in[2] ? bytes : 0, in[3] ? bytes : 0}, "mg_fpr_raw_op")) return rc;
+    u32 *dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 4 && e == hipSuccess; ++k)
+        if (in[k]) e = memcpy_sync(dev[k] = m.dev<u32>(k + 1), in[k], bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL((fpr_raw_op_kernel<C>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, setup_stream(), op, coding, dev[0], dev[1],
+                           dev[2], dev[3], m.dev<u32>(0), n);
+        e = memcpy_sync(out, m.dev<u32>(0), bytes, hipMemcpyDeviceToHost);
+    }
+    return e == hipSuccess ? MG_OK : hip_status(e, "mg_fpr_raw_op");
+}
+
+int fpr_raw_op(int field, int op, int coding, const u32 *a, const u32 *b, const u32 *c, const u32 *d, size_t n, u32 *out) {
+    if (!a || !out || n == 0 || n > ((size_t)1 << 24) || op < 0 || op > ROP_SUB2_12 || coding < 0 || coding > 1) return MG_ERR_ARG;
+    const int operands = op == ROP_SQR ? 1 : (op == ROP_MUL ? 2 : (op == ROP_SUB2_6 || op == ROP_SUB2_12 ? 3 : 4));
+    const u32 *const given[4] = {a, b, c, d};
+    for (int k = 1; k < operands; ++k)
+        if (!given[k]) return MG_ERR_ARG;
+    const u32 *const in[4] = {a, operands > 1 ? b : nullptr, operands > 2 ? c : nullptr, operands > 3 ? d : nullptr};
+    switch (field) {
+    case 0: return run_raw<Bn254FrCfg>(op, coding, in, n, out);
+    case 1: return run_raw<Bn254FqCfg>(op, coding, in, n, out);
+    case 2: return run_raw<Bls381FrCfg>(op, coding, in, n, out);
+    case 3: return run_raw<Bls381FqCfg>(op, coding, in, n, out);
+    }
+    return MG_ERR_ARG;
+}
+
+// the column plan of a field's flushed products (fpr_dev.h), host side: flush[k] = FPR_FLUSH_* bits of column k, peak[k] = the
+// planner's worst-case accumulator value of the column; returns the number of columns (2 K - 1) through *cols
+template <class C> static int plan_out(int kind, u32 *flush, u64 *peak, int *cols, int *limb_bits, int *flushed_routines) {
+    typedef FpR<C> R;
+    // the tables the product routines index (flush_before), not a second run of the planner
+    const typename R::Plan &pl = kind == FPR_KIND_MUL ? R::PLAN_MUL : (kind == FPR_KIND_SQR ? R::PLAN_SQR : R::PLAN_MUL_ADD);
+    for (int k = 0; k < R::COLS; ++k) {
+        if (flush) flush[k] = pl.flush[k];
+        if (peak) peak[k] = pl.peak[k];
+    }
+    if (cols) *cols = R::COLS;
+    if (limb_bits) *limb_bits = R::LB;
+    if (flushed_routines) *flushed_routines = 2 * R::K > R::CAP;
+    return pl.fits ? MG_OK : MG_ERR_ARG;
+}
+int fpr_column_plan_host(int field, int kind, u32 *flush, u64 *peak, int *cols, int *limb_bits, int *flushed_routines) {
+    if (kind < FPR_KIND_MUL || kind > FPR_KIND_MUL_ADD) return MG_ERR_ARG;
+    switch (field) {
+    case 0: return plan_out<Bn254FrCfg>(kind, flush, peak, cols, limb_bits, flushed_routines);
+    case 1: return plan_out<Bn254FqCfg>(kind, flush, peak, cols, limb_bits, flushed_routines);
+    case 2: return plan_out<Bls381FrCfg>(kind, flush, peak, cols, limb_bits, flushed_routines);
+    case 3: return plan_out<Bls381FqCfg>(kind, flush, peak, cols, limb_bits, flushed_routines);
+    }
+    return MG_ERR_ARG;
+}
+
 } // namespace mg
 
 // ---- clock probe (bench.py): what does the chip clock at under the accumulate kernel's kind of load? Every SIMD gets two

@@ -18,6 +18,15 @@
 //
 // Memory format: K u32 words per element. Conversion to/from the arkworks format (32-bit limbs,
 // R = 2^(32N)) happens once, when bases are registered and when the few result points are staged.
+//
+// (Since round 4 BLS12-381 Fq is K = 13 x 30 bits, R' = 2^390: its columns can pass 2^64 and are flushed by the column plan below.)
+//
+// Compile-time switches of this header, all for A/B builds (tools/build_variant.sh); the defaults are the measured choices:
+//   MG_FLUSH_BY_COUNT  flush the 30-bit field's columns by the product count (`2 n > CAP`) instead of the exact column plan
+//   MG_CHAIN_FLUSHED   single-chain coding of mul_t / sqr_t / mul_add_t<true> for the 30-bit field too (measured: no gain, off)
+//   MG_SUB2_64         the mixed addition's sub2n of the 30-bit field with 64-bit carries (= sub2) instead of signed 32-bit limbs
+//   MG_PACK_AFFINE     memory format of affine base coordinates (0 / 1 / 2, see load_aff)
+//   MG_FP2_CALLS, MG_FP2_KARATSUBA, MG_FP2_NO_MULB, MG_FP2_NO_SQRB   the Fp2 product forms of earlier rounds
 #pragma once
 #include "fp_dev.h"
 
@@ -48,6 +57,20 @@ MG_DEV void mad_chain_vv2(u64 &acc, u32 a0, u32 b0, u32 a1, u32 b1) {
 MG_DEV void mad_chain_vs2(u64 &acc, u32 m0, u32 k0, u32 m1, u32 k1) {
     asm("v_mad_u64_u32 %0, vcc, %1, %2, %0\n\tv_mad_u64_u32 %0, vcc, %3, %4, %0" : "+v"(acc) : "v"(m0), "s"(k0), "v"(m1), "s"(k1) : "vcc");
 }
+MG_DEV void mad_chain_vv4(u64 &acc, u32 a0, u32 b0, u32 a1, u32 b1, u32 a2, u32 b2, u32 a3, u32 b3) {
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, %0\n\tv_mad_u64_u32 %0, vcc, %3, %4, %0\n\t"
+        "v_mad_u64_u32 %0, vcc, %5, %6, %0\n\tv_mad_u64_u32 %0, vcc, %7, %8, %0"
+        : "+v"(acc)
+        : "v"(a0), "v"(b0), "v"(a1), "v"(b1), "v"(a2), "v"(b2), "v"(a3), "v"(b3)
+        : "vcc");
+}
+MG_DEV void mad_chain_vs4(u64 &acc, u32 m0, u32 k0, u32 m1, u32 k1, u32 m2, u32 k2, u32 m3, u32 k3) {
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, %0\n\tv_mad_u64_u32 %0, vcc, %3, %4, %0\n\t"
+        "v_mad_u64_u32 %0, vcc, %5, %6, %0\n\tv_mad_u64_u32 %0, vcc, %7, %8, %0"
+        : "+v"(acc)
+        : "v"(m0), "s"(k0), "v"(m1), "s"(k1), "v"(m2), "s"(k2), "v"(m3), "s"(k3)
+        : "vcc");
+}
 MG_DEV void mad_chain_triple(u64 &acc, u32 a, u32 b, u32 c, u32 d, u32 m, u32 k) { // a*b + c*d + m*k
     asm("v_mad_u64_u32 %0, vcc, %1, %2, %0\n\tv_mad_u64_u32 %0, vcc, %3, %4, %0\n\tv_mad_u64_u32 %0, vcc, %5, %6, %0"
         : "+v"(acc)
@@ -62,6 +85,61 @@ MG_DEV void mad_chain_triple2(u64 &acc, u32 a0, u32 b0, u32 c0, u32 d0, u32 m0, 
         : "vcc");
 }
 
+// ---- compile-time column plan of the flushed products (fields whose limbs are wide enough that a column of a product can pass
+// 2^64: LB = 30). A column k adds its products group by group -- a*b, then c*d (the fused product), then m*p -- into one 64-bit
+// accumulator; before a group that could carry the accumulator to 2^64 the accumulator's upper part is moved aside ("flush").
+// The planner walks the columns in the order the code adds them and keeps the EXACT worst case of every partial sum:
+//   carry-in  = floor(worst total of the previous column / 2^LB)   (a flush moves value aside, it does not change the total)
+//   a*b, c*d  = n * limb^2        (n products of the column; `limb` bounds every operand limb, 2^LB - 1 when normalised; the doubled
+//                                  operand of a squaring makes a cross product count twice, which is the same n * limb^2)
+//   m*p       = (2^LB - 1) * sum of the limbs p_j the column touches  (m_i is masked; p's limbs are the constants themselves)
+// After a flush the accumulator holds at most 2^LB - 1. The plan is built ONCE per field and kind (static constexpr members of
+// FpR below); the product routines only index it.
+enum { FPR_KIND_MUL = 0, FPR_KIND_SQR = 1, FPR_KIND_MUL_ADD = 2 };
+enum { FPR_FLUSH_AB = 1, FPR_FLUSH_CD = 2, FPR_FLUSH_MP = 4 }; // flush BEFORE the a*b / c*d / m*p group of the column
+template <int COLS> struct FprColumnPlan {
+    unsigned char flush[COLS]; // FPR_FLUSH_* bits per column
+    u64 peak[COLS];            // worst-case accumulator value of the column under this plan
+    u64 spill_peak;            // worst-case value of the spill word
+    int flushes;               // flushes in the whole product
+    bool fits;                 // no group alone reaches 2^64 (else there is no plan)
+};
+template <class C> constexpr FprColumnPlan<2 * C::RR_K - 1> fpr_column_plan(int kind, u64 limb) {
+    constexpr int K = C::RR_K, LB = C::RR_LB;
+    constexpr u64 MASK = ((u64)1 << LB) - 1, TOP = ~(u64)0;
+    FprColumnPlan<2 * K - 1> pl{};
+    pl.fits = limb <= 0xffffffffull;
+    u64 carry = 0;
+    for (int k = 0; k < 2 * K - 1 && pl.fits; ++k) {
+        const int lo = k < K ? 0 : k - K + 1, hi = k < K ? k : K - 1, n = hi - lo + 1;
+        u64 psum = 0;
+        for (int i = lo; i <= hi; ++i) psum += C::RR_P[k - i];
+        u64 group[3] = {0, 0, MASK * psum}; // (psum < K * 2^LB: no overflow for any LB <= 30)
+        const bool use[3] = {true, kind == FPR_KIND_MUL_ADD, true};
+        if (limb * limb > TOP / (u64)n) pl.fits = false; // n * limb^2 alone does not fit
+        else group[0] = group[1] = (u64)n * limb * limb;
+        u64 acc = carry, hi_part = carry >> LB, lo_part = carry & MASK, spill = 0; // column total = hi_part * 2^LB + lo_part
+        for (int g = 0; g < 3 && pl.fits; ++g) {
+            if (!use[g]) continue;
+            if (group[g] > TOP - acc) { // adding the group could reach 2^64
+                pl.flush[k] |= (unsigned char)(1 << g);
+                ++pl.flushes;
+                spill += acc >> LB;
+                acc = MASK;
+                if (group[g] > TOP - acc) pl.fits = false;
+            }
+            acc += group[g];
+            if (acc > pl.peak[k]) pl.peak[k] = acc;
+            lo_part += group[g] & MASK;
+            hi_part += (group[g] >> LB) + (lo_part >> LB);
+            lo_part &= MASK;
+        }
+        if (spill > pl.spill_peak) pl.spill_peak = spill;
+        carry = hi_part;
+    }
+    return pl;
+}
+
 template <class C> struct FpR {
     static constexpr int K = C::RR_K, LB = C::RR_LB;
     static constexpr int N = K; // words per element in memory
@@ -72,10 +150,25 @@ template <class C> struct FpR {
     // come near it (a fused column has 3 K <= 42 of them); with 30-bit limbs -- round 4: BLS12-381 Fq as 13 x 30 bits, 2 K^2 + K =
     // 351 multiply-adds per product instead of the 406 of 14 x 28 -- sixteen 60-bit products overflow, so a column that holds more
     // is FLUSHED between its product groups: the accumulator's upper part is moved aside (one 64-bit shift, one mask) and joined
-    // again when the column is done. Nine of a product's 25 columns need it; measured per product at the accumulate kernel's
-    // occupancy (tools/ubench_limbs.hip, profiles/r04_ubench_limbs.txt): 1960 against 2183 cycles (-10 %).
+    // again when the column is done. Measured per product at the accumulate kernel's occupancy, with the count rule's eleven flushed
+    // columns (tools/ubench_limbs.hip, profiles/r04_ubench_limbs.txt): 1960 against 2183 cycles (-10 %).
     static constexpr int CAP = LB >= 30 ? 15 : (LB == 29 ? 60 : 250);
     static constexpr int nprod(int k) { return k < K ? k + 1 : 2 * K - 1 - k; } // limb products a_i b_(k-i) of column k
+    // CAP only SELECTS the flushed routines. Where they flush is the exact plan (fpr_column_plan above), not a count of products:
+    // for 13 x 30 bits a plain product or squaring flushes in columns 10..14 only (5 flushes where the count rule had 11), the
+    // fused product 18 times (26). Operands are NORMALISED limbs (< 2^LB): lazy limbs exist only where nothing flushes (below).
+    static constexpr int COLS = 2 * K - 1;
+    typedef FprColumnPlan<COLS> Plan;
+    static constexpr Plan PLAN_MUL = fpr_column_plan<C>(FPR_KIND_MUL, MASK);
+    static constexpr Plan PLAN_SQR = fpr_column_plan<C>(FPR_KIND_SQR, MASK);
+    static constexpr Plan PLAN_MUL_ADD = fpr_column_plan<C>(FPR_KIND_MUL_ADD, MASK);
+    // a plan exists, so by its construction no column passes 2^64 - 1; the spill word collects at most two accumulators' upper parts
+    static_assert(PLAN_MUL.fits && PLAN_SQR.fits && PLAN_MUL_ADD.fits, "a product group alone overflows the column accumulator");
+    static_assert(PLAN_MUL.spill_peak < ((u64)1 << 40) && PLAN_SQR.spill_peak < ((u64)1 << 40) && PLAN_MUL_ADD.spill_peak < ((u64)1 << 40),
+                  "spill word overflow");
+    // the unflushed codings (28- and 29-bit limbs) interleave the groups: they need a plan WITHOUT flushes
+    static_assert(2 * K > CAP || (PLAN_MUL.flushes == 0 && PLAN_SQR.flushes == 0 && PLAN_MUL_ADD.flushes == 0), "column overflow");
+    static_assert((2 * K > CAP) == (3 * K > CAP), "mul and mul_add must select the flushed routines together");
     // bound bookkeeping consumed by ec_dev.h's Bv<> wrapper (values are "< B*p")
     static constexpr int BM = 2;            // a product is < 2p ...
     static constexpr int LIM = C::RR_LIM;   // ... whenever the operand bounds multiply to <= LIM
@@ -169,6 +262,36 @@ template <class C> struct FpR {
             return normalize(t);
         }
     }
+    // sub2 with every limb in signed 32 bits at LB = 30 too. REQUIRES normalised limbs (< 2^LB) in a, b and c.
+    // The plain t_i = a_i + (Mp)_i - b_i - 2 c_i of the narrower fields reaches -3 (2^30 - 1) < -2^31 at LB = 30; what is too wide
+    // is the 31-bit term 2 c_i, so bit LB-1 of c_i -- worth 2^LB once doubled -- is subtracted one limb higher:
+    //   t_i = a_i + (Mp)_i - b_i - 2 (c_i mod 2^(LB-1)) - (c_(i-1) >> (LB-1))   in [-2^31 + 2, 2^31 - 2],
+    // normalize()'s carry in [-2, 1] (floor((-2^31 + 2 - 2) / 2^30) = -2, floor((2^31 - 2 + 1) / 2^30) = 1), and t_i + carry in
+    // [-2^31, 2^31 - 1]: exact in int32. The top limb is neither split nor masked (arithmetic mod 2^32, as everywhere).
+    // Called by the G1 mixed addition alone (ec_dev.h madd_finish: X3 = R^2 + 6p - PPP - 2Q, three product outputs). The generic
+    // group operations keep sub2: inside the Fp2 operations of BLS12-381 G2 this form gave wrong column sums
+    // (tests/test_gpu_qap_columns.py) for a reason that is not established -- an open question recorded in
+    // profiles/fpr_column_plan_ab.txt; do not widen its use before that is answered. MG_SUB2_64 makes it sub2 again (A/B builds).
+    template <int M> static MG_DEV FpR sub2n(const FpR &a, const FpR &b, const FpR &c) {
+        static_assert(M <= C::RR_MAXM, "multiple table too short");
+        static_assert(LB <= 30, "sub2n: the limb-wise differences must fit signed 32 bits");
+#ifdef MG_SUB2_64
+        return sub2<M>(a, b, c);
+#else
+        if constexpr (LB >= 30) {
+            int t[K];
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+                const u32 low = i < K - 1 ? (c.v[i] & (MASK >> 1)) : c.v[i];
+                const u32 high = i > 0 ? (c.v[i - 1] >> (LB - 1)) : 0u;
+                t[i] = (int)a.v[i] + (int)C::RR_MULT[M][i] - (int)b.v[i] - (int)(2 * low + high);
+            }
+            return normalize(t);
+        } else {
+            return sub2<M>(a, b, c);
+        }
+#endif
+    }
     template <int M> static MG_DEV FpR neg(const FpR &a) { return sub<M>(zero(), a); }
 
     // ---- carry-free subtraction: a + M*p - b with NO normalisation pass. M*p is taken in the redundant limb form
@@ -182,6 +305,10 @@ template <class C> struct FpR {
     }
     // worst column of a fused product with lazy operands: K * (3*3 + 3*1 + 1) * 2^(2 LB) must stay below 2^64
     static constexpr bool LAZY_LIMBS = (double)K * 13.0 * (double)(1ull << LB) * (double)(1ull << LB) < 18446744073709551616.0;
+    // checked, not only stated: with limbs < 3 * 2^LB the plan of a fused product must exist and hold no flush
+    static_assert(!LAZY_LIMBS || (2 * K <= CAP && fpr_column_plan<C>(FPR_KIND_MUL_ADD, 3 * ((u64)1 << LB)).fits &&
+                                  fpr_column_plan<C>(FPR_KIND_MUL_ADD, 3 * ((u64)1 << LB)).flushes == 0),
+                  "lazy limbs need columns that never flush");
     template <int M> static MG_DEV FpR subl(const FpR &a, const FpR &b) { // a may itself have lazy limbs only if a is normalised: see call sites
         static_assert(M <= C::RR_MAXM, "multiple table too short");
         FpR r;
@@ -202,8 +329,6 @@ template <class C> struct FpR {
         r.v[K - 1] = a.v[K - 1] + c;
         return r;
     }
-    // (fused products with NORMALISED operands need K * 3 * 2^(2 LB) < 2^64: true for both fields)
-    static_assert(3 * K <= CAP || LB >= 30, "fused column overflow");
     // ---- fused almost-Montgomery product (a*b + c*d) * R'^-1 with ONE reduction: two double-width products share the
     // column accumulators and the m*p pass -- 3 K^2 + K multiply-adds instead of 4 K^2 + 2 K. Value < 2p whenever
     // Ba*Bb + Bc*Bd <= LIM; limbs of the operands may be lazy when LAZY_LIMBS (column bound above).
@@ -242,6 +367,23 @@ template <class C> struct FpR {
     }
     // ---- the three product routines for limbs wide enough that a column overflows (CAP): the products of a column are added group
     // by group -- a*b, then c*d, then m*p -- and the accumulator is flushed before a group that would not fit (see CAP)
+    // (the first group of a column never needs one: carry-in + n * limb^2 < 2^64 for every plan that exists, asserted here)
+    static constexpr bool plan_flushes_first_group(const Plan &p) {
+        for (int k = 0; k < COLS; ++k)
+            if (p.flush[k] & FPR_FLUSH_AB) return true;
+        return false;
+    }
+    static_assert(!plan_flushes_first_group(PLAN_MUL) && !plan_flushes_first_group(PLAN_SQR) && !plan_flushes_first_group(PLAN_MUL_ADD),
+                  "flush before the first group of a column");
+    // MG_FLUSH_BY_COUNT restores the rule of rounds 4-6 (A/B builds): flush when the column holds more than CAP / 2 products, and
+    // before the m*p group of the fused product when more than CAP / 3
+    static constexpr bool flush_before(int kind, int k, int group) {
+#ifdef MG_FLUSH_BY_COUNT
+        return 2 * nprod(k) > CAP || (kind == FPR_KIND_MUL_ADD && group == FPR_FLUSH_MP && 3 * nprod(k) > CAP);
+#else
+        return ((kind == FPR_KIND_MUL ? PLAN_MUL : (kind == FPR_KIND_SQR ? PLAN_SQR : PLAN_MUL_ADD)).flush[k] & group) != 0;
+#endif
+    }
     static MG_DEV void flush(u64 &acc, u64 &spill) {
         spill += acc >> LB;
         acc &= (u64)MASK;
@@ -252,14 +394,14 @@ template <class C> struct FpR {
         FpR t;
 #pragma unroll
         for (int k = 0; k < 2 * K - 1; ++k) {
-            const int lo = k < K ? 0 : k - K + 1, hi = k < K ? k : K - 1, n = hi - lo + 1;
+            const int lo = k < K ? 0 : k - K + 1, hi = k < K ? k : K - 1;
             u64 spill = 0;
 #pragma unroll
             for (int i = lo; i <= hi; ++i) acc += (u64)a.v[i] * b.v[k - i];
-            if (2 * n > CAP) flush(acc, spill);
+            if (flush_before(FPR_KIND_MUL_ADD, k, FPR_FLUSH_CD)) flush(acc, spill);
 #pragma unroll
             for (int i = lo; i <= hi; ++i) acc += (u64)c.v[i] * d.v[k - i];
-            if (2 * n > CAP || 3 * n > CAP) flush(acc, spill);
+            if (flush_before(FPR_KIND_MUL_ADD, k, FPR_FLUSH_MP)) flush(acc, spill);
 #pragma unroll
             for (int i = lo; i <= hi; ++i)
                 if (!(k < K && i == k)) acc += (u64)m[i] * C::RR_P[k - i];
@@ -281,11 +423,11 @@ template <class C> struct FpR {
         FpR t;
 #pragma unroll
         for (int k = 0; k < 2 * K - 1; ++k) {
-            const int lo = k < K ? 0 : k - K + 1, hi = k < K ? k : K - 1, n = hi - lo + 1;
+            const int lo = k < K ? 0 : k - K + 1, hi = k < K ? k : K - 1;
             u64 spill = 0;
 #pragma unroll
             for (int i = lo; i <= hi; ++i) acc += (u64)a.v[i] * b.v[k - i];
-            if (2 * n > CAP) flush(acc, spill);
+            if (flush_before(FPR_KIND_MUL, k, FPR_FLUSH_MP)) flush(acc, spill);
 #pragma unroll
             for (int i = lo; i <= hi; ++i)
                 if (!(k < K && i == k)) acc += (u64)m[i] * C::RR_P[k - i];
@@ -309,7 +451,7 @@ template <class C> struct FpR {
         for (int i = 0; i < K; ++i) a2[i] = a.v[i] << 1; // (< 2^31: a doubled cross product counts as two)
 #pragma unroll
         for (int k = 0; k < 2 * K - 1; ++k) {
-            const int lo = k < K ? 0 : k - K + 1, hi = k < K ? k : K - 1, n = hi - lo + 1;
+            const int lo = k < K ? 0 : k - K + 1, hi = k < K ? k : K - 1;
             u64 spill = 0;
 #pragma unroll
             for (int i = lo; i <= hi; ++i) {
@@ -317,7 +459,7 @@ template <class C> struct FpR {
                 if (i < j) acc += (u64)a2[i] * a.v[j];
                 if (i == j) acc += (u64)a.v[i] * a.v[i];
             }
-            if (2 * n > CAP) flush(acc, spill);
+            if (flush_before(FPR_KIND_SQR, k, FPR_FLUSH_MP)) flush(acc, spill);
 #pragma unroll
             for (int i = lo; i <= hi; ++i)
                 if (!(k < K && i == k)) acc += (u64)m[i] * C::RR_P[k - i];
@@ -385,8 +527,94 @@ template <class C> struct FpR {
         return t;
     }
     // single-chain codings (see mad_chain_vv) of mul / sqr / mul_add
+    // Fields that flush (13 x 30 bits) took the compiler's two-chain coding here through round 6. MG_CHAIN_FLUSHED gives them the
+    // single chain as well: a column the plan does not flush is coded as for the narrower limbs, a flushed one group by group
+    // -- one run of asm blocks per group (chain_vv / chain_vs: four, two or one links per block), the C flush between the runs.
+#ifdef MG_CHAIN_FLUSHED
+    static constexpr bool CHAIN_FLUSHED = true;
+#else
+    static constexpr bool CHAIN_FLUSHED = false;
+#endif
+    static constexpr bool CHAINED = 2 * K <= CAP || CHAIN_FLUSHED; // the _t<true> routines are single-chain codings
+    // acc += x_i y_(k-i), i = lo .. hi, as links of the chain
+    static MG_DEV void chain_vv(u64 &acc, const u32 (&x)[K], const u32 (&y)[K], int k, int lo, int hi) {
+        const int n = hi - lo + 1, n4 = n / 4, r = lo + 4 * n4;
+#pragma unroll
+        for (int q = 0; q < n4; ++q) {
+            const int i = lo + 4 * q;
+            mad_chain_vv4(acc, x[i], y[k - i], x[i + 1], y[k - i - 1], x[i + 2], y[k - i - 2], x[i + 3], y[k - i - 3]);
+        }
+        if (n & 2) mad_chain_vv2(acc, x[r], y[k - r], x[r + 1], y[k - r - 1]);
+        if (n & 1) mad_chain_vv(acc, x[hi], y[k - hi]);
+    }
+    // acc += m_i p_(k-i), i = lo .. hi
+    static MG_DEV void chain_vs(u64 &acc, const u32 (&m)[K], int k, int lo, int hi) {
+        const int n = hi - lo + 1, n4 = n / 4, r = lo + 4 * n4;
+#pragma unroll
+        for (int q = 0; q < n4; ++q) {
+            const int i = lo + 4 * q;
+            mad_chain_vs4(acc, m[i], C::RR_P[k - i], m[i + 1], C::RR_P[k - i - 1], m[i + 2], C::RR_P[k - i - 2], m[i + 3], C::RR_P[k - i - 3]);
+        }
+        if (n & 2) mad_chain_vs2(acc, m[r], C::RR_P[k - r], m[r + 1], C::RR_P[k - r - 1]);
+        if (n & 1) mad_chain_vs(acc, m[hi], C::RR_P[k - hi]);
+    }
+    // mul / mul_add with flushes: column k of a*b [+ c*d] + m*p; the m_k p_0 link and the column's end stay with the caller
+    template <bool FUSED>
+    static MG_DEV void chain_column(u64 &acc, u64 &spill, const FpR &a, const FpR &b, const FpR &c, const FpR &d, const u32 (&m)[K], int k) {
+        constexpr int KIND = FUSED ? FPR_KIND_MUL_ADD : FPR_KIND_MUL;
+        const int lo = k < K ? 0 : k - K + 1, hi = k < K ? k : K - 1, mhi = k < K ? k - 1 : K - 1; // m_k is not known yet
+        const bool f_cd = FUSED && flush_before(KIND, k, FPR_FLUSH_CD), f_mp = flush_before(KIND, k, FPR_FLUSH_MP);
+        if (!f_cd && !f_mp) { // an unflushed column: links interleaved as in the narrow-limb codings
+            const int n = mhi - lo + 1;
+#pragma unroll
+            for (int q = 0; q + 1 < n; q += 2) {
+                const int i = lo + q;
+                if constexpr (FUSED)
+                    mad_chain_triple2(acc, a.v[i], b.v[k - i], c.v[i], d.v[k - i], m[i], C::RR_P[k - i], a.v[i + 1], b.v[k - i - 1], c.v[i + 1],
+                                      d.v[k - i - 1], m[i + 1], C::RR_P[k - i - 1]);
+                else mad_chain_pair2(acc, a.v[i], b.v[k - i], m[i], C::RR_P[k - i], a.v[i + 1], b.v[k - i - 1], m[i + 1], C::RR_P[k - i - 1]);
+            }
+            if (n & 1) {
+                if constexpr (FUSED) mad_chain_triple(acc, a.v[mhi], b.v[k - mhi], c.v[mhi], d.v[k - mhi], m[mhi], C::RR_P[k - mhi]);
+                else mad_chain_pair(acc, a.v[mhi], b.v[k - mhi], m[mhi], C::RR_P[k - mhi]);
+            }
+            if (k < K) {
+                mad_chain_vv(acc, a.v[k], b.v[0]);
+                if constexpr (FUSED) mad_chain_vv(acc, c.v[k], d.v[0]);
+            }
+            return;
+        }
+        chain_vv(acc, a.v, b.v, k, lo, hi);
+        if constexpr (FUSED) {
+            if (f_cd) flush(acc, spill);
+            chain_vv(acc, c.v, d.v, k, lo, hi);
+        }
+        if (f_mp) flush(acc, spill);
+        if (mhi >= lo) chain_vs(acc, m, k, lo, mhi);
+    }
+    template <bool FUSED> static MG_DEV FpR chain_product(const FpR &a, const FpR &b, const FpR &c, const FpR &d) {
+        u64 acc = 0;
+        u32 m[K];
+        FpR t;
+#pragma unroll
+        for (int k = 0; k < 2 * K - 1; ++k) {
+            u64 spill = 0;
+            chain_column<FUSED>(acc, spill, a, b, c, d, m, k);
+            if (k < K) {
+                m[k] = ((u32)acc * C::RR_INV) & MASK;
+                mad_chain_vs(acc, m[k], C::RR_P[0]);
+            } else {
+                t.v[k - K] = (u32)acc & MASK;
+            }
+            acc >>= LB;
+            acc += spill;
+        }
+        t.v[K - 1] = (u32)acc;
+        return t;
+    }
     template <bool CH> static MG_DEV FpR mul_t(const FpR &a, const FpR &b) {
-        if constexpr (!CH || 2 * K > CAP) return mul(a, b); // (the single-chain codings below have no flushes)
+        if constexpr (!CH || !CHAINED) return mul(a, b);
+        if constexpr (2 * K > CAP) return chain_product<false>(a, b, a, b);
         u64 acc = 0;
         u32 m[K];
         FpR t;
@@ -417,7 +645,7 @@ template <class C> struct FpR {
         return t;
     }
     template <bool CH> static MG_DEV FpR sqr_t(const FpR &a) {
-        if constexpr (!CH || 2 * K > CAP) return sqr(a);
+        if constexpr (!CH || !CHAINED) return sqr(a);
         u64 acc = 0;
         u32 m[K], a2[K];
         FpR t;
@@ -431,6 +659,8 @@ template <class C> struct FpR {
             for (int i = ilo; i + 1 <= ihi; i += 2) mad_chain_vv2(acc, a2[i], a.v[k - i], a2[i + 1], a.v[k - i - 1]);
             if (k >= 1 && ((ihi - ilo + 1) & 1) && ihi >= ilo) mad_chain_vv(acc, a2[ihi], a.v[k - ihi]);
             if (!(k & 1)) mad_chain_vv(acc, a.v[k / 2], a.v[k / 2]);
+            u64 spill = 0;
+            if (flush_before(FPR_KIND_SQR, k, FPR_FLUSH_MP)) flush(acc, spill); // (13 x 30 bits only)
             // the m_i p_{k-i} terms already known, two per block
             const int mlo = k < K ? 0 : k - K + 1, mhi = k < K ? k - 1 : K - 1;
 #pragma unroll
@@ -443,12 +673,14 @@ template <class C> struct FpR {
                 t.v[k - K] = (u32)acc & MASK;
             }
             acc >>= LB;
+            acc += spill;
         }
         t.v[K - 1] = (u32)acc;
         return t;
     }
     template <bool CH> static MG_DEV FpR mul_add_t(const FpR &a, const FpR &b, const FpR &c, const FpR &d) {
-        if constexpr (!CH || 2 * K > CAP) return mul_add(a, b, c, d);
+        if constexpr (!CH || !CHAINED) return mul_add(a, b, c, d);
+        if constexpr (2 * K > CAP) return chain_product<true>(a, b, c, d);
         u64 acc = 0;
         u32 m[K];
         FpR t;

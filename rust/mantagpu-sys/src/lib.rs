@@ -319,6 +319,26 @@ extern "C" {
         n: usize,
         out: *mut u64,
     ) -> c_int;
+    pub fn mg_fpr_raw_op(
+        field: c_int,
+        op: c_int,
+        coding: c_int,
+        a: *const u32,
+        b: *const u32,
+        c: *const u32,
+        d: *const u32,
+        n: usize,
+        out: *mut u32,
+    ) -> c_int;
+    pub fn mg_fpr_column_plan(
+        field: c_int,
+        kind: c_int,
+        flush: *mut u32,
+        peak: *mut u64,
+        cols: *mut c_int,
+        limb_bits: *mut c_int,
+        flushed_routines: *mut c_int,
+    ) -> c_int;
     pub fn mg_msm_digits(
         curve: mg_curve_t,
         scalars: *const u64,
