@@ -196,9 +196,8 @@ int mg_field_op(int field, int op, int repr, int lazy_a, int lazy_b, const uint6
  *         (t + (t (-p^-1) mod R') p) / R' of t = a b [+ c d], K - 1 masked limbs and the unmasked top limb)
  *      3: a + 6 p - b - 2 c   4: a + 12 p - b - 2 c   (limbs normalised; need b + 2 c < 6 p, 12 p)
  *   coding 0: the plain routines (mul, sqr, mul_add, sub2); 1: what the accumulate kernel calls (mul_t / sqr_t / mul_add_t<true>,
- *   sub2n). For the 29-bit fields coding 1 is the single-chain coding of the products. For BLS12-381 Fq the shipped library
- *   builds those three as the plain routines (the single-chain coding of the flushed field is compiled only with
- *   -DMG_CHAIN_FLUSHED: an A/B twin, on which the raw tests have to be run again), so there only sub2n differs from coding 0.
+ *   sub2n). Coding 1 is the single-chain coding of the products for every field (asm links for the 29-bit fields, pinned C
+ *   for BLS12-381 Fq; -DMG_CHAIN_FLUSHED=0 builds the latter's three as the plain routines again: an A/B twin).
  * Operands an op does not take are ignored (may be NULL). n <= 2^24. */
 #define MG_FPR_MUL 0
 #define MG_FPR_SQR 1

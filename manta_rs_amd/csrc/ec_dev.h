@@ -174,7 +174,8 @@ template <class F> struct XYZZ {
     // 2.56 ms against 2.63 ms for the compiler's two-chain coding (-3 %; MSM 363 against 355 Mscalar/s). A first version with
     // one asm statement per multiply-add LOST 7 %: the compiler pads every asm statement with an s_nop (~3 400 per loop
     // body). BN254's 9-limb kernel gains the same 3 % (1.55 against 1.60 ms per batched launch). MG_ACC_TWO_CHAINS restores
-    // the C coding for re-measurement.
+    // the C coding for re-measurement. (Those figures are of the 14 x 28-bit BLS12-381 field of rounds 2-3. The 13 x 30-bit field
+    // that replaced it has its single chain in C, without asm and so without padding: fpr_dev.h mad_link, MG_CHAIN_FLUSHED.)
 #ifdef MG_ACC_TWO_CHAINS
     static constexpr bool THROUGHPUT_CH = false;
 #else

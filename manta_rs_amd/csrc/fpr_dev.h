@@ -23,12 +23,18 @@
 //
 // Compile-time switches of this header, all for A/B builds (tools/build_variant.sh); the defaults are the measured choices:
 //   MG_FLUSH_BY_COUNT  flush the 30-bit field's columns by the product count (`2 n > CAP`) instead of the exact column plan
-//   MG_CHAIN_FLUSHED   single-chain coding of mul_t / sqr_t / mul_add_t<true> for the 30-bit field too (measured: no gain, off)
+//   MG_CHAIN_FLUSHED   (default 1) single-chain coding of mul_t / sqr_t / mul_add_t<true> for the 30-bit field too: the flushed
+//                      routines with every multiply-add pinned in C (mad_link), no asm; 0 = the compiler's two chains per column.
+//                      Measurements in profiles/fpr_chain_padding_ab.txt
 //   MG_SUB2_64         the mixed addition's sub2n of the 30-bit field with 64-bit carries (= sub2) instead of signed 32-bit limbs
 //   MG_PACK_AFFINE     memory format of affine base coordinates (0 / 1 / 2, see load_aff)
 //   MG_FP2_CALLS, MG_FP2_KARATSUBA, MG_FP2_NO_MULB, MG_FP2_NO_SQRB   the Fp2 product forms of earlier rounds
 #pragma once
 #include "fp_dev.h"
+
+#ifndef MG_CHAIN_FLUSHED
+#define MG_CHAIN_FLUSHED 1
+#endif
 
 namespace mg {
 
@@ -56,20 +62,6 @@ MG_DEV void mad_chain_vv2(u64 &acc, u32 a0, u32 b0, u32 a1, u32 b1) {
 }
 MG_DEV void mad_chain_vs2(u64 &acc, u32 m0, u32 k0, u32 m1, u32 k1) {
     asm("v_mad_u64_u32 %0, vcc, %1, %2, %0\n\tv_mad_u64_u32 %0, vcc, %3, %4, %0" : "+v"(acc) : "v"(m0), "s"(k0), "v"(m1), "s"(k1) : "vcc");
-}
-MG_DEV void mad_chain_vv4(u64 &acc, u32 a0, u32 b0, u32 a1, u32 b1, u32 a2, u32 b2, u32 a3, u32 b3) {
-    asm("v_mad_u64_u32 %0, vcc, %1, %2, %0\n\tv_mad_u64_u32 %0, vcc, %3, %4, %0\n\t"
-        "v_mad_u64_u32 %0, vcc, %5, %6, %0\n\tv_mad_u64_u32 %0, vcc, %7, %8, %0"
-        : "+v"(acc)
-        : "v"(a0), "v"(b0), "v"(a1), "v"(b1), "v"(a2), "v"(b2), "v"(a3), "v"(b3)
-        : "vcc");
-}
-MG_DEV void mad_chain_vs4(u64 &acc, u32 m0, u32 k0, u32 m1, u32 k1, u32 m2, u32 k2, u32 m3, u32 k3) {
-    asm("v_mad_u64_u32 %0, vcc, %1, %2, %0\n\tv_mad_u64_u32 %0, vcc, %3, %4, %0\n\t"
-        "v_mad_u64_u32 %0, vcc, %5, %6, %0\n\tv_mad_u64_u32 %0, vcc, %7, %8, %0"
-        : "+v"(acc)
-        : "v"(m0), "s"(k0), "v"(m1), "s"(k1), "v"(m2), "s"(k2), "v"(m3), "s"(k3)
-        : "vcc");
 }
 MG_DEV void mad_chain_triple(u64 &acc, u32 a, u32 b, u32 c, u32 d, u32 m, u32 k) { // a*b + c*d + m*k
     asm("v_mad_u64_u32 %0, vcc, %1, %2, %0\n\tv_mad_u64_u32 %0, vcc, %3, %4, %0\n\tv_mad_u64_u32 %0, vcc, %5, %6, %0"
@@ -388,7 +380,22 @@ template <class C> struct FpR {
         spill += acc >> LB;
         acc &= (u64)MASK;
     }
-    static MG_DEV FpR mul_add_flushed(const FpR &a, const FpR &b, const FpR &c, const FpR &d) {
+    // One multiply-add of a column. CH = true keeps the column's multiply-adds in ONE dependent chain, in plain C. Left alone the
+    // compiler's reassociation orders the terms of a sum by depth; the running accumulator is the deepest, so the a*b products of
+    // a column are summed from zero and joined to it by a v_lshl_add_u64 (4.97 issue cycles, more than a multiply). The annotation
+    // is an identity the optimiser does not look through and the code generator drops: every partial sum stays where it is
+    // written, and no instruction is spent on it. (An assumption about the sum does the same only until the optimiser can prove
+    // it from the operands' ranges -- the first four or so terms behind a flush -- and then goes, the reordering with it.)
+    // The asm links of the narrower fields (mad_chain_*) buy the same chain with an s_nop behind every statement: the compiler
+    // takes every register an asm statement writes, vcc included, for a destination whose next reader or writer must wait one
+    // state, so neither a scalar-pair output in place of the vcc clobber nor longer blocks per column get rid of it
+    // (profiles/fpr_chain_padding_ab.txt).
+    template <bool CH> static MG_DEV void mad_link(u64 &acc, u32 x, u32 y) {
+        const u64 prod = (u64)x * y;
+        acc += prod;
+        if constexpr (CH) acc = __builtin_annotation(acc, "chain");
+    }
+    template <bool CH = false> static MG_DEV FpR mul_add_flushed(const FpR &a, const FpR &b, const FpR &c, const FpR &d) {
         u64 acc = 0;
         u32 m[K];
         FpR t;
@@ -397,17 +404,17 @@ template <class C> struct FpR {
             const int lo = k < K ? 0 : k - K + 1, hi = k < K ? k : K - 1;
             u64 spill = 0;
 #pragma unroll
-            for (int i = lo; i <= hi; ++i) acc += (u64)a.v[i] * b.v[k - i];
+            for (int i = lo; i <= hi; ++i) mad_link<CH>(acc, a.v[i], b.v[k - i]);
             if (flush_before(FPR_KIND_MUL_ADD, k, FPR_FLUSH_CD)) flush(acc, spill);
 #pragma unroll
-            for (int i = lo; i <= hi; ++i) acc += (u64)c.v[i] * d.v[k - i];
+            for (int i = lo; i <= hi; ++i) mad_link<CH>(acc, c.v[i], d.v[k - i]);
             if (flush_before(FPR_KIND_MUL_ADD, k, FPR_FLUSH_MP)) flush(acc, spill);
 #pragma unroll
             for (int i = lo; i <= hi; ++i)
-                if (!(k < K && i == k)) acc += (u64)m[i] * C::RR_P[k - i];
+                if (!(k < K && i == k)) mad_link<CH>(acc, m[i], C::RR_P[k - i]);
             if (k < K) {
                 m[k] = ((u32)acc * C::RR_INV) & MASK;
-                acc += (u64)m[k] * C::RR_P[0];
+                mad_link<CH>(acc, m[k], C::RR_P[0]);
             } else {
                 t.v[k - K] = (u32)acc & MASK;
             }
@@ -417,7 +424,7 @@ template <class C> struct FpR {
         t.v[K - 1] = (u32)acc;
         return t;
     }
-    static MG_DEV FpR mul_flushed(const FpR &a, const FpR &b) {
+    template <bool CH = false> static MG_DEV FpR mul_flushed(const FpR &a, const FpR &b) {
         u64 acc = 0;
         u32 m[K];
         FpR t;
@@ -426,14 +433,14 @@ template <class C> struct FpR {
             const int lo = k < K ? 0 : k - K + 1, hi = k < K ? k : K - 1;
             u64 spill = 0;
 #pragma unroll
-            for (int i = lo; i <= hi; ++i) acc += (u64)a.v[i] * b.v[k - i];
+            for (int i = lo; i <= hi; ++i) mad_link<CH>(acc, a.v[i], b.v[k - i]);
             if (flush_before(FPR_KIND_MUL, k, FPR_FLUSH_MP)) flush(acc, spill);
 #pragma unroll
             for (int i = lo; i <= hi; ++i)
-                if (!(k < K && i == k)) acc += (u64)m[i] * C::RR_P[k - i];
+                if (!(k < K && i == k)) mad_link<CH>(acc, m[i], C::RR_P[k - i]);
             if (k < K) {
                 m[k] = ((u32)acc * C::RR_INV) & MASK;
-                acc += (u64)m[k] * C::RR_P[0];
+                mad_link<CH>(acc, m[k], C::RR_P[0]);
             } else {
                 t.v[k - K] = (u32)acc & MASK;
             }
@@ -443,7 +450,7 @@ template <class C> struct FpR {
         t.v[K - 1] = (u32)acc;
         return t;
     }
-    static MG_DEV FpR sqr_flushed(const FpR &a) {
+    template <bool CH = false> static MG_DEV FpR sqr_flushed(const FpR &a) {
         u64 acc = 0;
         u32 m[K], a2[K];
         FpR t;
@@ -456,16 +463,16 @@ template <class C> struct FpR {
 #pragma unroll
             for (int i = lo; i <= hi; ++i) {
                 const int j = k - i;
-                if (i < j) acc += (u64)a2[i] * a.v[j];
-                if (i == j) acc += (u64)a.v[i] * a.v[i];
+                if (i < j) mad_link<CH>(acc, a2[i], a.v[j]);
+                if (i == j) mad_link<CH>(acc, a.v[i], a.v[i]);
             }
             if (flush_before(FPR_KIND_SQR, k, FPR_FLUSH_MP)) flush(acc, spill);
 #pragma unroll
             for (int i = lo; i <= hi; ++i)
-                if (!(k < K && i == k)) acc += (u64)m[i] * C::RR_P[k - i];
+                if (!(k < K && i == k)) mad_link<CH>(acc, m[i], C::RR_P[k - i]);
             if (k < K) {
                 m[k] = ((u32)acc * C::RR_INV) & MASK;
-                acc += (u64)m[k] * C::RR_P[0];
+                mad_link<CH>(acc, m[k], C::RR_P[0]);
             } else {
                 t.v[k - K] = (u32)acc & MASK;
             }
@@ -526,95 +533,15 @@ template <class C> struct FpR {
         t.v[K - 1] = (u32)acc;
         return t;
     }
-    // single-chain codings (see mad_chain_vv) of mul / sqr / mul_add
-    // Fields that flush (13 x 30 bits) took the compiler's two-chain coding here through round 6. MG_CHAIN_FLUSHED gives them the
-    // single chain as well: a column the plan does not flush is coded as for the narrower limbs, a flushed one group by group
-    // -- one run of asm blocks per group (chain_vv / chain_vs: four, two or one links per block), the C flush between the runs.
-#ifdef MG_CHAIN_FLUSHED
-    static constexpr bool CHAIN_FLUSHED = true;
-#else
-    static constexpr bool CHAIN_FLUSHED = false;
-#endif
+    // single-chain codings of mul / sqr / mul_add. The narrower limbs (no flush) code the chain as asm links (mad_chain_*, several
+    // links per statement). Fields that flush (13 x 30 bits) took the compiler's two-chain coding here through round 6; for them the
+    // single chain is the flushed routine itself with its multiply-adds pinned in C (mad_link<true>): no asm statement, so no
+    // padding. MG_CHAIN_FLUSHED=0 gives them the two-chain coding again (A/B builds).
+    static constexpr bool CHAIN_FLUSHED = MG_CHAIN_FLUSHED != 0;
     static constexpr bool CHAINED = 2 * K <= CAP || CHAIN_FLUSHED; // the _t<true> routines are single-chain codings
-    // acc += x_i y_(k-i), i = lo .. hi, as links of the chain
-    static MG_DEV void chain_vv(u64 &acc, const u32 (&x)[K], const u32 (&y)[K], int k, int lo, int hi) {
-        const int n = hi - lo + 1, n4 = n / 4, r = lo + 4 * n4;
-#pragma unroll
-        for (int q = 0; q < n4; ++q) {
-            const int i = lo + 4 * q;
-            mad_chain_vv4(acc, x[i], y[k - i], x[i + 1], y[k - i - 1], x[i + 2], y[k - i - 2], x[i + 3], y[k - i - 3]);
-        }
-        if (n & 2) mad_chain_vv2(acc, x[r], y[k - r], x[r + 1], y[k - r - 1]);
-        if (n & 1) mad_chain_vv(acc, x[hi], y[k - hi]);
-    }
-    // acc += m_i p_(k-i), i = lo .. hi
-    static MG_DEV void chain_vs(u64 &acc, const u32 (&m)[K], int k, int lo, int hi) {
-        const int n = hi - lo + 1, n4 = n / 4, r = lo + 4 * n4;
-#pragma unroll
-        for (int q = 0; q < n4; ++q) {
-            const int i = lo + 4 * q;
-            mad_chain_vs4(acc, m[i], C::RR_P[k - i], m[i + 1], C::RR_P[k - i - 1], m[i + 2], C::RR_P[k - i - 2], m[i + 3], C::RR_P[k - i - 3]);
-        }
-        if (n & 2) mad_chain_vs2(acc, m[r], C::RR_P[k - r], m[r + 1], C::RR_P[k - r - 1]);
-        if (n & 1) mad_chain_vs(acc, m[hi], C::RR_P[k - hi]);
-    }
-    // mul / mul_add with flushes: column k of a*b [+ c*d] + m*p; the m_k p_0 link and the column's end stay with the caller
-    template <bool FUSED>
-    static MG_DEV void chain_column(u64 &acc, u64 &spill, const FpR &a, const FpR &b, const FpR &c, const FpR &d, const u32 (&m)[K], int k) {
-        constexpr int KIND = FUSED ? FPR_KIND_MUL_ADD : FPR_KIND_MUL;
-        const int lo = k < K ? 0 : k - K + 1, hi = k < K ? k : K - 1, mhi = k < K ? k - 1 : K - 1; // m_k is not known yet
-        const bool f_cd = FUSED && flush_before(KIND, k, FPR_FLUSH_CD), f_mp = flush_before(KIND, k, FPR_FLUSH_MP);
-        if (!f_cd && !f_mp) { // an unflushed column: links interleaved as in the narrow-limb codings
-            const int n = mhi - lo + 1;
-#pragma unroll
-            for (int q = 0; q + 1 < n; q += 2) {
-                const int i = lo + q;
-                if constexpr (FUSED)
-                    mad_chain_triple2(acc, a.v[i], b.v[k - i], c.v[i], d.v[k - i], m[i], C::RR_P[k - i], a.v[i + 1], b.v[k - i - 1], c.v[i + 1],
-                                      d.v[k - i - 1], m[i + 1], C::RR_P[k - i - 1]);
-                else mad_chain_pair2(acc, a.v[i], b.v[k - i], m[i], C::RR_P[k - i], a.v[i + 1], b.v[k - i - 1], m[i + 1], C::RR_P[k - i - 1]);
-            }
-            if (n & 1) {
-                if constexpr (FUSED) mad_chain_triple(acc, a.v[mhi], b.v[k - mhi], c.v[mhi], d.v[k - mhi], m[mhi], C::RR_P[k - mhi]);
-                else mad_chain_pair(acc, a.v[mhi], b.v[k - mhi], m[mhi], C::RR_P[k - mhi]);
-            }
-            if (k < K) {
-                mad_chain_vv(acc, a.v[k], b.v[0]);
-                if constexpr (FUSED) mad_chain_vv(acc, c.v[k], d.v[0]);
-            }
-            return;
-        }
-        chain_vv(acc, a.v, b.v, k, lo, hi);
-        if constexpr (FUSED) {
-            if (f_cd) flush(acc, spill);
-            chain_vv(acc, c.v, d.v, k, lo, hi);
-        }
-        if (f_mp) flush(acc, spill);
-        if (mhi >= lo) chain_vs(acc, m, k, lo, mhi);
-    }
-    template <bool FUSED> static MG_DEV FpR chain_product(const FpR &a, const FpR &b, const FpR &c, const FpR &d) {
-        u64 acc = 0;
-        u32 m[K];
-        FpR t;
-#pragma unroll
-        for (int k = 0; k < 2 * K - 1; ++k) {
-            u64 spill = 0;
-            chain_column<FUSED>(acc, spill, a, b, c, d, m, k);
-            if (k < K) {
-                m[k] = ((u32)acc * C::RR_INV) & MASK;
-                mad_chain_vs(acc, m[k], C::RR_P[0]);
-            } else {
-                t.v[k - K] = (u32)acc & MASK;
-            }
-            acc >>= LB;
-            acc += spill;
-        }
-        t.v[K - 1] = (u32)acc;
-        return t;
-    }
     template <bool CH> static MG_DEV FpR mul_t(const FpR &a, const FpR &b) {
         if constexpr (!CH || !CHAINED) return mul(a, b);
-        if constexpr (2 * K > CAP) return chain_product<false>(a, b, a, b);
+        if constexpr (2 * K > CAP) return mul_flushed<true>(a, b);
         u64 acc = 0;
         u32 m[K];
         FpR t;
@@ -646,6 +573,7 @@ template <class C> struct FpR {
     }
     template <bool CH> static MG_DEV FpR sqr_t(const FpR &a) {
         if constexpr (!CH || !CHAINED) return sqr(a);
+        if constexpr (2 * K > CAP) return sqr_flushed<true>(a);
         u64 acc = 0;
         u32 m[K], a2[K];
         FpR t;
@@ -659,8 +587,6 @@ template <class C> struct FpR {
             for (int i = ilo; i + 1 <= ihi; i += 2) mad_chain_vv2(acc, a2[i], a.v[k - i], a2[i + 1], a.v[k - i - 1]);
             if (k >= 1 && ((ihi - ilo + 1) & 1) && ihi >= ilo) mad_chain_vv(acc, a2[ihi], a.v[k - ihi]);
             if (!(k & 1)) mad_chain_vv(acc, a.v[k / 2], a.v[k / 2]);
-            u64 spill = 0;
-            if (flush_before(FPR_KIND_SQR, k, FPR_FLUSH_MP)) flush(acc, spill); // (13 x 30 bits only)
             // the m_i p_{k-i} terms already known, two per block
             const int mlo = k < K ? 0 : k - K + 1, mhi = k < K ? k - 1 : K - 1;
 #pragma unroll
@@ -673,14 +599,13 @@ template <class C> struct FpR {
                 t.v[k - K] = (u32)acc & MASK;
             }
             acc >>= LB;
-            acc += spill;
         }
         t.v[K - 1] = (u32)acc;
         return t;
     }
     template <bool CH> static MG_DEV FpR mul_add_t(const FpR &a, const FpR &b, const FpR &c, const FpR &d) {
         if constexpr (!CH || !CHAINED) return mul_add(a, b, c, d);
-        if constexpr (2 * K > CAP) return chain_product<true>(a, b, c, d);
+        if constexpr (3 * K > CAP) return mul_add_flushed<true>(a, b, c, d);
         u64 acc = 0;
         u32 m[K];
         FpR t;
