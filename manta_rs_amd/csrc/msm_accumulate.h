@@ -7,9 +7,13 @@ namespace mg {
 // --------------------------------------------------------------------------------------------
 // K7a: chunk accumulate
 // --------------------------------------------------------------------------------------------
-// (BLS12-381 G1: 183 VGPRs with the straight loop, 199 with the rotated one, 228 with the fetch ahead, no scratch -> two wavefronts
-// per SIMD in each case, which already saturates the integer pipe; forcing three through the launch bounds spills and is
-// slower; a prefetch into a SECOND register set changed nothing in rounds 4 and 6. BN254 G1 holds 124 -> four per SIMD.)
+// (BLS12-381 G1: 212 VGPRs with the shipped loop (rotated, fetch ahead; 215 for the timed twin), 189 without the fetch ahead, no
+// scratch -> two wavefronts per SIMD in each case, which already saturates the integer pipe; forcing three through the launch
+// bounds spills and is slower; a prefetch into a SECOND register set changed nothing in rounds 4 and 6. BN254 G1 holds 124 -> four
+// per SIMD. THE ALLOCATION MUST STAY AT OR BELOW 216 (registers are allocated in steps of 8 out of 512 per SIMD lane): the largest
+// tail kernel of a neighbouring MSM, serial_reduce_coop, allocates 296 and has to fit beside ONE resident accumulate wavefront,
+// or the tails of the MSMs in flight wait for SIMDs that accumulate wavefronts keep refilling. 217 registers instead of 215 cost
+// the pipelined headline 10 %: DESIGN.md section 9, profiles/accumulate_ahead_frontend_ab.txt.)
 // PROBE = true is the measurement twin bench.py's roofline leg runs (kernel timing on): identical but for its first wavefront
 // bracketing its whole run with the shader clock counter (s_memtime) and the constant-rate wall clock -- ticks per wall-clock
 // second = the clock the kernel actually ran at. A template parameter, not a run-time test: the extra live values cost the
@@ -25,12 +29,14 @@ namespace mg {
 //   MG_ACC_BLOCK (default 0: a loss, 219 VGPRs; needs INPLACE)  keys and vals are read four entries at a time (dwordx4) in blocks
 //       aligned on the absolute pair index; the 0-3 entries in front of a chunk's first aligned index and behind its last
 //       full block take the one-dword path.
-//   MG_ACC_AHEAD (default 0: a loss where it counts; needs INPLACE)  the base record of entry j + 1 is gathered BETWEEN the
-//       halves of addition j, into the registers addition j has just finished reading, and the pair of entry j + 2 with it:
-//       no load of an iteration depends on another load of the same iteration. With 0 the same fetches are issued behind
-//       madd_finish and waited for at once. Shorter alone, slower with three MSMs in flight; the suspected cause (not
-//       measured): at 228 VGPRs two resident wavefronts leave a SIMD 56 registers and no tail kernel of a neighbouring MSM
-//       fits beside them.
+//   MG_ACC_AHEAD (default 1; needs INPLACE)  the base record of entry j + 1 is gathered BETWEEN the halves of addition j, into
+//       the registers addition j has just finished reading, and the pair of entry j + 2 with it: no load of an iteration depends
+//       on another load of the same iteration, and the gather has the ~2 100 multiply-adds of madd_finish to arrive in. With 0
+//       the same fetches are issued behind madd_finish and waited for at once. Measured twice as a loss of 4-9 % with three MSMs
+//       in flight, and both times the allocation was the cause, not the loop: at 224 or 232 registers serial_reduce_coop (296) no
+//       longer fits beside one accumulate wavefront. With the timed twin at 215 (allocated 216) the same loop is a gain of 3 %.
+//       Neither the front end of the next MSM (radix_scatter cut to 54 VGPRs changes nothing at 224) nor the kernel's own
+//       duration (depth 1: equal within noise) explains either result.
 //   MG_ACC_SINGLE_ROTATED (default 0: not measured)  the same rotated loop in accumulate_single.
 #ifndef MG_ACC_INPLACE
 #define MG_ACC_INPLACE 1
@@ -39,7 +45,7 @@ namespace mg {
 #define MG_ACC_BLOCK 0
 #endif
 #ifndef MG_ACC_AHEAD
-#define MG_ACC_AHEAD 0
+#define MG_ACC_AHEAD 1
 #endif
 #ifndef MG_ACC_SINGLE_ROTATED
 #define MG_ACC_SINGLE_ROTATED 0
@@ -66,8 +72,10 @@ __global__ __launch_bounds__(256) MG_ACC_ATTR void accumulate_chunks(const u32 *
     if (t >= T) return;
     long long c0 = 0;
     unsigned long long w0 = 0;
+    // (the rotated loop's twin lets EVERY wavefront read the clocks: uniform values stay in scalar registers, behind `t == 0` they
+    // are four VGPRs for the whole kernel -- 217 instead of 215, one allocation step too many: see the note on the allocation above)
     if constexpr (PROBE)
-        if (t == 0) c0 = clock64(), w0 = wall_clock64();
+        if (acc_chunks_rotated<F>() || t == 0) c0 = clock64(), w0 = wall_clock64();
     if (count) {
         M = *count; // compacted pairs: lanes past the last pair have nothing to do
         // adapt: the host launched ONE round of lanes (T = what the chip holds at this kernel's occupancy) without knowing how many

@@ -97,6 +97,9 @@ __global__ __launch_bounds__(256) void radix_scan_totals(u32 *__restrict__ total
     totals[threadIdx.x] = part[threadIdx.x] - mine;
 }
 
+// Register budget: at most 64 VGPRs (54 now), so that a workgroup finds room on a SIMD beside two resident BLS12-381 accumulate
+// wavefronts. A lane keeps its 16 keys and, two to a register, their 16 ranks across the ranking; the 16
+// values are requested behind it and arrive during the offset scan.
 __global__ __launch_bounds__(256) void radix_scatter(const u32 *__restrict__ keys_in, const u32 *__restrict__ vals_in,
                                                      u32 *__restrict__ keys_out, u32 *__restrict__ vals_out, u32 M,
                                                      int shift, u32 ntiles, const u32 *__restrict__ hist,
@@ -108,21 +111,25 @@ __global__ __launch_bounds__(256) void radix_scatter(const u32 *__restrict__ key
     __shared__ u32 wcount[4][256]; // per-wave running digit counts, then per-wave tile-local offsets
     __shared__ u32 gbase[256];     // global position of the tile's first element of each digit, minus its local offset
     __shared__ u32 sk[SORT_TILE], sv[SORT_TILE]; // the tile, locally sorted by digit (stable)
+    constexpr int HALF = SORT_ITEMS / 2;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
     for (int w = 0; w < 4; ++w) wcount[w][threadIdx.x] = 0;
     __syncthreads();
-    const size_t tile0 = (size_t)blockIdx.x * SORT_TILE;
-    const size_t base = tile0 + (size_t)wave * (SORT_ITEMS * 64);
-    u32 k[SORT_ITEMS], v[SORT_ITEMS];
-    unsigned short rk[SORT_ITEMS];
+    const u32 tile0 = blockIdx.x * (u32)SORT_TILE; // below M < 2^32
+    const u32 base = tile0 + (u32)wave * (SORT_ITEMS * 64) + (u32)lane;
+    const u32 left = M - tile0 > (u32)SORT_TILE ? (u32)SORT_TILE : M - tile0; // elements of this tile
+    const u32 mine = (u32)wave * (SORT_ITEMS * 64) + (u32)lane;              // tile-local index of this lane's item 0
+    u32 k[SORT_ITEMS], rk2[HALF]; // rk2[j / 2]: the ranks (< 1024) of items j (low half) and j + 1
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
 #pragma unroll
     for (int j = 0; j < SORT_ITEMS; ++j) {
-        const size_t e = base + (size_t)j * 64 + lane;
-        const bool valid = e < M;
-        k[j] = valid ? keys_in[e] : 0u;
-        v[j] = valid ? vals_in[e] : 0u;
+        const bool valid = mine + (u32)j * 64 < left;
+        k[j] = valid ? keys_in[(size_t)base + (size_t)j * 64] : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < SORT_ITEMS; ++j) {
+        const bool valid = mine + (u32)j * 64 < left;
         const u32 d = (sort_key(k[j], lowmask, inv_from) >> shift) & 255u;
         unsigned long long peers = __ballot(valid);
 #pragma unroll
@@ -133,9 +140,20 @@ __global__ __launch_bounds__(256) void radix_scatter(const u32 *__restrict__ key
         }
         const u32 before = wcount[wave][d]; // every peer reads the count, then the first peer bumps it
         const u32 r = (u32)__popcll(peers & lt_mask);
-        rk[j] = (unsigned short)(before + r);
+        if (j & 1)
+            rk2[j >> 1] |= (before + r) << 16;
+        else
+            rk2[j >> 1] = before + r;
+        asm volatile("" : "+v"(rk2[j >> 1])); // packed here and now: left to itself the compiler carries `before` and `r` to the placement
         if (valid && r == 0) wcount[wave][d] = before + (u32)__popcll(peers);
     }
+    // (the digits are worked out again behind the scan, from keys the compiler cannot see through: it would otherwise keep all 16
+    // digit addresses of the ranking alive beside the keys)
+#pragma unroll
+    for (int j = 0; j < SORT_ITEMS; ++j) asm volatile("" : "+v"(k[j]));
+    u32 v[SORT_ITEMS]; // requested here, in flight across the scan
+#pragma unroll
+    for (int j = 0; j < SORT_ITEMS; ++j) v[j] = mine + (u32)j * 64 < left ? vals_in[(size_t)base + (size_t)j * 64] : 0u;
     __syncthreads();
     { // tile-local exclusive offsets: digit-major, wave-minor (stable); one thread per digit + a 256-wide scan
         const u32 d = threadIdx.x;
@@ -160,16 +178,15 @@ __global__ __launch_bounds__(256) void radix_scatter(const u32 *__restrict__ key
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < SORT_ITEMS; ++j) {
-        const size_t e = base + (size_t)j * 64 + lane;
-        if (e < M) {
-            const u32 lp = wcount[wave][(sort_key(k[j], lowmask, inv_from) >> shift) & 255u] + rk[j];
+        if (mine + (u32)j * 64 < left) {
+            const u32 rank = (j & 1) ? rk2[j >> 1] >> 16 : rk2[j >> 1] & 0xffffu;
+            const u32 lp = wcount[wave][(sort_key(k[j], lowmask, inv_from) >> shift) & 255u] + rank;
             sk[lp] = k[j];
             sv[lp] = v[j];
         }
     }
     __syncthreads();
-    const u32 cnt = tile0 >= M ? 0u : (u32)((tile0 + SORT_TILE <= M) ? SORT_TILE : (M - tile0));
-    for (u32 t = threadIdx.x; t < cnt; t += 256) { // consecutive lanes -> consecutive addresses within a digit run
+    for (u32 t = threadIdx.x; t < left; t += 256) { // consecutive lanes -> consecutive addresses within a digit run
         const u32 kk = sk[t];
         const u32 pos = gbase[(sort_key(kk, lowmask, inv_from) >> shift) & 255u] + t;
         keys_out[pos] = kk;
