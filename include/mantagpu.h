@@ -595,6 +595,30 @@ int mg_points_encode(mg_curve_t curve, int group, const uint64_t *affine_mont, s
  * mg_groth16_verify_batch on the accepted rows. */
 int mg_proofs_decode(mg_curve_t curve, const uint8_t *proof_bytes, size_t k, uint64_t *points_out, uint8_t *ok);
 
+/* ---- the same codec for the point records of Perpetual Powers of Tau challenge / response files (`PpotSerializer`,
+ *      manta-trusted-setup/src/groth16/ppot/serialization.rs:52-379; per point on the host there: `read_g1_powers`,
+ *      `read_g2_powers`, `curve_point_checks`). Bn254 only -- the ceremony's curve; any other curve is
+ *      MG_ERROR_INVALID_ARGUMENT. A record is the concatenation of 32-byte BIG-endian base-field elements: G1 x | y (64 B),
+ *      compressed x (32 B); G2 x.c1 | x.c0 | y.c1 | y.c0 (128 B), compressed x.c1 | x.c0 (64 B). Bits 7 and 6 of byte 0 are
+ *      flags, cleared from the first element only: bit 6 = infinity (every other bit of the record must then be zero);
+ *      bit 7 = y is the greater of y, -y in a compressed record (arkworks order, c1 first), and "compressed" -- an error -- in
+ *      an uncompressed one. Coordinates are read mod q (`from_be_bytes_mod_order`): a value >= q is reduced, not rejected.
+ *      Same kernels, chunking, threading and output format as mg_points_decode / mg_points_encode.
+ *      status, first match: uncompressed -- bit 7: BAD_ENCODING (`ExpectedUncompressed`); bit 6: OK (infinity) if the rest
+ *      is zero, else BAD_ENCODING (`PointAtInfinity`); checked and off the curve: NOT_ON_CURVE; checked and [r]P != O:
+ *      NOT_IN_SUBGROUP. compressed -- bit 6: as above (bit 7 beside it is ignored); x^3 + b without a root: NOT_ON_CURVE;
+ *      checked and [r]P != O: NOT_IN_SUBGROUP. checked = 0 is legal for both forms (`deserialize_unchecked`; compressed:
+ *      `deserialize_compressed`, which leaves the subgroup test to its caller). An all-zero record is not infinity: it is
+ *      the point (0, 0) uncompressed and x = 0 compressed. ----------------------------------------------------------- */
+int mg_ppot_points_decode(mg_curve_t curve, int group, const uint8_t *bytes, size_t n, int compressed, int checked,
+                          uint64_t *out_affine_mont, uint8_t *status /* may be NULL */, size_t *n_bad /* may be NULL */);
+/* n affine Montgomery points -> PPoT records back to back (`PpotSerializer::serialize_compressed` / `_uncompressed`):
+ * infinity is byte 0 = 0x40 and zeros; compressed sets bit 7 when y > -y. */
+int mg_ppot_points_encode(mg_curve_t curve, int group, const uint64_t *affine_mont, size_t n, int compressed, uint8_t *out);
+/* Blake2b-512 (RFC 7693; unkeyed, no salt, no personalisation -- the reference's `Blake2b::default()`, the hash of a PPoT
+ * file's 64-byte header and of a response): host code, any length. */
+int mg_blake2b512(const uint8_t *data, size_t len, uint8_t out64[64]);
+
 /* ---- batched Poseidon over the scalar field and the hashing of manta's UTXO Merkle forest. Replaces, in bulk,
  *      `Hasher<S, T, ARITY>::hash` (manta-pay/src/crypto/poseidon/hash.rs:111-153) and the Poseidon permutation
  *      (poseidon/mod.rs:383-419), and the inner hashing of `merkle_tree::Full` (root, `Path`) of manta-pay's UTXO accumulator

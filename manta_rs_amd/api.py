@@ -73,6 +73,7 @@ EXPORTS = [
     "mg_ctx_opts_init", "mg_ctx_create_ex", "mg_ctx_create_from_bytes_ex", "mg_last_pass_host_ms",
     "mg_tuning_init", "mg_get_tuning", "mg_set_tuning", "mg_tuning_env_names",
     "mg_points_decode", "mg_points_check", "mg_points_encode", "mg_proofs_decode",
+    "mg_ppot_points_decode", "mg_ppot_points_encode", "mg_blake2b512",
     "mg_poseidon_create", "mg_poseidon_destroy", "mg_poseidon_permute", "mg_poseidon_hash", "mg_poseidon_hash_device",
     "mg_merkle_tree", "mg_merkle_forest_roots", "mg_merkle_forest_append",
     "mg_edwards_decode", "mg_edwards_encode", "mg_edwards_check", "mg_edwards_mul", "mg_edwards_add",
@@ -1057,6 +1058,53 @@ def points_encode(curve, group, points, compressed=True) -> bytes:
     out = ctypes.create_string_buffer(max(1, pts.shape[0] * point_bytes(curve, group, compressed)))
     _chk(LIB.mg_points_encode(curve, group, _p(pts), _sz(pts.shape[0]), int(compressed), out), "mg_points_encode")
     return out.raw[:pts.shape[0] * point_bytes(curve, group, compressed)]
+
+
+def ppot_point_bytes(group, compressed):
+    """bytes of one record of a Perpetual Powers of Tau file (Bn254): 64 / 32 (G1), 128 / 64 (G2)"""
+    return point_bytes(BN254, group, compressed)
+
+
+def _byte_view(data):
+    """a uint8 view of any buffer-protocol object (bytes, memoryview, mmap, ...): no copy, read-only buffers included"""
+    return np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(0, dtype=np.uint8)
+
+
+def ppot_points_decode(group, data, compressed, checked=True):
+    """Batched `PpotSerializer` reads on the GPU (`mg_ppot_points_decode`, Bn254): data = the records back to back, any
+    buffer (or a sequence of buffers, joined). Returns (points [n, limbs] affine Montgomery, zeros for infinity and for
+    rejected points; status [n] uint8, POINT_*). checked=False is `deserialize_unchecked` / `deserialize_compressed`, which
+    leave the curve (uncompressed) and subgroup tests out."""
+    if isinstance(data, (list, tuple)):
+        data = b"".join(data)
+    view = _byte_view(data)
+    nb = ppot_point_bytes(group, compressed)
+    if view.size % nb:
+        raise ValueError(f"{view.size} bytes is not a whole number of {nb}-byte records")
+    n = view.size // nb
+    out = np.zeros((n, affine_limbs(BN254, group)), dtype=np.uint64)
+    st = np.zeros(n, dtype=np.uint8)
+    _chk(LIB.mg_ppot_points_decode(BN254, group, _p(view), _sz(n), int(compressed), int(checked), _p(out), _p(st), None),
+         "mg_ppot_points_decode")
+    return out, st
+
+
+def ppot_points_encode(group, points, compressed) -> bytes:
+    """Batched `PpotSerializer` writes on the GPU (`mg_ppot_points_encode`, Bn254): the records back to back."""
+    pts = _u64(points).reshape(-1, affine_limbs(BN254, group))
+    nb = pts.shape[0] * ppot_point_bytes(group, compressed)
+    out = ctypes.create_string_buffer(max(1, nb))
+    _chk(LIB.mg_ppot_points_encode(BN254, group, _p(pts), _sz(pts.shape[0]), int(compressed), out), "mg_ppot_points_encode")
+    return out.raw[:nb]
+
+
+def blake2b512(data) -> bytes:
+    """Blake2b-512 (RFC 7693, unkeyed) of any buffer, read in place by the library's host code (`mg_blake2b512`): the hash of
+    PPoT file headers and responses"""
+    view = _byte_view(data)
+    out = ctypes.create_string_buffer(64)
+    _chk(LIB.mg_blake2b512(_p(view), _sz(view.size), out), "mg_blake2b512")
+    return out.raw
 
 
 def proofs_decode(curve, proofs):

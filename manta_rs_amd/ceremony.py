@@ -12,6 +12,8 @@ manta-trusted-setup's hot loops, every group operation through the C ABI (`mg_ec
     power_pairs / check_powers  util.rs:333-346, groth16/kzg.rs:508-521   consecutive powers differ by one ratio (kzg verifier)
     state_check                 groth16/mpc.rs:79-100                     every point of a proving key on the curve and in the subgroup
     Accumulator.encode / decode groth16/kzg.rs:560-690                    the accumulator's arkworks serialisation, checked (`C::check`)
+    Accumulator.verify_transform groth16/kzg.rs:481-521                   one contribution to the accumulator, minus the knowledge proofs
+    ppot.read_subaccumulator    groth16/ppot/serialization.rs:688-702     the accumulator from a Perpetual Powers of Tau file (ppot.py)
 
 Scalars are Python integers (the ceremony's RNG stays with the caller); points are [n, limbs] uint64 affine Montgomery
 arrays, infinity = zeros -- the C ABI's format. Not used by the prover; a ceremony is a one-off, which is why SURVEY.md
@@ -147,20 +149,50 @@ class Accumulator:
         self.beta_g2 = batch_mul_fixed_scalar(curve, 2, self.beta_g2, beta)
 
 
-    def check_powers(self) -> str:
+    def check_powers(self, rho=None) -> str:
         """kzg.rs:508-521, the power checks of the accumulator's `verify_transform`: every vector is a sequence of consecutive
-        powers of one tau (merged by `power_pairs`, compared with the first two G2 / G1 powers). "" or the error variant."""
+        powers of one tau (merged by `power_pairs`, compared with the first two G2 / G1 powers). "" or the error variant.
+        rho: the merging scalars as integers (tests; each vector takes as many as it has pairs), else drawn from the OS."""
         c = self.curve
-        lhs, rhs = power_pairs(c, 2, self.tau_powers_g2)
+
+        def pairs(group, points):
+            return power_pairs(c, group, points, None if rho is None else rho[:len(points) - 1])
+
+        lhs, rhs = pairs(2, self.tau_powers_g2)
         if not same(c, (self.tau_powers_g1[0], rhs), (self.tau_powers_g1[1], lhs)):
             return "TauG1Powers"
         t2 = (self.tau_powers_g2[1], self.tau_powers_g2[0])
         for vec, err in ((self.tau_powers_g1, "TauG2Powers"), (self.alpha_tau_powers_g1, "AlphaG1Powers"),
                          (self.beta_tau_powers_g1, "BetaG1Powers")):
-            lhs, rhs = power_pairs(c, 1, vec)
+            lhs, rhs = pairs(1, vec)
             if not same(c, (lhs, t2[0]), (rhs, t2[1])):
                 return err
         return ""
+
+    @staticmethod
+    def verify_transform(last, next, certificate, rho=None) -> str:
+        """kzg.rs:481-521 `Accumulator::verify_transform` minus the knowledge proofs: `next` was computed from `last` by one
+        contribution. certificate = the three G2 ratio pairs (tau, alpha, beta) that `Proof::verify` (kzg.rs:229-253) hands
+        back -- each (matching_point, challenge_point) = (s H, H) for the contribution's scalar s; the caller supplies them,
+        since the hash to G2 that yields H is not built (ppot.py). Returns "" or the reference's `VerificationError` variant:
+        PrimeSubgroupGeneratorG1 / G2, TauMultiplication, AlphaMultiplication, BetaMultiplication (either beta check), then
+        those of `check_powers` on `next`."""
+        from . import keygen
+        c = next.curve
+        tau, alpha, beta = certificate
+        if not np.array_equal(np.asarray(next.tau_powers_g1[0]).reshape(-1), keygen.generator(c, 1).reshape(-1)):
+            return "PrimeSubgroupGeneratorG1"
+        if not np.array_equal(np.asarray(next.tau_powers_g2[0]).reshape(-1), keygen.generator(c, 2).reshape(-1)):
+            return "PrimeSubgroupGeneratorG2"
+        if not same(c, (last.tau_powers_g1[1], tau[0]), (next.tau_powers_g1[1], tau[1])):
+            return "TauMultiplication"
+        if not same(c, (last.alpha_tau_powers_g1[0], alpha[0]), (next.alpha_tau_powers_g1[0], alpha[1])):
+            return "AlphaMultiplication"
+        if not same(c, (last.beta_tau_powers_g1[0], beta[0]), (next.beta_tau_powers_g1[0], beta[1])):
+            return "BetaMultiplication"
+        if not same(c, (last.beta_tau_powers_g1[0], next.beta_g2), (next.beta_tau_powers_g1[0], last.beta_g2)):
+            return "BetaMultiplication"
+        return next.check_powers(rho)
 
     FIELDS = (("tau_powers_g1", 1), ("tau_powers_g2", 2), ("alpha_tau_powers_g1", 1), ("beta_tau_powers_g1", 1), ("beta_g2", 2))
 

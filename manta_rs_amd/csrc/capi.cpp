@@ -915,6 +915,33 @@ MG_API int mg_proofs_decode(mg_curve_t curve, const uint8_t *proof_bytes, size_t
 }
 
 namespace mg {
+int ppot_points_decode(int curve, int group, const uint8_t *bytes, size_t n, int compressed, int checked, u64 *out,
+                       uint8_t *status, size_t *n_bad);
+int ppot_points_encode(int curve, int group, const u64 *affine, size_t n, int compressed, uint8_t *out);
+void blake2b512(const uint8_t *data, size_t len, uint8_t out[64]);
+} // namespace mg
+MG_API int mg_ppot_points_decode(mg_curve_t curve, int group, const uint8_t *bytes, size_t n, int compressed, int checked,
+                                 uint64_t *out_affine_mont, uint8_t *status, size_t *n_bad) {
+    MG_TRY
+    return ppot_points_decode((int)curve, group, bytes, n, compressed, checked, out_affine_mont, status, n_bad);
+    MG_CATCH
+}
+MG_API int mg_ppot_points_encode(mg_curve_t curve, int group, const uint64_t *affine_mont, size_t n, int compressed,
+                                 uint8_t *out) {
+    MG_TRY
+    return ppot_points_encode((int)curve, group, affine_mont, n, compressed, out);
+    MG_CATCH
+}
+MG_API int mg_blake2b512(const uint8_t *data, size_t len, uint8_t out64[64]) {
+    MG_TRY
+    if ((!data && len) || !out64) return MG_ERROR_INVALID_ARGUMENT;
+    static const uint8_t none = 0;
+    blake2b512(data ? data : &none, len, out64);
+    return MG_SUCCESS;
+    MG_CATCH
+}
+
+namespace mg {
 int poseidon_create(int curve, int width, int full_rounds, int partial_rounds, const uint8_t *bytes, size_t len,
                     mg_poseidon **out);
 void poseidon_destroy(mg_poseidon *h);

@@ -1,5 +1,5 @@
 // Host layer of the batched point codec (mantagpu.h mg_points_decode / mg_points_check / mg_points_encode /
-// mg_proofs_decode): argument checks, status counting and the proof split; kernels and chunking in point_codec.h.
+// mg_proofs_decode / mg_ppot_points_decode / mg_ppot_points_encode): argument checks, status counting and the proof split; kernels and chunking in point_codec.h.
 #include "point_codec.h"
 
 namespace mg {
@@ -39,6 +39,22 @@ int points_check(int curve, int group, const u64 *affine, size_t n, uint8_t *sta
 int points_encode(int curve, int group, const u64 *affine, size_t n, int compressed, uint8_t *out) {
     if (!valid(curve, group) || (n && (!affine || !out))) return MG_ERR_ARG;
     return run(curve, PointCodecArgs{group, 2, compressed != 0, 0, affine, n, out, nullptr});
+}
+
+// The PPoT record format (point_codec.h `Ppot`): Bn254 only, the ceremony's curve; both forms may be read unchecked
+int ppot_points_decode(int curve, int group, const uint8_t *bytes, size_t n, int compressed, int checked, u64 *out,
+                       uint8_t *status, size_t *n_bad) {
+    if (curve != 0 || !valid(curve, group) || (n && (!bytes || !out))) return MG_ERR_ARG;
+    std::vector<uint8_t> own;
+    status = status_or_own(status, n, own);
+    const int rc = run(curve, PointCodecArgs{group, 0, compressed != 0, checked != 0, bytes, n, out, status, 1});
+    if (rc == MG_OK && n_bad) *n_bad = count_bad(status, n);
+    return rc;
+}
+
+int ppot_points_encode(int curve, int group, const u64 *affine, size_t n, int compressed, uint8_t *out) {
+    if (curve != 0 || !valid(curve, group) || (n && (!affine || !out))) return MG_ERR_ARG;
+    return run(curve, PointCodecArgs{group, 2, compressed != 0, 0, affine, n, out, nullptr, 1});
 }
 
 // k compressed proofs a | b | c: the 2k G1 points (a_i, c_i) and the k G2 points go to the GPU as two batches

@@ -1,6 +1,8 @@
 // Batched arkworks 0.3 point codec on gfx950: decode (bytes -> checked affine Montgomery points), check (points already in
 // memory) and encode (affine Montgomery -> canonical bytes) for short-Weierstrass G1 / G2 of BN254 and BLS12-381, one point
 // per lane. Instantiated per curve in point_codec_<curve>.hip; the C ABI (mg_points_*) is in point_codec.cpp.
+// The same kernel bodies read and write a second record format, that of the Perpetual Powers of Tau files (BN254 only, C ABI
+// mg_ppot_points_*): the bodies take a format policy (`Arkworks`, `Ppot` below) that turns a record into x, y and flags, and back.
 //
 // Replaces, in bulk, the per-point host code of
 //   ark-ec 0.3 `GroupAffine<P>: CanonicalDeserialize` (compressed: x + SWFlags, y = sqrt(x^3 + b) picked by the flag;
@@ -178,28 +180,96 @@ template <class Curve, class F> MG_DEV bool times_r_is_zero(const Affine<F> &p) 
     return acc.is_inf();
 }
 
+// ---- record formats ---------------------------------------------------------------------------------------------------
+// A format reads a record of W words (W = F::N compressed, 2 F::N uncompressed; word k = bytes 4k..4k+3 of the record) into
+// x, y as plain integers (not yet Montgomery; y = 0 when compressed), flags (bit 7 = 0x80, bit 6 = 0x40: infinity) and its verdict
+// on the encoding (true = rejected), and writes canonical x, y with the flags back. Everything after that -- the curve equation,
+// the root and its sign, the subgroup test, the order of the statuses -- is the kernels' and the same for every format.
+template <class C> MG_DEV u32 top_flags(const Fp<C> &a) { return (a.v[C::N - 1] >> 24) & 0xc0u; }
+template <class C> MG_DEV u32 top_flags(const Fp2<C> &a) { return top_flags<C>(a.c1); }
+
+// arkworks 0.3 `CanonicalSerialize`: little-endian, Fq2 as c0 | c1, the flags in the last byte of the record
+struct Arkworks {
+    template <class Q, class F> static MG_DEV bool read(const u32 *rec, bool compressed, F &x, F &y, u32 &flags) {
+        x = F::load(rec), y = F::zero();
+        if (compressed) {
+            flags = top_flags<Q>(x);
+            clear_flags<Q>(x);
+        } else {
+            y = F::load(rec + F::N);
+            flags = top_flags<Q>(y);
+            clear_flags<Q>(y);
+        }
+        // SWFlags::from_u8 has no value for both bits; every coordinate read must be canonical, infinity included
+        return flags == 0xc0u || any_geq_p<Q>(x) || any_geq_p<Q>(y);
+    }
+    template <class Q, class F> static MG_DEV void write(u32 *o, bool compressed, F x, F y, u32 flags) {
+        if (compressed) {
+            set_flags<Q>(x, flags);
+            x.store(o);
+        } else {
+            set_flags<Q>(y, flags);
+            x.store(o);
+            y.store(o + F::N);
+        }
+    }
+};
+
+// Big-endian base-field elements: limb j of the element at words p[0 .. N) is the byte-swapped word N - 1 - j
+template <class C> MG_DEV void load_be(const u32 *p, Fp<C> &a) {
+#pragma unroll
+    for (int j = 0; j < C::N; ++j) a.v[j] = __builtin_bswap32(p[C::N - 1 - j]);
+}
+template <class C> MG_DEV void load_be(const u32 *p, Fp2<C> &a) { // c1 first
+    load_be<C>(p, a.c1);
+    load_be<C>(p + C::N, a.c0);
+}
+template <class C> MG_DEV void store_be(u32 *p, const Fp<C> &a) {
+#pragma unroll
+    for (int j = 0; j < C::N; ++j) p[C::N - 1 - j] = __builtin_bswap32(a.v[j]);
+}
+template <class C> MG_DEV void store_be(u32 *p, const Fp2<C> &a) {
+    store_be<C>(p, a.c1);
+    store_be<C>(p + C::N, a.c0);
+}
+// The serializer of the Perpetual Powers of Tau files (manta-trusted-setup/src/groth16/ppot/serialization.rs:52-379):
+// big-endian elements x | y (Fq2 as c1 | c0), the flags in bits 7 and 6 of byte 0 -- the top byte of the first element, which
+// is x's (x.c1's) whatever the form. Bit 7 on an uncompressed record is `ExpectedUncompressed`; bit 6 with any other bit of the
+// record set (byte 0 masked with 0x3f) is `PointAtInfinity`; bit 7 beside bit 6 on a compressed record is ignored (:116-126).
+// Coordinates are `from_be_bytes_mod_order`: never rejected. x and y leave here UNREDUCED (the first element < 2^254, the
+// others any 256-bit value) and the kernel's to_mont reduces them: Fp::mul(a, R2) computes t = (a R2 + m q) / R with a < R = 2^256,
+// R2 < q and m < R, so t < (R q + R q) / R = 2q < 2^255 and its final conditional subtraction leaves a R mod q < q for EVERY
+// 256-bit a; each column of the product holds at most 2 N terms < 2^64 in 96 bits whatever a is. No subtraction chain is needed.
+struct Ppot {
+    template <class Q, class F> static MG_DEV bool read(const u32 *rec, bool compressed, F &x, F &y, u32 &flags) {
+        load_be<Q>(rec, x);
+        y = F::zero();
+        if (!compressed) load_be<Q>(rec + F::N, y);
+        flags = top_flags<Q>(x);
+        clear_flags<Q>(x);
+        const bool inf_dirty = (flags & 0x40u) != 0 && !(x.is_zero() && y.is_zero());
+        return (!compressed && (flags & 0x80u) != 0) || inf_dirty;
+    }
+    template <class Q, class F> static MG_DEV void write(u32 *o, bool compressed, F x, F y, u32 flags) {
+        set_flags<Q>(x, flags);
+        store_be<Q>(o, x);
+        if (!compressed) store_be<Q>(o + F::N, y);
+    }
+};
+
 // ---- kernels ----------------------------------------------------------------------------------------------------------
-// n encodings of W words each (W = F::N compressed, 2 F::N uncompressed; the bytes are little-endian, so word k holds bytes
-// 4k..4k+3) -> affine Montgomery x || y (zeros for infinity and for every rejected point) and one status byte per point.
-template <class Curve, int G>
+// n records of W words each in format Fmt -> affine Montgomery x || y (zeros for infinity and for every rejected point) and
+// one status byte per point.
+template <class Curve, int G, class Fmt>
 __global__ __launch_bounds__(256) void point_decode_kernel(const u32 *__restrict__ in, size_t n, int compressed, int checked,
                                                            u32 *__restrict__ out, uint8_t *__restrict__ status) {
     typedef typename Group<Curve, G>::F F;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const u32 *rec = in + i * (size_t)(compressed ? F::N : 2 * F::N);
-    F x = F::load(rec), y = F::zero();
+    F x, y;
     u32 flags;
-    if (compressed) {
-        flags = (rec[F::N - 1] >> 24) & 0xc0u;
-        clear_flags<typename Curve::Fq>(x);
-    } else {
-        y = F::load(rec + F::N);
-        flags = (rec[2 * F::N - 1] >> 24) & 0xc0u;
-        clear_flags<typename Curve::Fq>(y);
-    }
-    // SWFlags::from_u8 has no value for both bits; every coordinate read must be canonical, infinity included
-    const bool bad = flags == 0xc0u || any_geq_p<typename Curve::Fq>(x) || any_geq_p<typename Curve::Fq>(y);
+    const bool bad = Fmt::template read<typename Curve::Fq, F>(rec, compressed != 0, x, y, flags);
     const bool inf = (flags & 0x40u) != 0;
     x = to_mont<typename Curve::Fq>(x);
     const F rhs = curve_rhs(x, Group<Curve, G>::b());
@@ -239,9 +309,9 @@ __global__ __launch_bounds__(256) void point_check_kernel(const u32 *__restrict_
     status[i] = bad ? PT_BAD_ENCODING : inf ? PT_OK : !on ? PT_NOT_ON_CURVE : !in_group ? PT_NOT_IN_SUBGROUP : PT_OK;
 }
 
-// affine Montgomery -> arkworks canonical bytes (x, flags: bit 7 = y is the larger root; or x || y), infinity = zeros
-// with bit 6 -- byte for byte HPoint::serialize
-template <class Curve, int G>
+// affine Montgomery -> records of format Fmt: canonical x (flags: bit 7 = y is the larger root) or x, y; infinity = zeros
+// with bit 6 -- for Arkworks byte for byte HPoint::serialize
+template <class Curve, int G, class Fmt>
 __global__ __launch_bounds__(256) void point_encode_kernel(const u32 *__restrict__ aff, size_t n, int compressed,
                                                            u32 *__restrict__ out) {
     typedef typename Group<Curve, G>::F F;
@@ -250,16 +320,13 @@ __global__ __launch_bounds__(256) void point_encode_kernel(const u32 *__restrict
     const Affine<F> p = Affine<F>::load(aff + i * (size_t)(2 * F::N));
     const bool inf = p.x.is_zero() && p.y.is_zero();
     const F z = F::zero();
-    F x = F::select(inf, z, from_mont<typename Curve::Fq>(p.x));
+    const F x = F::select(inf, z, from_mont<typename Curve::Fq>(p.x));
     u32 *o = out + i * (size_t)(compressed ? F::N : 2 * F::N);
     if (compressed) {
-        set_flags<typename Curve::Fq>(x, inf ? 0x40u : is_high<typename Curve::Fq>(p.y) ? 0x80u : 0u);
-        x.store(o);
+        Fmt::template write<typename Curve::Fq, F>(o, true, x, z, inf ? 0x40u : is_high<typename Curve::Fq>(p.y) ? 0x80u : 0u);
     } else {
-        F y = F::select(inf, z, from_mont<typename Curve::Fq>(p.y));
-        set_flags<typename Curve::Fq>(y, inf ? 0x40u : 0u);
-        x.store(o);
-        y.store(o + F::N);
+        const F y = F::select(inf, z, from_mont<typename Curve::Fq>(p.y));
+        Fmt::template write<typename Curve::Fq, F>(o, false, x, y, inf ? 0x40u : 0u);
     }
 }
 
@@ -271,7 +338,7 @@ __global__ __launch_bounds__(256) void point_encode_kernel(const u32 *__restrict
 constexpr size_t POINT_CODEC_CHUNK = size_t(1) << 16;
 constexpr Staging POINT_CODEC_STAGING{POINT_CODEC_CHUNK, true};
 
-template <class Curve, int G> struct PointCodecT {
+template <class Curve, int G, class Fmt> struct PointCodecT {
     typedef typename codec::Group<Curve, G>::F F;
     static constexpr size_t COORD = (size_t)F::N * 4; // bytes of one coordinate = words of F x 4
     static unsigned blocks(size_t cnt) { return (unsigned)((cnt + 255) / 256); }
@@ -280,7 +347,7 @@ template <class Curve, int G> struct PointCodecT {
         return run_chunks(POINT_CODEC_STAGING, n, nullptr, 0,
                           {Span::in(bytes, (compressed ? 1 : 2) * COORD), Span::out(out, 2 * COORD), Span::out(status, 1)}, 0,
                           [&](const Chunk &c) {
-                              hipLaunchKernelGGL((codec::point_decode_kernel<Curve, G>), dim3(blocks(c.n)), dim3(256), 0, c.stream,
+                              hipLaunchKernelGGL((codec::point_decode_kernel<Curve, G, Fmt>), dim3(blocks(c.n)), dim3(256), 0, c.stream,
                                                  (const u32 *)c.a[0], c.n, cf, ck, (u32 *)c.a[1], c.a[2]);
                               return hipGetLastError();
                           });
@@ -296,30 +363,31 @@ template <class Curve, int G> struct PointCodecT {
         const int cf = compressed;
         return run_chunks(POINT_CODEC_STAGING, n, nullptr, 0, {Span::in(aff, 2 * COORD), Span::out(out, (compressed ? 1 : 2) * COORD)}, 0,
                           [&](const Chunk &c) {
-                              hipLaunchKernelGGL((codec::point_encode_kernel<Curve, G>), dim3(blocks(c.n)), dim3(256), 0, c.stream,
+                              hipLaunchKernelGGL((codec::point_encode_kernel<Curve, G, Fmt>), dim3(blocks(c.n)), dim3(256), 0, c.stream,
                                                  (const u32 *)c.a[0], c.n, cf, (u32 *)c.a[1]);
                               return hipGetLastError();
                           });
     }
 };
 
-// per-curve entry points (point_codec_<curve>.hip): op 0 decode, 1 check, 2 encode
+// per-curve entry points (point_codec_<curve>.hip): op 0 decode, 1 check, 2 encode; format 0 arkworks, 1 PPoT (Bn254 only)
 struct PointCodecArgs {
     int group, op, compressed, checked;
     const void *in;
     size_t n;
     void *out;
     uint8_t *status;
+    int format = 0;
 };
-template <class Curve> int point_codec_dispatch(const PointCodecArgs &a) {
+template <class Curve, class Fmt> int point_codec_dispatch(const PointCodecArgs &a) {
     if (a.group != 1 && a.group != 2) return MG_ERR_ARG;
     if (a.group == 1) {
-        typedef PointCodecT<Curve, 1> P;
+        typedef PointCodecT<Curve, 1, Fmt> P;
         if (a.op == 0) return P::decode((const uint8_t *)a.in, a.n, a.compressed, a.checked, (u64 *)a.out, a.status);
         if (a.op == 1) return P::check((const u64 *)a.in, a.n, a.status);
         return P::encode((const u64 *)a.in, a.n, a.compressed, (uint8_t *)a.out);
     }
-    typedef PointCodecT<Curve, 2> P;
+    typedef PointCodecT<Curve, 2, Fmt> P;
     if (a.op == 0) return P::decode((const uint8_t *)a.in, a.n, a.compressed, a.checked, (u64 *)a.out, a.status);
     if (a.op == 1) return P::check((const u64 *)a.in, a.n, a.status);
     return P::encode((const u64 *)a.in, a.n, a.compressed, (uint8_t *)a.out);

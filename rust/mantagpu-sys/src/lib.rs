@@ -555,6 +555,20 @@ extern "C" {
     pub fn mg_points_check(curve: mg_curve_t, group: c_int, affine_mont: *const u64, n: usize, status: *mut u8, n_bad: *mut usize) -> c_int;
     pub fn mg_points_encode(curve: mg_curve_t, group: c_int, affine_mont: *const u64, n: usize, compressed: c_int, out: *mut u8) -> c_int;
     pub fn mg_proofs_decode(curve: mg_curve_t, proof_bytes: *const u8, k: usize, points_out: *mut u64, ok: *mut u8) -> c_int;
+    // the same codec for the records of Perpetual Powers of Tau files (Bn254 only; `status` and `n_bad` may be null)
+    pub fn mg_ppot_points_decode(
+        curve: mg_curve_t,
+        group: c_int,
+        bytes: *const u8,
+        n: usize,
+        compressed: c_int,
+        checked: c_int,
+        out_affine_mont: *mut u64,
+        status: *mut u8,
+        n_bad: *mut usize,
+    ) -> c_int;
+    pub fn mg_ppot_points_encode(curve: mg_curve_t, group: c_int, affine_mont: *const u64, n: usize, compressed: c_int, out: *mut u8) -> c_int;
+    pub fn mg_blake2b512(data: *const u8, len: usize, out64: *mut u8) -> c_int;
 
     // ---- batched Poseidon over Fr and the UTXO Merkle forest's hashing (MG_POSEIDON_CHUNK states per device pass)
     pub fn mg_poseidon_create(
