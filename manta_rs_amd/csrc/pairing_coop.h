@@ -1,24 +1,42 @@
 // Wave-cooperative pairing: ONE WAVEFRONT per pairing, the Fq12 state in LDS, one Fq2 product per lane.
 //
-// pairing_dev.h runs a pairing on one lane; that is the right shape for hundreds of independent pairings but leaves a
-// single Groth16 verification (three Miller loops and one final exponentiation) with 54 dependent Fq
-// products per Fq12 product: 45.7 ms per verification on MI355X, 26.9 ms of it the final exponentiation on ONE lane
-// (profiles/r02_verify_*.txt). Here an Fq12 is a polynomial of degree < 6 in w over Fq2 (w^6 = xi, w^2 = v of the
-// arkworks tower), a product is the 36 coefficient products a_i b_j on 36 lanes followed by six lanes folding them
-// (c_m = sum_{i+j=m} + xi sum_{i+j=m+6}), i.e. ONE Fq2 product deep instead of eighteen; line multiplications use 18 lanes,
-// Frobenius maps six, the G2 doubling / addition steps of G2Prepared up to five. The arithmetic (canonical saturated
-// Montgomery Fp<> of fp_dev.h) and every formula are those of pairing_dev.h, so results are the same bytes -- the
-// committed verifying keys of the reference stay the known-answer test.
+// This header is the whole GPU pairing: the Miller loop, G2Prepared::from and the final exponentiation (pairing_dev.h holds
+// the types, sizes and constants). A pairing on one lane -- the first version -- is the right shape for hundreds of
+// independent pairings but leaves a single Groth16 verification (three Miller loops and one final exponentiation, SURVEY.md
+// row f-2) with 54 dependent Fq products per Fq12 product: 45.7 ms per verification on MI355X, 26.9 ms of it the final
+// exponentiation on ONE lane (profiles/r02_verify_*.txt). Here an Fq12 is a polynomial of degree < 6 in w over Fq2
+// (w^6 = xi, w^2 = v of the arkworks tower) and a product is the 36 coefficient products a_i b_j on 36 lanes followed by
+// twelve lanes folding them (c_m = sum_{i+j=m} + xi sum_{i+j=m+6}), i.e. ONE Fq2 product deep instead of eighteen; squarings,
+// line multiplications and the G2 doubling / addition steps of G2Prepared go one step further, ONE Fq product per lane and
+// table-driven small-integer combinations behind it; Frobenius maps use six lanes. The arithmetic is the canonical saturated
+// Montgomery Fp<> of fp_dev.h and the formulas are arkworks' (ark-ec 0.3 models/{bn,bls12}), so results are the same bytes
+// as the reference's -- its committed verifying keys stay the known-answer test.
 //
 // LDS layout: slots of one Fq2 (2N words). Slots 0..35 hold the coefficient products; Fq12 register r occupies the six
 // slots REG0 + 6 r .. in arkworks' memory order c0.c0, c0.c1, c0.c2, c1.c0, c1.c1, c1.c2 (slot s = 3 i + j holds the
 // coefficient of w^(i + 2 j)). A workgroup is exactly one wavefront, so __syncthreads() is a wave-level fence.
 #pragma once
+#include <type_traits>
 #include "pairing_dev.h"
 
 namespace mg {
 
 extern __shared__ u32 mg_pairing_lds[];
+
+// One lane's entry of a second-stage table (PairingWave::combine), packed into words that stay in registers: the Fq slots
+// of M operands in the product area, BITS bits each, and the signed coefficients of those and of X extra operands that the
+// caller supplies, a byte each: magnitude | MINUS. An operand that was never set has coefficient zero.
+constexpr u32 MINUS = 0x80u;
+template <int M_, int BITS, int X_ = 0> struct LaneTab {
+    static constexpr int M = M_, X = X_, PER = 32 / BITS, SW = (M + PER - 1) / PER, CW = (M + X + 3) / 4;
+    u32 w[SW + CW] = {};
+    constexpr void set(int e, u32 slot, u32 cf) { w[e / PER] |= slot << (BITS * (e % PER)), set_cf(e, cf); } // operand e < M
+    constexpr void set_cf(int e, u32 cf) { w[SW + e / 4] |= cf << (8 * (e % 4)); } // (alone: extra operand e - M)
+    MG_DEV u32 slot(int e) const { return (w[e / PER] >> (BITS * (e % PER))) & ((1u << BITS) - 1u); }
+    MG_DEV u32 cf(int e) const { return (w[SW + e / 4] >> (8 * (e % 4))) & 255u; }
+    MG_DEV u32 pos(int e) const { return (cf(e) & MINUS) ? 0u : cf(e); }
+    MG_DEV u32 neg(int e) const { return (cf(e) & MINUS) ? cf(e) & 0x7fu : 0u; }
+};
 
 template <class K> struct PairingWave {
     typedef Pairing<K> P;
@@ -38,9 +56,9 @@ template <class K> struct PairingWave {
     static MG_DEV u32 *base() { return mg_pairing_lds + wave_id() * MILLER_WORDS; }
     static MG_DEV F2 ld(int slot) { return F2::load(base() + slot * W); }
     static MG_DEV void st(int slot, const F2 &v) { v.store(base() + slot * W); }
-    // Fq2 products inlined down to the Fq product (a real function with its operands in VGPRs, fp_dev.h); pairing_dev.h's
-    // out-of-line Fq2 helpers pass their operands through scratch memory, which costs more than the arithmetic here
-    // (by value: operands and result travel in VGPRs; the three Karatsuba products run interleaved, Fp::mul_many)
+    // Fq2 products, out of line with operands and result BY VALUE: they travel in VGPRs (by reference they would pass
+    // through scratch memory, which costs more than the arithmetic here); inside, everything is inlined down to the Fq
+    // product (a real function with its operands in VGPRs, fp_dev.h) and the Karatsuba products run interleaved (Fp::mul_many)
     static __device__ __noinline__ F2 mul2(const F2 a, const F2 b) {
         const F x[3] = {a.c0, a.c1, F::add(a.c0, a.c1)}, y[3] = {b.c0, b.c1, F::add(b.c0, b.c1)};
         F v[3];
@@ -54,20 +72,12 @@ template <class K> struct PairingWave {
         return F2{v[0], v[1]};
     }
     static MG_DEV F2 sqr2(const F2 &a) { return mul2(a, a); }
-    // 9 a mod p as ONE small multiple: t = 9 a (N + 1 words), a quotient estimate q from its top 64 bits (never above
-    // floor(t / p), at most one below: the divisor is p's top word + 1 and the float product is biased down by 2^-20), then
-    // t - q p < 2p and one conditional subtraction -- ~45 instructions against 4 modular additions (~150): xi = 9 + u is
-    // applied to every wrapped coefficient product (1.7 -> 0.9 us of an Fq12 product's 6.3 us on BN254)
-    static MG_DEV F times9(const F &a) {
-        u32 t[N + 1];
-        u64 c = 0;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            c += (u64)a.v[i] * 9u;
-            t[i] = (u32)c;
-            c >>= 32;
-        }
-        t[N] = (u32)c;
+    // t mod p for a small multiple of p's size, t < 2^9 p in N + 1 words: a quotient estimate q from t's top 64 bits, then
+    // t - q p and one conditional subtraction. q is never above floor(t / p): the divisor is p's top word + 1 and the float
+    // product is biased down by 2^-20, more than the roundings of the conversion, the division and the product add. It is at
+    // most one below: the bias, the roundings and the + 1 in a divisor above 2^28 lose less than 2^-19 of t / p < 2^9. So
+    // t - q p < 2p. ~45 instructions.
+    static MG_DEV F reduce_top(const u32 t[N + 1]) {
         const u64 top64 = ((u64)t[N] << 32) | t[N - 1];
         const float inv = (1.0f - 1.0f / 1048576.0f) / (float)((u64)K::Fq::P[N - 1] + 1u);
         const u32 q = (u32)((float)top64 * inv);
@@ -83,6 +93,20 @@ template <class K> struct PairingWave {
             m >>= 32;
         }
         return F::reduce_once(r, t[N] - (u32)m - bw);
+    }
+    // 9 a mod p as ONE small multiple, t = 9 a, against 4 modular additions (~150 instructions): xi = 9 + u is applied to
+    // every wrapped coefficient product (1.7 -> 0.9 us of an Fq12 product's 6.3 us on BN254)
+    static MG_DEV F times9(const F &a) {
+        u32 t[N + 1];
+        u64 c = 0;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            c += (u64)a.v[i] * 9u;
+            t[i] = (u32)c;
+            c >>= 32;
+        }
+        t[N] = (u32)c;
+        return reduce_top(t);
     }
     static MG_DEV F xi_real(const F &a) { // U0 a, xi = U0 + u
         if constexpr (K::U0 == 9) return times9(a);
@@ -159,10 +183,9 @@ template <class K> struct PairingWave {
         fold(d, 0x3fu);
     }
     // (sum of c_m w_m) mod p for small per-lane integers c_m = cp_m - cn_m (one of the two zero, either sum below 256), canonical
-    // in and out: the two sums as 64-bit columns without carries, t = pos + 256 p - neg in N + 1 words, one quotient estimate from
-    // its top 64 bits (never above floor(t / p), at most one below -- as in times9), one conditional subtraction. A chain of
-    // modular additions costs ~90 instructions per operand (sum, comparison with p, selection); this is two multiply-adds per
-    // operand word and ~150 instructions at the end, and small multiples (3 T - 2 a, xi = 9 + u) come for free.
+    // in and out: the two sums as 64-bit columns without carries, t = pos + 256 p - neg < 2^9 p in N + 1 words, one `reduce_top`.
+    // A chain of modular additions costs ~90 instructions per operand (sum, comparison with p, selection); this is two
+    // multiply-adds per operand word and ~150 instructions at the end, and small multiples (3 T - 2 a, xi = 9 + u) come for free.
     template <int M> static MG_DEV F lincomb(const F *w, const u32 *cp, const u32 *cn) {
         u64 pos[N], neg[N];
 #pragma unroll
@@ -188,21 +211,65 @@ template <class K> struct PairingWave {
             t[i] = (u32)d;
             bw = (u32)(d >> 63);
         }
-        const u64 top64 = ((u64)t[N] << 32) | t[N - 1];
-        const float inv = (1.0f - 1.0f / 1048576.0f) / (float)((u64)K::Fq::P[N - 1] + 1u);
-        const u32 q = (u32)((float)top64 * inv);
-        F r;
-        u64 mm = 0;
-        bw = 0;
+        return reduce_top(t);
+    }
+    // (b = base(), looked up ONCE per out-of-line function: finding the workgroup's LDS block there is a scalar load)
+    static MG_DEV u32 *prod_fq(u32 *b, int s) { return b + PROD * W + s * N; }                                // Fq slot s of the product area (72 of them)
+    static MG_DEV u32 *comp_of(u32 *b, int r, int l) { return b + (r + slot_of(l >> 1)) * W + (l & 1) * N; } // lane l < 12's Fq component of register r
+    // operand k of Karatsuba's three Fq products behind an Fq2 product: x, y, x + y
+    static MG_DEV F kara(int k, const F2 &a) { return F::select(k == 0, a.c0, F::select(k == 1, a.c1, F::add(a.c0, a.c1))); }
+    // this lane's entry of a compile-time table of L entries, the first n of them in use (`none` on the other lanes), for any
+    // struct of u32 words: worked out once per kernel as a chain of selects over compile-time values and kept in registers,
+    // so that all lanes run one instruction stream
+    template <class T, int L> static MG_DEV T lane_select(const T (&e)[L], int n = L, const T none = T{}) {
+        static_assert(std::is_trivially_copyable<T>::value && sizeof(T) % sizeof(u32) == 0, "a struct of u32 words");
+        struct Words {
+            u32 w[sizeof(T) / sizeof(u32)];
+        };
+        Words v = __builtin_bit_cast(Words, none);
 #pragma unroll
-        for (int i = 0; i < N; ++i) {
-            mm += (u64)q * K::Fq::P[i];
-            const u64 d = (u64)t[i] - (u32)mm - bw;
-            r.v[i] = (u32)d;
-            bw = (u32)(d >> 63);
-            mm >>= 32;
+        for (int l = 0; l < L; ++l) {
+            const Words t = __builtin_bit_cast(Words, e[l]);
+            const bool me = l < n && lane_id() == l;
+#pragma unroll
+            for (size_t k = 0; k < sizeof(T) / sizeof(u32); ++k) v.w[k] = me ? t.w[k] : v.w[k];
         }
-        return F::reduce_once(r, t[N] - (u32)mm - bw);
+        return __builtin_bit_cast(T, v);
+    }
+    // this lane's entry of a second-stage table, the twelve entries made by ENTRY(l) at compile time
+    template <auto ENTRY> static MG_DEV auto lane_tab() {
+        struct Entries {
+            decltype(ENTRY(0)) e[12] = {};
+            constexpr Entries() {
+                for (int l = 0; l < 12; ++l) e[l] = ENTRY(l);
+            }
+        };
+        constexpr Entries t;
+        return lane_select(t.e);
+    }
+    // The second stage of a product level whose first stage left one Fq product per lane in the product area: twelve lanes,
+    // lane l makes component l & 1 of coefficient l >> 1 of register d as ONE `lincomb` of the operands its table entry names
+    // -- Tab::M products and, where Tab::X = 1, the Fq element at `extra` -- with Karatsuba's differences, doublings and xi
+    // folded into the coefficients.
+    template <class Tab> static MG_DEV void combine(const Tab tab, u32 *b, int d, const u32 *extra) {
+        static_assert(Tab::X <= 1, "one extra operand at most");
+        const int l = lane_id();
+        if (l < 12) {
+            constexpr int OPS = Tab::M + Tab::X;
+            F w[OPS];
+            u32 cp[OPS], cn[OPS];
+#pragma unroll
+            for (int e = 0; e < OPS; ++e) {
+                cp[e] = tab.pos(e), cn[e] = tab.neg(e);
+                w[e] = F::load(e < Tab::M ? prod_fq(b, tab.slot(e)) : extra);
+            }
+            lincomb<OPS>(w, cp, cn).store(comp_of(b, d, l));
+        }
+        sync();
+    }
+    template <class Tab> static MG_DEV void combine(const Tab tab, u32 *b, int d) {
+        static_assert(Tab::X == 0, "this table's extra operand is missing");
+        combine(tab, b, d, nullptr);
     }
     // d = a^2 (registers; d may be a) with ONE Fq product per lane. With a lone wavefront on its SIMD every instruction costs
     // 5-9 cycles whether or not it depends on the one before (profiles/r02_ubench_pairing.txt), so what counts is the length of
@@ -213,15 +280,11 @@ template <class K> struct PairingWave {
     // into the coefficients, |c| <= 2 U0 + 2), one `lincomb`. Round 3 did this in two stages of modular additions (42 + 12
     // lanes): 5.2 us; now 3.2. Same field elements as mul12(d, a, a), canonical throughout.
     static constexpr u64 SQ_PAIR_I = 0x433222111100000ull, SQ_PAIR_J = 0x554543543254321ull; // (i, j), i < j, a nibble per pair
-    static constexpr int SQ_OPS = 10;
-    struct SqTab {
-        u32 idx[2], cf[3]; // this lane's stage B: ten product slots (6 bits each), ten coefficients (a byte each: magnitude | 0x80 minus)
-    };
+    typedef LaneTab<10, 6> SqTab;
     static constexpr SqTab sq_entry(int l) {
         const int m = l >> 1, comp = l & 1, k = K::U0;
-        u32 slot[SQ_OPS] = {}, cf[SQ_OPS] = {};
+        SqTab t;
         int n = 0, pair = 0;
-        constexpr u32 MINUS = 0x80u;
         for (int i = 0; i < 6; ++i)
             for (int j = i; j < 6; ++j) {
                 const int p = pair;
@@ -230,127 +293,83 @@ template <class K> struct PairingWave {
                 const bool wrap = i + j >= 6;
                 if (i == j) { // a_i^2 = P + 2 Q u; times xi: (k P - 2 Q) + (2 k Q + P) u
                     const u32 P = 2 * i, Q = 2 * i + 1;
-                    if (!wrap) slot[n] = comp ? Q : P, cf[n] = comp ? 2 : 1, ++n;
-                    else if (!comp) slot[n] = P, cf[n] = k, ++n, slot[n] = Q, cf[n] = 2 | MINUS, ++n;
-                    else slot[n] = Q, cf[n] = 2 * k, ++n, slot[n] = P, cf[n] = 1, ++n;
+                    if (!wrap) t.set(n++, comp ? Q : P, comp ? 2 : 1);
+                    else if (!comp) t.set(n++, P, k), t.set(n++, Q, 2 | MINUS);
+                    else t.set(n++, Q, 2 * k), t.set(n++, P, 1);
                 } else { // 2 a_i a_j = 2 (t0 - t1) + 2 (t2 - t0 - t1) u; times xi: ((2k+2) t0 - (2k-2) t1 - 2 t2) + (2k t2 - (2k-2) t0 - (2k+2) t1) u
                     const u32 t0 = 12 + 3 * p, t1 = t0 + 1, t2 = t0 + 2;
-                    if (!wrap && !comp) slot[n] = t0, cf[n] = 2, ++n, slot[n] = t1, cf[n] = 2 | MINUS, ++n;
-                    else if (!wrap) slot[n] = t2, cf[n] = 2, ++n, slot[n] = t0, cf[n] = 2 | MINUS, ++n, slot[n] = t1, cf[n] = 2 | MINUS, ++n;
+                    if (!wrap && !comp) t.set(n++, t0, 2), t.set(n++, t1, 2 | MINUS);
+                    else if (!wrap) t.set(n++, t2, 2), t.set(n++, t0, 2 | MINUS), t.set(n++, t1, 2 | MINUS);
                     else if (!comp) {
-                        slot[n] = t0, cf[n] = 2 * k + 2, ++n, slot[n] = t2, cf[n] = 2 | MINUS, ++n;
-                        if (k > 1) slot[n] = t1, cf[n] = (2 * k - 2) | MINUS, ++n;
+                        t.set(n++, t0, 2 * k + 2), t.set(n++, t2, 2 | MINUS);
+                        if (k > 1) t.set(n++, t1, (2 * k - 2) | MINUS);
                     } else {
-                        slot[n] = t2, cf[n] = 2 * k, ++n, slot[n] = t1, cf[n] = (2 * k + 2) | MINUS, ++n;
-                        if (k > 1) slot[n] = t0, cf[n] = (2 * k - 2) | MINUS, ++n;
+                        t.set(n++, t2, 2 * k), t.set(n++, t1, (2 * k + 2) | MINUS);
+                        if (k > 1) t.set(n++, t0, (2 * k - 2) | MINUS);
                     }
                 }
             }
-        SqTab t{{0, 0}, {0, 0, 0}};
-        for (int e = 0; e < SQ_OPS; ++e) t.idx[e / 5] |= slot[e] << (6 * (e % 5)), t.cf[e / 4] |= cf[e] << (8 * (e % 4));
-        return t;
-    }
-    static MG_DEV SqTab sq_tab() { // this lane's entry (once per kernel)
-        SqTab v{{0, 0}, {0, 0, 0}};
-#pragma unroll
-        for (int l = 0; l < 12; ++l) {
-            const SqTab t = sq_entry(l);
-            const bool me = lane_id() == l;
-            v.idx[0] = me ? t.idx[0] : v.idx[0], v.idx[1] = me ? t.idx[1] : v.idx[1];
-            v.cf[0] = me ? t.cf[0] : v.cf[0], v.cf[1] = me ? t.cf[1] : v.cf[1], v.cf[2] = me ? t.cf[2] : v.cf[2];
-        }
-        return v;
+        return t; // (operands n .. 9: coefficient zero)
     }
     static __device__ __noinline__ void sqr12(int d, int a, const SqTab tab) {
         const int l = lane_id();
-        u32 *q = base() + PROD * W; // Fq slot t = q + t N (72 of them)
+        u32 *const b = base();
         if (l < 57) {
             const bool sq = l < 12;
             const int p = sq ? 0 : (l - 12) / 3;
             const int k = sq ? (l & 1) : (l - 12) - 3 * p;
             const int i = sq ? (l >> 1) : (int)((SQ_PAIR_I >> (4 * p)) & 15u), j = sq ? i : (int)((SQ_PAIR_J >> (4 * p)) & 15u);
             const F2 ai = ld(a + slot_of(i)), aj = ld(a + slot_of(j));
-            const F si = F::add(ai.c0, ai.c1), sj = F::add(aj.c0, aj.c1), di = F::sub(ai.c0, ai.c1);
             // squares: k = 0 (x + y)(x - y), k = 1 x y; pairs: k = 0 x_i x_j, k = 1 y_i y_j, k = 2 (x_i + y_i)(x_j + y_j)
-            const F x = sq ? F::select(k == 0, si, ai.c0) : F::select(k == 0, ai.c0, F::select(k == 1, ai.c1, si));
-            const F y = sq ? F::select(k == 0, di, ai.c1) : F::select(k == 0, aj.c0, F::select(k == 1, aj.c1, sj));
-            F::mul(x, y).store(q + l * N);
+            // (both operands by selects, no branch: with `sq ? .. : kara(k, aj)` the loads of a_j move behind a branch of their own)
+            const F x = kara(sq ? 2 - 2 * k : k, ai);
+            const F y = F::select(sq, F::select(k == 0, F::sub(ai.c0, ai.c1), ai.c1), kara(k, aj));
+            F::mul(x, y).store(prod_fq(b, l));
         }
         sync();
-        if (l < 12) {
-            F w[SQ_OPS];
-            u32 cp[SQ_OPS], cn[SQ_OPS];
-#pragma unroll
-            for (int e = 0; e < SQ_OPS; ++e) {
-                const u32 cf = (tab.cf[e / 4] >> (8 * (e % 4))) & 255u;
-                cp[e] = (cf & 0x80u) ? 0u : cf, cn[e] = (cf & 0x80u) ? (cf & 0x7fu) : 0u;
-                w[e] = F::load(q + ((tab.idx[e / 5] >> (6 * (e % 5))) & 63u) * N);
-            }
-            lincomb<SQ_OPS>(w, cp, cn).store(base() + (d + slot_of(l >> 1)) * W + (l & 1) * N);
-        }
-        sync();
+        combine(tab, b, d);
     }
-    struct CycTab {
-        u32 idx, clo, chi; // stage B of this lane: six product slots, 5 bits each; seven coefficients (six products and a), a byte each: magnitude | 0x80 minus
-    };
+    // d = a^2 for a in the cyclotomic subgroup (Granger-Scott; registers, d may be a). Twenty-four lanes, one Fq product
+    // each: (x + y)(x - y) and 2 x y of every coefficient, the four Fq products of 2 a_i a_{i+3} for i < 3. Then every
+    // component of the result is 3 T +- 2 a: one `lincomb` of at most six products and this component of a itself, the
+    // table's extra operand.
+    typedef LaneTab<6, 5, 1> CycTab;
     static constexpr CycTab cyc_entry(int l) {
         const int m = l >> 1, c = l & 1;
-        u32 w[6] = {0, 0, 0, 0, 0, 0}, k[7] = {0, 0, 0, 0, 0, 0, 0};
-        constexpr u32 MINUS = 0x80u, T3 = 3u, XI3 = 3u * (u32)K::U0; // result = 3 T +- 2 a, T = X + U0 Y +- Z
+        CycTab t;
+        constexpr u32 T3 = 3u, XI3 = 3u * (u32)K::U0;
         if (!(m & 1)) { // a_m' = 3 (a_i^2 + xi a_j^2) - 2 a_m, i = m / 2, j = i + 3: P_i + U0 P_j - Q_j | Q_i + U0 Q_j + P_j
             const int i = m >> 1, j = i + 3;
-            w[0] = 2 * i + c, k[0] = T3;
-            w[2] = 2 * j + c, k[2] = XI3;
-            w[4] = 2 * j + (c ^ 1), k[4] = T3 | (c ? 0u : MINUS);
-            k[6] = 2u | MINUS;
+            t.set(0, 2 * i + c, T3);
+            t.set(2, 2 * j + c, XI3);
+            t.set(4, 2 * j + (c ^ 1), T3 | (c ? 0u : MINUS));
+            t.set_cf(6, 2u | MINUS);
         } else { // a_3' = 3 (2 a0 a3) + 2 a_3, a_5' = 3 (2 a1 a4) + 2 a_5, a_1' = 3 xi (2 a2 a5) + 2 a_1
             const int base = 12 + 4 * (m == 3 ? 0 : (m == 5 ? 1 : 2));
             const int o = m == 1 ? 2 : 0; // a_1' takes xi t5: U0 times this component of the product, +- the other one
-            w[o] = base + 2 * c, k[o] = m == 1 ? XI3 : T3;
-            w[o + 1] = base + 2 * c + 1, k[o + 1] = (m == 1 ? XI3 : T3) | (c ? 0u : MINUS); // c0 = U0' - U1', c1 = U2' + U3'
+            t.set(o, base + 2 * c, m == 1 ? XI3 : T3);
+            t.set(o + 1, base + 2 * c + 1, (m == 1 ? XI3 : T3) | (c ? 0u : MINUS)); // c0 = U0' - U1', c1 = U2' + U3'
             if (m == 1) {
-                w[4] = base + 2 * (c ^ 1), k[4] = T3 | (c ? 0u : MINUS);
-                w[5] = base + 2 * (c ^ 1) + 1, k[5] = T3 | MINUS; // c0: -(U2' + U3'); c1: + (U0' - U1')
+                t.set(4, base + 2 * (c ^ 1), T3 | (c ? 0u : MINUS));
+                t.set(5, base + 2 * (c ^ 1) + 1, T3 | MINUS); // c0: -(U2' + U3'); c1: + (U0' - U1')
             }
-            k[6] = 2u;
+            t.set_cf(6, 2u);
         }
-        return CycTab{w[0] | w[1] << 5 | w[2] << 10 | w[3] << 15 | w[4] << 20 | w[5] << 25, k[0] | k[1] << 8 | k[2] << 16 | k[3] << 24,
-                      k[4] | k[5] << 8 | k[6] << 16};
-    }
-    static MG_DEV CycTab cyc_tab() { // this lane's entry (once per kernel)
-        CycTab v{0u, 0u, 0u};
-#pragma unroll
-        for (int l = 0; l < 12; ++l) {
-            const CycTab t = cyc_entry(l);
-            const bool me = lane_id() == l;
-            v.idx = me ? t.idx : v.idx, v.clo = me ? t.clo : v.clo, v.chi = me ? t.chi : v.chi;
-        }
-        return v;
+        return t;
     }
     static __device__ __noinline__ void cyc_sqr12(int d, int a, const CycTab tab) {
         const int l = lane_id();
-        u32 *q = base() + PROD * W;
+        u32 *const b = base();
         if (l < 24) {
             const bool isq = l < 12;
             const int i = isq ? (l >> 1) : ((l - 12) >> 2), kk = isq ? (l & 1) : ((l - 12) & 3);
             const F2 ai = ld(a + slot_of(i)), aj = ld(a + slot_of(isq ? i : i + 3));
             const F s1 = F::select(isq || !(kk & 1), ai.c0, ai.c1), s2 = F::select(isq, F::select(kk != 0, ai.c0, ai.c1), s1);
             const F vs = F::select(isq, ai.c1, F::select(kk == 0 || kk == 3, aj.c0, aj.c1));
-            F::mul(F::add(s1, s2), F::select(isq && kk == 0, F::sub(ai.c0, ai.c1), vs)).store(q + l * N);
+            F::mul(F::add(s1, s2), F::select(isq && kk == 0, F::sub(ai.c0, ai.c1), vs)).store(prod_fq(b, l));
         }
         sync();
-        if (l < 12) {
-            F w[7];
-            u32 cp[7], cn[7];
-#pragma unroll
-            for (int k = 0; k < 7; ++k) {
-                const u32 cf = ((k < 4 ? tab.clo : tab.chi) >> (8 * (k & 3))) & 255u;
-                cp[k] = (cf & 0x80u) ? 0u : cf, cn[k] = (cf & 0x80u) ? (cf & 0x7fu) : 0u;
-                w[k] = k < 6 ? F::load(q + ((tab.idx >> (5 * k)) & 31u) * N) : F::load(base() + (a + slot_of(l >> 1)) * W + (l & 1) * N);
-            }
-            lincomb<7>(w, cp, cn).store(base() + (d + slot_of(l >> 1)) * W + (l & 1) * N);
-        }
-        sync();
+        combine(tab, b, d, comp_of(b, a, l));
     }
     // f *= line(P), arkworks `ell`: D-type twist (BN254) c0 py + (c1 px) w + c2 w^3 (mul_by_034), M-type (BLS12-381)
     // c0 + (c1 px) w^2 + (c2 py) w^3 (mul_by_014). Round 4: ONE Fq PRODUCT PER LANE. The line arrives as a ring entry made by
@@ -361,13 +380,10 @@ template <class K> struct PairingWave {
     // coefficient product, then a fold).
     static constexpr int LINE_J(int t) { return K::TWIST_D ? (t == 2 ? 3 : t) : (t == 0 ? 0 : t + 1); } // L_t sits at w^LINE_J(t)
     static constexpr int RINGW = 3 * W; // ring entry: L_0, L_1, L_2
-    struct EllTab {
-        u32 idx[2], cf[3]; // this lane's second stage: nine product slots (6 bits each) and coefficients (a byte each: magnitude | 0x80 minus)
-    };
+    typedef LaneTab<9, 6> EllTab;
     static constexpr EllTab ell_entry(int l) {
         const int m = l >> 1, comp = l & 1, k = K::U0;
-        constexpr u32 MINUS = 0x80u;
-        EllTab r{{0, 0}, {0, 0, 0}};
+        EllTab r;
         for (int t = 0; t < 3; ++t) {
             int i = m - LINE_J(t);
             const bool wrap = i < 0;
@@ -375,48 +391,20 @@ template <class K> struct PairingWave {
             const u32 t0 = 3 * (3 * i + t), c0 = !wrap ? (comp ? 1 | MINUS : 1) : (comp ? (k - 1) | MINUS : k + 1),
                       c1 = !wrap ? 1 | MINUS : (comp ? (k + 1) | MINUS : (k - 1) | MINUS), c2 = !wrap ? (comp ? 1 : 0) : (comp ? k : 1 | MINUS);
             const u32 sl[3] = {t0, t0 + 1, t0 + 2}, cf[3] = {c0, c1, c2}; // v = (t0 - t1) + (t2 - t0 - t1) u; xi v = ((k+1) t0 - (k-1) t1 - t2) + (k t2 - (k-1) t0 - (k+1) t1) u
-            for (int e = 0; e < 3; ++e) {
-                const int o = 3 * t + e;
-                r.idx[o / 5] |= sl[e] << (6 * (o % 5)), r.cf[o / 4] |= ((cf[e] & 0x7fu) ? cf[e] : 0u) << (8 * (o % 4));
-            }
+            for (int e = 0; e < 3; ++e) r.set(3 * t + e, sl[e], (cf[e] & 0x7fu) ? cf[e] : 0u); // (no "minus zero")
         }
         return r;
     }
-    static MG_DEV EllTab ell_tab() { // this lane's entry (once per kernel)
-        EllTab v{{0, 0}, {0, 0, 0}};
-#pragma unroll
-        for (int l = 0; l < 12; ++l) {
-            const EllTab t = ell_entry(l);
-            const bool me = lane_id() == l;
-            v.idx[0] = me ? t.idx[0] : v.idx[0], v.idx[1] = me ? t.idx[1] : v.idx[1];
-            v.cf[0] = me ? t.cf[0] : v.cf[0], v.cf[1] = me ? t.cf[1] : v.cf[1], v.cf[2] = me ? t.cf[2] : v.cf[2];
-        }
-        return v;
-    }
     static __device__ __noinline__ void ell(int f, int o, const EllTab tab) {
         const int l = lane_id();
+        u32 *const b = base();
         const u32 *e = ring_slot(o);
-        u32 *q = base() + PROD * W; // Fq slot s = q + s N (72 of them)
         if (l < 54) {
             const int pr = l / 3, k = l - 3 * pr, i = pr / 3, t = pr - 3 * i;
-            const F2 fi = ld(f + slot_of(i)), lt = F2::load(e + t * W);
-            const F x = F::select(k == 0, fi.c0, F::select(k == 1, fi.c1, F::add(fi.c0, fi.c1)));
-            const F y = F::select(k == 0, lt.c0, F::select(k == 1, lt.c1, F::add(lt.c0, lt.c1)));
-            F::mul(x, y).store(q + l * N);
+            F::mul(kara(k, ld(f + slot_of(i))), kara(k, F2::load(e + t * W))).store(prod_fq(b, l));
         }
         sync();
-        if (l < 12) {
-            F w[9];
-            u32 cp[9], cn[9];
-#pragma unroll
-            for (int c = 0; c < 9; ++c) {
-                const u32 cf = (tab.cf[c / 4] >> (8 * (c % 4))) & 255u;
-                cp[c] = (cf & 0x80u) ? 0u : cf, cn[c] = (cf & 0x80u) ? (cf & 0x7fu) : 0u;
-                w[c] = F::load(q + ((tab.idx[c / 5] >> (6 * (c % 5))) & 63u) * N);
-            }
-            lincomb<9>(w, cp, cn).store(base() + (f + slot_of(l >> 1)) * W + (l & 1) * N);
-        }
-        sync();
+        combine(tab, b, f);
     }
     static MG_DEV void set_one(int d) {
         if (lane_id() < 6) st(d + lane_id(), lane_id() == 0 ? F2::one() : F2::zero());
@@ -518,7 +506,7 @@ template <class K> struct PairingWave {
     // d = 1 / a (registers; t1, t2 scratch; d, t1, t2 distinct from a): 1/a = conj(a) / (a conj(a)), and a conj(a) lies in
     // Fq6 (its odd coefficients cancel exactly), whose inverse is ark-ff's Fp6 formula with the Fq2 products of each level
     // on different lanes; the one Fq inversion at the bottom stays on lane 0. (The first version ran the whole tower
-    // inversion on lane 0 through pairing_dev.h's out-of-line helpers: 0.38 ms of a 4.6 ms verification.)
+    // inversion on lane 0 through out-of-line single-lane helpers: 0.38 ms of a 4.6 ms verification.)
     static __device__ __noinline__ void inv12(int d, int a, int t1, int t2) {
         copy12(t1, a);
         conj12(t1);
@@ -608,11 +596,11 @@ template <class K> struct PairingWave {
         if constexpr (K::X_NEG) conj12(d);
     }
     static constexpr int FINAL_EXP_REGS = 22; // 0 .. 18: the sequence below; 19 .. 21: pow_x's odd powers
-    // register 0 := final_exponentiation(register 0); registers 1..21 are scratch. The sequence is pairing_dev.h's
-    // final_exp (ark-ec 0.3 models/{bn,bls12}/mod.rs); squarings of the hard part in the cyclotomic subgroup (cyc_sqr12).
+    // register 0 := final_exponentiation(register 0); registers 1..21 are scratch. The sequence is ark-ec 0.3's
+    // final_exponentiation (models/{bn,bls12}/mod.rs); squarings of the hard part in the cyclotomic subgroup (cyc_sqr12).
     static __device__ void final_exp() {
         const int f = R(0), f1 = R(1), f2 = R(2), r = R(3);
-        const CycTab ct = cyc_tab();
+        const CycTab ct = lane_tab<cyc_entry>();
         copy12(f1, f);
         conj12(f1);
         inv12(f2, f, R(4), R(5));
@@ -682,9 +670,16 @@ template <class K> struct PairingWave {
     }
     // ---- the ring through which wave 1 of the Miller kernel hands lines to wave 0. An entry is what `ell` multiplies with
     // (RINGW words: the coefficients scaled by px / py); wave 1 makes it either from G2Prepared::from(Q) as that
-    // runs (prepare<true>, below) or from a stored coefficient table (scale_stored)
-    static constexpr int PREP_WORDS_ = 45 * W; // = PREP_SLOTS * W (the enum is declared further down)
-    static constexpr int RING_OFF = MILLER_WORDS + PREP_WORDS_, CNT_OFF = RING_OFF + RING * RINGW;
+    // runs (prepare<true>, below) or from a stored coefficient table (scale_stored). It lies behind wave 1's Fq2 slots,
+    // those of `prepare`:
+    enum { SX = 0, SY, SZ, XY, BB, CC, JJ, YZ, NE, FV, MM, GG, HH, CB3, CB9, ZERO, QX, QY, TH, LA, AC, AD, AE, AF, AG, AG2, AH, GH,
+           CR0, CR1, CR2, // line coefficients before their scaling by px / py
+           PXY,           // (px, py)
+           PZ,            // (pz, 0): the factor of the coefficient that px / py do not touch (1 for an affine P)
+           QP,            // QP .. QP + 11 hold the (up to twenty-four) Fq products of a level
+           PREP_SLOTS = QP + 12 };
+    static constexpr size_t prep_lds_bytes() { return (size_t)PREP_SLOTS * W * 4; }
+    static constexpr int RING_OFF = MILLER_WORDS + PREP_SLOTS * W, CNT_OFF = RING_OFF + RING * RINGW;
     static constexpr size_t miller_lds_bytes() { return (size_t)(CNT_OFF + 2) * 4; }
     static MG_DEV volatile u32 *counters() { return (volatile u32 *)(mg_pairing_lds + CNT_OFF); } // [0] produced, [1] consumed
     static MG_DEV u32 *ring_slot(int o) { return mg_pairing_lds + RING_OFF + (o % RING) * RINGW; }
@@ -708,8 +703,8 @@ template <class K> struct PairingWave {
     }
     // register f := Miller loop of ONE pair; the NCOEFF lines come through the ring in the order of G2Prepared's table
     static __device__ void miller(int f) {
-        const SqTab st = sq_tab();
-        const EllTab et = ell_tab();
+        const SqTab st = lane_tab<sq_entry>();
+        const EllTab et = lane_tab<ell_entry>();
         set_one(f);
         int o = 0;
         auto line = [&]() {
@@ -763,13 +758,6 @@ template <class K> struct PairingWave {
     //   addition: qy z, qx z | theta, lambda | theta^2, lambda^2, theta qx, lambda qy | c, d, j = theta qx - lambda qy, -theta |
     //             e = lambda d, f = z c, g = x d | e, f, g, 2g | h = e + f - 2g, g - h = g + 2g - e - f |
     //             lambda h, theta (g - h), e y, z e | x3, y3, z3        (-Q: the signs of the qy terms flip, no other change)
-    enum { SX = 0, SY, SZ, XY, BB, CC, JJ, YZ, NE, FV, MM, GG, HH, CB3, CB9, ZERO, QX, QY, TH, LA, AC, AD, AE, AF, AG, AG2, AH, GH,
-           CR0, CR1, CR2, // line coefficients before their scaling by px / py
-           PXY,           // (px, py)
-           PZ,            // (pz, 0): the factor of the coefficient that px / py do not touch (1 for an affine P)
-           QP,            // QP .. QP + 11 hold the (up to twenty-four) Fq products of a level
-           PREP_SLOTS = QP + 12 };
-    static constexpr size_t prep_lds_bytes() { return (size_t)PREP_SLOTS * W * 4; }
     static constexpr int LANES = 24; // lanes that take part in a stage, at most
     struct Lin {
         u32 ops, dst;
@@ -915,28 +903,6 @@ template <class K> struct PairingWave {
         return t;
     }
     static_assert(T_ADD_LA == T_PY, "lambda is the coefficient scaled by py");
-    // this lane's entry of a table (worked out once per kernel: a chain of selects over compile-time values)
-    template <class Tab> static MG_DEV u32 lane_prod(const Tab t) {
-        u32 v = NONE;
-#pragma unroll
-        for (int l = 0; l < LANES; ++l) v = (l < t.n && lane_id() == l) ? t.e[l] : v;
-        return v;
-    }
-    static MG_DEV Lin lane_lin(const LinTab t) {
-        Lin v{0u, NONE};
-#pragma unroll
-        for (int l = 0; l < LANES; ++l) {
-            const bool me = l < t.n && lane_id() == l;
-            v.ops = me ? t.e[l].ops : v.ops, v.dst = me ? t.e[l].dst : v.dst;
-        }
-        return v;
-    }
-    static MG_DEV u32 lane_flip(const LinTab t) {
-        u32 v = 0;
-#pragma unroll
-        for (int l = 0; l < LANES; ++l) v = (l < t.n && lane_id() == l) ? t.flip[l] : v;
-        return v;
-    }
     static MG_DEV F ldq(u32 q) { return F::load(base() + q * N); }
     // u + v or u - v (canonical in and out): p - v stands in for -v (p itself when v = 0; u + p comes back to u)
     static MG_DEV F addsub(const F &u, const F &v, bool neg) {
@@ -974,14 +940,16 @@ template <class K> struct PairingWave {
     // The NCOEFF line-coefficient triples of Q (affine, not infinity) in the order the Miller loop consumes them: as arkworks'
     // table in global memory (RG = false: g2_prepare_kernel), or as ring entries for wave 0's Miller loop with P = (px, py)
     template <bool RG> static __device__ void prepare(const F2 &qx, const F2 &qy, u32 *out, const F &px, const F &py, const F &pz) {
-        static_assert(PREP_SLOTS * W == PREP_WORDS_, "layout");
         static_assert(fq(PREP_SLOTS, 0) <= 128, "seven bits per operand");
-        const u32 ds1 = lane_prod(d_s1()), ds2 = lane_prod(d_s2()), ds3 = lane_prod(d_s3<RG>());
-        const Lin dr1 = lane_lin(d_r1()), dr2 = lane_lin(d_r2<RG>()), dr3 = lane_lin(d_r3<RG>());
-        const u32 as1 = lane_prod(a_s1()), as2 = lane_prod(a_s2()), as3 = lane_prod(a_s3<RG>()), as4 = lane_prod(a_s4());
-        const Lin ar1 = lane_lin(a_r1<RG>()), ar2 = lane_lin(a_r2<RG>()), ar3a = lane_lin(a_r3a<RG>()), ar3b = lane_lin(a_r3b()),
-                  ar4 = lane_lin(a_r4());
-        const u32 f1 = lane_flip(a_r1<RG>()), f2 = lane_flip(a_r2<RG>());
+        // this lane's part of every stage
+        const auto prod = [](const ProdTab t) { return lane_select(t.e, t.n, NONE); };
+        const auto lin = [](const LinTab t) { return lane_select(t.e, t.n, Lin{0u, NONE}); };
+        const auto flip = [](const LinTab t) { return lane_select(t.flip, t.n, 0u); };
+        const u32 ds1 = prod(d_s1()), ds2 = prod(d_s2()), ds3 = prod(d_s3<RG>());
+        const Lin dr1 = lin(d_r1()), dr2 = lin(d_r2<RG>()), dr3 = lin(d_r3<RG>());
+        const u32 as1 = prod(a_s1()), as2 = prod(a_s2()), as3 = prod(a_s3<RG>()), as4 = prod(a_s4());
+        const Lin ar1 = lin(a_r1<RG>()), ar2 = lin(a_r2<RG>()), ar3a = lin(a_r3a<RG>()), ar3b = lin(a_r3b()), ar4 = lin(a_r4());
+        const u32 f1 = flip(a_r1<RG>()), f2 = flip(a_r2<RG>());
         if (lane_id() == 0) {
             const F2 b3 = triple(P::f2const(K::B2));
             st(SX, qx), st(SY, qy), st(SZ, F2::one()), st(QX, qx), st(QY, qy), st(ZERO, F2::zero()), st(CB3, b3), st(CB9, triple(b3));

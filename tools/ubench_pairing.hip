@@ -17,9 +17,9 @@ template <int MODE> __global__ __launch_bounds__(64) void bench(u32 *buf, int it
     }
     if (threadIdx.x < 3) P::F2::load(buf + threadIdx.x * P::F2W).store(PW::ring_slot(0) + threadIdx.x * P::F2W); // a line for `ell`
     PW::sync();
-    const auto st = PW::sq_tab();
-    const auto et = PW::ell_tab();
-    const auto ct = PW::cyc_tab();
+    const auto st = PW::lane_tab<PW::sq_entry>();
+    const auto et = PW::lane_tab<PW::ell_entry>();
+    const auto ct = PW::lane_tab<PW::cyc_entry>();
     const typename P::F px = P::F::load(buf), py = P::F::load(buf + P::N);
     const typename P::F2 qx = P::F2::load(buf), qy = P::F2::load(buf + P::F2W);
     typename P::F2 qacc = qy;
@@ -51,16 +51,24 @@ int main() {
     hipEvent_t e0, e1;
     hipEventCreate(&e0), hipEventCreate(&e1);
     const char *names[14] = {"mul12", "ell (line product)", "frob12<1>", "inv12 (lane 0)", "sqr12", "cyc_sqr12", "G2Prepared::from (all steps)", "conj12", "Fq2 product (registers)", "xi * Fq2", "Fq2 add", "Fq product", "LDS store + sync + load", "Fq inverse (binary Euclid, lane 0)"};
+    constexpr int LAUNCHES = 16;
     auto run = [&](int mode, auto kern, int iters) {
         hipLaunchKernelGGL(kern, dim3(1), dim3(64), PW::miller_lds_bytes(), 0, buf, 1);
         hipDeviceSynchronize();
-        hipEventRecord(e0);
-        hipLaunchKernelGGL(kern, dim3(1), dim3(64), PW::miller_lds_bytes(), 0, buf, iters);
-        hipEventRecord(e1);
-        hipEventSynchronize(e1);
-        float ms;
-        hipEventElapsedTime(&ms, e0, e1);
-        printf("%-28s %9.2f us each (%d iterations)\n", names[mode], ms * 1e3 / iters, iters);
+        // the mean of LAUNCHES launches: where the dispatcher puts a lone wavefront rotates with the launch count, and its speed
+        // follows by several per cent (min and max are printed) -- one launch per operation compared positions, not code
+        float sum = 0, lo = 1e30f, hi = 0;
+        for (int r = 0; r < LAUNCHES; ++r) {
+            hipEventRecord(e0);
+            hipLaunchKernelGGL(kern, dim3(1), dim3(64), PW::miller_lds_bytes(), 0, buf, iters);
+            hipEventRecord(e1);
+            hipEventSynchronize(e1);
+            float ms;
+            hipEventElapsedTime(&ms, e0, e1);
+            sum += ms, lo = ms < lo ? ms : lo, hi = ms > hi ? ms : hi;
+        }
+        printf("%-28s %9.2f us each (%d iterations x %d launches, %.2f .. %.2f)\n", names[mode], sum / LAUNCHES * 1e3 / iters, iters, LAUNCHES,
+               lo * 1e3 / iters, hi * 1e3 / iters);
     };
     run(0, bench<0>, 2000); run(1, bench<1>, 2000); run(2, bench<2>, 2000); run(3, bench<3>, 20);
     run(4, bench<4>, 2000); run(5, bench<5>, 2000); run(6, bench<6>, 20); run(7, bench<7>, 2000);
