@@ -7,11 +7,18 @@
 // accumulate kernel. Per pass:
 //   radix_hist     per 4096-element tile, digit counts in LDS (ds_add) -> hist[digit][tile]
 //   radix_scan_*   exclusive scan over hist (digit-major): one workgroup per digit row, then the 256 row totals
-//   radix_scatter  every wavefront ranks its 1024 elements 64 at a time with ballots: the lanes holding
-//                  the same digit are found by intersecting eight v_cmp/ballot masks (wave64 "match"),
-//                  their rank is a popcount of the lanes before them plus the wave's running count for the
-//                  digit; no atomics, stable by construction. The tile is then laid out digit-sorted in LDS so
-//                  that consecutive lanes store to consecutive addresses within each digit run.
+//   radix_scatter  every wavefront ranks its 1024 elements 64 at a time through a table of 256 lane masks of
+//                  its own in LDS: the lanes OR their bit into the mask of their digit (ds_or_b64, nothing
+//                  returned) and read it back; an element's rank is the count of the mask's bits below its
+//                  lane (v_mbcnt) plus the wave's running count for the digit, and the first lane of a mask
+//                  adds the mask's popcount to that count and clears the mask for the next 64. Lanes in lane
+//                  order, steps in program order: stable by construction. The masks (4 x 256 x 8 B) lie in
+//                  the first 8 KB of the tile buffer, which is not written before the barrier behind the
+//                  offset scan, so they add nothing to the kernel's LDS. With -DMG_SCATTER_MASKS=0 the lanes
+//                  holding the same digit are found by intersecting eight v_cmp/ballot masks instead
+//                  (wave64 "match", ~80 VALU an element against ~10; profiles/radix_scatter_masks_ab.txt).
+//                  The tile is then laid out digit-sorted in LDS so that consecutive lanes store to
+//                  consecutive addresses within each digit run.
 // 20 B of HBM traffic per element per pass. The only sort on the product path: keys wider than 32 bits' worth of
 // 8-bit passes do not occur (msm_launch caps the bucket-key space at 2^24), and no library sort is linked.
 #include "engine.h"
@@ -97,9 +104,17 @@ __global__ __launch_bounds__(256) void radix_scan_totals(u32 *__restrict__ total
     totals[threadIdx.x] = part[threadIdx.x] - mine;
 }
 
+// MG_SCATTER_MASKS (default 1): the ranking inside a wave-step goes through the per-wave LDS lane masks; 0: the eight-ballot
+// "match" (an A/B twin through tools/build_variant.sh; both are measured in profiles/radix_scatter_masks_ab.txt).
+#ifndef MG_SCATTER_MASKS
+#define MG_SCATTER_MASKS 1
+#endif
+
 // Register budget: at most 64 VGPRs (54 now), so that a workgroup finds room on a SIMD beside two resident BLS12-381 accumulate
 // wavefronts. A lane keeps its 16 keys and, two to a register, their 16 ranks across the ranking; the 16
 // values are requested behind it and arrive during the offset scan.
+// IDENT: lowmask == ~0, the sort key is the key itself (a single MSM) and a digit is one bit-field extract of it.
+template <bool IDENT>
 __global__ __launch_bounds__(256) void radix_scatter(const u32 *__restrict__ keys_in, const u32 *__restrict__ vals_in,
                                                      u32 *__restrict__ keys_out, u32 *__restrict__ vals_out, u32 M,
                                                      int shift, u32 ntiles, const u32 *__restrict__ hist,
@@ -110,27 +125,73 @@ __global__ __launch_bounds__(256) void radix_scatter(const u32 *__restrict__ key
     if ((size_t)blockIdx.x * SORT_TILE >= M) return; // a tile past the last element
     __shared__ u32 wcount[4][256]; // per-wave running digit counts, then per-wave tile-local offsets
     __shared__ u32 gbase[256];     // global position of the tile's first element of each digit, minus its local offset
-    __shared__ u32 sk[SORT_TILE], sv[SORT_TILE]; // the tile, locally sorted by digit (stable)
+    // the tile, locally sorted by digit (stable): 4096 keys, then 4096 values. Up to the barrier behind the offset scan its first
+    // 8 KB are the lane masks of the ranking, [wave][digit]: bit l is set while lane l of the wave-step in hand holds that digit
+    typedef unsigned long long __attribute__((may_alias)) lane_mask;
+    __shared__ __attribute__((aligned(8))) u32 tile[2 * SORT_TILE];
+    u32 *const sk = tile, *const sv = tile + SORT_TILE;
+    lane_mask *const masks = (lane_mask *)tile;
     constexpr int HALF = SORT_ITEMS / 2;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const auto digit = [&](u32 key) { return ((IDENT ? key : sort_key(key, lowmask, inv_from)) >> shift) & 255u; };
 #pragma unroll
-    for (int w = 0; w < 4; ++w) wcount[w][threadIdx.x] = 0;
+    for (int w = 0; w < 4; ++w) {
+        wcount[w][threadIdx.x] = 0;
+        if (MG_SCATTER_MASKS) masks[w * 256 + threadIdx.x] = 0;
+    }
     __syncthreads();
     const u32 tile0 = blockIdx.x * (u32)SORT_TILE; // below M < 2^32
     const u32 base = tile0 + (u32)wave * (SORT_ITEMS * 64) + (u32)lane;
     const u32 left = M - tile0 > (u32)SORT_TILE ? (u32)SORT_TILE : M - tile0; // elements of this tile
     const u32 mine = (u32)wave * (SORT_ITEMS * 64) + (u32)lane;              // tile-local index of this lane's item 0
     u32 k[SORT_ITEMS], rk2[HALF]; // rk2[j / 2]: the ranks (< 1024) of items j (low half) and j + 1
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
 #pragma unroll
     for (int j = 0; j < SORT_ITEMS; ++j) {
         const bool valid = mine + (u32)j * 64 < left;
         k[j] = valid ? keys_in[(size_t)base + (size_t)j * 64] : 0u;
     }
+#if MG_SCATTER_MASKS
+    // The rank of an item inside its wave-step is the number of lower lanes that hold its digit. Every valid lane ORs its bit into
+    // the digit's mask, reads the mask back and counts the bits below its own; the first of the peers adds all of them to the
+    // wave's count and clears the mask for the next step. Lanes past the count set no bit and clear nothing (they are the highest
+    // lanes of the step, so a mask's first lane is never one of them). The LDS executes one wavefront's operations in program
+    // order, so OR -> read -> clear needs no barrier; the wavefront-scope fences only keep the compiler from moving or merging them.
+    lane_mask *const wmask = masks + wave * 256;
+    const unsigned long long lane_bit = 1ull << lane;
+    unsigned long long none = 0;
+    asm volatile("" : "+v"(none)); // the cleared mask in a register pair: as a constant it is materialised again for every item
 #pragma unroll
     for (int j = 0; j < SORT_ITEMS; ++j) {
         const bool valid = mine + (u32)j * 64 < left;
-        const u32 d = (sort_key(k[j], lowmask, inv_from) >> shift) & 255u;
+        const u32 d = digit(k[j]);
+        if (valid) __hip_atomic_fetch_or(&wmask[d], lane_bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const unsigned long long peers = __hip_atomic_load(&wmask[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        const u32 before = wcount[wave][d]; // every peer reads the count, then the first peer bumps it
+        const u32 lo = (u32)peers, hi = (u32)(peers >> 32);
+        const u32 rank = __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, before)); // + the peers in the lanes below
+        const bool first = valid && rank == before;
+        if (j & 1)
+            rk2[j >> 1] |= rank << 16;
+        else
+            rk2[j >> 1] = rank;
+        asm volatile("" : "+v"(rk2[j >> 1])); // packed here and now: left to itself the compiler carries the ranks unpacked to the placement
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (first) {
+            wcount[wave][d] = (u32)__builtin_popcount(hi) + ((u32)__builtin_popcount(lo) + before);
+            __hip_atomic_store(&wmask[d], none, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+#else
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int j = 0; j < SORT_ITEMS; ++j) {
+        const bool valid = mine + (u32)j * 64 < left;
+        const u32 d = digit(k[j]);
         unsigned long long peers = __ballot(valid);
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
@@ -147,6 +208,7 @@ __global__ __launch_bounds__(256) void radix_scatter(const u32 *__restrict__ key
         asm volatile("" : "+v"(rk2[j >> 1])); // packed here and now: left to itself the compiler carries `before` and `r` to the placement
         if (valid && r == 0) wcount[wave][d] = before + (u32)__popcll(peers);
     }
+#endif
     // (the digits are worked out again behind the scan, from keys the compiler cannot see through: it would otherwise keep all 16
     // digit addresses of the ranking alive beside the keys)
 #pragma unroll
@@ -175,12 +237,12 @@ __global__ __launch_bounds__(256) void radix_scatter(const u32 *__restrict__ key
         wcount[3][d] = loc + c0 + c1 + c2;
         gbase[d] = hist[(size_t)d * ntiles + blockIdx.x] + totals[d] - loc;
     }
-    __syncthreads();
+    __syncthreads(); // every wavefront is past its ranking: the lane masks are dead and the tile may be written
 #pragma unroll
     for (int j = 0; j < SORT_ITEMS; ++j) {
         if (mine + (u32)j * 64 < left) {
             const u32 rank = (j & 1) ? rk2[j >> 1] >> 16 : rk2[j >> 1] & 0xffffu;
-            const u32 lp = wcount[wave][(sort_key(k[j], lowmask, inv_from) >> shift) & 255u] + rank;
+            const u32 lp = wcount[wave][digit(k[j])] + rank;
             sk[lp] = k[j];
             sv[lp] = v[j];
         }
@@ -188,7 +250,7 @@ __global__ __launch_bounds__(256) void radix_scatter(const u32 *__restrict__ key
     __syncthreads();
     for (u32 t = threadIdx.x; t < left; t += 256) { // consecutive lanes -> consecutive addresses within a digit run
         const u32 kk = sk[t];
-        const u32 pos = gbase[(sort_key(kk, lowmask, inv_from) >> shift) & 255u] + t;
+        const u32 pos = gbase[digit(kk)] + t;
         keys_out[pos] = kk;
         vals_out[pos] = sv[t];
     }
@@ -218,7 +280,8 @@ int sort_pairs(const u32 *keys_in, u32 *keys_out, const u32 *vals_in, u32 *vals_
         hipLaunchKernelGGL(radix_hist, dim3(ntiles), dim3(256), 0, s, ik, M, 8 * p, ntiles, hist, d_count, lowmask, inv_from);
         hipLaunchKernelGGL(radix_scan_rows, dim3(256), dim3(256), 0, s, hist, ntiles, totals);
         hipLaunchKernelGGL(radix_scan_totals, dim3(1), dim3(256), 0, s, totals);
-        hipLaunchKernelGGL(radix_scatter, dim3(ntiles), dim3(256), 0, s, ik, iv, ok, ov, M, 8 * p, ntiles, hist, totals, d_count, lowmask, inv_from);
+        hipLaunchKernelGGL(lowmask == 0xffffffffu ? radix_scatter<true> : radix_scatter<false>, dim3(ntiles), dim3(256), 0, s, ik, iv, ok, ov, M,
+                           8 * p, ntiles, hist, totals, d_count, lowmask, inv_from);
         ik = ok;
         iv = ov;
     }
