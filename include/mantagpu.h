@@ -195,9 +195,10 @@ int mg_field_op(int field, int op, int repr, int lazy_a, int lazy_b, const uint6
  *   op 0: a b R'^-1   1: a^2 R'^-1   2: (a b + c d) R'^-1   (almost-Montgomery, R' = 2^(K LB): the exact integer
  *         (t + (t (-p^-1) mod R') p) / R' of t = a b [+ c d], K - 1 masked limbs and the unmasked top limb)
  *      3: a + 6 p - b - 2 c   4: a + 12 p - b - 2 c   (limbs normalised; need b + 2 c < 6 p, 12 p)
- *   coding 0: the plain routines (mul, sqr, mul_add, sub2); 1: what the accumulate kernel calls (mul_t / sqr_t / mul_add_t<true>,
- *   sub2n). Coding 1 is the single-chain coding of the products for every field (asm links for the 29-bit fields, pinned C
- *   for BLS12-381 Fq; -DMG_CHAIN_FLUSHED=0 builds the latter's three as the plain routines again: an A/B twin).
+ *   coding 0: the plain routines (mul, sqr, mul_add -- for BLS12-381 Fq one column walker for all three -- and sub2); 1: what the
+ *   accumulate kernel calls (mul_t / sqr_t / mul_add_t<true>, sub2n). Coding 1 is the single-chain coding of the products for
+ *   every field (asm links for the 29-bit fields; the same walker with its multiply-adds pinned in C for BLS12-381 Fq, where
+ *   -DMG_CHAIN_FLUSHED=0 builds the three as the plain routines again: an A/B twin).
  * Operands an op does not take are ignored (may be NULL). n <= 2^24. */
 #define MG_FPR_MUL 0
 #define MG_FPR_SQR 1
@@ -210,7 +211,7 @@ int mg_fpr_raw_op(int field, int op, int coding, const uint32_t *a, const uint32
  * plan of the kernels, readable without a GPU. kind = MG_FPR_MUL / MG_FPR_SQR / MG_FPR_MUL_ADD. flush[k], k < 2 K - 1:
  * bit 0 / 1 / 2 = flush before the a b / c d / m p products of column k; peak[k] = the planner's worst-case accumulator value
  * of the column. *cols = 2 K - 1 (flush and peak hold at least 25 entries), *limb_bits = LB, *flushed_routines = 1 when the
- * field's products run the group-by-group routines that consult the plan at all. Any output may be NULL. */
+ * field's plans hold a flush at all (its products then walk their columns by the plan). Any output may be NULL. */
 int mg_fpr_column_plan(int field, int kind, uint32_t *flush, uint64_t *peak, int *cols, int *limb_bits, int *flushed_routines);
 /* The first two stages of the MSM pipeline, each alone over host arrays: parity-test surfaces for the kernels that
  * mg_msm_launch runs (the same digit kernel, the same radix sort), not needed by the shim. Synchronous; one device

@@ -475,7 +475,8 @@ def fpr_raw_op(field, op, a, b=None, c=None, d=None, chain=False) -> np.ndarray:
     """One reduced-radix routine of the MSM kernels over RAW limb vectors (`mg_fpr_raw_op`): a, b, c, d = [n, K] uint32
     limbs, no conversion on the way in or out. op = "mul" | "sqr" | "mul_add" | "sub2_6" | "sub2_12" (a + 6p / 12p - b - 2c).
     chain selects what the accumulate kernel calls: mul_t / sqr_t / mul_add_t<true> and sub2n. For every field those are the
-    single-chain codings of the products (BLS12-381 Fq: the plain routines again with -DMG_CHAIN_FLUSHED=0)."""
+    single-chain codings of the products: asm links for the 29-bit fields, the plain routines' column walker with pinned
+    multiply-adds for BLS12-381 Fq (the plain routines themselves with -DMG_CHAIN_FLUSHED=0)."""
     K = FPR_LIMBS[field][0]
     arrs = [None if x is None else np.ascontiguousarray(x, dtype=np.uint32) for x in (a, b, c, d)]
     need = {"sqr": 1, "mul": 2, "sub2_6": 3, "sub2_12": 3, "mul_add": 4}[op]

@@ -16,6 +16,17 @@
 
 namespace mg {
 
+// the ABI's field ids -> f(an object of the field's configuration struct)
+template <class F> static int with_field(int field, F f) {
+    switch (field) {
+    case 0: return f(Bn254FrCfg{});
+    case 1: return f(Bn254FqCfg{});
+    case 2: return f(Bls381FrCfg{});
+    case 3: return f(Bls381FqCfg{});
+    }
+    return MG_ERR_ARG;
+}
+
 enum { FOP_ADD = 0, FOP_SUB = 1, FOP_MUL = 2, FOP_SQR = 3, FOP_NEG = 4, FOP_FROM_CANONICAL = 5, FOP_TO_CANONICAL = 6, FOP_INV = 7 };
 
 template <class C> __device__ FpR<C> lazy_rep(const Fp<C> &s, int k) { // from_std(s) + k p, limbs renormalised
@@ -101,19 +112,15 @@ int field_op(int field, int op, int repr, int lazy_a, int lazy_b, const u32 *a, 
     const bool binary = op == FOP_ADD || op == FOP_SUB || op == FOP_MUL;
     if (binary && !b) return MG_ERR_ARG;
     if (!binary) b = nullptr;
-    switch (field) {
-    case 0: return run<Bn254FrCfg>(op, repr, lazy_a, lazy_b, a, b, n, out);
-    case 1: return run<Bn254FqCfg>(op, repr, lazy_a, lazy_b, a, b, n, out);
-    case 2: return run<Bls381FrCfg>(op, repr, lazy_a, lazy_b, a, b, n, out);
-    case 3: return run<Bls381FqCfg>(op, repr, lazy_a, lazy_b, a, b, n, out);
-    }
-    return MG_ERR_ARG;
+    return with_field(field, [&](auto cfg) { return run<decltype(cfg)>(op, repr, lazy_a, lazy_b, a, b, n, out); });
 }
 
 // ---- the reduced-radix routines on RAW limb vectors (`mg_fpr_raw_op`): operands and result are K words of LB-bit limbs as the
 // MSM kernels hold them, with no from_std / to_std around the operation -- mg_field_op above only ever feeds canonical values
 // plus k p, which never puts a large value into every limb, the case the column accumulators of the products are sized for.
-// coding 0 = FpR::mul / sqr / mul_add / sub2, 1 = the accumulate kernel's mul_t<true> / sqr_t<true> / mul_add_t<true> / sub2n.
+// coding 0 = FpR::mul / sqr / mul_add (the column walker FpR::product for BLS12-381 Fq, the interleaved bodies for the 29-bit fields)
+// / sub2, 1 = the accumulate kernel's mul_t<true> / sqr_t<true> / mul_add_t<true> (the walker as a single chain for BLS12-381 Fq,
+// the asm chains for the 29-bit fields) / sub2n.
 enum { ROP_MUL = 0, ROP_SQR = 1, ROP_MUL_ADD = 2, ROP_SUB2_6 = 3, ROP_SUB2_12 = 4 };
 
 template <class C>
@@ -158,20 +165,14 @@ int fpr_raw_op(int field, int op, int coding, const u32 *a, const u32 *b, const 
     for (int k = 1; k < operands; ++k)
         if (!given[k]) return MG_ERR_ARG;
     const u32 *const in[4] = {a, operands > 1 ? b : nullptr, operands > 2 ? c : nullptr, operands > 3 ? d : nullptr};
-    switch (field) {
-    case 0: return run_raw<Bn254FrCfg>(op, coding, in, n, out);
-    case 1: return run_raw<Bn254FqCfg>(op, coding, in, n, out);
-    case 2: return run_raw<Bls381FrCfg>(op, coding, in, n, out);
-    case 3: return run_raw<Bls381FqCfg>(op, coding, in, n, out);
-    }
-    return MG_ERR_ARG;
+    return with_field(field, [&](auto cfg) { return run_raw<decltype(cfg)>(op, coding, in, n, out); });
 }
 
-// the column plan of a field's flushed products (fpr_dev.h), host side: flush[k] = FPR_FLUSH_* bits of column k, peak[k] = the
+// the column plan of a field's products (fpr_dev.h), host side: flush[k] = FPR_FLUSH_* bits of column k, peak[k] = the
 // planner's worst-case accumulator value of the column; returns the number of columns (2 K - 1) through *cols
 template <class C> static int plan_out(int kind, u32 *flush, u64 *peak, int *cols, int *limb_bits, int *flushed_routines) {
     typedef FpR<C> R;
-    // the tables the product routines index (flush_before), not a second run of the planner
+    // the tables the column walker indexes (flush_before), not a second run of the planner
     const typename R::Plan &pl = kind == FPR_KIND_MUL ? R::PLAN_MUL : (kind == FPR_KIND_SQR ? R::PLAN_SQR : R::PLAN_MUL_ADD);
     for (int k = 0; k < R::COLS; ++k) {
         if (flush) flush[k] = pl.flush[k];
@@ -179,18 +180,12 @@ template <class C> static int plan_out(int kind, u32 *flush, u64 *peak, int *col
     }
     if (cols) *cols = R::COLS;
     if (limb_bits) *limb_bits = R::LB;
-    if (flushed_routines) *flushed_routines = 2 * R::K > R::CAP;
+    if (flushed_routines) *flushed_routines = R::FLUSHES;
     return pl.fits ? MG_OK : MG_ERR_ARG;
 }
 int fpr_column_plan_host(int field, int kind, u32 *flush, u64 *peak, int *cols, int *limb_bits, int *flushed_routines) {
     if (kind < FPR_KIND_MUL || kind > FPR_KIND_MUL_ADD) return MG_ERR_ARG;
-    switch (field) {
-    case 0: return plan_out<Bn254FrCfg>(kind, flush, peak, cols, limb_bits, flushed_routines);
-    case 1: return plan_out<Bn254FqCfg>(kind, flush, peak, cols, limb_bits, flushed_routines);
-    case 2: return plan_out<Bls381FrCfg>(kind, flush, peak, cols, limb_bits, flushed_routines);
-    case 3: return plan_out<Bls381FqCfg>(kind, flush, peak, cols, limb_bits, flushed_routines);
-    }
-    return MG_ERR_ARG;
+    return with_field(field, [&](auto cfg) { return plan_out<decltype(cfg)>(kind, flush, peak, cols, limb_bits, flushed_routines); });
 }
 
 } // namespace mg

@@ -1,34 +1,37 @@
 // Reduced-radix ("carry-free") prime-field arithmetic for gfx950 -- the internal representation of
-// the G1 MSM kernels.
+// the MSM, tail, table, QAP and group-NTT kernels.
 //
 // Why: CDNA4 has no multiply-with-carry-in. With saturated 32-bit limbs every 32x32 product costs one
 // v_mad_u64_u32 (4.2 cycles/wave) PLUS one v_addc_co_u32 (4.3 cycles, serialised through VCC) -- half of
 // Fp::mul's cycles are carries (measured: tools/ubench3.hip, profiles/r01_ubench3_reduced_radix_mul.txt).
-// With K limbs of LB < 32 bits a whole column of 2K products fits a 64-bit accumulator, so a product is
+// With K limbs of LB < 32 bits a column of products fits a 64-bit accumulator, so a product is
 // exactly one v_mad_u64_u32 and a column costs one shift + mask: 1.55x faster at the accumulate kernel's
 // occupancy, although it needs (K/N)^2 ~ 1.3x more multiplies.
 //
-//   BLS12-381 Fq: K = 14 limbs x 28 bits (R' = 2^392);  BN254 Fq: K = 9 x 29 bits (R' = 2^261).
+//   BN254 Fq, BN254 Fr, BLS12-381 Fr: K = 9 limbs x 29 bits (R' = 2^261);  BLS12-381 Fq: K = 13 x 30 bits (R' = 2^390).
+//
+// A column of 29-bit limbs never comes near 2^64. With 30-bit limbs sixteen products do, so the column plan below says where
+// such a column moves its accumulator's upper part aside ("flush"). ONE routine, FpR::product, walks the columns of a*b, a^2
+// and a*b + c*d by that plan, group by group; it is the product of the field that flushes, in both of its C codings. A plan
+// without flushes would make it the plain product of the 29-bit fields as well, but there the interleaved bodies (mul, sqr,
+// mul_add below) are kept: grouped, the BN254 kernels cost the dense single proof 1.5 % (profiles/fpr_product_walker.txt).
 //
 // Values are kept LAZILY reduced: limbs are always normalised (< 2^LB), the integer value may be any
 // representative below a small multiple of p (bounds are tracked per call site in ec_dev.h). Because
-// R' >= 2^7 p, an "almost Montgomery" product of inputs a < Ba*p, b < Bb*p is < 2p whenever
-// Ba*Bb <= 128 (BN254) / 2048 (BLS12-381), with no final subtraction. Subtractions add a multiple M*p
+// R' >= 2^6 p, an "almost Montgomery" product of inputs a < Ba*p, b < Bb*p is < 2p whenever
+// Ba*Bb <= RR_LIM = floor(R'/p) (70 .. 630 over the four fields), with no final subtraction. Subtractions add a multiple M*p
 // chosen from the subtrahend's bound. Exact tests (is_zero_mod) compare against the multiples of p.
 //
 // Memory format: K u32 words per element. Conversion to/from the arkworks format (32-bit limbs,
 // R = 2^(32N)) happens once, when bases are registered and when the few result points are staged.
 //
-// (Since round 4 BLS12-381 Fq is K = 13 x 30 bits, R' = 2^390: its columns can pass 2^64 and are flushed by the column plan below.)
-//
 // Compile-time switches of this header, all for A/B builds (tools/build_variant.sh); the defaults are the measured choices:
-//   MG_FLUSH_BY_COUNT  flush the 30-bit field's columns by the product count (`2 n > CAP`) instead of the exact column plan
-//   MG_CHAIN_FLUSHED   (default 1) single-chain coding of mul_t / sqr_t / mul_add_t<true> for the 30-bit field too: the flushed
-//                      routines with every multiply-add pinned in C (mad_link), no asm; 0 = the compiler's two chains per column.
+//   MG_CHAIN_FLUSHED   (default 1) single-chain coding of mul_t / sqr_t / mul_add_t<true> for the 30-bit field too: the column
+//                      walker with every multiply-add pinned in C (mad_link), no asm; 0 = the compiler's two chains per column.
 //                      Measurements in profiles/fpr_chain_padding_ab.txt
 //   MG_SUB2_64         the mixed addition's sub2n of the 30-bit field with 64-bit carries (= sub2) instead of signed 32-bit limbs
 //   MG_PACK_AFFINE     memory format of affine base coordinates (0 / 1 / 2, see load_aff)
-//   MG_FP2_CALLS, MG_FP2_KARATSUBA, MG_FP2_NO_MULB, MG_FP2_NO_SQRB   the Fp2 product forms of earlier rounds
+// (Retired switches and what they measured: profiles/history/code_comment_measurements.md.)
 #pragma once
 #include "fp_dev.h"
 
@@ -77,7 +80,7 @@ MG_DEV void mad_chain_triple2(u64 &acc, u32 a0, u32 b0, u32 c0, u32 d0, u32 m0, 
         : "vcc");
 }
 
-// ---- compile-time column plan of the flushed products (fields whose limbs are wide enough that a column of a product can pass
+// ---- compile-time column plan of the products (it holds a flush only for limbs wide enough that a column of a product can pass
 // 2^64: LB = 30). A column k adds its products group by group -- a*b, then c*d (the fused product), then m*p -- into one 64-bit
 // accumulator; before a group that could carry the accumulator to 2^64 the accumulator's upper part is moved aside ("flush").
 // The planner walks the columns in the order the code adds them and keeps the EXACT worst case of every partial sum:
@@ -138,17 +141,17 @@ template <class C> struct FpR {
     static constexpr bool EXT = false;
     static constexpr bool LAZY = true;
     static constexpr u32 MASK = (1u << LB) - 1;
-    // Products of two LB-bit limbs a 64-bit column accumulator holds next to a carry-in (< 2^36). 28- and 29-bit limbs never
-    // come near it (a fused column has 3 K <= 42 of them); with 30-bit limbs -- round 4: BLS12-381 Fq as 13 x 30 bits, 2 K^2 + K =
-    // 351 multiply-adds per product instead of the 406 of 14 x 28 -- sixteen 60-bit products overflow, so a column that holds more
-    // is FLUSHED between its product groups: the accumulator's upper part is moved aside (one 64-bit shift, one mask) and joined
-    // again when the column is done. Measured per product at the accumulate kernel's occupancy, with the count rule's eleven flushed
-    // columns (tools/ubench_limbs.hip, profiles/r04_ubench_limbs.txt): 1960 against 2183 cycles (-10 %).
-    static constexpr int CAP = LB >= 30 ? 15 : (LB == 29 ? 60 : 250);
-    static constexpr int nprod(int k) { return k < K ? k + 1 : 2 * K - 1 - k; } // limb products a_i b_(k-i) of column k
-    // CAP only SELECTS the flushed routines. Where they flush is the exact plan (fpr_column_plan above), not a count of products:
-    // for 13 x 30 bits a plain product or squaring flushes in columns 10..14 only (5 flushes where the count rule had 11), the
-    // fused product 18 times (26). Operands are NORMALISED limbs (< 2^LB): lazy limbs exist only where nothing flushes (below).
+    // A 64-bit column accumulator holds a carry-in (< 2^36) and the column's products of two LB-bit limbs. 29-bit limbs never
+    // come near its end (a fused column has 3 K = 27 products); with 30-bit limbs -- BLS12-381 Fq as 13 x 30 bits, 2 K^2 + K =
+    // 351 multiply-adds per product instead of the 406 of 14 x 28 -- sixteen 60-bit products overflow, so such a column is
+    // FLUSHED between its product groups: the accumulator's upper part is moved aside (one 64-bit shift, one mask) and joined
+    // again when the column is done (tools/ubench_limbs.hip, profiles/r04_ubench_limbs.txt: 1960 against 2183 cycles, -10 %).
+    // Where a product flushes is the exact plan (fpr_column_plan above) and nothing else: for 13 x 30 bits a plain product or
+    // squaring flushes in columns 10..14 only, the fused product 18 times; the 29-bit fields' plans hold no flush at all.
+    // The plans are for NORMALISED limbs (< 2^LB). Wider ("lazy") limbs reach a product in one place today, and only where nothing
+    // flushes: the register DIT butterfly of the Fr NTT (fr_impl.h ntt_butterfly) multiplies a subl<3> / limb-wise sum (limbs
+    // < 2^31) by a normalised twiddle, a plain product of a 9 x 29 field: K 2^31 2^LB + K 2^(2 LB) = 9 2^60 + 9 2^58 < 2^64 in any
+    // order of the groups. (LAZY_LIMBS below, the switch of the group law's carry-free subtractions, is false for all four fields.)
     static constexpr int COLS = 2 * K - 1;
     typedef FprColumnPlan<COLS> Plan;
     static constexpr Plan PLAN_MUL = fpr_column_plan<C>(FPR_KIND_MUL, MASK);
@@ -158,9 +161,10 @@ template <class C> struct FpR {
     static_assert(PLAN_MUL.fits && PLAN_SQR.fits && PLAN_MUL_ADD.fits, "a product group alone overflows the column accumulator");
     static_assert(PLAN_MUL.spill_peak < ((u64)1 << 40) && PLAN_SQR.spill_peak < ((u64)1 << 40) && PLAN_MUL_ADD.spill_peak < ((u64)1 << 40),
                   "spill word overflow");
-    // the unflushed codings (28- and 29-bit limbs) interleave the groups: they need a plan WITHOUT flushes
-    static_assert(2 * K > CAP || (PLAN_MUL.flushes == 0 && PLAN_SQR.flushes == 0 && PLAN_MUL_ADD.flushes == 0), "column overflow");
-    static_assert((2 * K > CAP) == (3 * K > CAP), "mul and mul_add must select the flushed routines together");
+    // "this field's products flush": the one rule that sends mul / sqr / mul_add and their single-chain codings (mul_t below) to
+    // the column walker, and what mg_fpr_column_plan reports. A field that does not flush keeps the interleaved bodies.
+    static constexpr bool FLUSHES = PLAN_MUL.flushes != 0;
+    static_assert((PLAN_SQR.flushes != 0) == FLUSHES && (PLAN_MUL_ADD.flushes != 0) == FLUSHES, "the three plans of a field must flush together");
     // bound bookkeeping consumed by ec_dev.h's Bv<> wrapper (values are "< B*p")
     static constexpr int BM = 2;            // a product is < 2p ...
     static constexpr int LIM = C::RR_LIM;   // ... whenever the operand bounds multiply to <= LIM
@@ -290,15 +294,19 @@ template <class C> struct FpR {
     //   q_0 = m_0 + 2^LB,  q_i = m_i + 2^LB - 1 (0 < i < K-1),  q_{K-1} = m_{K-1} - 1      (same value: each limb lends one
     // unit of 2^LB to the limb below), so that q_i - b_i >= 0 for every NORMALISED b (limbs < 2^LB, and b < (M-1)*p keeps
     // the top limb non-negative: m_{K-1}(M) - 1 >= m_{K-1}(M-1) + p_top - 2 >= b_top). The result's limbs are < 3 * 2^LB
-    // ("lazy limbs"); it is a legal multiplication operand wherever the column accumulators have the room (LAZY_LIMBS
-    // below), which saves the 3-instructions-per-limb carry pass of `sub`.
+    // ("lazy limbs"); it is a legal multiplication operand wherever the column accumulators have the room, which saves the
+    // 3-instructions-per-limb carry pass of `sub`. Two users with two bounds: the NTT butterfly (ONE lazy operand of a plain
+    // product, see the plans above) and the mixed addition of ec_dev.h, which wants lazy operands on both sides of a fused
+    // product and asks LAZY_LIMBS first.
     static constexpr u32 multb(int M, int i) {
         return i == 0 ? C::RR_MULT[M][0] + (1u << LB) : (i < K - 1 ? C::RR_MULT[M][i] + MASK : C::RR_MULT[M][K - 1] - 1u);
     }
     // worst column of a fused product with lazy operands: K * (3*3 + 3*1 + 1) * 2^(2 LB) must stay below 2^64
+    // (true for 14 x 28, FALSE for 9 x 29 -- 117 * 2^58 -- and 13 x 30: no shipped field takes the group law's lazy path, and the
+    // static_assert below binds only a future layout that does)
     static constexpr bool LAZY_LIMBS = (double)K * 13.0 * (double)(1ull << LB) * (double)(1ull << LB) < 18446744073709551616.0;
     // checked, not only stated: with limbs < 3 * 2^LB the plan of a fused product must exist and hold no flush
-    static_assert(!LAZY_LIMBS || (2 * K <= CAP && fpr_column_plan<C>(FPR_KIND_MUL_ADD, 3 * ((u64)1 << LB)).fits &&
+    static_assert(!LAZY_LIMBS || (fpr_column_plan<C>(FPR_KIND_MUL_ADD, 3 * ((u64)1 << LB)).fits &&
                                   fpr_column_plan<C>(FPR_KIND_MUL_ADD, 3 * ((u64)1 << LB)).flushes == 0),
                   "lazy limbs need columns that never flush");
     template <int M> static MG_DEV FpR subl(const FpR &a, const FpR &b) { // a may itself have lazy limbs only if a is normalised: see call sites
@@ -325,7 +333,7 @@ template <class C> struct FpR {
     // column accumulators and the m*p pass -- 3 K^2 + K multiply-adds instead of 4 K^2 + 2 K. Value < 2p whenever
     // Ba*Bb + Bc*Bd <= LIM; limbs of the operands may be lazy when LAZY_LIMBS (column bound above).
     static MG_DEV FpR mul_add(const FpR &a, const FpR &b, const FpR &c, const FpR &d) {
-        if constexpr (3 * K > CAP) return mul_add_flushed(a, b, c, d);
+        if constexpr (FLUSHES) return product<FPR_KIND_MUL_ADD, false>(a, b, c, d);
         u64 acc = 0;
         u32 m[K];
         FpR t;
@@ -357,8 +365,10 @@ template <class C> struct FpR {
         t.v[K - 1] = (u32)acc;
         return t;
     }
-    // ---- the three product routines for limbs wide enough that a column overflows (CAP): the products of a column are added group
-    // by group -- a*b, then c*d, then m*p -- and the accumulator is flushed before a group that would not fit (see CAP)
+    // ---- the column walker, the one body of all three products of a field that flushes (its plain and its single-chain coding):
+    // the products of a column are added group by group -- a*b, then c*d, then m*p -- and the accumulator is flushed before a
+    // group exactly where the plan says it would not fit. It is written for any plan; with none of the flushes it is the grouped
+    // twin of the interleaved bodies, which the raw-limb tests could compare it with the day the 29-bit fields take it.
     // (the first group of a column never needs one: carry-in + n * limb^2 < 2^64 for every plan that exists, asserted here)
     static constexpr bool plan_flushes_first_group(const Plan &p) {
         for (int k = 0; k < COLS; ++k)
@@ -367,14 +377,8 @@ template <class C> struct FpR {
     }
     static_assert(!plan_flushes_first_group(PLAN_MUL) && !plan_flushes_first_group(PLAN_SQR) && !plan_flushes_first_group(PLAN_MUL_ADD),
                   "flush before the first group of a column");
-    // MG_FLUSH_BY_COUNT restores the rule of rounds 4-6 (A/B builds): flush when the column holds more than CAP / 2 products, and
-    // before the m*p group of the fused product when more than CAP / 3
     static constexpr bool flush_before(int kind, int k, int group) {
-#ifdef MG_FLUSH_BY_COUNT
-        return 2 * nprod(k) > CAP || (kind == FPR_KIND_MUL_ADD && group == FPR_FLUSH_MP && 3 * nprod(k) > CAP);
-#else
         return ((kind == FPR_KIND_MUL ? PLAN_MUL : (kind == FPR_KIND_SQR ? PLAN_SQR : PLAN_MUL_ADD)).flush[k] & group) != 0;
-#endif
     }
     static MG_DEV void flush(u64 &acc, u64 &spill) {
         spill += acc >> LB;
@@ -395,78 +399,36 @@ template <class C> struct FpR {
         acc += prod;
         if constexpr (CH) acc = __builtin_annotation(acc, "chain");
     }
-    template <bool CH = false> static MG_DEV FpR mul_add_flushed(const FpR &a, const FpR &b, const FpR &c, const FpR &d) {
-        u64 acc = 0;
-        u32 m[K];
-        FpR t;
-#pragma unroll
-        for (int k = 0; k < 2 * K - 1; ++k) {
-            const int lo = k < K ? 0 : k - K + 1, hi = k < K ? k : K - 1;
-            u64 spill = 0;
-#pragma unroll
-            for (int i = lo; i <= hi; ++i) mad_link<CH>(acc, a.v[i], b.v[k - i]);
-            if (flush_before(FPR_KIND_MUL_ADD, k, FPR_FLUSH_CD)) flush(acc, spill);
-#pragma unroll
-            for (int i = lo; i <= hi; ++i) mad_link<CH>(acc, c.v[i], d.v[k - i]);
-            if (flush_before(FPR_KIND_MUL_ADD, k, FPR_FLUSH_MP)) flush(acc, spill);
-#pragma unroll
-            for (int i = lo; i <= hi; ++i)
-                if (!(k < K && i == k)) mad_link<CH>(acc, m[i], C::RR_P[k - i]);
-            if (k < K) {
-                m[k] = ((u32)acc * C::RR_INV) & MASK;
-                mad_link<CH>(acc, m[k], C::RR_P[0]);
-            } else {
-                t.v[k - K] = (u32)acc & MASK;
-            }
-            acc >>= LB;
-            acc += spill;
-        }
-        t.v[K - 1] = (u32)acc;
-        return t;
-    }
-    template <bool CH = false> static MG_DEV FpR mul_flushed(const FpR &a, const FpR &b) {
-        u64 acc = 0;
-        u32 m[K];
-        FpR t;
-#pragma unroll
-        for (int k = 0; k < 2 * K - 1; ++k) {
-            const int lo = k < K ? 0 : k - K + 1, hi = k < K ? k : K - 1;
-            u64 spill = 0;
-#pragma unroll
-            for (int i = lo; i <= hi; ++i) mad_link<CH>(acc, a.v[i], b.v[k - i]);
-            if (flush_before(FPR_KIND_MUL, k, FPR_FLUSH_MP)) flush(acc, spill);
-#pragma unroll
-            for (int i = lo; i <= hi; ++i)
-                if (!(k < K && i == k)) mad_link<CH>(acc, m[i], C::RR_P[k - i]);
-            if (k < K) {
-                m[k] = ((u32)acc * C::RR_INV) & MASK;
-                mad_link<CH>(acc, m[k], C::RR_P[0]);
-            } else {
-                t.v[k - K] = (u32)acc & MASK;
-            }
-            acc >>= LB;
-            acc += spill;
-        }
-        t.v[K - 1] = (u32)acc;
-        return t;
-    }
-    template <bool CH = false> static MG_DEV FpR sqr_flushed(const FpR &a) {
+    // KIND = FPR_KIND_MUL: a*b (c, d unused), FPR_KIND_SQR: a^2 (b, c, d unused), FPR_KIND_MUL_ADD: a*b + c*d; all times R'^-1 mod p.
+    // A squaring's a*b group is its cross products a_i a_j (i < j) once, against the doubled operand, and the squares a_i^2.
+    template <int KIND, bool CH> static MG_DEV FpR product(const FpR &a, const FpR &b, const FpR &c, const FpR &d) {
         u64 acc = 0;
         u32 m[K], a2[K];
         FpR t;
+        if constexpr (KIND == FPR_KIND_SQR) {
 #pragma unroll
-        for (int i = 0; i < K; ++i) a2[i] = a.v[i] << 1; // (< 2^31: a doubled cross product counts as two)
+            for (int i = 0; i < K; ++i) a2[i] = a.v[i] << 1; // (< 2^31: a doubled cross product counts as two)
+        }
 #pragma unroll
-        for (int k = 0; k < 2 * K - 1; ++k) {
+        for (int k = 0; k < COLS; ++k) {
             const int lo = k < K ? 0 : k - K + 1, hi = k < K ? k : K - 1;
             u64 spill = 0;
 #pragma unroll
             for (int i = lo; i <= hi; ++i) {
                 const int j = k - i;
-                if (i < j) mad_link<CH>(acc, a2[i], a.v[j]);
-                if (i == j) mad_link<CH>(acc, a.v[i], a.v[i]);
+                if constexpr (KIND == FPR_KIND_SQR) {
+                    if (i < j) mad_link<CH>(acc, a2[i], a.v[j]);
+                    if (i == j) mad_link<CH>(acc, a.v[i], a.v[i]);
+                } else {
+                    mad_link<CH>(acc, a.v[i], b.v[j]);
+                }
             }
-            if (flush_before(FPR_KIND_SQR, k, FPR_FLUSH_MP)) flush(acc, spill);
+            if constexpr (KIND == FPR_KIND_MUL_ADD) {
+                if (flush_before(KIND, k, FPR_FLUSH_CD)) flush(acc, spill);
+#pragma unroll
+                for (int i = lo; i <= hi; ++i) mad_link<CH>(acc, c.v[i], d.v[k - i]);
+            }
+            if (flush_before(KIND, k, FPR_FLUSH_MP)) flush(acc, spill);
 #pragma unroll
             for (int i = lo; i <= hi; ++i)
                 if (!(k < K && i == k)) mad_link<CH>(acc, m[i], C::RR_P[k - i]);
@@ -504,7 +466,7 @@ template <class C> struct FpR {
     template <int A, int B> static MG_DEV FpR mulb(const FpR &a, const FpR &b) { return mul(a, b); }
     // ---- almost-Montgomery product: a*b*R'^-1 mod p, result < 2p (see header for the input bounds)
     static MG_DEV FpR mul(const FpR &a, const FpR &b) {
-        if constexpr (2 * K > CAP) return mul_flushed(a, b);
+        if constexpr (FLUSHES) return product<FPR_KIND_MUL, false>(a, b, a, b);
         u64 acc = 0;
         u32 m[K];
         FpR t;
@@ -533,15 +495,14 @@ template <class C> struct FpR {
         t.v[K - 1] = (u32)acc;
         return t;
     }
-    // single-chain codings of mul / sqr / mul_add. The narrower limbs (no flush) code the chain as asm links (mad_chain_*, several
-    // links per statement). Fields that flush (13 x 30 bits) took the compiler's two-chain coding here through round 6; for them the
-    // single chain is the flushed routine itself with its multiply-adds pinned in C (mad_link<true>): no asm statement, so no
-    // padding. MG_CHAIN_FLUSHED=0 gives them the two-chain coding again (A/B builds).
+    // single-chain codings of mul / sqr / mul_add, for the accumulate kernel (CH = true). The field that flushes (13 x 30 bits)
+    // has the column walker itself with its multiply-adds pinned in C (mad_link<true>): no asm statement, so no padding;
+    // MG_CHAIN_FLUSHED=0 gives it the compiler's two-chain coding again (A/B builds). The 29-bit fields code the chain as asm links
+    // (mad_chain_*, several links per statement): the three bodies below, with the a*b, c*d and m*p terms interleaved.
     static constexpr bool CHAIN_FLUSHED = MG_CHAIN_FLUSHED != 0;
-    static constexpr bool CHAINED = 2 * K <= CAP || CHAIN_FLUSHED; // the _t<true> routines are single-chain codings
     template <bool CH> static MG_DEV FpR mul_t(const FpR &a, const FpR &b) {
-        if constexpr (!CH || !CHAINED) return mul(a, b);
-        if constexpr (2 * K > CAP) return mul_flushed<true>(a, b);
+        if constexpr (!CH) return mul(a, b);
+        if constexpr (FLUSHES) return product<FPR_KIND_MUL, CHAIN_FLUSHED>(a, b, a, b);
         u64 acc = 0;
         u32 m[K];
         FpR t;
@@ -572,8 +533,8 @@ template <class C> struct FpR {
         return t;
     }
     template <bool CH> static MG_DEV FpR sqr_t(const FpR &a) {
-        if constexpr (!CH || !CHAINED) return sqr(a);
-        if constexpr (2 * K > CAP) return sqr_flushed<true>(a);
+        if constexpr (!CH) return sqr(a);
+        if constexpr (FLUSHES) return product<FPR_KIND_SQR, CHAIN_FLUSHED>(a, a, a, a);
         u64 acc = 0;
         u32 m[K], a2[K];
         FpR t;
@@ -604,8 +565,8 @@ template <class C> struct FpR {
         return t;
     }
     template <bool CH> static MG_DEV FpR mul_add_t(const FpR &a, const FpR &b, const FpR &c, const FpR &d) {
-        if constexpr (!CH || !CHAINED) return mul_add(a, b, c, d);
-        if constexpr (3 * K > CAP) return mul_add_flushed<true>(a, b, c, d);
+        if constexpr (!CH) return mul_add(a, b, c, d);
+        if constexpr (FLUSHES) return product<FPR_KIND_MUL_ADD, CHAIN_FLUSHED>(a, b, c, d);
         u64 acc = 0;
         u32 m[K];
         FpR t;
@@ -638,17 +599,9 @@ template <class C> struct FpR {
         t.v[K - 1] = (u32)acc;
         return t;
     }
-    // the same as real functions: for callers whose register budget cannot take the inlined products
-    static __device__ __noinline__ FpR mul_call(const FpR a, const FpR b) { return mul(a, b); }
-    static __device__ __noinline__ FpR sqr_call(const FpR a) { return sqr(a); }
-    // (operands by REFERENCE: with four 14-limb structs passed by value -- 56 VGPRs of arguments -- hipcc of ROCm 7.2 produced a
-    // function that returned wrong products on gfx950: BLS12-381 G2 MSMs failed against the oracle, the by-reference build of the
-    // same source passes; found by bisecting builds on the GPU, round 4)
-    static __device__ __noinline__ FpR mul_add_call(const FpR &a, const FpR &b, const FpR &c, const FpR &d) { return mul_add(a, b, c, d); }
     template <int A> static MG_DEV FpR sqrb(const FpR &a) { return sqr(a); }
-    // square: cross products once, against the doubled operand
     static MG_DEV FpR sqr(const FpR &a) {
-        if constexpr (2 * K > CAP) return sqr_flushed(a);
+        if constexpr (FLUSHES) return product<FPR_KIND_SQR, false>(a, a, a, a);
         u64 acc = 0;
         u32 m[K], a2[K];
         FpR t;
@@ -692,89 +645,44 @@ template <class C> struct FpR {
         return acc;
     }
 
-    // ---- cheap conversions for fields with R'/R = 2^(LB*K - 32N) small (Fr: 2^261 / 2^256 = 2^5): the arkworks Montgomery
-    // form a*R is turned into a*R' by SHIFTING the integer left while repacking its limbs (value < 2^5 p) and one reduce --
-    // no multiplication; and a*R' becomes the canonical integer a by one almost-Montgomery product with the integer 1.
-    static MG_DEV FpR from_std_shift(const Std &s) {
-        constexpr int SH = LB * K - 32 * C::N; // R' = 2^SH * R
-        static_assert(SH >= 0 && SH < 8 && (1 << SH) <= 64 && (1 << SH) <= C::RR_LIM, "shift conversion needs a small R'/R");
-        FpR r;
-#pragma unroll
-        for (int i = 0; i < K; ++i) {
-            const int bit = i * LB - SH; // limb i of (value << SH) = bits [bit, bit + LB) of value
-            u64 x = 0;
-            const int w = bit >= 0 ? (bit >> 5) : -1, o = bit >= 0 ? (bit & 31) : 0;
-            if (bit >= 0) {
-                x = w < C::N ? s.v[w] : 0;
-                if (w + 1 < C::N) x |= (u64)s.v[w + 1] << 32;
-                r.v[i] = (u32)(x >> o) & MASK;
-            } else { // only limb 0: its low SH bits are zero
-                r.v[i] = ((u32)s.v[0] << (-bit)) & MASK;
-            }
-        }
-        return reduce<(1 << SH)>(r);
-    }
-    // value (< 4p, any representative) -> the canonical integer a, as 32-bit words (ark-ff into_repr)
-    MG_DEV Std to_canonical() const {
-        FpR one_plain = zero();
-        one_plain.v[0] = 1;
-        return mul(*this, one_plain).canonical_words();
-    }
-    // a value < 2p with normalised limbs -> fully reduced, repacked into 32-bit words
-    MG_DEV Std canonical_words() const {
-        FpR y = *this;
-        int t[K];
-#pragma unroll
-        for (int i = 0; i < K; ++i) t[i] = (int)y.v[i] - (int)C::RR_P[i];
-        int cy = 0;
-        u32 d[K];
-#pragma unroll
-        for (int i = 0; i < K; ++i) {
-            const int sum = t[i] + cy;
-            cy = sum >> LB;
-            d[i] = (u32)sum & MASK;
-        }
-        const bool ge = cy == 0;
-#pragma unroll
-        for (int i = 0; i < K; ++i) y.v[i] = ge ? d[i] : y.v[i];
+    // ---- the K limbs of LB bits repacked as N words of 32 bits and back, no arithmetic: a NORMALISED value below 2^(32 N)
+    MG_DEV Std to_words() const {
         Std r;
 #pragma unroll
         for (int w = 0; w < C::N; ++w) {
             u64 x = 0;
 #pragma unroll
             for (int i = 0; i < K; ++i) {
-                const int lo = i * LB - w * 32;
-                if (lo > -LB && lo < 32) x |= lo >= 0 ? ((u64)y.v[i] << lo) : ((u64)y.v[i] >> (-lo));
+                const int lo = i * LB - w * 32; // position of limb i relative to word w
+                if (lo > -LB && lo < 32) x |= lo >= 0 ? ((u64)v[i] << lo) : ((u64)v[i] >> (-lo));
             }
             r.v[w] = (u32)x;
         }
         return r;
     }
-    // ---- conversions to / from the arkworks (32-bit limb, R = 2^(32N)) Montgomery form
-    static MG_DEV FpR from_std(const Std &s) {
-        Std c;
-#pragma unroll
-        for (int i = 0; i < C::N; ++i) c.v[i] = C::RR_TO[i];
-        const Std t = Std::mul(s, c); // a*R * R' * R^-1 = a*R' mod p, canonical
+    // limb i = bits [i LB - SH, (i + 1) LB - SH) of the N words: the limbs of (value << SH), which must stay below 2^(LB K)
+    template <int SH = 0> static MG_DEV FpR from_words(const u32 (&t)[C::N]) {
+        static_assert(SH >= 0 && SH < LB, "only limb 0 may start below bit 0");
         FpR r;
 #pragma unroll
         for (int i = 0; i < K; ++i) {
-            const int bit = i * LB, w = bit >> 5, o = bit & 31;
-            u64 x = w < C::N ? t.v[w] : 0;
-            if (w + 1 < C::N) x |= (u64)t.v[w + 1] << 32;
-            r.v[i] = (u32)(x >> o) & MASK;
+            const int bit = i * LB - SH;
+            if (bit < 0) { // limb 0: its low SH bits are zero
+                r.v[i] = (t[0] << (-bit)) & MASK;
+            } else {
+                const int w = bit >> 5, o = bit & 31;
+                u64 x = w < C::N ? t[w] : 0;
+                if (w + 1 < C::N) x |= (u64)t[w + 1] << 32;
+                r.v[i] = (u32)(x >> o) & MASK;
+            }
         }
         return r;
     }
-    MG_DEV Std to_std() const {
-        FpR c;
-#pragma unroll
-        for (int i = 0; i < K; ++i) c.v[i] = C::RR_FROM[i];
-        FpR y = mul(*this, c); // a*R' * R * R'^-1 = a*R mod p, in [0, 2p)
-        // one conditional subtraction of p
+    // a value < 2p with normalised limbs -> fully reduced: one conditional subtraction of p
+    MG_DEV FpR sub_p_if_ge() const {
         int t[K];
 #pragma unroll
-        for (int i = 0; i < K; ++i) t[i] = (int)y.v[i] - (int)C::RR_P[i];
+        for (int i = 0; i < K; ++i) t[i] = (int)v[i] - (int)C::RR_P[i];
         int cy = 0;
         u32 d[K];
 #pragma unroll
@@ -783,21 +691,41 @@ template <class C> struct FpR {
             cy = s >> LB;
             d[i] = (u32)s & MASK;
         }
-        const bool ge = cy == 0; // no final borrow: y >= p
+        const bool ge = cy == 0; // no final borrow: value >= p
+        FpR r;
 #pragma unroll
-        for (int i = 0; i < K; ++i) y.v[i] = ge ? d[i] : y.v[i];
-        Std r;
-#pragma unroll
-        for (int w = 0; w < C::N; ++w) { // gather 32-bit words from the LB-bit limbs
-            u64 x = 0;
-#pragma unroll
-            for (int i = 0; i < K; ++i) {
-                const int lo = i * LB - w * 32; // position of limb i relative to word w
-                if (lo > -LB && lo < 32) x |= lo >= 0 ? ((u64)y.v[i] << lo) : ((u64)y.v[i] >> (-lo));
-            }
-            r.v[w] = (u32)x;
-        }
+        for (int i = 0; i < K; ++i) r.v[i] = ge ? d[i] : v[i];
         return r;
+    }
+    // ---- cheap conversions for fields with R'/R = 2^(LB*K - 32N) small (Fr: 2^261 / 2^256 = 2^5): the arkworks Montgomery
+    // form a*R is turned into a*R' by SHIFTING the integer left while repacking its limbs (value < 2^5 p) and one reduce --
+    // no multiplication; and a*R' becomes the canonical integer a by one almost-Montgomery product with the integer 1.
+    static MG_DEV FpR from_std_shift(const Std &s) {
+        constexpr int SH = LB * K - 32 * C::N; // R' = 2^SH * R
+        static_assert(SH >= 0 && SH < 8 && (1 << SH) <= 64 && (1 << SH) <= C::RR_LIM, "shift conversion needs a small R'/R");
+        return reduce<(1 << SH)>(from_words<SH>(s.v));
+    }
+    // value (< 4p, any representative) -> the canonical integer a, as 32-bit words (ark-ff into_repr)
+    MG_DEV Std to_canonical() const {
+        FpR one_plain = zero();
+        one_plain.v[0] = 1;
+        return mul(*this, one_plain).canonical_words();
+    }
+    // a value < 2p with normalised limbs -> fully reduced, repacked into 32-bit words
+    MG_DEV Std canonical_words() const { return sub_p_if_ge().to_words(); }
+    // ---- conversions to / from the arkworks (32-bit limb, R = 2^(32N)) Montgomery form
+    static MG_DEV FpR from_std(const Std &s) {
+        Std c;
+#pragma unroll
+        for (int i = 0; i < C::N; ++i) c.v[i] = C::RR_TO[i];
+        const Std t = Std::mul(s, c); // a*R * R' * R^-1 = a*R' mod p, canonical
+        return from_words(t.v);
+    }
+    MG_DEV Std to_std() const {
+        FpR c;
+#pragma unroll
+        for (int i = 0; i < K; ++i) c.v[i] = C::RR_FROM[i];
+        return mul(*this, c).canonical_words(); // a*R' * R * R'^-1 = a*R mod p, in [0, 2p)
     }
 
     static MG_DEV FpR load(const u32 *p) {
@@ -813,31 +741,12 @@ template <class C> struct FpR {
     // 32 N-bit form of a NORMALISED value below 2^(32 N) (any lazily reduced value < 2p): the LB-bit limbs repacked into N
     // words, no arithmetic. What an NTT pass leaves in HBM for the next one: 32 B instead of 36 per element, and two adjacent
     // elements are one aligned 64 B sector where the 72 B of the limb form straddle two.
-    MG_DEV void store_packed(u32 *p) const {
-#pragma unroll
-        for (int w = 0; w < C::N; ++w) {
-            u64 x = 0;
-#pragma unroll
-            for (int i = 0; i < K; ++i) {
-                const int lo = i * LB - w * 32; // position of limb i relative to word w
-                if (lo > -LB && lo < 32) x |= lo >= 0 ? ((u64)v[i] << lo) : ((u64)v[i] >> (-lo));
-            }
-            p[w] = (u32)x;
-        }
-    }
+    MG_DEV void store_packed(u32 *p) const { to_words().store(p); }
     static MG_DEV FpR load_packed(const u32 *p) {
         u32 t[C::N];
 #pragma unroll
         for (int w = 0; w < C::N; ++w) t[w] = p[w];
-        FpR r;
-#pragma unroll
-        for (int i = 0; i < K; ++i) {
-            const int bit = i * LB, w = bit >> 5, o = bit & 31;
-            u64 x = w < C::N ? t[w] : 0;
-            if (w + 1 < C::N) x |= (u64)t[w + 1] << 32;
-            r.v[i] = (u32)(x >> o) & MASK;
-        }
-        return r;
+        return from_words(t);
     }
     // ---- memory format of AFFINE base coordinates (the records the accumulate kernels gather). A coordinate is < 2p with
     // normalised limbs, so it fits the 32 N-bit packed form: BN254 G1 = 2 x 32 B = ONE aligned 64 B sector per gathered point
@@ -937,55 +846,27 @@ template <class C> struct Fp2R {
     template <int A> static MG_DEV Fp2R reduce(const Fp2R &a) {
         return Fp2R{B::template reduce<A>(a.c0), B::template reduce<A>(a.c1)};
     }
-    // 14-limb products (BLS12-381 in rounds 1-3) were calls here: four of them inlined per Fp2 product overflowed the
-    // register file in the group operations
-    // (round 4: with 13 limbs the inlined form compiles -- 442 unified registers, one wavefront per SIMD like the calls build -- and
-    // the BLS12-381 G2 accumulate kernel is 1.65x faster without the scratch traffic of the calls: 2^20 G2 MSM 24.0 -> 14.8 ms
-    // uniform, 13.6 -> 8.1 ms witness-like; MG_FP2_CALLS restores the calls)
-#ifdef MG_FP2_CALLS
-    static constexpr bool CALLS = B::K > 9;
-#else
-    static constexpr bool CALLS = B::K > 13;
-#endif
-    static MG_DEV B bmul(const B &x, const B &y) {
-        if constexpr (CALLS) return B::mul_call(x, y);
-        else return B::mul(x, y);
-    }
-    static MG_DEV B bsqr(const B &x) {
-        if constexpr (CALLS) return B::sqr_call(x);
-        else return B::sqr(x);
-    }
+    // (the base products are inlined for every field: profiles/history/code_comment_measurements.md has the calls they once were)
     static MG_DEV Fp2R mul(const Fp2R &a, const Fp2R &b) {
-        const B v0 = bmul(a.c0, b.c0), v1 = bmul(a.c1, b.c1);
-        const B x = bmul(a.c0, b.c1), y = bmul(a.c1, b.c0);
+        const B v0 = B::mul(a.c0, b.c0), v1 = B::mul(a.c1, b.c1);
+        const B x = B::mul(a.c0, b.c1), y = B::mul(a.c1, b.c0);
         return Fp2R{B::template sub<2>(v0, v1), B::add(x, y)};
     }
-    // product of operands with component bounds A, B. Where the headroom allows the operand sums
-    // (4 A B <= R'/p) this is Karatsuba -- 3 base products + one cheap reduction of c1 back below 2p -- else
-    // the 4-product schoolbook form above. Either way the components of the result are < 4p.
-    static MG_DEV B bmul_add(const B &x, const B &y, const B &z, const B &w) {
-        if constexpr (CALLS) return B::mul_add_call(x, y, z, w);
-        else return B::mul_add(x, y, z, w);
-    }
-    // Round 4: c0 = a0 b0 + a1 (M p - b1) and c1 = a0 b1 + a1 b0 as TWO FUSED products (FpR::mul_add: both double-width
-    // products of a component share the column accumulators and ONE Montgomery reduction) -- 6 K^2 + 2 K multiply-adds, the
-    // same as Karatsuba's three products (3 (2 K^2 + K)), but none of Karatsuba's linear work: two operand sums, the sum
-    // v0 + v1, two subtractions and a reduce<6> (about 200 VALU instructions per product at K = 9) become ONE negation.
-    // The G2 accumulate kernel issued 63 % non-multiply instructions (34 % of the multiply-add issue peak against 67 % for
-    // G1: gpurun r4f). Components of the result are < 2p. Needs (A Bb + A Bb) <= LIM.
-#ifndef MG_FP2_KARATSUBA // A/B builds: the round-1..3 Karatsuba / schoolbook forms
+    // product of operands with component bounds A, Bb: c0 = a0 b0 + a1 (M p - b1) and c1 = a0 b1 + a1 b0 as TWO FUSED products
+    // (FpR::mul_add: both double-width products of a component share the column accumulators and ONE Montgomery reduction) --
+    // 6 K^2 + 2 K multiply-adds, the same as Karatsuba's three products (3 (2 K^2 + K)), but none of Karatsuba's linear work:
+    // two operand sums, the sum v0 + v1, two subtractions and a reduce<6> (about 200 VALU instructions per product at K = 9)
+    // become ONE negation. The G2 accumulate kernel issued 63 % non-multiply instructions with Karatsuba (34 % of the
+    // multiply-add issue peak against 67 % for G1). Components of the result are < 2p. Needs (A Bb + A Bb) <= LIM; where the
+    // bounds do not allow it, mulb_karatsuba below.
     template <int A, int Bb> static MG_DEV Fp2R mulb(const Fp2R &a, const Fp2R &b) {
-#ifdef MG_FP2_NO_MULB
-        if constexpr (false) {
-#else
         if constexpr (2L * A * Bb <= LIM && (A <= MAXM || Bb <= MAXM)) {
-#endif
             if constexpr (Bb <= A || A > MAXM) { // negate the component with the smaller bound (the smaller multiple of p)
                 const B nb1 = B::template neg<Bb>(b.c1);
-                return Fp2R{bmul_add(a.c0, b.c0, a.c1, nb1), bmul_add(a.c0, b.c1, a.c1, b.c0)};
+                return Fp2R{B::mul_add(a.c0, b.c0, a.c1, nb1), B::mul_add(a.c0, b.c1, a.c1, b.c0)};
             } else {
                 const B na1 = B::template neg<A>(a.c1);
-                return Fp2R{bmul_add(a.c0, b.c0, na1, b.c1), bmul_add(a.c0, b.c1, a.c1, b.c0)};
+                return Fp2R{B::mul_add(a.c0, b.c0, na1, b.c1), B::mul_add(a.c0, b.c1, a.c1, b.c0)};
             }
         } else {
             return mulb_karatsuba<A, Bb>(a, b);
@@ -994,26 +875,21 @@ template <class C> struct Fp2R {
     // (a0 + a1)(a0 - a1) and 2 a0 a1: two products where the operand sums fit the headroom (4 A^2 <= LIM), else a0^2 - a1^2 as
     // one fused product; either way one reduction per component and a result < 2p
     template <int A> static MG_DEV Fp2R sqrb(const Fp2R &a) {
-#ifdef MG_FP2_NO_SQRB
-        return sqr(a);
-#endif
         if constexpr (4L * A * A <= LIM && A <= MAXM) {
             const B s = B::add(a.c0, a.c1), d = B::template sub<A>(a.c0, a.c1);
-            return Fp2R{bmul(s, d), bmul(B::dbl(a.c0), a.c1)};
+            return Fp2R{B::mul(s, d), B::mul(B::dbl(a.c0), a.c1)};
         } else if constexpr (2L * A * A <= LIM && A <= MAXM) {
-            return Fp2R{bmul_add(a.c0, a.c0, a.c1, B::template neg<A>(a.c1)), bmul(B::dbl(a.c0), a.c1)};
+            return Fp2R{B::mul_add(a.c0, a.c0, a.c1, B::template neg<A>(a.c1)), B::mul(B::dbl(a.c0), a.c1)};
         } else {
             return sqr(a);
         }
     }
-#else
-    template <int A, int Bb> static MG_DEV Fp2R mulb(const Fp2R &a, const Fp2R &b) { return mulb_karatsuba<A, Bb>(a, b); }
-    template <int A> static MG_DEV Fp2R sqrb(const Fp2R &a) { return sqr(a); }
-#endif
+    // Where the headroom allows the operand sums (4 A Bb <= R'/p) Karatsuba -- 3 base products + one cheap reduction of c1 back
+    // below 2p -- else the 4-product schoolbook form above. Either way the components of the result are < 4p.
     template <int A, int Bb> static MG_DEV Fp2R mulb_karatsuba(const Fp2R &a, const Fp2R &b) {
         if constexpr (4L * A * Bb <= LIM && 2 * A <= 16 && 2 * Bb <= 16) {
-            const B v0 = bmul(a.c0, b.c0), v1 = bmul(a.c1, b.c1);
-            const B s = bmul(B::add(a.c0, a.c1), B::add(b.c0, b.c1));
+            const B v0 = B::mul(a.c0, b.c0), v1 = B::mul(a.c1, b.c1);
+            const B s = B::mul(B::add(a.c0, a.c1), B::add(b.c0, b.c1));
             const B c1 = B::template reduce<6>(B::template sub<4>(s, B::add(v0, v1))); // s + 4p - v0 - v1 < 6p
             return Fp2R{B::template sub<2>(v0, v1), c1};
         } else {
@@ -1021,7 +897,7 @@ template <class C> struct Fp2R {
         }
     }
     static MG_DEV Fp2R sqr(const Fp2R &a) {
-        const B v0 = bsqr(a.c0), v1 = bsqr(a.c1), x = bmul(a.c0, a.c1);
+        const B v0 = B::sqr(a.c0), v1 = B::sqr(a.c1), x = B::mul(a.c0, a.c1);
         return Fp2R{B::template sub<2>(v0, v1), B::dbl(x)};
     }
     static __device__ __noinline__ Fp2R inv(const Fp2R &a) { // one-off use only

@@ -25,10 +25,8 @@ template <class Curve> struct GT<Curve, 1> {
     typedef host::HFp<typename Curve::Fq> HF;
 };
 template <class Curve> struct GT<Curve, 2> {
-    // G2 on the lazily-reduced Fp2R as well. Over BLS12-381 (an XYZZ point is 112 words) the 14-limb base
-    // products inside Fp2R are calls (fpr_dev.h `CALLS`): fully inlined, those kernels need 256 VGPRs + 1.4 KB of
-    // scratch per lane and -- observed on MI355X, ROCm 7.2 -- do not terminate. MG_G2_SATURATED keeps the
-    // canonical 32-bit Fp2 path for A/B.
+    // G2 on the lazily-reduced Fp2R as well, its base products inlined (13 limbs over BLS12-381; the calls that 14 limbs needed
+    // are recorded in profiles/history/code_comment_measurements.md). MG_G2_SATURATED keeps the canonical 32-bit Fp2 path for A/B.
 #ifdef MG_G2_SATURATED
     typedef Fp2<typename Curve::Fq> F;
 #else

@@ -5,10 +5,13 @@ for, which canonical values plus k p (mg_field_op) never produce. Expected value
   sub2<6>    a + 6 p - b - 2 c
 compared limb for limb: K - 1 masked limbs and the unmasked top limb.
 
-The "kernel" cases run what the accumulate kernel calls (mul_t / sqr_t / mul_add_t<true>, sub2n). For the 29-bit fields that is the
-single-chain coding of the products. For BLS12-381 Fq the shipped library builds the three products as the plain routines, so
-there the case repeats "plain" and only sub2n differs; the single-chain coding of that field exists behind -DMG_CHAIN_FLUSHED
-only, and this file has to be run again on such a twin of the library (MANTA_LIB) whenever that coding is touched."""
+The "plain" cases run FpR::mul / sqr / mul_add: for BLS12-381 Fq one column walker (FpR::product) for the three products, for the
+29-bit fields the interleaved bodies. The "kernel" cases run what the accumulate kernel calls (mul_t / sqr_t / mul_add_t<true>, sub2n): the single-chain coding of the
+products, which is asm links for the 29-bit fields and the same walker with its multiply-adds pinned in C for BLS12-381 Fq
+(MG_CHAIN_FLUSHED, default 1). A twin of the library built with -DMG_CHAIN_FLUSHED=0 (MANTA_LIB) makes that field's "kernel"
+products the plain routines again; there only sub2n differs between the two cases.
+
+The lazy-limb test feeds the products of the 29-bit fields what a carry-free subtraction (subl) leaves: limbs up to 3 * 2^LB."""
 import numpy as np
 import pytest
 
@@ -88,20 +91,27 @@ def arr(rows, col):
     return np.array([r[col] for r in rows], dtype=np.uint32)
 
 
+def reducer(field):
+    """t -> the limbs of (t + (t (-p^-1) mod R') p) / R'"""
+    K, LB = LIMBS[field]
+    p, Rp = MODULUS[field], 1 << (K * LB)
+    ninv = (-pow(p, -1, Rp)) % Rp
+
+    def redc(t):
+        m = (t * ninv) % Rp
+        assert (t + m * p) % Rp == 0
+        return split((t + m * p) // Rp, K, LB)
+
+    return redc
+
+
 @pytest.fixture(scope="module")
 def expected():
     """per field: the operand rows and the exact results of the three products, computed once for both codings"""
     out = {}
     for field, (K, LB) in LIMBS.items():
-        p, Rp = MODULUS[field], 1 << (K * LB)
-        ninv = (-pow(p, -1, Rp)) % Rp
+        redc = reducer(field)
         rows = operand_rows(field)
-
-        def redc(t):
-            m = (t * ninv) % Rp
-            assert (t + m * p) % Rp == 0
-            return split((t + m * p) // Rp, K, LB)
-
         vals = [tuple(value(x, LB) for x in r) for r in rows]
         out[field] = dict(rows=rows,
                           mul=np.array([redc(a * b) for a, b, _, _ in vals], dtype=np.uint32),
@@ -121,6 +131,66 @@ def test_raw_products_match_exact_integers(gpu, expected, field, chain):
         got = gpu.fpr_raw_op(field, op, *args, chain=chain)
         bad = np.nonzero((got != e[op]).any(axis=1))[0]
         assert bad.size == 0, (op, "first wrong row", int(bad[0]), rows[int(bad[0])], got[bad[0]].tolist(), e[op][bad[0]].tolist())
+
+
+LAZY_FIELDS = sorted(f for f, (K, LB) in LIMBS.items() if LB == 29)  # the fields whose plans hold no flush: the NTT butterfly feeds them subl<3> limbs
+
+
+def lazy_limbs(field, a, b):
+    """the limbs FpR::subl<3> leaves for normalised a, b < 2p: a_i + q_i - b_i with 3p in the redundant form q (each limb lends one
+    unit of 2^LB to the limb below), no carry pass: limbs below 3 * 2^LB, value a + 3p - b < 5p"""
+    K, LB = LIMBS[field]
+    p = MODULUS[field]
+    assert 0 <= a < 2 * p and 0 <= b < 2 * p
+    m = split(3 * p, K, LB)
+    q = [m[0] + (1 << LB)] + [m[i] + (1 << LB) - 1 for i in range(1, K - 1)] + [m[K - 1] - 1]
+    r = [x + y - z for x, y, z in zip(split(a, K, LB), q, split(b, K, LB))]
+    assert all(0 <= x < 3 << LB for x in r) and value(r, LB) == a + 3 * p - b
+    return r
+
+
+def lazy_rows(field):
+    """rows (a, b, y, c, d, w) of integers below 2p: the products are lazy(a, b) * y and lazy(a, b) * y + lazy(c, d) * w"""
+    K, LB = LIMBS[field]
+    p = MODULUS[field]
+    L = (1 << LB) - 1
+    edge = [0, 1, p - 1, p, 2 * p - 1]
+    top = min(L, (2 * p - 1) >> ((K - 1) * LB))
+    full = ((top - 1) << ((K - 1) * LB)) | ((1 << ((K - 1) * LB)) - 1)  # every lower limb at its maximum, value below 2p
+    single = [(L if i < K - 1 else top) << (i * LB) for i in range(K)]  # one limb at its maximum
+    assert full < 2 * p and all(v < 2 * p for v in single)
+    rows = [(a, b, y, b, a, edge[(k + 2) % 5]) for a in edge for b in edge for k, y in enumerate(edge)]
+    rows += [(full, 0, full, full, 0, full), (0, full, full, full, 0, full), (full, 0, full, 0, full, 1), (2 * p - 1, 0, 2 * p - 1, 2 * p - 1, 0, 2 * p - 1)]
+    rows += [(si, 0, sj, sj, 0, si) for si in single for sj in single]       # the largest lazy limb i against the largest limb j
+    rows += [(0, si, full, full, si, single[K - 1 - i]) for i, si in enumerate(single)]  # ... and the smallest
+    rng = np.random.default_rng(31 + K)
+    rows += [tuple(int.from_bytes(rng.bytes(48), "little") % (2 * p) for _ in range(6)) for _ in range(200)]
+    return rows
+
+
+@pytest.mark.parametrize("chain", [False, True], ids=["plain", "kernel"])
+@pytest.mark.parametrize("field", LAZY_FIELDS)
+def test_raw_products_of_lazy_limb_operands_match_exact_integers(gpu, field, chain):
+    """The plain and the fused product with the limbs of a carry-free subtraction (subl<3>, limbs up to 3 * 2^LB) as one operand
+    of each pair and a normalised value below 2p as the other: operand bounds 5 * 2 + 5 * 2 <= RR_LIM, so the result is below 2p
+    and its limbs are those of the exact reduction."""
+    K, LB = LIMBS[field]
+    redc = reducer(field)
+    rows = lazy_rows(field)
+    assert len(rows) < 1000
+    x = np.array([lazy_limbs(field, a, b) for a, b, _, _, _, _ in rows], dtype=np.uint32)
+    z = np.array([lazy_limbs(field, c, d) for _, _, _, c, d, _ in rows], dtype=np.uint32)
+    y = np.array([split(r[2], K, LB) for r in rows], dtype=np.uint32)
+    w = np.array([split(r[5], K, LB) for r in rows], dtype=np.uint32)
+    assert int(x.max()) > 5 << (LB - 1), "no limb above 2.5 * 2^LB: the rows miss the case"
+    p = MODULUS[field]
+    lv = lambda a, b: a + 3 * p - b
+    want = {"mul": np.array([redc(lv(a, b) * yy) for a, b, yy, _, _, _ in rows], dtype=np.uint32),
+            "mul_add": np.array([redc(lv(a, b) * yy + lv(c, d) * ww) for a, b, yy, c, d, ww in rows], dtype=np.uint32)}
+    for op, args in (("mul", (x, y)), ("mul_add", (x, y, z, w))):
+        got = gpu.fpr_raw_op(field, op, *args, chain=chain)
+        bad = np.nonzero((got != want[op]).any(axis=1))[0]
+        assert bad.size == 0, (op, "first wrong row", int(bad[0]), rows[int(bad[0])], got[bad[0]].tolist(), want[op][bad[0]].tolist())
 
 
 @pytest.mark.parametrize("field", sorted(LIMBS))
