@@ -95,6 +95,13 @@ inline hipError_t setup_sync() { // everything this thread enqueued on its setup
     hipStream_t s = setup_stream();
     return s ? hipStreamSynchronize(s) : hipErrorOutOfMemory;
 }
+// the end of a call that enqueued on `s`: waits for the stream whatever happened before (the call's device memory goes next), and
+// reports `e`, the first error of the enqueueing, ahead of the wait's own
+inline int sync_status(hipStream_t s, hipError_t e, const char *what, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
+    const hipError_t e2 = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = e2;
+    return e == hipSuccess ? MG_OK : hip_status(e, what, file, line);
+}
 hipStream_t stream_pool_get();
 void stream_pool_put(hipStream_t s);
 hipStream_t stream_pool_get_normal(); // normal-priority streams: pooled and never destroyed either (runtime.cpp)
@@ -334,10 +341,8 @@ class GroupEngine {
     // Horner doublings): enqueues one small kernel behind the MSM on its stream and leaves ws->batch arkworks-format XYZZ
     // points, out_stride_words u32 apart, at d_out (device memory) -- for consumers that live on the device, i.e. the
     // partial-point exchange of the sharded paths (RCCL all_gather straight from HBM, no host bounce). The workspace is
-    // still handed back through msm_finish / msm_discard.
+    // still handed back through msm_finish.
     virtual int msm_fold_device(MsmWorkspace *ws, u32 *d_out, size_t out_stride_words, hipStream_t on = nullptr) = 0;
-    // an MSM whose result was taken on the device: wait for its stream, clear `pending`
-    virtual int msm_discard(MsmWorkspace *ws) = 0;
     // The first stage of msm_launch on its own -- the plan, the key layout and the digit-kernel launch of a set of c.n stored bases,
     // no points involved -- as a parity-test surface (tests/test_gpu_msm_frontend.py)
     virtual int msm_digits(const MsmDigitsCall &c) = 0;
@@ -366,17 +371,13 @@ class GroupEngine {
     // element-wise group operations on host arrays of affine points (the primitive menu of
     // manta-benchmark/src/ecc.rs; op codes in mantagpu.h), run with the MSM kernels' device functions
     virtual int ec_elementwise(int op, const u32 *a_host, const u32 *b_host, size_t n, u32 *out_affine_host) = 0;
-    // the same, results left as XYZZ points (xyzz_words() words each; no inversion on the device), and the host conversion of
-    // such an array to affine points with one inversion for all of them
-    virtual int ec_elementwise_xyzz(int op, const u32 *a_host, const u32 *b_host, size_t n, u32 *out_xyzz_host) = 0;
-    virtual void xyzz_batch_to_affine(const u32 *xyzz_host, size_t n, u32 *out_affine_host) const = 0;
-    // k_i P_i around other work: begin() uploads into ws's scratch buffer and launches on ws's stream, finish() waits and fetches
-    // the n XYZZ results (nothing else may use ws in between)
+    // k_i P_i ahead of other work: begin() uploads into ws's scratch buffer and launches on ws's stream; the n XYZZ results
+    // (xyzz_words() words each, no inversion) stay in device memory for a consumer on that stream (nothing else may use ws's
+    // scratch buffer until it has run)
     // glv_beta_std (G1 only; the field element beta of phi(x, y) = (beta x, y) = lambda (x, y), arkworks-format words): the
     // multipliers are then k1 + lambda k2 with k1, k2 the low two u64 of each 4 x u64 scalar -- one chain of 64 doublings
     virtual int ec_mul_xyzz_begin(const u32 *a_affine_host, const u32 *k_canonical_host, size_t n, MsmWorkspace *ws,
                                   const u32 *glv_beta_std = nullptr) = 0;
-    virtual int ec_mul_xyzz_finish(MsmWorkspace *ws, size_t n, u32 *out_xyzz_host, bool glv = false) = 0;
     virtual const u32 *ec_mul_xyzz_device(MsmWorkspace *ws, size_t n, bool glv = false) const = 0; // the results in device memory (valid on ws's stream after begin())
     // radix-2 (I)NTT over a vector of 2^lg group elements (host affine in/out, natural order); d_twiddles_mont = the Fr
     // domain's omega^k table on the device, n_inv_canonical != nullptr scales by n^-1 (inverse transform)
@@ -396,8 +397,6 @@ class GroupEngine {
                             u32 *out_affine_host) = 0;
     virtual void scalar_one_mont(u64 out[4]) const = 0; // 1 in Fr, Montgomery form
     virtual u64 qap_max_columns() const = 0;            // the most columns qap_columns takes: its sums are indexed in 32-bit words
-    // sum of affine points (device) -> host point
-    virtual int sum_affine(const u32 *d_pts, size_t n, HostPoint *out) = 0;
 
     MsmWorkspace *ws_acquire();
     void ws_release(MsmWorkspace *);

@@ -1,4 +1,4 @@
-// Shared by the parts of msm_impl.h: includes and the register-cap attributes of the tail kernels.
+// Shared by the parts of msm_impl.h: includes, cdiv for grid sizes and the register-cap attributes of the tail kernels.
 #pragma once
 #include "ec_dev.h"
 #include "engine.h"
@@ -14,6 +14,8 @@
 #include <type_traits>
 
 namespace mg {
+
+static inline u32 cdiv(size_t a, size_t b) { return (u32)((a + b - 1) / b); }
 
 // Register caps of the tail kernels (merge, bucket reduce; msm_reduce.h): none for the scan kernels and the cooperative ones
 #define MG_TAIL_ATTR

@@ -1,12 +1,11 @@
-// Host orchestration of the MSM pipeline: GroupEngineT (base sets, plan, launch, finish) -- one instantiation per (curve, group).
+// Host orchestration of the MSM pipeline: GroupEngineT (base sets, plan, launch stages, finish and fold, the digit stage alone, QAP
+// column sums) -- one instantiation per (curve, group), on top of the bulk group operations of GroupOpsT (group_ops.h).
 // Part of msm_impl.h.
 #pragma once
-#include "msm_common.h"
-#include "staging.h"
+#include "group_ops.h" // (first: it compiles without anything below)
 #include "msm_digits.h"
 #include "msm_accumulate.h"
 #include "msm_reduce.h"
-#include "msm_tables.h"
 #include "qap_columns.h"
 
 namespace mg {
@@ -14,29 +13,6 @@ namespace mg {
 // --------------------------------------------------------------------------------------------
 // host orchestration
 // --------------------------------------------------------------------------------------------
-template <class Curve, int GROUP> struct GT;
-template <class Curve> struct GT<Curve, 1> {
-#ifdef MG_G1_SATURATED
-    typedef Fp<typename Curve::Fq> F; // 32-bit saturated limbs everywhere (A/B reference build)
-#else
-    typedef FpR<typename Curve::Fq> F; // internal: reduced radix, lazily reduced
-#endif
-    typedef Fp<typename Curve::Fq> FIO; // arkworks memory format at the ABI
-    typedef host::HFp<typename Curve::Fq> HF;
-};
-template <class Curve> struct GT<Curve, 2> {
-    // G2 on the lazily-reduced Fp2R as well, its base products inlined (13 limbs over BLS12-381; the calls that 14 limbs needed
-    // are recorded in profiles/history/code_comment_measurements.md). MG_G2_SATURATED keeps the canonical 32-bit Fp2 path for A/B.
-#ifdef MG_G2_SATURATED
-    typedef Fp2<typename Curve::Fq> F;
-#else
-    typedef Fp2R<typename Curve::Fq> F;
-#endif
-    typedef Fp2<typename Curve::Fq> FIO;
-    typedef host::HFp2<typename Curve::Fq> HF;
-};
-
-static inline u32 cdiv(size_t a, size_t b) { return (u32)((a + b - 1) / b); }
 
 // The zero-fills of an MSM launch (pair counter, bucket array or direct result, timing words) as ONE kernel of ours instead of
 // hipMemsetAsync calls: inside a stream capture those become memset nodes, and a memset node of a LINEAR captured graph was found
@@ -105,60 +81,30 @@ struct MsmKnobs {
     // workgroup of the compacting digit kernel, 256 / 512 / 1024 -- measured: 256 beats 512 and 1024 on the same box
     u32 digits_threads = [](int v) { return (u32)(v == 256 || v == 512 || v == 1024 ? v : 256); }(ab_knob("MANTA_DIGITS_THREADS", 0));
     bool z3_sort = ab_knob("MANTA_Z3_SORT", 0) != 0;
-    size_t fixed_base_table_min = (size_t)ab_knob("MANTA_FIXED_BASE_TABLE_MIN", 16384); // fixed_base_mul's table from this many on
 };
 static const MsmKnobs &msm_knobs() {
     static const MsmKnobs k; // (first use: the first MSM of the process)
     return k;
 }
 
-template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public GroupEngine {
+template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public GroupOpsT<Curve, CURVE_ID, GROUP> {
   public:
-    typedef typename GT<Curve, GROUP>::F F;
-    typedef typename GT<Curve, GROUP>::FIO FIO;
-    typedef typename GT<Curve, GROUP>::HF HF;
-    typedef host::HPoint<HF> HP;
-    typedef typename Curve::Fr FrC;
-    static constexpr int AW = Affine<F>::WORDS, XW = XYZZ<F>::WORDS;           // internal formats
-    static constexpr int AW_IO = Affine<FIO>::WORDS, XW_IO = XYZZ<FIO>::WORDS; // arkworks formats (ABI, staging)
+    typedef GroupOpsT<Curve, CURVE_ID, GROUP> Ops; // its types, formats and host-point cast, by name
+    using typename Ops::F;
+    using typename Ops::FIO;
+    using typename Ops::HP;
+    using typename Ops::FrC;
+    using Ops::AW;
+    using Ops::XW;
+    using Ops::AW_IO;
+    using Ops::XW_IO;
+    using Ops::hp;
     static constexpr bool SAME = std::is_same<F, FIO>::value;
     // stride of one point in a BaseSet: the internal affine record padded to a multiple of 32 B (BLS12-381
     // G1: 28 -> 32 words = one 128 B line per gathered point instead of a record straddling two)
     static constexpr int AWS = SAME ? AW : (AW + 7) / 8 * 8;
-    static_assert(sizeof(HP) <= sizeof(HostPoint), "HostPoint too small");
 
-    int curve() const override { return CURVE_ID; }
-    int group() const override { return GROUP; }
-    int affine_words() const override { return AW_IO; }
-    int xyzz_words() const override { return XW_IO; }
-    int scalar_bits() const override { return FrC::BITS; }
     int base_record_bytes() const override { return AWS * 4; }
-    int point_bytes(bool compressed) const override { return compressed ? HF::BYTES : 2 * HF::BYTES; }
-
-    static HP &hp(HostPoint *p) { return *reinterpret_cast<HP *>(p); }
-    static const HP &hp(const HostPoint *p) { return *reinterpret_cast<const HP *>(p); }
-    void hp_set_inf(HostPoint *p) const override { hp(p) = HP::inf(); }
-    void hp_from_affine(HostPoint *p, const u32 *w) const override { hp(p) = HP::from_affine_words(w); }
-    void hp_from_xyzz(HostPoint *p, const u32 *w) const override { hp(p) = HP::from_xyzz_words(w); }
-    void hp_add(HostPoint *a, const HostPoint *o) const override { hp(a) = HP::add(hp(a), hp(o)); }
-    void hp_neg(HostPoint *p) const override { hp(p) = hp(p).neg(); }
-    void hp_mul(HostPoint *p, const u64 *k4) const override { hp(p) = HP::mul(hp(p), k4, 4); }
-    void hp_mul2(const HostPoint *p, const u64 *k1, const HostPoint *q, const u64 *k2, HostPoint *out) const override {
-        hp(out) = HP::mul2(hp(p), k1, hp(q), k2, 4);
-    }
-    void *hp_table_create(const HostPoint *base) const override {
-        auto *t = new host::FixedBaseTable<HP>();
-        t->build(hp(base));
-        return t;
-    }
-    void hp_table_mul(const void *table, const u64 *k4, HostPoint *out) const override {
-        hp(out) = static_cast<const host::FixedBaseTable<HP> *>(table)->mul(k4);
-    }
-    void hp_table_free(void *table) const override { delete static_cast<host::FixedBaseTable<HP> *>(table); }
-    void hp_to_affine(const HostPoint *p, u32 *w) const override { hp(p).to_affine_words(w); }
-    void hp_serialize(const HostPoint *p, unsigned char *out, bool compressed) const override {
-        hp(p).serialize(out, compressed);
-    }
 
     // ---------------------------------------------------------------- bases
     int bases_create(const u32 *pts_in, size_t n_in, bool src_on_device, int pre_c, BaseSet **out,
@@ -277,9 +223,7 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         if (e != hipSuccess) return hip_failure(e, "hipMalloc(precompute tmp)", MG_ERR_OOM);
         hipLaunchKernelGGL((precompute_chain<F>), dim3(cdiv(n, 256)), dim3(256), 0, setup_stream(), dst, (u32)AWS, (u32)n,
                            pre_c, W, tmp);
-        constexpr int KB = 16;
-        hipLaunchKernelGGL((xyzz_to_affine_batch<F, KB>), dim3(cdiv(cdiv(cnt, KB), 256)), dim3(256), 0, setup_stream(), tmp,
-                           cnt, dst + n * AWS, (u32)AWS);
+        xyzz_to_affine_launch<F>(setup_stream(), tmp, cnt, dst + n * AWS, AWS);
         e = setup_sync();
         hipFree(tmp);
         return e == hipSuccess ? MG_OK : hip_failure(e, "precompute kernels", MG_ERR_HIP);
@@ -297,8 +241,7 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
             const size_t cntp = pairs - j0 < slice ? pairs - j0 : slice;
             hipLaunchKernelGGL((full_table_chain<F>), dim3(cdiv(cntp, 256)), dim3(256), 0, setup_stream(), win_pts, (u32)AWS, j0, (u32)cntp, FB,
                                tmp);
-            hipLaunchKernelGGL((xyzz_to_affine_batch<F, KBF>), dim3(cdiv(cdiv(cntp * FB, KBF), 256)), dim3(256), 0, setup_stream(), tmp,
-                               cntp * FB, final_pts + j0 * FB * AWS, (u32)AWS);
+            xyzz_to_affine_launch<F, KBF>(setup_stream(), tmp, cntp * FB, final_pts + j0 * FB * AWS, AWS);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = setup_sync();
@@ -511,42 +454,42 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         const u32 Wb = (u32)pl.Wb, segs = t.segs, T1 = t.T1, nP = t.nP;
         const u32 *st = (const u32 *)ws->h_stage;
         for (u32 q = 0; q < ws->batch; ++q) {
-        HP total = HP::inf();
-        for (int w = (int)((q + 1) * Wb) - 1; w >= (int)(q * Wb); --w) {
-            HP win;
-            if (t.kind == TAIL_WINDOW_SUMS) { // the staged point is the window sum
-                win = HP::from_xyzz_words(st + (size_t)w * XW_IO);
-            } else if (t.kind == TAIL_X_SUMS) { // fused reduce: (X, sumS) per window, window = sumS + 64 X
-                const HP X = HP::from_xyzz_words(st + ((size_t)w * 2 + 0) * XW_IO);
-                const HP sumS = HP::from_xyzz_words(st + ((size_t)w * 2 + 1) * XW_IO);
-                win = HP::add(sumS, HP::mul_pow2(X, 6));
-            } else { // TAIL_TWO_LEVELS
-                const u32 *A1 = st + ((size_t)w * T1) * XW_IO;
-                const u32 *S1 = st + ((size_t)segs * T1 + (size_t)w * T1) * XW_IO;
-                const u32 *P0 = st + ((size_t)segs * 2 * T1 + (size_t)w * nP) * XW_IO;
-                // X = sum_{t>=1} t*A0[t] = sum_u ( S1[u] + 64*u*A1[u] )
-                HP sumS = HP::inf(), run = HP::inf(), uA = HP::inf();
-                for (int u = (int)T1 - 1; u >= 0; --u) {
-                    sumS = HP::add(sumS, HP::from_xyzz_words(S1 + (size_t)u * XW_IO));
-                    if (u >= 1) {
-                        run = HP::add(run, HP::from_xyzz_words(A1 + (size_t)u * XW_IO));
-                        uA = HP::add(uA, run); // sum_u u*A1[u]
+            HP total = HP::inf();
+            for (int w = (int)((q + 1) * Wb) - 1; w >= (int)(q * Wb); --w) {
+                HP win;
+                if (t.kind == TAIL_WINDOW_SUMS) { // the staged point is the window sum
+                    win = HP::from_xyzz_words(st + (size_t)w * XW_IO);
+                } else if (t.kind == TAIL_X_SUMS) { // fused reduce: (X, sumS) per window, window = sumS + 64 X
+                    const HP X = HP::from_xyzz_words(st + ((size_t)w * 2 + 0) * XW_IO);
+                    const HP sumS = HP::from_xyzz_words(st + ((size_t)w * 2 + 1) * XW_IO);
+                    win = HP::add(sumS, HP::mul_pow2(X, 6));
+                } else { // TAIL_TWO_LEVELS
+                    const u32 *A1 = st + ((size_t)w * T1) * XW_IO;
+                    const u32 *S1 = st + ((size_t)segs * T1 + (size_t)w * T1) * XW_IO;
+                    const u32 *P0 = st + ((size_t)segs * 2 * T1 + (size_t)w * nP) * XW_IO;
+                    // X = sum_{t>=1} t*A0[t] = sum_u ( S1[u] + 64*u*A1[u] )
+                    HP sumS = HP::inf(), run = HP::inf(), uA = HP::inf();
+                    for (int u = (int)T1 - 1; u >= 0; --u) {
+                        sumS = HP::add(sumS, HP::from_xyzz_words(S1 + (size_t)u * XW_IO));
+                        if (u >= 1) {
+                            run = HP::add(run, HP::from_xyzz_words(A1 + (size_t)u * XW_IO));
+                            uA = HP::add(uA, run); // sum_u u*A1[u]
+                        }
                     }
+                    HP X = HP::add(sumS, HP::mul_pow2(uA, 6));
+                    HP sumP = HP::inf();
+                    for (u32 u = 0; u < nP; ++u) sumP = HP::add(sumP, HP::from_xyzz_words(P0 + (size_t)u * XW_IO));
+                    win = HP::add(sumP, HP::mul_pow2(X, 6));
                 }
-                HP X = HP::add(sumS, HP::mul_pow2(uA, 6));
-                HP sumP = HP::inf();
-                for (u32 u = 0; u < nP; ++u) sumP = HP::add(sumP, HP::from_xyzz_words(P0 + (size_t)u * XW_IO));
-                win = HP::add(sumP, HP::mul_pow2(X, 6));
+                if (t.tail_shift) win = HP::mul_pow2(win, t.tail_shift); // front levels: window = 2^shift * tail + extras
+                for (u32 e = 0; e < t.n_extra; ++e) {
+                    const HP x = HP::from_xyzz_words(st + (t.extra_off_pts + (size_t)e * segs + (size_t)w) * XW_IO);
+                    win = HP::add(win, t.extra_shift[e] ? HP::mul_pow2(x, t.extra_shift[e]) : x);
+                }
+                if (w != (int)((q + 1) * Wb) - 1) total = HP::mul_pow2(total, (unsigned)pl.c);
+                total = HP::add(total, win);
             }
-            if (t.tail_shift) win = HP::mul_pow2(win, t.tail_shift); // front levels: window = 2^shift * tail + extras
-            for (u32 e = 0; e < t.n_extra; ++e) {
-                const HP x = HP::from_xyzz_words(st + (t.extra_off_pts + (size_t)e * segs + (size_t)w) * XW_IO);
-                win = HP::add(win, t.extra_shift[e] ? HP::mul_pow2(x, t.extra_shift[e]) : x);
-            }
-            if (w != (int)((q + 1) * Wb) - 1) total = HP::mul_pow2(total, (unsigned)pl.c);
-            total = HP::add(total, win);
-        }
-        hp(out + q) = total;
+            hp(out + q) = total;
         }
         return MG_OK;
     }
@@ -560,12 +503,6 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         for (u32 e = 0; e < t.n_extra; ++e) d.extra_shift[e] = t.extra_shift[e];
         hipLaunchKernelGGL((fold_windows<F>), dim3(ws->batch), dim3(64), 0, on ? on : msm_stream_of(ws), d, d_out, out_stride_words);
         MG_HIP(hipGetLastError());
-        return MG_OK;
-    }
-    int msm_discard(MsmWorkspace *ws) override {
-        if (!ws) return MG_ERR_STATE;
-        ws->pending = 0;
-        MG_HIP(hipStreamSynchronize(msm_stream_of(ws)));
         return MG_OK;
     }
 
@@ -614,192 +551,9 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         if (e == hipSuccess) e = hipMemcpyAsync(c.keys, d_keys, pb, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(c.vals, d_vals, pb, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess && c.compact) e = hipMemcpyAsync(c.count, r.d_count, 4, hipMemcpyDeviceToHost, s);
-        const hipError_t e2 = hipStreamSynchronize(s);
+        const int rc = sync_status(s, e, "mg_msm_digits");
         bs.d_map = nullptr; // the block's
-        return e != hipSuccess ? hip_status(e, "mg_msm_digits") : e2 != hipSuccess ? hip_status(e2, "mg_msm_digits") : MG_OK;
-    }
-
-    // ---------------------------------------------------------------- fixed-base batch mul
-    int fixed_base_mul(const u32 *base_affine_host, const u32 *d_scalars, size_t n, u32 *d_out_affine,
-                       hipStream_t s) override {
-        if (!s) s = setup_stream(); // (never the NULL stream: engine.h)
-        DevBlock m, table; // base | XYZZ results; the 32 x 255 multiples of the base as XYZZ | affine
-        if (const int rc = m.alloc({AW_IO * 4, n * XW_IO * 4}, "hipMalloc(fixed_base_mul)")) return rc;
-        u32 *d_base = m.dev<u32>(0), *tmp = m.dev<u32>(1);
-        hipMemcpyAsync(d_base, base_affine_host, AW_IO * 4, hipMemcpyHostToDevice, s);
-        constexpr int KB = 16;
-        constexpr size_t TN = 32 * 255;
-        // many multiples of one base: 32 table additions each instead of ~380 group operations -- when the table's memory can be had
-        if (n >= msm_knobs().fixed_base_table_min && table.try_alloc({TN * XW_IO * 4, TN * AW_IO * 4})) {
-            u32 *t_xyzz = table.dev<u32>(0), *t_aff = table.dev<u32>(1);
-            hipLaunchKernelGGL((fixed_base_table_kernel<FIO>), dim3(cdiv(TN, 256)), dim3(256), 0, s, d_base, t_xyzz);
-            hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(TN, KB), 256)), dim3(256), 0, s, t_xyzz, TN, t_aff,
-                               (u32)AW_IO);
-            hipLaunchKernelGGL((fixed_base_mul_table_kernel<FIO>), dim3(cdiv(n, 256)), dim3(256), 0, s, t_aff, d_scalars, n, tmp);
-        } else {
-            hipLaunchKernelGGL((fixed_base_mul_kernel<FIO>), dim3(cdiv(n, 256)), dim3(256), 0, s, d_base, d_scalars, n, tmp);
-        }
-        hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(n, KB), 256)), dim3(256), 0, s, tmp, n,
-                           d_out_affine, (u32)AW_IO);
-        const hipError_t e = hipStreamSynchronize(s);
-        return e == hipSuccess ? MG_OK : hip_status(e, "fixed_base_mul");
-    }
-
-    int ec_elementwise(int op, const u32 *a_host, const u32 *b_host, size_t n, u32 *out_affine_host) override {
-        return ec_elementwise_impl(op, a_host, b_host, n, out_affine_host, false);
-    }
-    // the same results as XYZZ points (XW_IO words each): no inversion on the device -- xyzz_batch_to_affine() turns them
-    // into affine points on the host with one inversion for all of them
-    int ec_elementwise_xyzz(int op, const u32 *a_host, const u32 *b_host, size_t n, u32 *out_xyzz_host) override {
-        return ec_elementwise_impl(op, a_host, b_host, n, out_xyzz_host, true);
-    }
-    // the multiplication k_i P_i (op MG_EC_MUL) as two calls around other work: begin() uploads into the workspace's grow-only
-    // scratch buffer and launches on the workspace's stream (no hipMalloc / hipFree / stream 0: nothing else on the device
-    // waits for it and it waits for nothing), finish() waits and fetches the XYZZ results
-    int ec_mul_xyzz_begin(const u32 *a_host, const u32 *k_host, size_t n, MsmWorkspace *ws, const u32 *glv_beta_std) override {
-        if (!a_host || !k_host || !n || !ws) return MG_ERR_ARG;
-        const size_t ab = n * AW_IO * 4, bb = n * 32 + (glv_beta_std ? (size_t)AW_IO / 2 * 4 : 0), tb = n * XW_IO * 4;
-        int rc = ws->scratch.reserve(ab + bb + tb);
-        if (rc) return rc;
-        unsigned char *d = (unsigned char *)ws->scratch.p;
-        hipError_t e = hipMemcpyAsync(d, a_host, ab, hipMemcpyHostToDevice, ws->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d + ab, k_host, n * 32, hipMemcpyHostToDevice, ws->stream);
-        if (e == hipSuccess && glv_beta_std)
-            e = hipMemcpyAsync(d + ab + n * 32, glv_beta_std, (size_t)AW_IO / 2 * 4, hipMemcpyHostToDevice, ws->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL((ec_elementwise_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, ws->stream, glv_beta_std ? 6 : 3, (const u32 *)d,
-                               (const u32 *)(d + ab), n, (u32 *)(d + ab + bb));
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) {
-            hipStreamSynchronize(ws->stream);
-            set_last_hip_error(e, "ec_mul_xyzz", __FILE__, __LINE__);
-            return MG_ERR_HIP;
-        }
-        return MG_OK;
-    }
-    const u32 *ec_mul_xyzz_device(MsmWorkspace *ws, size_t n, bool glv) const override { // where begin()'s kernel leaves the n results
-        const size_t ab = n * AW_IO * 4, bb = n * 32 + (glv ? (size_t)AW_IO / 2 * 4 : 0);
-        return ws && ws->scratch.p ? (const u32 *)((unsigned char *)ws->scratch.p + ab + bb) : nullptr;
-    }
-    int ec_mul_xyzz_finish(MsmWorkspace *ws, size_t n, u32 *out_xyzz_host, bool glv) override {
-        if (!ws || !n || !out_xyzz_host) return MG_ERR_ARG;
-        const size_t ab = n * AW_IO * 4, bb = n * 32 + (glv ? (size_t)AW_IO / 2 * 4 : 0), tb = n * XW_IO * 4;
-        hipError_t e = hipMemcpyAsync(out_xyzz_host, (unsigned char *)ws->scratch.p + ab + bb, tb, hipMemcpyDeviceToHost, ws->stream);
-        const hipError_t e2 = hipStreamSynchronize(ws->stream);
-        if (e == hipSuccess) e = e2;
-        if (e != hipSuccess) {
-            set_last_hip_error(e, "ec_mul_xyzz", __FILE__, __LINE__);
-            return MG_ERR_HIP;
-        }
-        return MG_OK;
-    }
-    void xyzz_batch_to_affine(const u32 *xyzz_host, size_t n, u32 *out_affine_host) const override {
-        typedef decltype(HP{}.x) HF;
-        std::vector<HF> den(n), pre(n);
-        HF acc = HF::one();
-        for (size_t i = 0; i < n; ++i) { // Montgomery's trick: prefix products of the denominators ZZ ZZZ (1 for infinity)
-            const HP q = HP::from_xyzz_words(xyzz_host + i * XW_IO);
-            den[i] = q.is_inf() ? HF::one() : HF::mul(q.zz, q.zzz);
-            pre[i] = acc;
-            acc = HF::mul(acc, den[i]);
-        }
-        HF inv = HF::inv(acc);
-        for (size_t i = n; i-- > 0;) {
-            const HP q = HP::from_xyzz_words(xyzz_host + i * XW_IO);
-            const HF t = HF::mul(inv, pre[i]); // 1 / (ZZ ZZZ) of point i
-            inv = HF::mul(inv, den[i]);
-            u32 *o = out_affine_host + i * AW_IO;
-            if (q.is_inf()) {
-                std::memset(o, 0, AW_IO * 4);
-                continue;
-            }
-            HF::mul(q.x, HF::mul(t, q.zzz)).store_words(o);
-            HF::mul(q.y, HF::mul(t, q.zz)).store_words(o + HF::WORDS);
-        }
-    }
-    int ec_elementwise_impl(int op, const u32 *a_host, const u32 *b_host, size_t n, u32 *out_host, bool xyzz) {
-        if (op < 0 || op > 5 || !a_host || !out_host || n == 0 || (op != 2 && !b_host)) return MG_ERR_ARG;
-        const size_t ab = n * AW_IO * 4, bb = op == 3 ? n * 32 : (op == 5 ? 32 : ab);
-        // a stream of its own (not stream 0: a synchronous copy anywhere else in the process -- another thread creating a base
-        // set, say -- would wait for this kernel, a millisecond of one-lane latency for 128-bit multipliers)
-        hipStream_t st = stream_pool_get_normal(); // (pooled: the library destroys no stream, runtime.cpp)
-        if (!st) return hip_status(hipErrorOutOfMemory, "ec_elementwise");
-        DevBlock m; // a | b | XYZZ results | affine results
-        hipError_t e = hipSuccess;
-        int rc = m.alloc({ab, bb, n * XW_IO * 4, xyzz ? 0 : ab}, "ec_elementwise");
-        if (!rc) {
-            u32 *da = m.dev<u32>(0), *db = m.dev<u32>(1), *tmp = m.dev<u32>(2), *dout = m.dev<u32>(3);
-            e = hipMemcpyAsync(da, a_host, ab, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess && op != 2) e = hipMemcpyAsync(db, b_host, bb, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL((ec_elementwise_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, op, da, db, n, tmp);
-                if (xyzz) {
-                    e = hipMemcpyAsync(out_host, tmp, n * XW_IO * 4, hipMemcpyDeviceToHost, st);
-                } else {
-                    constexpr int KB = 16;
-                    hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(n, KB), 256)), dim3(256), 0, st, tmp, n, dout,
-                                       (u32)AW_IO);
-                    e = hipMemcpyAsync(out_host, dout, ab, hipMemcpyDeviceToHost, st);
-                }
-            }
-            const hipError_t e2 = hipStreamSynchronize(st);
-            if (e == hipSuccess) e = e2;
-        }
-        stream_pool_put_normal(st);
-        return rc ? rc : e == hipSuccess ? MG_OK : hip_status(e, "ec_elementwise");
-    }
-
-    // NTT over group elements: host affine in, host affine out (natural order both); tw = the Fr domain's device twiddle
-    // table (omega^k, k < n/2, Montgomery), n_inv_canonical = n^-1 for the inverse transform (nullptr: forward)
-    int group_ntt(const u32 *in_affine_host, unsigned lg, const u32 *d_twiddles_mont, const u32 *n_inv_canonical,
-                  u32 *out_affine_host) override {
-        if (!in_affine_host || !out_affine_host || lg > 26 || (lg > 0 && !d_twiddles_mont)) return MG_ERR_ARG;
-        const size_t n = (size_t)1 << lg, ab = n * AW_IO * 4;
-        DevBlock m; // affine in | affine out
-        if (const int rc = m.alloc({ab, ab}, "group_ntt")) return rc;
-        hipError_t e = memcpy_sync(m.dev(0), in_affine_host, ab, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_status(e, "group_ntt");
-        if (const int rc = group_ntt_device(m.dev<u32>(0), lg, d_twiddles_mont, n_inv_canonical, m.dev<u32>(1))) return rc;
-        e = memcpy_sync(out_affine_host, m.dev(1), ab, hipMemcpyDeviceToHost);
-        return e == hipSuccess ? MG_OK : hip_status(e, "group_ntt");
-    }
-    // the transform itself, device array to device array (`mpc::initialize`: the Lagrange bases never leave HBM)
-    int group_ntt_device(const u32 *d_in, unsigned lg, const u32 *d_twiddles_mont, const u32 *n_inv_canonical, u32 *d_out) override {
-        if (!d_in || !d_out || lg > 26 || (lg > 0 && !d_twiddles_mont)) return MG_ERR_ARG;
-        hipStream_t st = setup_stream();
-        if (!st) return MG_ERR_OOM;
-        const size_t n = (size_t)1 << lg;
-        DevBlock m; // working XYZZ | arkworks-format XYZZ | n^-1 (inverse transform only)
-        if (const int rc = m.alloc({n * XW * 4, n * XW_IO * 4, n_inv_canonical ? 32u : 0u}, "group_ntt")) return rc;
-        u32 *d_pts = m.dev<u32>(0), *d_std = m.dev<u32>(1), *d_sc = m.dev<u32>(2);
-        hipError_t e = n_inv_canonical ? memcpy_sync(d_sc, n_inv_canonical, 32, hipMemcpyHostToDevice) : hipSuccess;
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL((group_ntt_load_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, d_in, lg, d_pts);
-            for (unsigned s = 1; s <= lg; ++s)
-                hipLaunchKernelGGL((group_ntt_stage_kernel<F, FrC>), dim3(cdiv(n / 2, 256)), dim3(256), 0, st, d_pts, d_twiddles_mont, lg, s);
-            hipLaunchKernelGGL((group_scale_store_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, d_pts, (const u32 *)d_sc, n, d_std);
-            constexpr int KB = 16;
-            hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(n, KB), 256)), dim3(256), 0, st, d_std, n, d_out, (u32)AW_IO);
-            e = hipGetLastError();
-            const hipError_t e2 = hipStreamSynchronize(st);
-            if (e == hipSuccess) e = e2;
-        }
-        return e == hipSuccess ? MG_OK : hip_status(e, "group_ntt");
-    }
-    int sub_device(const u32 *d_a, const u32 *d_b, size_t n, u32 *d_out) override {
-        if (!d_a || !d_b || !d_out || n == 0) return MG_ERR_ARG;
-        hipStream_t st = setup_stream();
-        if (!st) return MG_ERR_OOM;
-        DevBlock m; // XYZZ results
-        if (const int rc = m.alloc({n * XW_IO * 4}, "sub_device")) return rc;
-        constexpr int KB = 16;
-        hipLaunchKernelGGL((ec_elementwise_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, 4, d_a, d_b, n, m.dev<u32>(0));
-        hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(n, KB), 256)), dim3(256), 0, st, m.dev<u32>(0), n, d_out, (u32)AW_IO);
-        hipError_t e = hipGetLastError();
-        const hipError_t e2 = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = e2;
-        return e == hipSuccess ? MG_OK : hip_status(e, "sub_device");
+        return rc;
     }
 
     // ---------------------------------------------------------------- QAP column sums (qap_columns.h)
@@ -864,36 +618,16 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
                                    invalid, sums, m.dev<u32>(PK0), m.dev<u32>(PP0), T);
                 u32 *pk[2] = {m.dev<u32>(PK0), m.dev<u32>(PK1)}, *pp[2] = {m.dev<u32>(PP0), m.dev<u32>(PP1)};
                 merge_levels(st, pk, pp, 2 * T, merge_g1(N), invalid, sums, (u32 *)nullptr);
-                constexpr int KB = 16;
                 hipLaunchKernelGGL((group_scale_store_kernel<F>), dim3(cdiv(n_cols, 256)), dim3(256), 0, st, sums, (const u32 *)nullptr,
                                    (size_t)n_cols, m.dev<u32>(STD));
-                hipLaunchKernelGGL((xyzz_to_affine_batch<FIO, KB>), dim3(cdiv(cdiv(n_cols, KB), 256)), dim3(256), 0, st, m.dev<u32>(STD),
-                                   (size_t)n_cols, m.dev<u32>(AFF), (u32)AW_IO);
+                xyzz_to_affine_launch<FIO>(st, m.dev<u32>(STD), (size_t)n_cols, m.dev<u32>(AFF), AW_IO);
                 e = hipGetLastError();
                 if (e == hipSuccess) e = hipMemcpyAsync(stage.data(), m.dev(AFF), out_bytes, hipMemcpyDeviceToHost, st);
             }
         }
-        const hipError_t e2 = hipStreamSynchronize(st); // (before the block goes, whatever failed)
-        if (rc) return rc;
-        if (e == hipSuccess) e = e2;
-        if (e != hipSuccess) return hip_status(e, "qap_columns");
+        const int synced = sync_status(st, e, "qap_columns"); // (before the block goes, whatever failed)
+        if (rc || synced) return rc ? rc : synced;
         std::memcpy(out_affine_host, stage.data(), out_bytes);
-        return MG_OK;
-    }
-
-    int sum_affine(const u32 *d_pts, size_t n, HostPoint *out) override {
-        const u32 T = n < 4096 ? (u32)(n ? n : 1) : 4096;
-        std::vector<u32> h((size_t)T * XW_IO);
-        {
-            DevBlock m;
-            if (const int rc = m.alloc({h.size() * 4}, "hipMalloc(sum_affine)")) return rc;
-            hipLaunchKernelGGL((sum_affine_kernel<FIO>), dim3(cdiv(T, 256)), dim3(256), 0, setup_stream(), d_pts, n, T, m.dev<u32>(0));
-            const hipError_t e = memcpy_sync(h.data(), m.dev<u32>(0), h.size() * 4, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) return hip_status(e, "sum_affine");
-        }
-        HP acc = HP::inf();
-        for (u32 t = 0; t < T; ++t) acc = HP::add(acc, HP::from_xyzz_words(h.data() + (size_t)t * XW_IO));
-        hp(out) = acc;
         return MG_OK;
     }
 

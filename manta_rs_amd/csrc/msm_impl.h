@@ -27,7 +27,10 @@
 //   msm_accumulate.h  K7a  accumulate_chunks / accumulate_single
 //   msm_reduce.h      K7b-K9 merge_partials*, tile_reduce*, serial_reduce*, reduce_level1* (each plain / _coop pair: one body, two
 //                     instantiations), fold_windows
-//   msm_tables.h      bases_to_internal, window / full tables, fixed-base, group NTT, element-wise kernels
-//   msm_engine.h      GroupEngineT: base sets, plan, launch, finish (host)
+//   msm_tables.h      bases_to_internal, window / full tables, xyzz_to_affine_batch and its launcher
+//   group_ops.h       beside the MSM: fixed-base, group NTT and element-wise kernels (one double-and-add ladder), and GroupOpsT, the
+//                     host side of those operations and of the host-point helpers; includes nothing of the MSM's
+//   qap_columns.h     qap_entry_kernel, qap_segsum_kernel
+//   msm_engine.h      GroupEngineT on top of GroupOpsT: base sets, plan, launch stages, finish and fold, msm_digits, qap_columns (host)
 #pragma once
 #include "msm_engine.h"

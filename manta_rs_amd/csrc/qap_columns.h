@@ -11,7 +11,8 @@
 //               P + P and P + (-P) exact): runs that start and end inside the lane go straight to out[col], the lane's first
 //               and last run leave as partials -- the layout accumulate_chunks leaves
 //   merge       merge_partials (msm_reduce.h) folds the partials of one column, 64 G -> 2 per wave and level
-//   normalise   XYZZ -> arkworks-format XYZZ -> affine with one inversion per 16 points (xyzz_to_affine_batch)
+//   normalise   XYZZ -> arkworks-format XYZZ (group_scale_store_kernel, group_ops.h) -> affine with one inversion per 16 points
+//               (xyzz_to_affine_launch, msm_tables.h)
 //
 // Launches per call: 1 zero-fill + 4 per radix pass (at most 4 passes) + 2 + the merge levels (log_64 of the lane count) + 2;
 // copies: 4 uploads (basis rows, coefficients, columns, entry ids), 1 download -- and in front of it mg_qap_columns uploads the

@@ -71,6 +71,56 @@ def test_scalar_multiplication_is_consistent(gpu, curve, group):
     assert (got == want).all()
 
 
+LIMB_BITS = (0, 31, 32, 63, 64, 127, 128, 223, 224, 252)  # one set bit on either side of a 32-bit limb boundary; 2^252 < r
+
+
+@pytest.mark.parametrize("curve,group", CASES)
+def test_scalar_multiplication_at_limb_boundaries(gpu, curve, group):
+    """The 256-bit double-and-add walk of every kernel that has one, on scalars whose set bits sit at the ends of
+    32-bit limbs: point i times scalar i (EC_MUL), every point times one scalar (EC_MUL_FIXED) and one base times
+    every scalar on the per-lane path of fixed_base_mul (n below the table threshold)."""
+    from manta_rs_amd import ceremony
+    n = 20
+    r = synth.FR_MODULUS[curve]
+    rng = synth.XorShift(310 + curve)
+    ks = [1 << b for b in LIMB_BITS] + [(1 << 32) - 1, (1 << 224) - 1]
+    ks += [rng.field(r) for _ in range(n - len(ks))]
+    assert len(ks) == n and all(v < r for v in ks)
+    k = synth.ints_to_limbs(ks, 4)
+    a = H.random_points(curve, group, n, seed=307)
+    want = np.stack([O.g_mul(curve, group, a[i], k[i]) for i in range(n)])
+    assert (gpu.ec_elementwise(curve, group, gpu.EC_MUL, a, k) == want).all()
+    for j, b in enumerate(LIMB_BITS):
+        got = ceremony.batch_mul_fixed_scalar(curve, group, a[:3], 1 << b)
+        wantb = np.stack([O.g_mul(curve, group, a[i], k[j]) for i in range(3)])
+        assert (got == wantb).all(), b
+    got = gpu.fixed_base_mul(curve, group, a[0], gpu.DeviceBuffer.from_numpy(k[:12]), 12)
+    got = got.to_numpy(shape=(12, gpu.affine_limbs(curve, group)))
+    assert (got == O.fixed_base_mul(curve, group, a[0], k[:12])).all()
+
+
+@pytest.mark.parametrize("curve,group", CASES)
+def test_normalising_tail_at_its_batch_boundaries(gpu, curve, group):
+    """The XYZZ -> affine tail inverts once per 16 results and skips infinity: sizes around one and two batches, a
+    whole batch of infinity results (its running product stays 1), a single infinity result at the ends of a batch,
+    a last batch of one element."""
+    N = 33
+    a0 = H.random_points(curve, group, N, seed=308)
+    b0 = H.random_points(curve, group, N, seed=309)
+    wsub = np.stack([O.g_add(curve, group, a0[i], _neg(curve, group, b0[i])) for i in range(N)])
+    wdbl = np.stack([O.g_add(curve, group, a0[i], a0[i]) for i in range(N)])
+    for n in (1, 15, 16, 17, 33):
+        holes = [[]] + [[p] for p in sorted({0, 15, 16, n - 1}) if p < n] + ([list(range(16))] if n >= 16 else [])
+        for hole in holes:
+            a, b, ws, wd = a0[:n].copy(), b0[:n].copy(), wsub[:n].copy(), wdbl[:n].copy()
+            b[hole] = a[hole]  # P - P = infinity
+            ws[hole] = 0
+            assert (gpu.ec_elementwise(curve, group, gpu.EC_SUB_MIXED, a, b) == ws).all(), (n, hole)
+            a[hole] = 0        # 2 * infinity = infinity
+            wd[hole] = 0
+            assert (gpu.ec_elementwise(curve, group, gpu.EC_DOUBLE, a) == wd).all(), (n, hole)
+
+
 def test_batch_normalisation_of_2_16_points(gpu):
     """ecc.rs:114-119 normalises 2^16 projective points at once: 2^16 doublings on the GPU, every affine output on
     the curve, spot-checked against the oracle, and the sum of all outputs equal to twice the sum of the inputs
