@@ -626,8 +626,8 @@ int mg_blake2b512(const uint8_t *data, size_t len, uint8_t out64[64]);
  *      (config/utxo.rs:1200-1301): one state per GPU lane. Field elements are Montgomery limbs (4 x u64) of Fr of `curve`.
  *      Synchronous, thread-safe and re-entrant, on the calling thread's setup stream. permute / hash run at most
  *      MG_POSEIDON_CHUNK states at a time: device memory of a call < MG_POSEIDON_CHUNK x 192 B (96 MiB) + the parameters,
- *      whatever n, and no pinned host memory. A tree keeps every level on the device for its paths (about 2 n x 32 B); a
- *      forest alternates two level buffers (about 1.5 x its leaves x 32 B). ------------------------------------------------ */
+ *      whatever n, and no pinned host memory. A tree and a forest keep every level on the device (about 2 x their leaves x
+ *      32 B: 64 MB for 2^20 leaves). ------------------------------------------------------------------------------------- */
 #define MG_POSEIDON_CHUNK (1u << 19)
 typedef struct mg_poseidon mg_poseidon; /* a decoded parameter set (host memory only: creating one needs no GPU) */
 /* bytes = the manta codec of `Hasher<S, T, ARITY>` (hash.rs:155-192, mod.rs:465-506): (full_rounds + partial_rounds) x width

@@ -1,8 +1,8 @@
 // Batched Poseidon over the BN254 / BLS12-381 scalar fields on gfx950, and the hashing inside manta's Merkle trees: the
 // permutation and `Hasher::hash` with one state per lane (width t = 3..6 a template parameter, round counts and constants
-// runtime data), one kernel per tree level over every tree of a forest, the top levels of each tree in LDS, and path gathering.
-// Instantiated per scalar field in poseidon_<curve>.hip; the host layer and the C ABI (mg_poseidon_*, mg_merkle_*) are in
-// poseidon.cpp.
+// runtime data), and the three tree kernels: one level of every tree of a forest, the top levels of each tree in LDS, and path
+// gathering. One typed launch function per kernel (PoseidonKernels), instantiated per scalar field in poseidon_<curve>.hip;
+// the host layer and the C ABI (mg_poseidon_*, mg_merkle_*) are in poseidon.cpp.
 //
 // Semantics (manta-pay/src/crypto/poseidon/mod.rs:383-439, hash.rs:111-153): round r adds keys[r t + i] to word i, applies
 // x^5 to every word (full round) or to word 0 only (partial round), then new[i] = sum_j mds[t i + j] st[j]; FULL/2 full rounds,
@@ -15,14 +15,17 @@
 // Merkle trees (manta-crypto/src/merkle_tree/{full,inner_tree}.rs): leaves are level 0; node j of level l + 1 is
 // hash(node 2j, node 2j + 1) with an absent right child taken as 0; level l holds ceil(n / 2^l) nodes, the rest are the
 // sentinel 0. A forest is a table of per-tree segment offsets per level (off[l (n_trees + 1) + k]): tree k's nodes of level l
-// are entries off[l][k] .. off[l][k + 1] of that level's buffer.
+// are entries off[l][k] .. off[l][k + 1] of the node buffer.
 //
-// Appending (merkle_tree/{single_path,partial}.rs, tree.rs:351-406, path.rs:416): a tree is known by its leaf count n_old, its
-// last leaf and that leaf's Path. Appending b leaves (n_new = n_old + b) recomputes on level l the nodes s_l = n_old >> l ..
-// ceil(n_new / 2^l) - 1; only those are stored (the table's segments hold them, segment entry i = node s_l + i). The one older
-// node that work reads is node(l, s_l - 1) for odd s_l, the level's seed: the old path's entry l when n_old mod 2^l != 0, else
-// (l = ctz(n_old)) the last leaf's ancestor a_l, a_0 = last leaf, a_{j+1} = hash(path[j], a_j). That chain is one extra lane
-// per tree in each level pass (pass l -> l + 1 computes a_{l+1} while l < ctz(n_old)), never a fold of its own.
+// Every tree pass is an append (merkle_tree/{single_path,partial}.rs, tree.rs:351-406, path.rs:416): a tree is known by its leaf
+// count n_old, its last leaf and that leaf's Path. Appending b leaves (n_new = n_old + b) computes on level l the nodes
+// s_l = n_old >> l .. ceil(n_new / 2^l) - 1; only those are stored (the table's segments hold them, segment entry i = node
+// s_l + i). The one older node that work reads is node(l, s_l - 1) for odd s_l, the level's seed: the old path's entry l when
+// n_old mod 2^l != 0, else (l = ctz(n_old)) the last leaf's ancestor a_l, a_0 = last leaf, a_{j+1} = hash(path[j], a_j). That
+// chain is one extra lane per tree in each level pass (pass l -> l + 1 computes a_{l+1} while l < ctz(n_old)), never a fold of
+// its own. Building a tree from its leaves is the append to the empty state: n_old = 0, so s_l = 0, every node of the tree is
+// computed, no level has a seed and no chain runs; the old state is then read only for a tree that stays empty (its current path
+// and last leaf are copied through), so it must be device memory all the same.
 #pragma once
 #include "engine.h"
 #include "fp_dev.h"
@@ -30,41 +33,40 @@
 
 namespace mg {
 
-// the device side of one append to a forest (APPEND_*): the old state, the kept recomputed nodes and their table
-struct MerkleAppend {
-    const u64 *n_old, *n_new; // [n_trees] leaf counts before and after
+// the device side of one pass over a forest: the state it starts from, the nodes it computes and their table
+struct MerkleForest {
+    const u64 *n_old, *n_new; // [n_trees] leaf counts before and after (a build: n_old = 0)
     const u32 *last, *cur;    // the old state: last leaves [n_trees], current paths [n_trees][height - 1]
-    u32 *anc;                 // [n_trees] the ancestor chain: starts as a copy of `last`, ends as a_ctz(n_old)
+    u32 *anc;                 // [n_trees] the ancestor chain: starts as a copy of `last`, ends as a_ctz(n_old); the top kernel
+                              // carries it through LDS for every tree, whether its chain runs or not
     u32 *nodes;               // every recomputed node, level after level
     const u64 *off;           // [height][n_trees + 1] absolute segment offsets into `nodes`
     int n_trees, height;
 };
 
-// keys | mds | tag in Montgomery words of 8 x u32 per element
-struct PoseidonLaunch {
-    enum Op { PERMUTE = 0, HASH = 1, LEVEL = 2, TOP = 3, PATHS = 4, APPEND_LEVEL = 5, APPEND_TOP = 6, APPEND_GATHER = 7 };
-    int op, width, half_full, partial;
-    const u32 *prm;      // device parameters
-    const u32 *in;       // PERMUTE: n states (in place, = out); HASH: n x (t - 1) inputs; LEVEL / TOP: the source level
-    u32 *out;            // PERMUTE: states; HASH: n digests; LEVEL: the next level; PATHS: k x (height - 1) digests
-    size_t n;            // states / digests / parents of the level / paths
-    const u64 *src_off;  // LEVEL: offsets of the source level; TOP / PATHS: the whole table
-    const u64 *dst_off;  // LEVEL: offsets of the destination level
-    int n_trees, level, height;
-    u32 *keep;           // TOP: where the levels above `level` are written (the table's absolute offsets), or null
-    u32 *roots;          // TOP: n_trees roots
-    const u64 *indices;  // PATHS: leaf indices; APPEND_GATHER: the requests' leaf indices
-    // APPEND_LEVEL: level -> level + 1 over n parents and the chain lanes; APPEND_TOP: finishes from `level`, roots; APPEND_GATHER:
-    // n requests (trees `req_trees`, leaves `indices`) then one per tree for its new current path -> out [n + n_trees] paths,
-    // and the new last leaves -> roots
-    MerkleAppend app;
-    const u64 *req_trees;
-    hipStream_t stream;
+// a hasher on the device: keys | mds | tag in Montgomery words of 8 x u32 per element, and its shape
+struct PoseidonDev {
+    const u32 *prm;
+    int width, half_full, partial;
 };
-hipError_t poseidon_launch_bn254(const PoseidonLaunch &a);
-hipError_t poseidon_launch_bls381(const PoseidonLaunch &a);
 
-constexpr int MERKLE_TOP = 1024; // a level of at most this many nodes per tree is finished in LDS by merkle_top_kernel
+// One launch function per kernel: device pointers, on `s`; nothing is launched for no lanes. Defined below, compiled only where
+// they are instantiated (poseidon_bn254.hip, poseidon_bls381.hip): every other unit sees the declarations alone.
+template <class C> struct PoseidonKernels {
+    static hipError_t permute(hipStream_t s, const PoseidonDev &h, u32 *states, size_t n); // in place; width 3..6
+    static hipError_t hash(hipStream_t s, const PoseidonDev &h, const u32 *in, size_t n, u32 *digests);
+    // level l -> l + 1 of every tree: n_parents = all nodes of level l + 1 in the table
+    static hipError_t merkle_level(hipStream_t s, const PoseidonDev &h, const MerkleForest &t, int l, size_t n_parents);
+    // levels l0 .. height - 1 of every tree, each with at most MERKLE_TOP nodes on level l0; roots [n_trees]
+    static hipError_t merkle_top(hipStream_t s, const PoseidonDev &h, const MerkleForest &t, int l0, u32 *roots);
+    // paths [n_req + n_trees][height - 1]: the requests' (tree, leaf index), refreshed in place, then the new current paths
+    static hipError_t merkle_gather(hipStream_t s, const MerkleForest &t, const u64 *req_trees, const u64 *req_idx, size_t n_req,
+                                    u32 *paths, u32 *new_last);
+};
+extern template struct PoseidonKernels<Bn254FrCfg>;
+extern template struct PoseidonKernels<Bls381FrCfg>;
+
+constexpr int MERKLE_TOP = 1024; // a level of at most this many nodes per tree is finished in LDS by pos::merkle_top
 constexpr int POSEIDON_BLOCK = 256;
 
 namespace pos {
@@ -165,93 +167,21 @@ MG_DEV int tree_of(const u64 *__restrict__ off, int n_trees, u64 e) {
     return lo;
 }
 
-// one level of every tree: parent j of tree k = hash(child 2j, child 2j + 1 or 0 when absent); one lane per parent
-template <class C>
-__global__ __launch_bounds__(POSEIDON_BLOCK) void level_kernel(const u32 *__restrict__ prm, int hf, int partial,
-                                                               const u32 *__restrict__ src, const u64 *__restrict__ src_off,
-                                                               u32 *__restrict__ dst, const u64 *__restrict__ dst_off, int n_trees,
-                                                               size_t n_parents) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_parents) return;
-    const u64 e = dst_off[0] + i;
-    const int k = tree_of(dst_off, n_trees, e);
-    const u64 j = e - dst_off[k], c = src_off[k + 1] - src_off[k];
-    const u32 *ch = src + (src_off[k] + 2 * j) * 8;
-    const Fp<C> l = Fp<C>::load(ch);
-    const Fp<C> r = 2 * j + 1 < c ? Fp<C>::load(ch + 8) : Fp<C>::zero();
-    hash2<C>(l, r, prm, hf, partial).store(dst + e * 8);
-}
-
-// the top of each tree, one block per tree: level `l0` (at most MERKLE_TOP nodes per tree) is loaded into LDS and reduced
-// level by level to the root, two parents per lane; with `keep` every level above l0 is also written to its place in the table
-template <class C>
-__global__ __launch_bounds__(POSEIDON_BLOCK) void top_kernel(const u32 *__restrict__ prm, int hf, int partial,
-                                                             const u32 *__restrict__ src, const u64 *__restrict__ off, int n_trees,
-                                                             int l0, int height, u32 *__restrict__ keep, u32 *__restrict__ roots) {
-    __shared__ u32 lds[MERKLE_TOP * 8];
-    const int k = blockIdx.x, tid = threadIdx.x;
-    const size_t stride = (size_t)n_trees + 1;
-    const u64 base = off[l0 * stride + k];
-    u32 c = (u32)(off[l0 * stride + k + 1] - base);
-#pragma unroll 1
-    for (u32 j = tid; j < c; j += POSEIDON_BLOCK) Fp<C>::load(src + (base + j) * 8).store(lds + j * 8);
-    __syncthreads();
-#pragma unroll 1
-    for (int l = l0; l < height - 1; ++l) {
-        const u32 cp = (c + 1) >> 1;
-        Fp<C> h[MERKLE_TOP / 2 / POSEIDON_BLOCK];
-#pragma unroll 1
-        for (int q = 0; q < MERKLE_TOP / 2 / POSEIDON_BLOCK; ++q) {
-            const u32 j = tid + q * POSEIDON_BLOCK;
-            if (j < cp) {
-                const Fp<C> a = Fp<C>::load(lds + 2 * j * 8);
-                const Fp<C> b = 2 * j + 1 < c ? Fp<C>::load(lds + (2 * j + 1) * 8) : Fp<C>::zero();
-                h[q] = hash2<C>(a, b, prm, hf, partial);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < MERKLE_TOP / 2 / POSEIDON_BLOCK; ++q) {
-            const u32 j = tid + q * POSEIDON_BLOCK;
-            if (j < cp) {
-                h[q].store(lds + j * 8);
-                if (keep) h[q].store(keep + (off[(l + 1) * stride + k] + j) * 8);
-            }
-        }
-        __syncthreads();
-        c = cp;
-    }
-    if (tid == 0) (c ? Fp<C>::load(lds) : Fp<C>::zero()).store(roots + (size_t)k * 8);
-}
-
-// manta's Path of leaf idx: sibling of its ancestor on levels 0 .. height - 2, 0 where absent; one lane per (path, level)
-template <class C>
-__global__ __launch_bounds__(POSEIDON_BLOCK) void paths_kernel(const u32 *__restrict__ levels, const u64 *__restrict__ off,
-                                                               int height, const u64 *__restrict__ idx, size_t k,
-                                                               u32 *__restrict__ out) {
-    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int len = height - 1;
-    if (g >= k * (size_t)len) return;
-    const size_t q = g / len;
-    const int l = (int)(g % len);
-    const u64 s = (idx[q] >> l) ^ 1, lo = off[2 * l], c = off[2 * l + 1] - lo;
-    (s < c ? Fp<C>::load(levels + (lo + s) * 8) : Fp<C>::zero()).store(out + g * 8);
-}
-
-// ---- appending: the same three steps over the recomputed ranges only ------------------------------------------------------
+// ---- the trees: level passes, the finish in LDS, the gather -- all over the recomputed ranges (a build: the whole tree) -------
 MG_DEV u64 nodes_end(u64 n, int l) { return (n + ((u64)1 << l) - 1) >> l; } // ceil(n / 2^l)
-// does pass l -> l + 1 advance tree's ancestor chain: l < ctz(n_old)
+// does pass l -> l + 1 advance tree's ancestor chain: l < ctz(n_old); never for n_old = 0
 MG_DEV bool chain_runs(u64 n_old, int l) { return n_old && !(n_old & (((u64)2 << l) - 1)); }
 // node(l, s_l - 1) of tree k for odd s_l; `anc` is where the chain stands (t.anc, or the top kernel's copy in LDS)
-template <class C> MG_DEV Fp<C> seed_of(const MerkleAppend &t, int k, int l, u64 n_old, const u32 *anc) {
+template <class C> MG_DEV Fp<C> seed_of(const MerkleForest &t, int k, int l, u64 n_old, const u32 *anc) {
     return Fp<C>::load(n_old & (((u64)1 << l) - 1) ? t.cur + ((size_t)k * (t.height - 1) + l) * 8 : anc);
 }
 
-// level l -> l + 1 of every tree's recomputed range, one lane per parent: a left child one below the segment start is the
-// level's seed; after the parents one lane per tree hashes the next link of its chain
+// level l -> l + 1 of every tree's recomputed range, one lane per parent: parent = hash(left child, right child or 0 past the
+// level's end), a left child one below the segment start being the level's seed (n_old = 0: s_l = 0, the left child is always in
+// the segment); after the parents one lane per tree hashes the next link of its chain
 template <class C>
-__global__ __launch_bounds__(POSEIDON_BLOCK) void append_level_kernel(const u32 *__restrict__ prm, int hf, int partial,
-                                                                      MerkleAppend t, int l, size_t n_parents) {
+__global__ __launch_bounds__(POSEIDON_BLOCK) void merkle_level(const u32 *__restrict__ prm, int hf, int partial, MerkleForest t,
+                                                               int l, size_t n_parents) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_parents + t.n_trees) return;
     Fp<C> a, b;
@@ -277,19 +207,19 @@ __global__ __launch_bounds__(POSEIDON_BLOCK) void append_level_kernel(const u32 
     hash2<C>(a, b, prm, hf, partial).store(dst);
 }
 
-// the finish of each tree in LDS, one block per tree, from level `l0` (at most MERKLE_TOP recomputed nodes per tree): levels
-// alternate between two LDS buffers, every level is also written to its segment (the gather reads it), and the chain is one
-// more item of a level while it runs
-constexpr int APPEND_LDS_B = MERKLE_TOP, APPEND_LDS_ANC = MERKLE_TOP + MERKLE_TOP / 2 + 8; // a level above l0 has <= TOP / 2 + 1
+// the finish of each tree in LDS, one block per tree, from level `l0` (at most MERKLE_TOP recomputed nodes per tree) to the
+// root, instead of up to 19 tiny launches: levels alternate between two LDS buffers, every level is also written to its segment
+// (the gather reads it), and the chain is one more item of a level while it runs
+constexpr int TOP_LDS_B = MERKLE_TOP, TOP_LDS_ANC = MERKLE_TOP + MERKLE_TOP / 2 + 8; // a level above l0 has <= TOP / 2 + 1
 template <class C>
-__global__ __launch_bounds__(POSEIDON_BLOCK) void append_top_kernel(const u32 *__restrict__ prm, int hf, int partial,
-                                                                    MerkleAppend t, int l0, u32 *__restrict__ roots) {
-    __shared__ u32 lds[(APPEND_LDS_ANC + 1) * 8];
+__global__ __launch_bounds__(POSEIDON_BLOCK) void merkle_top(const u32 *__restrict__ prm, int hf, int partial, MerkleForest t,
+                                                             int l0, u32 *__restrict__ roots) {
+    __shared__ u32 lds[(TOP_LDS_ANC + 1) * 8];
     const int k = blockIdx.x, tid = threadIdx.x;
     const size_t stride = (size_t)t.n_trees + 1;
     const u64 n_old = t.n_old[k], n_new = t.n_new[k];
-    u32 *const anc = lds + APPEND_LDS_ANC * 8;
-    u32 src = 0, dst = APPEND_LDS_B * 8; // word offsets of the level read and the level written
+    u32 *const anc = lds + TOP_LDS_ANC * 8;
+    u32 src = 0, dst = TOP_LDS_B * 8; // word offsets of the level read and the level written
     const u64 base = t.off[l0 * stride + k];
     u32 c = (u32)(t.off[l0 * stride + k + 1] - base);
 #pragma unroll 1
@@ -330,14 +260,14 @@ __global__ __launch_bounds__(POSEIDON_BLOCK) void append_top_kernel(const u32 *_
     }
 }
 
-// one lane per (request, level): entry l of the Path of leaf idx in the new tree is 0 past the level's last node, a recomputed
-// node from s_l on, the level's seed for a new leaf, and otherwise -- an older leaf's older sibling -- left as it is in `out`.
-// Requests n_req .. n_req + n_trees - 1 are the trees' new current paths (the old one when nothing was appended); the last
-// n_trees lanes write the new last leaves.
+// manta's Path of leaf idx: the sibling of its ancestor on levels 0 .. height - 2. One lane per (request, level): entry l in the
+// new tree is 0 past the level's last node, a recomputed node from s_l on (n_old = 0: every node), the level's seed for a new
+// leaf, and otherwise -- an older leaf's older sibling -- left as it is in `out`. Requests n_req .. n_req + n_trees - 1 are the
+// trees' new current paths (the old one when nothing was appended); the last n_trees lanes write the new last leaves.
 template <class C>
-__global__ __launch_bounds__(POSEIDON_BLOCK) void append_gather_kernel(MerkleAppend t, const u64 *__restrict__ req_trees,
-                                                                       const u64 *__restrict__ req_idx, size_t n_req,
-                                                                       u32 *__restrict__ out, u32 *__restrict__ new_last) {
+__global__ __launch_bounds__(POSEIDON_BLOCK) void merkle_gather(MerkleForest t, const u64 *__restrict__ req_trees,
+                                                                const u64 *__restrict__ req_idx, size_t n_req,
+                                                                u32 *__restrict__ out, u32 *__restrict__ new_last) {
     const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int len = t.height - 1;
     const size_t entries = (n_req + t.n_trees) * (size_t)len;
@@ -366,62 +296,52 @@ __global__ __launch_bounds__(POSEIDON_BLOCK) void append_gather_kernel(MerkleApp
 
 } // namespace pos
 
-template <class C> hipError_t poseidon_launch(const PoseidonLaunch &a) {
-    const auto grid = [](size_t n) { return dim3((unsigned)((n + POSEIDON_BLOCK - 1) / POSEIDON_BLOCK)); };
-    const dim3 blk(POSEIDON_BLOCK);
-    switch (a.op) {
-    case PoseidonLaunch::PERMUTE:
-    case PoseidonLaunch::HASH: {
-        if (a.n == 0) return hipSuccess;
-#define MG_POSEIDON_WIDTH(T)                                                                                                     \
-    case T:                                                                                                                      \
-        if (a.op == PoseidonLaunch::PERMUTE)                                                                                     \
-            hipLaunchKernelGGL((pos::permute_kernel<C, T>), grid(a.n), blk, 0, a.stream, a.prm, a.half_full, a.partial, a.out,   \
-                               a.n);                                                                                             \
-        else                                                                                                                     \
-            hipLaunchKernelGGL((pos::hash_kernel<C, T>), grid(a.n), blk, 0, a.stream, a.prm, a.half_full, a.partial, a.in, a.n,  \
-                               a.out);                                                                                           \
-        break;
-        switch (a.width) {
-            MG_POSEIDON_WIDTH(3)
-            MG_POSEIDON_WIDTH(4)
-            MG_POSEIDON_WIDTH(5)
-            MG_POSEIDON_WIDTH(6)
-        default: return hipErrorInvalidValue;
-        }
-#undef MG_POSEIDON_WIDTH
-        break;
-    }
-    case PoseidonLaunch::LEVEL:
-        if (a.n == 0) return hipSuccess;
-        hipLaunchKernelGGL((pos::level_kernel<C>), grid(a.n), blk, 0, a.stream, a.prm, a.half_full, a.partial, a.in, a.src_off,
-                           a.out, a.dst_off, a.n_trees, a.n);
-        break;
-    case PoseidonLaunch::TOP:
-        if (a.n_trees == 0) return hipSuccess;
-        hipLaunchKernelGGL((pos::top_kernel<C>), dim3((unsigned)a.n_trees), blk, 0, a.stream, a.prm, a.half_full, a.partial, a.in,
-                           a.src_off, a.n_trees, a.level, a.height, a.keep, a.roots);
-        break;
-    case PoseidonLaunch::PATHS:
-        if (a.n == 0) return hipSuccess;
-        hipLaunchKernelGGL((pos::paths_kernel<C>), grid(a.n * (size_t)(a.height - 1)), blk, 0, a.stream, a.in, a.src_off,
-                           a.height, a.indices, a.n, a.out);
-        break;
-    case PoseidonLaunch::APPEND_LEVEL:
-        hipLaunchKernelGGL((pos::append_level_kernel<C>), grid(a.n + a.app.n_trees), blk, 0, a.stream, a.prm, a.half_full, a.partial,
-                           a.app, a.level, a.n);
-        break;
-    case PoseidonLaunch::APPEND_TOP:
-        hipLaunchKernelGGL((pos::append_top_kernel<C>), dim3((unsigned)a.app.n_trees), blk, 0, a.stream, a.prm, a.half_full,
-                           a.partial, a.app, a.level, a.roots);
-        break;
-    case PoseidonLaunch::APPEND_GATHER:
-        hipLaunchKernelGGL((pos::append_gather_kernel<C>), grid((a.n + a.app.n_trees) * (size_t)a.app.height), blk, 0, a.stream,
-                           a.app, a.req_trees, a.indices, a.n, a.out, a.roots);
-        break;
+// ---- the launch functions --------------------------------------------------------------------------------------------------
+// `kernel` over `lanes` lanes in blocks of POSEIDON_BLOCK; nothing is launched for none
+template <class Kernel, class... Args> hipError_t poseidon_lanes(Kernel kernel, hipStream_t s, size_t lanes, Args... args) {
+    if (lanes == 0) return hipSuccess;
+    kernel<<<dim3((unsigned)((lanes + POSEIDON_BLOCK - 1) / POSEIDON_BLOCK)), dim3(POSEIDON_BLOCK), 0, s>>>(args...);
+    return hipGetLastError();
+}
+
+template <class C> hipError_t PoseidonKernels<C>::permute(hipStream_t s, const PoseidonDev &h, u32 *states, size_t n) {
+    switch (h.width) {
+    case 3: return poseidon_lanes(pos::permute_kernel<C, 3>, s, n, h.prm, h.half_full, h.partial, states, n);
+    case 4: return poseidon_lanes(pos::permute_kernel<C, 4>, s, n, h.prm, h.half_full, h.partial, states, n);
+    case 5: return poseidon_lanes(pos::permute_kernel<C, 5>, s, n, h.prm, h.half_full, h.partial, states, n);
+    case 6: return poseidon_lanes(pos::permute_kernel<C, 6>, s, n, h.prm, h.half_full, h.partial, states, n);
     default: return hipErrorInvalidValue;
     }
+}
+
+template <class C>
+hipError_t PoseidonKernels<C>::hash(hipStream_t s, const PoseidonDev &h, const u32 *in, size_t n, u32 *digests) {
+    switch (h.width) {
+    case 3: return poseidon_lanes(pos::hash_kernel<C, 3>, s, n, h.prm, h.half_full, h.partial, in, n, digests);
+    case 4: return poseidon_lanes(pos::hash_kernel<C, 4>, s, n, h.prm, h.half_full, h.partial, in, n, digests);
+    case 5: return poseidon_lanes(pos::hash_kernel<C, 5>, s, n, h.prm, h.half_full, h.partial, in, n, digests);
+    case 6: return poseidon_lanes(pos::hash_kernel<C, 6>, s, n, h.prm, h.half_full, h.partial, in, n, digests);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+template <class C>
+hipError_t PoseidonKernels<C>::merkle_level(hipStream_t s, const PoseidonDev &h, const MerkleForest &t, int l, size_t n_parents) {
+    return poseidon_lanes(pos::merkle_level<C>, s, n_parents + t.n_trees, h.prm, h.half_full, h.partial, t, l, n_parents);
+}
+
+template <class C>
+hipError_t PoseidonKernels<C>::merkle_top(hipStream_t s, const PoseidonDev &h, const MerkleForest &t, int l0, u32 *roots) {
+    if (t.n_trees == 0) return hipSuccess;
+    pos::merkle_top<C><<<dim3((unsigned)t.n_trees), dim3(POSEIDON_BLOCK), 0, s>>>(h.prm, h.half_full, h.partial, t, l0, roots);
     return hipGetLastError();
+}
+
+template <class C>
+hipError_t PoseidonKernels<C>::merkle_gather(hipStream_t s, const MerkleForest &t, const u64 *req_trees, const u64 *req_idx,
+                                             size_t n_req, u32 *paths, u32 *new_last) {
+    const size_t lanes = (n_req + t.n_trees) * (size_t)(t.height - 1) + t.n_trees;
+    return poseidon_lanes(pos::merkle_gather<C>, s, lanes, t, req_trees, req_idx, n_req, paths, new_last);
 }
 
 } // namespace mg

@@ -1,5 +1,5 @@
 // Poseidon and Merkle-tree kernels instantiated over the BN254 scalar field.
 #include "poseidon.h"
 namespace mg {
-hipError_t poseidon_launch_bn254(const PoseidonLaunch &a) { return poseidon_launch<Bn254FrCfg>(a); }
+template struct PoseidonKernels<Bn254FrCfg>;
 } // namespace mg

@@ -6,6 +6,7 @@ import threading
 import numpy as np
 import pytest
 
+import merkle_append_ref as A
 import poseidon_ref as P
 from manta_rs_amd import synth
 from test_poseidon_host import POS, bls_kat_params
@@ -108,13 +109,13 @@ def test_batch_across_a_chunk_boundary(gpu, name):
     assert (d_out.to_numpy(shape=(n, 4)) == dig).all()
 
 
-def check_tree(gpu, h, p, height, leaves_int, n, idx):
+def check_tree(gpu, h, p, height, leaves_int, n, idx, r=R):
     ref = P.Tree(p, leaves_int)
-    root, paths = gpu.merkle_tree(h, height, mont(leaves_int[:n]).reshape(n, 4), indices=idx)
+    root, paths = gpu.merkle_tree(h, height, mont(leaves_int[:n], r).reshape(n, 4), indices=idx)
     want = ref.root(height, n)
-    assert ints(root) == [want], (height, n)
+    assert ints(root, r) == [want], (height, n)
     for q, i in enumerate(idx):
-        path = ints(paths[q])
+        path = ints(paths[q], r)
         assert path == ref.path(height, n, i), (height, n, i)
         assert P.fold(p, leaves_int[i], i, path) == want, (height, n, i)
     return want
@@ -146,6 +147,30 @@ def test_small_trees_up_to_full_capacity(gpu, height):
     for n in range(cap + 1):
         idx = list(range(n)) if height < 8 else sorted({0, n - 1, n // 2, (3 * n) // 4}) if n else []
         check_tree(gpu, h, p, height, leaves, n, idx)
+
+
+def test_full_capacity_under_the_level_launch(gpu):
+    """height 12 at and one below its capacity: level 0 has more than 1 024 nodes, so one level launch runs before the finish
+    in LDS, which starts at level 1 with 1 024 nodes, its most"""
+    data, p = P.load(MODEL)
+    h = gpu.PoseidonHasher.decode(gpu.BN254, data)
+    p = A.Memo(p)  # the two trees share every node over the first 2 046 leaves
+    leaves = rand_ints(2048, seed=12)
+    for n in (2047, 2048):
+        check_tree(gpu, h, p, 12, leaves, n, sorted({0, 1023, 1024, n - 2, n - 1}))
+
+
+def test_bls12_381_trees_and_forest(gpu):
+    """the build on the other field: every tree of height 3 with every path, then the five trees as one forest"""
+    r = P.R_BLS381
+    p = bls_kat_params()
+    h = gpu.PoseidonHasher(gpu.BLS12_381, 3, 8, 55, p.encode())
+    leaves = rand_ints(4, seed=3810, r=r)
+    want = [check_tree(gpu, h, p, 3, leaves, n, list(range(n)), r=r) for n in range(5)]
+    assert want[0] == 0 and len(set(want)) == 5
+    off = np.concatenate([[0], np.cumsum(range(5))]).astype(np.uint64)
+    roots = gpu.merkle_forest_roots(h, 3, mont([x for n in range(5) for x in leaves[:n]], r).reshape(-1, 4), off)
+    assert ints(roots, r) == want
 
 
 def test_full_tree_of_2_19_leaves(gpu):
@@ -208,6 +233,24 @@ def test_forests(gpu):
     for k in range(256):
         r1, _ = gpu.merkle_tree(h, 20, lv[int(off2[k]):int(off2[k + 1])])
         assert (roots2[k] == r1).all(), k
+
+
+def test_forest_with_two_level_launches(gpu):
+    """tree 0 has 2 049 leaves, 1 025 nodes on level 1 and 513 on level 2, so two level launches run before the finish in LDS,
+    beside an empty tree, a single leaf, a tree with one level launch of its own and a pair; the roots as a build, then roots
+    and states as an append to the empty forest, both against the restatement"""
+    data, p = P.load(MODEL)
+    h = gpu.PoseidonHasher.decode(gpu.BN254, data)
+    H, counts = 20, [2049, 0, 1, 1025, 2]
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+    leaves = rand_ints(int(off[-1]), seed=2049)
+    trees = [P.Tree(p, leaves[int(off[k]):int(off[k + 1])]) for k in range(5)]
+    want = [t.root(H, n) for t, n in zip(trees, counts)]
+    lv = mont(leaves).reshape(-1, 4)
+    assert ints(gpu.merkle_forest_roots(h, H, lv, off)) == want
+    roots, state, _, _ = gpu.merkle_forest_append(h, H, gpu.MerkleState.empty(5, H), lv, off)
+    assert ints(roots) == want
+    assert A.unpack_state(state) == [A.state_of(t, H, n) for t, n in zip(trees, counts)]
 
 
 def test_concurrent_callers(gpu):
