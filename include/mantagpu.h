@@ -553,9 +553,34 @@ int mg_groth16_verify(const mg_vk *vk, const uint64_t *inputs_mont, const uint64
  * lambda the eigenvalue of G1's endomorphism (x, y) -> (beta x, y): 2^128 - 1 distinct non-zero values, and k_i A_i
  * then costs 64 doublings instead of 128. k + 3 Miller loops (two wavefronts each), k scalar multiplications, two small
  * MSMs and one final exponentiation. *ok = 1 iff ALL k proofs verify (up to the 2^-128 soundness error of the
- * combination); on 0 fall back to mg_groth16_verify to find the offender. */
+ * combination); on 0 call mg_groth16_verify_each on the same rows to find the offenders: one pass over the block, not k
+ * single verifications. */
 int mg_groth16_verify_batch(const mg_vk *vk, uint64_t k, const uint64_t *inputs_mont, const uint64_t *proof_points,
                             const uint64_t *rand128, int *ok);
+/* ---- a verdict per item: many small independent pairing products in one pass. The pairs of MG_VERIFY_EACH_CHUNK groups
+ *      go through ONE Miller-loop launch (two wavefronts per pair) and ONE launch of a wavefront per group that multiplies
+ *      the group's Miller values, runs the final exponentiation and compares on the device; only the verdict bytes come
+ *      back. Larger calls run chunk after chunk, so device and pinned memory of a call do not depend on the count: per
+ *      pair 0.7 KB (BN254) / 1.1 KB (BLS12-381) of pooled workspace (G1, G2, coefficient pointer, flag, the Miller value
+ *      and its share of a scratch array), i.e. at most 2.8 / 4.1 MB for the three pairs of a proof and 59 / 88 MB at the
+ *      largest group size, the pool's growth margin of a quarter included; plus for mg_groth16_verify_each the pooled workspace of one MSM of
+ *      MG_VERIFY_EACH_CHUNK x n_inputs scalars. Synchronous, thread-safe, re-entrant; pooled workspaces and streams only
+ *      (no allocation per call once the pool is warm, nothing on the NULL stream). The time does not depend on the
+ *      verdicts, and the return value reports operational failures only. */
+#define MG_VERIFY_EACH_CHUNK 1024u
+/* n_groups independent mg_pairing_check's of group_size pairs each: ok[t] = 1 iff prod_j e(P[t][j], Q[t][j]) == 1.
+ * g1_affine / g2_affine: [n_groups][group_size] points, group-major as a caller holds them. n_groups = 0 succeeds and
+ * writes nothing; group_size = 0 or above 64, or a NULL array with n_groups > 0: MG_ERROR_INVALID_ARGUMENT. */
+int mg_pairing_check_each(mg_curve_t curve, const uint64_t *g1_affine, const uint64_t *g2_affine, size_t group_size,
+                          size_t n_groups, uint8_t *ok);
+/* k proofs against one key, a verdict each: ok[i] is exactly what mg_groth16_verify would answer for row i (rows with
+ * points at infinity included). inputs_mont and proof_points as for mg_groth16_verify_batch. The prepared inputs of a chunk
+ * are one batched MSM over the key's tables, folded on the device and read there by the Miller loops. Where an MSM launch
+ * takes fewer scalar vectors than the chunk (65 535 vectors, 2^31 digit pairs, a key space of 2^24) the chunk shrinks to
+ * that. k = 0 succeeds and writes nothing; k above 2^20, a NULL array, or inputs_mont = NULL with n_inputs > 1:
+ * MG_ERROR_INVALID_ARGUMENT before any device work. */
+int mg_groth16_verify_each(const mg_vk *vk, uint64_t k, const uint64_t *inputs_mont, const uint64_t *proof_points,
+                           uint8_t *ok);
 /* prod_i e(P_i, Q_i) == 1 ? -- the pairing-product test behind `PairingEngineExt::has_same` / `same_ratio`
  * (manta-crypto/src/arkworks/pairing.rs:88-109), which the trusted-setup verifier applies to random linear
  * combinations of whole queries (`verify_transform`, manta-trusted-setup/src/groth16/mpc.rs:470-508). P_i affine

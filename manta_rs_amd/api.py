@@ -83,6 +83,7 @@ EXPORTS = [
     "mg_blake2s", "mg_aes256_gcm", "mg_address_partitions", "mg_merkle_shard_indices",
     "mg_light_notes_encrypt", "mg_light_notes_open", "mg_outgoing_notes_encrypt", "mg_outgoing_notes_open",
     "mg_qap_columns", "mg_mpc_initialize", "mg_fpr_raw_op", "mg_fpr_column_plan",
+    "mg_pairing_check_each", "mg_groth16_verify_each",
 ]
 
 
@@ -1715,3 +1716,46 @@ def groth16_verify_batch(context: VerifyingContext, inputs, proofs, rand128) -> 
     _chk(LIB.mg_groth16_verify_batch(context.handle, ctypes.c_uint64(k), _p(inp), _p(_u64(pts)), _p(rnd), ctypes.byref(ok)),
          "mg_groth16_verify_batch")
     return bool(ok.value)
+
+
+VERIFY_EACH_CHUNK = 1024  # MG_VERIFY_EACH_CHUNK: proofs / pairing groups per device pass of the *_each calls
+
+
+def _verdicts(n, out):
+    """the byte array a *_each call writes its n verdicts to: the caller's (uint8, at least n) or a fresh one"""
+    if out is None:
+        return np.zeros(n, dtype=np.uint8)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < n:
+        raise ValueError("out: a contiguous uint8 array of at least one byte per verdict")
+    return out
+
+
+def groth16_verify_each(context: VerifyingContext, inputs, proofs, out=None) -> np.ndarray:
+    """k proofs of one key, a verdict each (`mg_groth16_verify_each`): element i is what `groth16_verify` answers for
+    (inputs[i], proofs[i]), in one pass over the block. inputs [k, P - 1, 4] (None or empty for a key without public inputs),
+    proofs = k proof byte strings or [k, limbs] points. The verdicts are also written to `out` (uint8) when given."""
+    k = len(proofs)
+    n_in = context.num_inputs - 1
+    inp = np.zeros((k, 0, 4), dtype=np.uint64) if inputs is None else _u64(inputs)
+    if inp.size != k * n_in * 4:
+        raise ValueError(f"{inp.size // 4} public inputs for {k} proofs, the key takes {n_in} each")
+    inp = inp.reshape(k, n_in, 4)
+    ok = _verdicts(k, out)
+    pts = _u64(np.stack([_proof_points(context.curve, p) for p in proofs])) if k else np.zeros((0, 1), dtype=np.uint64)
+    _chk(LIB.mg_groth16_verify_each(context.handle, ctypes.c_uint64(k), _p(inp) if n_in and k else None, _p(pts) if k else None,
+                                    _p(ok)), "mg_groth16_verify_each")
+    return ok[:k].astype(bool)
+
+
+def pairing_check_each(curve, g1_points, g2_points, out=None) -> np.ndarray:
+    """n_groups independent `pairing_check`s in one pass (`mg_pairing_check_each`): g1_points [n_groups, group_size, 2 * limbs],
+    g2_points [n_groups, group_size, 4 * limbs] affine Montgomery; element t says whether prod_j e(P[t][j], Q[t][j]) == 1."""
+    g1, g2 = _u64(g1_points), _u64(g2_points)
+    if g1.ndim != 3 or g2.ndim != 3 or g1.shape[:2] != g2.shape[:2] or g1.shape[2] != affine_limbs(curve, 1) or \
+            g2.shape[2] != affine_limbs(curve, 2):
+        raise ValueError("pairing_check_each: [n_groups, group_size, limbs] arrays, as many G1 as G2 points")
+    n, g = g1.shape[:2]
+    ok = _verdicts(n, out)
+    _chk(LIB.mg_pairing_check_each(curve, _p(g1) if n else None, _p(g2) if n else None, ctypes.c_size_t(g), ctypes.c_size_t(n),
+                                   _p(ok)), "mg_pairing_check_each")
+    return ok[:n].astype(bool)

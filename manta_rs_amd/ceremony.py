@@ -8,6 +8,7 @@ manta-trusted-setup's hot loops, every group operation through the C ABI (`mg_ec
     lagrange_basis / initialize groth16/mpc.rs:355-431                    group-domain IFFTs of the powers, then the QAP sums (`mg_mpc_initialize`)
     merge_pairs_affine          util.rs:314-332                           one random linear combination of two point vectors (2 MSMs)
     same_ratio                  manta-crypto/src/arkworks/pairing.rs:88-109   e(a0, b1) == e(a1, b0) as one pairing product (`mg_pairing_check`)
+    same_each                   pairing.rs `same`, for a list of pairs        one verdict each in one pass (`mg_pairing_check_each`)
     check_transform             groth16/mpc.rs:487-508                    the verifier's consistency checks of one contribution
     power_pairs / check_powers  util.rs:333-346, groth16/kzg.rs:508-521   consecutive powers differ by one ratio (kzg verifier)
     state_check                 groth16/mpc.rs:79-100                     every point of a proving key on the curve and in the subgroup
@@ -101,6 +102,17 @@ def same(curve, lhs, rhs) -> bool:
     (a, b), (c, d) = lhs, rhs
     return api.pairing_check(curve, np.stack([np.asarray(a, dtype=np.uint64).reshape(-1), g1_neg(curve, c)]),
                              np.stack([np.asarray(b, dtype=np.uint64).reshape(-1), np.asarray(d, dtype=np.uint64).reshape(-1)]))
+
+
+def same_each(curve, pairs) -> np.ndarray:
+    """`same` for a list of ((a, b), (c, d)): one bool each, all in one pass over the GPU (`mg_pairing_check_each` with groups
+    of two pairs) -- the shape of a verifier's four to eight consistency checks, which `same` runs one latency chain at a time."""
+    flat = lambda p: np.asarray(p, dtype=np.uint64).reshape(-1)
+    if len(pairs) == 0:
+        return np.zeros(0, dtype=bool)
+    g1 = np.stack([np.stack([flat(a), g1_neg(curve, c)]) for (a, _), (c, _) in pairs])
+    g2 = np.stack([np.stack([flat(b), flat(d)]) for (_, b), (_, d) in pairs])
+    return api.pairing_check_each(curve, g1, g2)
 
 
 def power_pairs(curve, group, points, rho=None):

@@ -878,6 +878,21 @@ MG_API int mg_pairing_check(mg_curve_t curve, const uint64_t *g1_affine, const u
     return pe->product_is_one((const u32 *)g1_affine, (const u32 *)g2_affine, n, ok);
     MG_CATCH
 }
+MG_API int mg_pairing_check_each(mg_curve_t curve, const uint64_t *g1_affine, const uint64_t *g2_affine, size_t group_size,
+                                 size_t n_groups, uint8_t *ok) {
+    MG_TRY
+    PairingEngine *pe = get_pairing_engine((int)curve);
+    if (!pe || group_size == 0 || group_size > 64) return MG_ERROR_INVALID_ARGUMENT;
+    return pe->product_is_one_each((const u32 *)g1_affine, (const u32 *)g2_affine, group_size, n_groups, ok);
+    MG_CATCH
+}
+MG_API int mg_groth16_verify_each(const mg_vk *vk, uint64_t k, const uint64_t *inputs_mont, const uint64_t *proof_points,
+                                  uint8_t *ok) {
+    MG_TRY
+    if (!vk) return MG_ERROR_INVALID_ARGUMENT;
+    return vk->v->verify_each(k, inputs_mont, proof_points, ok);
+    MG_CATCH
+}
 MG_API int mg_proof_decode(mg_curve_t curve, const uint8_t *proof_bytes, uint64_t *points_out) {
     MG_TRY
     return proof_decode((int)curve, proof_bytes, points_out);

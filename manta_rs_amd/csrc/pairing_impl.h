@@ -105,6 +105,34 @@ template <class K> __global__ __launch_bounds__(64) void final_exp_kernel(const 
     if (threadIdx.x < 6) w::ld(PW::R(0) + threadIdx.x).store(out + threadIdx.x * P::F2W);
 }
 
+// workgroup t (one wavefront): verdict[t] = (final_exponentiation(prod_{j < g} in[j * stride + t]) == target), an Fq12 each --
+// the Miller values of a launch whose pairs lie member-major (all first members of the groups, then all second ones, ...).
+// The comparison is on the canonical words the host compares after final_exp_kernel.
+template <class K>
+__global__ __launch_bounds__(64) void pairing_group_tail_kernel(const u32 *__restrict__ in, u32 g, size_t stride,
+                                                                const u32 *__restrict__ target, unsigned char *__restrict__ verdict) {
+    typedef Pairing<K> P;
+    typedef PairingWave<K> PW;
+    typedef PW w;
+    const size_t t = blockIdx.x;
+    if (threadIdx.x < 6) w::st(PW::R(0) + threadIdx.x, P::F2::load(in + t * P::F12W + threadIdx.x * P::F2W));
+    PW::sync();
+    for (u32 j = 1; j < g; ++j) {
+        if (threadIdx.x < 6) w::st(PW::R(1) + threadIdx.x, P::F2::load(in + (j * stride + t) * P::F12W + threadIdx.x * P::F2W));
+        PW::sync();
+        w::mul12(PW::R(0), PW::R(0), PW::R(1));
+    }
+    w::final_exp();
+    u32 diff = 0;
+    if (threadIdx.x < 6) {
+        const typename P::F2 a = w::ld(PW::R(0) + threadIdx.x), b = P::F2::load(target + threadIdx.x * P::F2W);
+#pragma unroll
+        for (int k = 0; k < P::N; ++k) diff |= (a.c0.v[k] ^ b.c0.v[k]) | (a.c1.v[k] ^ b.c1.v[k]);
+    }
+    const bool same = __ballot(diff != 0) == 0;
+    if (threadIdx.x == 0) verdict[t] = same ? 1 : 0;
+}
+
 template <class K> class PairingEngineT : public PairingEngine {
   public:
     typedef Pairing<K> P;
@@ -270,6 +298,48 @@ template <class K> class PairingEngineT : public PairingEngine {
         ws_put(w);
     }
 
+    // n_groups independent products of group_size pairs, a verdict each: ONE Miller launch over all the pairs (begin_impl's
+    // upload, workspace and wait for the producer of the XYZZ prefix), then one tail wavefront per group on the same stream;
+    // only the verdict bytes come back. The pairs lie member-major, so group t owns the Miller values t, n_groups + t, ...
+    int pairing_check_groups(const u32 *p_affine_host, const u32 *d_p_xyzz, size_t n_xyzz, void *producer, const u32 *const *d_coeffs,
+                             const u32 *q_affine_host, const unsigned char *skip, size_t group_size, size_t n_groups,
+                             const u32 *d_target, unsigned char *verdict_host) override {
+        if (!group_size || group_size > 64 || !n_groups || n_groups > MG_VERIFY_EACH_CHUNK || !verdict_host) return MG_ERR_ARG;
+        const size_t n = group_size * n_groups;
+        if (n_xyzz > n || (n_xyzz && (!d_p_xyzz || !producer))) return MG_ERR_ARG;
+        if (!d_target && !(d_target = d_one())) return MG_ERR_OOM;
+        void *h = nullptr;
+        const int rc = begin_impl(p_affine_host, d_coeffs, q_affine_host, skip, n, n, &h, d_p_xyzz, n_xyzz, (hipStream_t)producer);
+        if (rc) return rc;
+        Ws *w = (Ws *)h;
+        unsigned char *dv = w->d + w->o_g; // (the product tree's array: at least 128 bytes per group)
+        hipLaunchKernelGGL((pairing_group_tail_kernel<K>), dim3((unsigned)n_groups), dim3(64), PW::lds_bytes(PW::FINAL_EXP_REGS), w->s,
+                           (const u32 *)(w->d + w->o_f), (u32)group_size, n_groups, d_target, dv);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(w->h, dv, n_groups, hipMemcpyDeviceToHost, w->s);
+        const hipError_t e2 = hipStreamSynchronize(w->s);
+        if (e == hipSuccess) e = e2;
+        if (e == hipSuccess) std::memcpy(verdict_host, w->h, n_groups);
+        ws_put(w);
+        return e == hipSuccess ? MG_OK : hip_status(e, "pairing check groups");
+    }
+    // the Fq12 one in device memory: the target of a plain pairing check (made once per engine)
+    std::mutex one_mu_;
+    u32 *d_one_ = nullptr;
+    const u32 *d_one() {
+        std::lock_guard<std::mutex> g(one_mu_);
+        if (d_one_) return d_one_;
+        u32 one[P::F12W] = {};
+        for (int k = 0; k < P::N; ++k) one[k] = K::Fq::R[k];
+        u32 *d = nullptr;
+        if (hipMalloc((void **)&d, sizeof(one)) != hipSuccess) return nullptr;
+        if (memcpy_sync(d, one, sizeof(one), hipMemcpyHostToDevice) != hipSuccess) {
+            hipFree(d);
+            return nullptr;
+        }
+        return d_one_ = d;
+    }
+
     // ---- workspace pool (per engine = per device and curve)
     struct Ws {
         unsigned char *d = nullptr;
@@ -343,6 +413,34 @@ template <class K> class PairingEngineT : public PairingEngine {
         bool one = true;
         for (int k = 0; k < P::F12W; ++k) one = one && out[k] == (k < P::N ? K::Fq::R[k] : 0u);
         *ok = one ? 1 : 0;
+        return MG_OK;
+    }
+    // product_is_one for n_groups groups of group_size pairs each (host arrays, group-major): MG_VERIFY_EACH_CHUNK groups per
+    // pass, transposed into the member-major order of pairing_check_groups
+    int product_is_one_each(const u32 *p_affine_host, const u32 *q_affine_host, size_t group_size, size_t n_groups,
+                            unsigned char *ok) override {
+        if (!n_groups) return MG_OK;
+        if (!p_affine_host || !q_affine_host || !ok || !group_size || group_size > 64) return MG_ERR_ARG;
+        constexpr size_t PW1 = 2 * P::N, QW = 2 * P::F2W;
+        const size_t chunk = n_groups < MG_VERIFY_EACH_CHUNK ? n_groups : (size_t)MG_VERIFY_EACH_CHUNK;
+        std::vector<u32> ps(chunk * group_size * PW1), qs(chunk * group_size * QW);
+        std::vector<const u32 *> cp(chunk * group_size, nullptr);
+        std::vector<unsigned char> skip(chunk * group_size);
+        for (size_t lo = 0; lo < n_groups; lo += chunk) {
+            const size_t m = n_groups - lo < chunk ? n_groups - lo : chunk;
+            for (size_t t = 0; t < m; ++t)
+                for (size_t j = 0; j < group_size; ++j) {
+                    const size_t src = (lo + t) * group_size + j, dst = j * m + t;
+                    std::memcpy(&ps[dst * PW1], p_affine_host + src * PW1, PW1 * 4);
+                    std::memcpy(&qs[dst * QW], q_affine_host + src * QW, QW * 4);
+                    u32 any = 0;
+                    for (size_t k = 0; k < QW; ++k) any |= qs[dst * QW + k];
+                    skip[dst] = any == 0;
+                }
+            const int rc = pairing_check_groups(ps.data(), nullptr, 0, nullptr, cp.data(), qs.data(), skip.data(), group_size, m, nullptr,
+                                                ok + lo);
+            if (rc) return rc;
+        }
         return MG_OK;
     }
 };

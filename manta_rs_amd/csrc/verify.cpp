@@ -12,11 +12,16 @@
 // mod.rs:626-651): for caller-drawn 128-bit r_i,
 //     prod_i ML(r_i A_i, B_i) . ML(sum_i r_i PI_i, -gamma) . ML(sum_i r_i C_i, -delta) . ML(-(sum_i r_i) alpha, beta)  -> 1
 // i.e. k + 3 Miller loops (one wavefront each, pairing_coop.h), two small MSMs and ONE final exponentiation for k proofs.
+//
+// A verdict per proof (mg_groth16_verify_each, what a ledger asks after a batch check said no): the first equation for every
+// row of a block in one pass -- one batched MSM for the prepared inputs, 3 k Miller loops in one launch, k final
+// exponentiations in one launch, compared with e(alpha, beta) on the device.
 #include "verify.h"
 #include "tuning.h"
 #include "host_ec.h"
 #include "params_gen.h"
 #include "prover.h"
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -122,6 +127,7 @@ template <class Curve, class K> class VerifierT : public Verifier {
     std::vector<u64> alpha_, beta_, gamma_, delta_, abc_;           // affine Montgomery limbs
     std::vector<u32> alpha_beta_, gneg_host_, dneg_host_;           // e(alpha, beta); line coefficients (Montgomery words)
     u32 *d_gneg_ = nullptr, *d_dneg_ = nullptr, *d_beta_ = nullptr; // prepared -gamma, -delta, beta on the device
+    u32 *d_alpha_beta_ = nullptr;                                   // e(alpha, beta) on the device: the target of verify_each
     BaseSet *abc_bs_ = nullptr;                                     // gamma_abc_g1[0..P) as MSM bases
     std::mutex mu_;
     // G1's endomorphism phi(x, y) = (beta x, y) = lambda (x, y) (beta^3 = 1 in Fq, lambda^3 = 1 in Fr): the batch check draws
@@ -177,6 +183,7 @@ template <class Curve, class K> class VerifierT : public Verifier {
         if (d_gneg_) hipFree(d_gneg_);
         if (d_dneg_) hipFree(d_dneg_);
         if (d_beta_) hipFree(d_beta_);
+        if (d_alpha_beta_) hipFree(d_alpha_beta_);
         if (abc_bs_) g1_->bases_destroy(abc_bs_);
         hipSetDevice(prev);
     }
@@ -298,7 +305,13 @@ template <class Curve, class K> class VerifierT : public Verifier {
         alpha_beta_.resize(pe_->f12_words());
         const u32 *cp[1] = {d_beta_};
         unsigned char skip[1] = {(unsigned char)is_zero_limbs(beta, G2L)};
-        return pe_->pairing_product((const u32 *)alpha_.data(), cp, nullptr, skip, 1, true, alpha_beta_.data());
+        if ((rc = pe_->pairing_product((const u32 *)alpha_.data(), cp, nullptr, skip, 1, true, alpha_beta_.data()))) return rc;
+        return upload_alpha_beta();
+    }
+    int upload_alpha_beta() { // once per key: verify_each compares with it on the device
+        MG_HIP(hipMalloc((void **)&d_alpha_beta_, alpha_beta_.size() * 4));
+        MG_HIP(memcpy_sync(d_alpha_beta_, alpha_beta_.data(), alpha_beta_.size() * 4, hipMemcpyHostToDevice));
+        return MG_OK;
     }
     const u32 *d_gamma_neg() const { return d_gneg_; }
     const u32 *d_delta_neg() const { return d_dneg_ ? d_dneg_ : d_gneg_ + (size_t)pe_->n_coeffs() * pe_->coeff_words(); }
@@ -358,7 +371,7 @@ template <class Curve, class K> class VerifierT : public Verifier {
         MG_HIP(hipMalloc((void **)&d_gneg_, 2 * cw * 4));
         MG_HIP(memcpy_sync(d_gneg_, gneg_host_.data(), cw * 4, hipMemcpyHostToDevice));
         MG_HIP(memcpy_sync(d_gneg_ + cw, dneg_host_.data(), cw * 4, hipMemcpyHostToDevice));
-        return MG_OK;
+        return upload_alpha_beta();
     }
 
     // sum_j scalars_j * gamma_abc_g1[j] on the GPU (scalars Montgomery Fr, n <= P)
@@ -518,6 +531,83 @@ template <class Curve, class K> class VerifierT : public Verifier {
         std::vector<u32> one(out.size(), 0u);
         HF::one().store_words(one.data());
         *ok = std::memcmp(out.data(), one.data(), out.size() * 4) == 0;
+        return MG_OK;
+    }
+
+    // k proofs, a verdict each. Per proof the three pairs of verify(): (L_i, -gamma), (A_i, B_i), (C_i, -delta), compared with
+    // e(alpha, beta) on the device. A chunk of m proofs is ONE batched MSM over the key's tables for the m points L_i (folded
+    // on the device into XYZZ, where the Miller kernel reads them), ONE Miller launch of 3 m pairs laid out member-major --
+    // all L_i, then all A_i, then all C_i -- and ONE tail launch of m wavefronts (pairing_check_groups).
+    int verify_each(u64 k, const u64 *inputs, const u64 *proofs, uint8_t *ok) override {
+        if (k == 0) return MG_OK;
+        if (k > (1u << 20) || (!inputs && P_ > 1) || !proofs || !ok) return MG_ERR_ARG;
+        DeviceScope on_device(dev_);
+        const size_t PL = 2 * G1L + G2L; // limbs per proof
+        // the chunk: MG_VERIFY_EACH_CHUNK proofs, fewer where the MSM launch takes fewer scalar vectors (65 535 of them, 2^31
+        // digit pairs, a key space of 2^24)
+        size_t chunk = MG_VERIFY_EACH_CHUNK;
+        if (P_ > 1) {
+            const MsmPlan pl = g1_->plan_for(abc_bs_, P_, 0, 2);
+            const u64 pairs = P_ * (u64)pl.W, keys = (u64)pl.Wb * (pl.full ? 1u : pl.B);
+            const u64 most = std::min<u64>(std::min<u64>(((1ull << 31) - 1) / pairs, ((1ull << 24) - 1) / keys), 65535);
+            if (most == 0) return MG_ERR_ARG;
+            if (chunk > most) chunk = (size_t)most;
+        }
+        if (chunk > k) chunk = (size_t)k;
+        const size_t n = 3 * chunk;
+        std::vector<u64> ps(n * G1L), qs(n * G2L), sc(P_ > 1 ? chunk * P_ * 4 : 0);
+        std::vector<const u32 *> cp(n);
+        std::vector<unsigned char> skip(n);
+        const HR one = HR::one();
+        for (u64 lo = 0; lo < k; lo += chunk) {
+            const size_t m = (size_t)(k - lo < chunk ? k - lo : chunk);
+            MsmWorkspace *ws = nullptr;
+            int rc = MG_OK;
+            if (P_ > 1) { // L_i = abc[0] + sum_j x_ij abc[j + 1]: the scalar 1 in front of every row
+                for (size_t i = 0; i < m; ++i) {
+                    std::memcpy(&sc[i * P_ * 4], one.v, 32);
+                    std::memcpy(&sc[i * P_ * 4 + 4], inputs + (lo + i) * (P_ - 1) * 4, (P_ - 1) * 32);
+                }
+                if (!(ws = g1_->ws_acquire())) return MG_ERR_HIP;
+                const size_t xw = (size_t)g1_->xyzz_words();
+                rc = ws->scratch.reserve(m * P_ * 32);
+                if (!rc) rc = ws->folded.reserve(m * xw * 4);
+                if (!rc && hipMemcpyAsync(ws->scratch.p, sc.data(), m * P_ * 32, hipMemcpyHostToDevice, ws->stream) != hipSuccess)
+                    rc = hip_status(hipGetLastError(), "verify_each: scalars");
+                if (!rc) {
+                    rc = g1_->msm_launch(abc_bs_, ws->scratch.as<u32>(), P_, SCALARS_MONT, 0, ws, (u32)m, (size_t)P_ * 8);
+                    // (the key's tables hold every multiple of every window; a key built on plain bases -- the diagnosis
+                    // library's MANTA_VERIFY_ABC_C = 0 -- is refused here: its Horner fold is a host job)
+                    if (!rc) rc = g1_->msm_fold_device(ws, ws->folded.as<u32>(), xw);
+                }
+                if (rc) {
+                    hipStreamSynchronize(ws->stream), ws->pending = 0;
+                    g1_->ws_release(ws);
+                    return rc;
+                }
+            }
+            // the Miller launch's upload is assembled while the MSM runs
+            std::memset(qs.data(), 0, 3 * m * G2L * 8);
+            for (size_t i = 0; i < m; ++i) {
+                const u64 *pr = proofs + (lo + i) * PL;
+                if (P_ == 1) std::memcpy(&ps[i * G1L], abc_.data(), G1L * 8);
+                else std::memset(&ps[i * G1L], 0, G1L * 8); // (ignored: the XYZZ prefix)
+                std::memcpy(&ps[(m + i) * G1L], pr, G1L * 8);
+                std::memcpy(&ps[(2 * m + i) * G1L], pr + G1L + G2L, G1L * 8);
+                std::memcpy(&qs[(m + i) * G2L], pr + G1L, G2L * 8);
+                cp[i] = d_gamma_neg(), cp[m + i] = nullptr, cp[2 * m + i] = d_delta_neg();
+                skip[i] = 0, skip[m + i] = (unsigned char)is_zero_limbs(pr + G1L, G2L), skip[2 * m + i] = 0;
+            }
+            const bool xyzz = P_ > 1;
+            rc = pe_->pairing_check_groups((const u32 *)ps.data(), xyzz ? ws->folded.as<u32>() : nullptr, xyzz ? m : 0,
+                                           xyzz ? (void *)ws->stream : nullptr, cp.data(), (const u32 *)qs.data(), skip.data(), 3, m,
+                                           d_alpha_beta_, ok + lo);
+            if (ws) { // (also on the error paths: nothing of this call stays in flight; the host fold is not needed)
+                hipStreamSynchronize(ws->stream), ws->pending = 0;
+                g1_->ws_release(ws);
+            }
+            if (rc) return rc;
+        }
         return MG_OK;
     }
 

@@ -36,6 +36,18 @@ class PairingEngine {
     // *ok = (prod_i e(P_i, Q_i) == 1): all points host affine Montgomery words, every Q_i prepared on the fly; a pair with an
     // infinity member (all-zero words) contributes 1
     virtual int product_is_one(const u32 *p_affine_host, const u32 *q_affine_host, size_t n, int *ok) = 0;
+    // n_groups <= MG_VERIFY_EACH_CHUNK independent products of group_size <= 64 pairs each, a verdict each:
+    //     verdict_host[t] = (final_exponentiation(prod_{j < group_size} MillerLoop(P_{t,j}, Q_{t,j})) == target)
+    // The pairs lie MEMBER-MAJOR -- pair j of group t at index j * n_groups + t in every array -- and are otherwise given as to
+    // pairing_product_xyzz, the XYZZ prefix included (n_xyzz = n_groups: the first member of every group comes from the
+    // device). d_target: an Fq12 in device memory, null = 1. One Miller launch and one tail launch whatever the verdicts;
+    // only the verdict bytes are downloaded.
+    virtual int pairing_check_groups(const u32 *p_affine_host, const u32 *d_p_xyzz, size_t n_xyzz, void *producer,
+                                     const u32 *const *d_coeffs, const u32 *q_affine_host, const unsigned char *skip, size_t group_size,
+                                     size_t n_groups, const u32 *d_target, unsigned char *verdict_host) = 0;
+    // product_is_one per group: points [n_groups][group_size], group-major as a caller holds them; any n_groups (chunked)
+    virtual int product_is_one_each(const u32 *p_affine_host, const u32 *q_affine_host, size_t group_size, size_t n_groups,
+                                    unsigned char *ok) = 0;
 };
 PairingEngine *make_pairing_engine_bn254();
 PairingEngine *make_pairing_engine_bls381();
@@ -49,6 +61,8 @@ class Verifier {
     virtual int verify(const u64 *inputs_mont, const u64 *proof_points, int *ok) = 0;
     // k proofs at once by random linear combination; rand = k x 2 u64 (128-bit coefficients from the caller's RNG)
     virtual int verify_batch(u64 k, const u64 *inputs_mont, const u64 *proof_points, const u64 *rand128, int *ok) = 0;
+    // k proofs, a verdict each: ok[i] = what verify() answers for row i (three pairs per proof, MG_VERIFY_EACH_CHUNK proofs per pass)
+    virtual int verify_each(u64 k, const u64 *inputs_mont, const u64 *proof_points, uint8_t *ok) = 0;
     virtual size_t encoded_size() const = 0;
     virtual int encode(uint8_t *out) const = 0;          // VerifyingContext wire format, groth16.rs:337-361
     virtual int alpha_beta_bytes(uint8_t *out) const = 0; // 12 canonical Fq elements, arkworks order

@@ -560,6 +560,29 @@ impl<E: Mi355xCurve> GpuVerifyingContext<E> {
         check(unsafe { sys::mg_groth16_verify_batch(self.vk, k as u64, flat.as_ptr(), points.as_ptr(), rand.as_ptr(), &mut ok) })?;
         Ok(ok == 1)
     }
+
+    /// k proofs against this key, a verdict each (`mg_groth16_verify_each`): element i is what [`Self::verify`] answers
+    /// for `(inputs[i], proofs[i])`, in one pass over the block -- the answer to a `verify_many` that said `false`.
+    pub fn verify_each(&self, inputs: &[Vec<E::Fr>], proofs: &[Proof<E>]) -> Result<Vec<bool>, Error> {
+        let k = proofs.len();
+        if inputs.len() != k {
+            return Err(Error);
+        }
+        // SAFETY: plain getter
+        let n = unsafe { sys::mg_vk_num_inputs(self.vk) } as usize;
+        let (mut flat, mut points) = (Vec::new(), Vec::new());
+        for (input, proof) in inputs.iter().zip(proofs) {
+            if input.len() + 1 != n {
+                return Err(Error);
+            }
+            flat.extend(input.iter().flat_map(|f| E::fr_limbs(f)));
+            points.extend_from_slice(&Self::proof_limbs(proof));
+        }
+        let mut ok = vec![0u8; k];
+        // SAFETY: k inputs / proofs as declared, one verdict byte each
+        check(unsafe { sys::mg_groth16_verify_each(self.vk, k as u64, flat.as_ptr(), points.as_ptr(), ok.as_mut_ptr()) })?;
+        Ok(ok.into_iter().map(|v| v == 1).collect())
+    }
 }
 
 /// `PairingEngineExt::has_same` / `same` (`manta-crypto/src/arkworks/pairing.rs:76-98`) on the GPU: `e(lhs.0, lhs.1) ==

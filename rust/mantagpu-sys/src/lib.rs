@@ -73,6 +73,7 @@ pub struct mg_poseidon {
     _private: [u8; 0],
 }
 pub const MG_POSEIDON_CHUNK: usize = 1 << 19;
+pub const MG_VERIFY_EACH_CHUNK: usize = 1024;
 /// The per-tree state `mg_merkle_forest_append` reads and writes: leaf count, last leaf and its `Path` (arrays over the trees).
 #[repr(C)]
 pub struct mg_merkle_state {
@@ -538,6 +539,16 @@ extern "C" {
         ok: *mut c_int,
     ) -> c_int;
     pub fn mg_pairing_check(curve: mg_curve_t, g1_affine: *const u64, g2_affine: *const u64, n: usize, ok: *mut c_int) -> c_int;
+    // a verdict per item, MG_VERIFY_EACH_CHUNK groups / proofs per device pass
+    pub fn mg_pairing_check_each(
+        curve: mg_curve_t,
+        g1_affine: *const u64,
+        g2_affine: *const u64,
+        group_size: usize,
+        n_groups: usize,
+        ok: *mut u8,
+    ) -> c_int;
+    pub fn mg_groth16_verify_each(vk: *const mg_vk, k: u64, inputs_mont: *const u64, proof_points: *const u64, ok: *mut u8) -> c_int;
     pub fn mg_proof_decode(curve: mg_curve_t, proof_bytes: *const u8, points_out: *mut u64) -> c_int;
 
     // ---- batched point codec (arkworks 0.3 encodings, per-point status MG_POINT_*)
