@@ -218,9 +218,7 @@ static void job_abandon(mg_msm_job *job) {
     DeviceGuard guard;
     for (JobShard &j : job->sh) {
         hipSetDevice(j.device);
-        hipStreamSynchronize(msm_stream_of(j.ws));
-        if (j.ws->side_stream) hipStreamSynchronize(j.ws->side_stream);
-        j.ws->pending = 0;
+        j.eng->msm_abandon(j.ws);
         j.eng->ws_release(j.ws);
         if (j.d_tmp) hipFree(j.d_tmp);
     }
@@ -307,13 +305,8 @@ MG_API int mg_msm_finish(mg_msm_job *job, uint64_t *out_affine) {
     for (JobShard &j : job->sh) {
         hipSetDevice(j.device);
         int rc2 = j.eng->msm_finish(j.ws, &hp);
-        if (rc2) {
-            hipStreamSynchronize(msm_stream_of(j.ws));
-            if (j.ws->side_stream) hipStreamSynchronize(j.ws->side_stream);
-            j.ws->pending = 0;
-        } else {
-            e0->hp_add(&total, &hp);
-        }
+        if (rc2) j.eng->msm_abandon(j.ws);
+        else e0->hp_add(&total, &hp);
         if (!rc) rc = rc2;
         j.eng->ws_release(j.ws);
         if (j.d_tmp) hipFree(j.d_tmp);

@@ -400,6 +400,14 @@ class GroupEngine {
 
     MsmWorkspace *ws_acquire();
     void ws_release(MsmWorkspace *);
+    // Gives up what a workspace has in flight (a launch or finish that failed, a result nobody will fold on the host): waits
+    // for its MSM stream and, once a launch of it has used the engine's side stream, for that one too, and clears `pending`
+    // -- after this the workspace may go back to the pool. (The prover's graph slots drain their five streams their own way.)
+    static void msm_abandon(MsmWorkspace *ws) {
+        hipStreamSynchronize(msm_stream_of(ws));
+        if (ws->side_stream) hipStreamSynchronize(ws->side_stream);
+        ws->pending = 0;
+    }
 
     static constexpr size_t MAX_IDLE_WS = 24;
 

@@ -15,6 +15,16 @@ namespace host {
 typedef uint64_t u64;
 typedef unsigned __int128 u128;
 
+// the u64 of arkworks' wire formats (lengths, counts): little-endian
+inline u64 get_u64le(const unsigned char *in) {
+    u64 v = 0;
+    for (int i = 0; i < 8; ++i) v |= (u64)in[i] << (8 * i);
+    return v;
+}
+inline void put_u64le(unsigned char *out, u64 v) {
+    for (int i = 0; i < 8; ++i) out[i] = (unsigned char)(v >> (8 * i));
+}
+
 template <class C> struct HFp {
     static constexpr int N = C::N64;
     u64 v[N];
@@ -151,6 +161,19 @@ template <class C> struct HFp {
     void write_canonical(unsigned char *out) const {
         HFp c = from_mont(*this);
         for (int i = 0; i < BYTES; ++i) out[i] = (unsigned char)(c.v[i >> 3] >> ((i & 7) * 8));
+    }
+    // canonical little-endian bytes -> Montgomery; the bits of top_mask in the last byte are a point encoding's flags, not part
+    // of the integer. False for an integer >= p, as `Fp::from_repr` fails on it
+    static bool read_canonical(const unsigned char *in, unsigned char top_mask, HFp &out) {
+        HFp c = zero();
+        for (int i = 0; i < BYTES; ++i) {
+            unsigned char b = in[i];
+            if (i == BYTES - 1) b &= (unsigned char)~top_mask;
+            c.v[i >> 3] |= (u64)b << ((i & 7) * 8);
+        }
+        if (geq_p(c.v)) return false;
+        out = to_mont(c);
+        return true;
     }
     void load_words(const uint32_t *w) {
         for (int i = 0; i < N; ++i) v[i] = (u64)w[2 * i] | ((u64)w[2 * i + 1] << 32);

@@ -159,20 +159,9 @@ template <class K> class PairingEngineT : public PairingEngine {
         return MG_OK;
     }
 
-    int pairing_product(const u32 *p_affine_host, const u32 *const *d_coeffs, const u32 *q_affine_host,
-                        const unsigned char *skip, size_t n, bool do_final_exp, u32 *out_f12_host) override {
+    int pairing_product(const PairList &pairs, bool do_final_exp, u32 *out_f12_host) override {
         void *h = nullptr;
-        const int rc = pairing_product_begin(p_affine_host, d_coeffs, q_affine_host, skip, n, n, &h);
-        return rc ? rc : pairing_product_end(h, nullptr, do_final_exp, out_f12_host);
-    }
-    // the same with the G1 points of the first n_xyzz pairs taken from DEVICE memory as (X, Y, ZZ, ZZZ) -- what `producer`, the
-    // stream of the kernel that makes them, leaves there (p_affine_host's first n_xyzz entries are ignored)
-    int pairing_product_xyzz(const u32 *p_affine_host, const u32 *d_p_xyzz, size_t n_xyzz, void *producer, const u32 *const *d_coeffs,
-                             const u32 *q_affine_host, const unsigned char *skip, size_t n, bool do_final_exp,
-                             u32 *out_f12_host) override {
-        if (n_xyzz > n || (n_xyzz && (!d_p_xyzz || !producer))) return MG_ERR_ARG;
-        void *h = nullptr;
-        const int rc = begin_impl(p_affine_host, d_coeffs, q_affine_host, skip, n, n, &h, d_p_xyzz, n_xyzz, (hipStream_t)producer);
+        const int rc = pairing_product_begin(pairs, pairs.n, &h);
         return rc ? rc : pairing_product_end(h, nullptr, do_final_exp, out_f12_host);
     }
 
@@ -183,13 +172,13 @@ template <class K> class PairingEngineT : public PairingEngine {
     // factors per wavefront and level of the product tree: a level is chunk - 1 dependent Fq12 products (5.6 us each), so a batch
     // of 259 Miller values costs 18 of them in chunks of 8 (three levels) and 11 in chunks of 3 (six levels)
     static constexpr size_t PRODUCT_CHUNK = 3;
-    int pairing_product_begin(const u32 *p_affine_host, const u32 *const *d_coeffs, const u32 *q_affine_host,
-                              const unsigned char *skip, size_t n, size_t n_early, void **handle) override {
-        return begin_impl(p_affine_host, d_coeffs, q_affine_host, skip, n, n_early, handle, nullptr, 0, nullptr);
-    }
-    int begin_impl(const u32 *p_affine_host, const u32 *const *d_coeffs, const u32 *q_affine_host, const unsigned char *skip, size_t n,
-                   size_t n_early, void **handle, const u32 *d_p_xyzz, size_t n_xyzz, hipStream_t producer) {
+    // every entry point's way in: checks the list, stages and uploads it, launches the Miller loops of the first n_early pairs
+    int pairing_product_begin(const PairList &pairs, size_t n_early, void **handle) override {
+        const size_t n = pairs.n, n_xyzz = pairs.n_xyzz;
+        const u32 *const p_affine_host = pairs.p_affine_host, *const q_affine_host = pairs.q_affine_host;
+        const u32 *const *const d_coeffs = pairs.d_coeffs;
         if (!p_affine_host || !d_coeffs || !n || !handle || n_early > n || !n_early) return MG_ERR_ARG;
+        if (n_xyzz > n_early || (n_xyzz && (!pairs.d_p_xyzz || !pairs.producer))) return MG_ERR_ARG; // (the late launch reads no prefix)
         for (size_t i = 0; i < n; ++i)
             if (!d_coeffs[i] && (!q_affine_host || i >= n_early)) return MG_ERR_ARG;
         // one device block and one upload: [P | Q | coefficient pointers | skip flags] then the Fq12 work arrays
@@ -208,19 +197,25 @@ template <class K> class PairingEngineT : public PairingEngine {
         std::memcpy(stage, p_affine_host, n_early * 2 * P::N * 4);
         if (qb) std::memcpy(stage + o_q, q_affine_host, qb);
         std::memcpy(stage + o_c, d_coeffs, cb);
-        if (skip) std::memcpy(stage + o_s, skip, n);
+        // the flags: the caller's, and every fresh Q_i at infinity (all zero) -- wave 1 would prepare lines from the point (0, 0)
+        constexpr size_t QW = 2 * P::F2W;
+        for (size_t i = 0; i < n; ++i) {
+            u32 any = d_coeffs[i] ? 1u : 0u;
+            for (size_t k = 0; !any && k < QW; ++k) any = q_affine_host[i * QW + k];
+            stage[o_s + i] = (pairs.skip && pairs.skip[i]) || !any;
+        }
         w->n = n, w->n_early = n_early, w->o_q = qb ? o_q : 0, w->o_c = o_c, w->o_s = o_s, w->o_f = o_f, w->o_g = o_g, w->h_late = hmain;
         unsigned char *d = w->d;
         hipError_t e = hipMemcpyAsync(d, stage, in_bytes, hipMemcpyHostToDevice, w->s);
         if (e == hipSuccess && n_early < n) e = hipEventRecord(w->ev, w->s); // the late pairs' coefficient pointers and flags sit in the block this upload fills
         if (e == hipSuccess && n_xyzz) { // the points another stream's kernel is still making
-            e = hipEventRecord(w->evx, producer);
+            e = hipEventRecord(w->evx, (hipStream_t)pairs.producer);
             if (e == hipSuccess) e = hipStreamWaitEvent(w->s, w->evx, 0);
         }
         if (e == hipSuccess)
             hipLaunchKernelGGL((miller_kernel<K>), dim3((unsigned)n_early), dim3(128), PW::miller_lds_bytes(), w->s, (const u32 *)d,
                                (const u32 *const *)(d + o_c), qb ? (const u32 *)(d + o_q) : nullptr, (const unsigned char *)(d + o_s),
-                               n_early, (u32 *)(d + o_f), G1Arg<K>{}, d_p_xyzz, (u32)(n_xyzz < n_early ? n_xyzz : n_early));
+                               n_early, (u32 *)(d + o_f), G1Arg<K>{}, pairs.d_p_xyzz, (u32)n_xyzz);
         if (e == hipSuccess && n_early < n) e = hipEventRecord(w->ev3, w->s); // the early Miller loops are done
         if (e != hipSuccess) {
             hipStreamSynchronize(w->s);
@@ -298,18 +293,16 @@ template <class K> class PairingEngineT : public PairingEngine {
         ws_put(w);
     }
 
-    // n_groups independent products of group_size pairs, a verdict each: ONE Miller launch over all the pairs (begin_impl's
+    // n_groups independent products of group_size pairs, a verdict each: ONE Miller launch over all the pairs (begin()'s
     // upload, workspace and wait for the producer of the XYZZ prefix), then one tail wavefront per group on the same stream;
     // only the verdict bytes come back. The pairs lie member-major, so group t owns the Miller values t, n_groups + t, ...
-    int pairing_check_groups(const u32 *p_affine_host, const u32 *d_p_xyzz, size_t n_xyzz, void *producer, const u32 *const *d_coeffs,
-                             const u32 *q_affine_host, const unsigned char *skip, size_t group_size, size_t n_groups,
-                             const u32 *d_target, unsigned char *verdict_host) override {
+    int pairing_check_groups(const PairList &pairs, size_t group_size, size_t n_groups, const u32 *d_target,
+                             unsigned char *verdict_host) override {
         if (!group_size || group_size > 64 || !n_groups || n_groups > MG_VERIFY_EACH_CHUNK || !verdict_host) return MG_ERR_ARG;
-        const size_t n = group_size * n_groups;
-        if (n_xyzz > n || (n_xyzz && (!d_p_xyzz || !producer))) return MG_ERR_ARG;
+        if (pairs.n != group_size * n_groups) return MG_ERR_ARG;
         if (!d_target && !(d_target = d_one())) return MG_ERR_OOM;
         void *h = nullptr;
-        const int rc = begin_impl(p_affine_host, d_coeffs, q_affine_host, skip, n, n, &h, d_p_xyzz, n_xyzz, (hipStream_t)producer);
+        const int rc = pairing_product_begin(pairs, pairs.n, &h);
         if (rc) return rc;
         Ws *w = (Ws *)h;
         unsigned char *dv = w->d + w->o_g; // (the product tree's array: at least 128 bytes per group)
@@ -400,15 +393,11 @@ template <class K> class PairingEngineT : public PairingEngine {
     int product_is_one(const u32 *p_affine_host, const u32 *q_affine_host, size_t n, int *ok) override {
         if (!p_affine_host || !q_affine_host || !n || !ok) return MG_ERR_ARG;
         *ok = 0;
-        std::vector<const u32 *> cp(n, nullptr);
-        std::vector<unsigned char> skip(n, 0);
-        for (size_t i = 0; i < n; ++i) {
-            u32 any = 0;
-            for (int k = 0; k < 2 * P::F2W; ++k) any |= q_affine_host[i * 2 * P::F2W + k];
-            skip[i] = any == 0;
-        }
+        const std::vector<const u32 *> fresh(n, nullptr); // every Q_i prepared on the fly
+        PairList pairs;
+        pairs.n = n, pairs.p_affine_host = p_affine_host, pairs.d_coeffs = fresh.data(), pairs.q_affine_host = q_affine_host;
         std::vector<u32> out(P::F12W);
-        const int rc = pairing_product(p_affine_host, cp.data(), q_affine_host, skip.data(), n, true, out.data());
+        const int rc = pairing_product(pairs, true, out.data());
         if (rc) return rc;
         bool one = true;
         for (int k = 0; k < P::F12W; ++k) one = one && out[k] == (k < P::N ? K::Fq::R[k] : 0u);
@@ -424,8 +413,9 @@ template <class K> class PairingEngineT : public PairingEngine {
         constexpr size_t PW1 = 2 * P::N, QW = 2 * P::F2W;
         const size_t chunk = n_groups < MG_VERIFY_EACH_CHUNK ? n_groups : (size_t)MG_VERIFY_EACH_CHUNK;
         std::vector<u32> ps(chunk * group_size * PW1), qs(chunk * group_size * QW);
-        std::vector<const u32 *> cp(chunk * group_size, nullptr);
-        std::vector<unsigned char> skip(chunk * group_size);
+        const std::vector<const u32 *> fresh(chunk * group_size, nullptr);
+        PairList pairs;
+        pairs.p_affine_host = ps.data(), pairs.d_coeffs = fresh.data(), pairs.q_affine_host = qs.data();
         for (size_t lo = 0; lo < n_groups; lo += chunk) {
             const size_t m = n_groups - lo < chunk ? n_groups - lo : chunk;
             for (size_t t = 0; t < m; ++t)
@@ -433,12 +423,9 @@ template <class K> class PairingEngineT : public PairingEngine {
                     const size_t src = (lo + t) * group_size + j, dst = j * m + t;
                     std::memcpy(&ps[dst * PW1], p_affine_host + src * PW1, PW1 * 4);
                     std::memcpy(&qs[dst * QW], q_affine_host + src * QW, QW * 4);
-                    u32 any = 0;
-                    for (size_t k = 0; k < QW; ++k) any |= qs[dst * QW + k];
-                    skip[dst] = any == 0;
                 }
-            const int rc = pairing_check_groups(ps.data(), nullptr, 0, nullptr, cp.data(), qs.data(), skip.data(), group_size, m, nullptr,
-                                                ok + lo);
+            pairs.n = group_size * m;
+            const int rc = pairing_check_groups(pairs, group_size, m, nullptr, ok + lo);
             if (rc) return rc;
         }
         return MG_OK;

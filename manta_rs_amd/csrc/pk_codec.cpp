@@ -31,26 +31,9 @@ struct Reader {
     }
     uint64_t u64le() {
         const uint8_t *q = take(8);
-        if (!q) return 0;
-        uint64_t v = 0;
-        for (int i = 0; i < 8; ++i) v |= (uint64_t)q[i] << (8 * i);
-        return v;
+        return q ? host::get_u64le(q) : 0;
     }
 };
-
-template <class C> bool read_fp(const uint8_t *b, unsigned char top_mask, uint64_t *out_mont) {
-    typedef host::HFp<C> HF;
-    HF c = HF::zero();
-    for (int i = 0; i < HF::BYTES; ++i) {
-        uint8_t v = b[i];
-        if (i == HF::BYTES - 1) v &= (uint8_t)~top_mask;
-        c.v[i >> 3] |= (uint64_t)v << ((i & 7) * 8);
-    }
-    if (HF::geq_p(c.v)) return false; // Fp::from_repr fails on non-canonical input
-    HF m = HF::to_mont(c);
-    std::memcpy(out_mont, m.v, sizeof(m.v));
-    return true;
-}
 
 // one uncompressed point with `deg` base-field coordinates per coordinate (1 = G1, 2 = G2)
 template <class C> bool read_point(Reader &r, int deg, uint64_t *out) {
@@ -65,7 +48,9 @@ template <class C> bool read_point(Reader &r, int deg, uint64_t *out) {
     }
     for (int k = 0; k < 2 * deg; ++k) {
         const bool last = k == 2 * deg - 1;
-        if (!read_fp<C>(b + (size_t)k * nb, last ? 0xC0 : 0, out + (size_t)k * n64)) return false;
+        HF m;
+        if (!HF::read_canonical(b + (size_t)k * nb, last ? 0xC0 : 0, m)) return false;
+        std::memcpy(out + (size_t)k * n64, m.v, sizeof(m.v));
     }
     return true;
 }

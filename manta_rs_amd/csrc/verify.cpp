@@ -97,18 +97,76 @@ template <class C> bool hsqrt2(const HFp2<C> &a, HFp2<C> &r) {
     r = HFp2<C>{x0, x1};
     return HFp2<C>::sqr(r).c0 == a.c0 && HFp2<C>::sqr(r).c1 == a.c1;
 }
-template <class C> bool read_fq(const uint8_t *in, unsigned char mask_top, HFp<C> &out) { // canonical LE bytes -> Montgomery
-    typedef HFp<C> HF;
-    HF c = HF::zero();
-    for (int i = 0; i < HF::BYTES; ++i) {
-        uint8_t v = in[i];
-        if (i == HF::BYTES - 1) v &= (uint8_t)~mask_top;
-        c.v[i >> 3] |= (u64)v << ((i & 7) * 8);
+// The pairs of one engine call: owns the four parallel arrays a PairList points into. clear() keeps the storage, so a chunk
+// loop fills it again without allocating. A null G1 point stands for one the engine gets another way (the XYZZ prefix, the
+// late pairs of a two-step product): its entry is zero and not read.
+template <int G1L, int G2L> class PairBuilder {
+    std::vector<u64> ps_, qs_;
+    std::vector<const u32 *> cp_;
+    std::vector<unsigned char> skip_;
+    bool any_fresh_ = false;
+    void add(const u64 *p, const u64 *q, const u32 *d_coeffs, bool left_out) {
+        if (p) ps_.insert(ps_.end(), p, p + G1L);
+        else ps_.resize(ps_.size() + G1L, 0);
+        if (q) qs_.insert(qs_.end(), q, q + G2L);
+        else qs_.resize(qs_.size() + G2L, 0);
+        cp_.push_back(d_coeffs), skip_.push_back(left_out);
     }
-    if (HF::geq_p(c.v)) return false;
-    out = HF::to_mont(c);
-    return true;
+
+  public:
+    void clear() { ps_.clear(), qs_.clear(), cp_.clear(), skip_.clear(), any_fresh_ = false; }
+    // (P, Q) with Q an affine point new to the engine; Q = infinity (all zero) is the engine's to notice
+    void fresh(const u64 *p, const u64 *q) { add(p, q, nullptr, false), any_fresh_ = true; }
+    // (P, Q) with Q prepared in device memory; left_out: Q was infinity, its coefficient block must not be consumed
+    void prepared(const u64 *p, const u32 *d_coeffs, bool left_out = false) { add(p, nullptr, d_coeffs, left_out); }
+    PairList list() const {
+        PairList l;
+        l.n = cp_.size(), l.p_affine_host = (const u32 *)ps_.data(), l.d_coeffs = cp_.data(), l.skip = skip_.data();
+        l.q_affine_host = any_fresh_ ? (const u32 *)qs_.data() : nullptr;
+        return l;
+    }
+};
+
+// A workspace of an engine for the length of a scope (none for a null engine). What it still has in flight when the scope
+// ends -- a launch that failed half-way, a result that was consumed on the device and never folded on the host -- is given up
+// (msm_abandon) before the workspace goes back to the pool.
+struct WsScope {
+    GroupEngine *const eng;
+    MsmWorkspace *const ws;
+    bool in_flight = false; // set by whoever enqueues on the workspace; cleared by finish()
+    explicit WsScope(GroupEngine *e) : eng(e), ws(e ? e->ws_acquire() : nullptr) {}
+    ~WsScope() {
+        if (!ws) return;
+        if (in_flight || ws->pending) eng->msm_abandon(ws);
+        eng->ws_release(ws);
+    }
+    WsScope(const WsScope &) = delete;
+    WsScope &operator=(const WsScope &) = delete;
+    int finish(HostPoint *out) {
+        const int rc = eng->msm_finish(ws, out);
+        if (!rc) in_flight = false;
+        return rc;
+    }
+};
+// An MSM over scalars the host holds (batch vectors of n, stride_words u32 apart), launched on w's workspace: the scalars ride
+// in the workspace's own grow-only buffer, on its stream -- no hipMalloc / hipFree per verification (hipFree synchronises
+// the whole device: every proof in flight on this GPU would wait for it)
+int msm_from_host(WsScope &w, const BaseSet *bs, const u64 *scalars, size_t n, int scalar_mode, u32 batch = 1, size_t stride_words = 0) {
+    if (!w.ws) return MG_ERR_HIP;
+    const size_t bytes = (size_t)batch * n * 32;
+    w.in_flight = true;
+    if (const int rc = w.ws->scratch.reserve(bytes)) return rc;
+    if (hipMemcpyAsync(w.ws->scratch.p, scalars, bytes, hipMemcpyHostToDevice, w.ws->stream) != hipSuccess)
+        return hip_status(hipGetLastError(), "verifier MSM: scalars");
+    return w.eng->msm_launch(bs, w.ws->scratch.as<u32>(), n, scalar_mode, 0, w.ws, batch, stride_words);
 }
+struct BasesScope { // a base set made for one call
+    GroupEngine *const eng;
+    BaseSet *bs = nullptr;
+    ~BasesScope() {
+        if (bs) eng->bases_destroy(bs);
+    }
+};
 
 template <class Curve, class K> class VerifierT : public Verifier {
   public:
@@ -126,7 +184,8 @@ template <class Curve, class K> class VerifierT : public Verifier {
     u64 P_ = 0;
     std::vector<u64> alpha_, beta_, gamma_, delta_, abc_;           // affine Montgomery limbs
     std::vector<u32> alpha_beta_, gneg_host_, dneg_host_;           // e(alpha, beta); line coefficients (Montgomery words)
-    u32 *d_gneg_ = nullptr, *d_dneg_ = nullptr, *d_beta_ = nullptr; // prepared -gamma, -delta, beta on the device
+    u32 *d_gneg_ = nullptr, *d_beta_ = nullptr; // prepared -gamma and -delta (one allocation, in this order), beta on the device
+    bool beta_inf_ = false;                     // beta_g2 = infinity: its prepared block is all zero and every pair with it left out
     u32 *d_alpha_beta_ = nullptr;                                   // e(alpha, beta) on the device: the target of verify_each
     BaseSet *abc_bs_ = nullptr;                                     // gamma_abc_g1[0..P) as MSM bases
     std::mutex mu_;
@@ -177,15 +236,11 @@ template <class Curve, class K> class VerifierT : public Verifier {
     }
 
     ~VerifierT() override {
-        int prev = 0;
-        hipGetDevice(&prev);
-        hipSetDevice(dev_);
+        DeviceScope on_device(dev_);
         if (d_gneg_) hipFree(d_gneg_);
-        if (d_dneg_) hipFree(d_dneg_);
         if (d_beta_) hipFree(d_beta_);
         if (d_alpha_beta_) hipFree(d_alpha_beta_);
         if (abc_bs_) g1_->bases_destroy(abc_bs_);
-        hipSetDevice(prev);
     }
     u64 n_inputs() const override { return P_; }
 
@@ -209,7 +264,7 @@ template <class Curve, class K> class VerifierT : public Verifier {
         // ark-serialize 0.3 reads the field element first (rejecting x >= p) and the flags with it: `SWFlags::from_u8` has no
         // value for "both bits set", and an infinity encoding still has to carry a canonical x (its value is ignored)
         if ((flags & 0xC0) == 0xC0) return false;
-        if (!read_fq<C>(in, 0xC0, x)) return false;
+        if (!HF::read_canonical(in, 0xC0, x)) return false;
         if (flags & 0x40) {
             std::memset(out, 0, G1L * 8);
             return true;
@@ -227,7 +282,7 @@ template <class Curve, class K> class VerifierT : public Verifier {
         const uint8_t flags = in[2 * FB - 1];
         HF2 x, y;
         if ((flags & 0xC0) == 0xC0) return false; // no such SWFlags value
-        if (!read_fq<C>(in, 0, x.c0) || !read_fq<C>(in + FB, 0xC0, x.c1)) return false; // canonical even when infinity is flagged
+        if (!HF::read_canonical(in, 0, x.c0) || !HF::read_canonical(in + FB, 0xC0, x.c1)) return false; // canonical even when infinity is flagged
         if (flags & 0x40) {
             std::memset(out, 0, G2L * 8);
             return true;
@@ -257,6 +312,12 @@ template <class Curve, class K> class VerifierT : public Verifier {
         for (int i = 0; i < n; ++i) x |= p[i];
         return x == 0;
     }
+    typedef PairBuilder<G1L, G2L> Pairs;
+    struct Row { // a proof row a | b | c
+        static constexpr size_t LIMBS = 2 * G1L + G2L;
+        const u64 *a, *b, *c;
+        explicit Row(const u64 *r) : a(r), b(r + G1L), c(r + G1L + G2L) {}
+    };
 
     int common_init(int curve) {
         curve_ = curve;
@@ -275,6 +336,7 @@ template <class Curve, class K> class VerifierT : public Verifier {
         int rc = g1_->bases_create((const u32 *)abc_.data(), P_, false, abc_c, &abc_bs_);
         if (rc) return rc;
         glv_init();
+        beta_inf_ = is_zero_limbs(beta_.data(), G2L);
         return pe_->prepare((const u32 *)beta_.data(), 1, &d_beta_);
     }
 
@@ -296,16 +358,15 @@ template <class Curve, class K> class VerifierT : public Verifier {
         hipError_t e = memcpy_sync(gneg_host_.data(), d2, cw * 4, hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = memcpy_sync(dneg_host_.data(), d2 + cw, cw * 4, hipMemcpyDeviceToHost);
         d_gneg_ = d2; // the two blocks stay in this one allocation
-        d_dneg_ = nullptr;
         if (e != hipSuccess) {
             set_last_hip_error(e, "verifier init", __FILE__, __LINE__);
             return MG_ERR_HIP;
         }
         // e(alpha_g1, beta_g2) with arkworks' final exponentiation
         alpha_beta_.resize(pe_->f12_words());
-        const u32 *cp[1] = {d_beta_};
-        unsigned char skip[1] = {(unsigned char)is_zero_limbs(beta, G2L)};
-        if ((rc = pe_->pairing_product((const u32 *)alpha_.data(), cp, nullptr, skip, 1, true, alpha_beta_.data()))) return rc;
+        Pairs pairs;
+        pairs.prepared(alpha_.data(), d_beta_, beta_inf_);
+        if ((rc = pe_->pairing_product(pairs.list(), true, alpha_beta_.data()))) return rc;
         return upload_alpha_beta();
     }
     int upload_alpha_beta() { // once per key: verify_each compares with it on the device
@@ -314,7 +375,7 @@ template <class Curve, class K> class VerifierT : public Verifier {
         return MG_OK;
     }
     const u32 *d_gamma_neg() const { return d_gneg_; }
-    const u32 *d_delta_neg() const { return d_dneg_ ? d_dneg_ : d_gneg_ + (size_t)pe_->n_coeffs() * pe_->coeff_words(); }
+    const u32 *d_delta_neg() const { return d_gneg_ + (size_t)pe_->n_coeffs() * pe_->coeff_words(); }
 
     // from the wire format: the prepared parts are taken from the bytes, as `VerifyingContext::deserialize` does
     int init_from_bytes(int curve, const uint8_t *in, size_t len) {
@@ -330,8 +391,7 @@ template <class Curve, class K> class VerifierT : public Verifier {
             if (!g2_decompress(in + off, g2s[k])) return MG_ERR_ARG;
             off += g2b;
         }
-        u64 P = 0;
-        for (int i = 0; i < 8; ++i) P |= (u64)in[off + i] << (8 * i);
+        const u64 P = host::get_u64le(in + off);
         off += 8;
         if (P < 1 || P > (len - off) / g1b) return MG_ERR_ARG;
         P_ = P;
@@ -347,21 +407,20 @@ template <class Curve, class K> class VerifierT : public Verifier {
         alpha_beta_.resize(pe_->f12_words());
         for (int k = 0; k < 12; ++k) {
             HF v;
-            if (!read_fq<C>(in + off, 0, v)) return MG_ERR_ARG;
+            if (!HF::read_canonical(in + off, 0, v)) return MG_ERR_ARG;
             v.store_words(alpha_beta_.data() + (size_t)k * 2 * N64);
             off += FB;
         }
         std::vector<u32> *dst[2] = {&gneg_host_, &dneg_host_};
         for (int b = 0; b < 2; ++b) {
             if (!need(8)) return MG_ERR_ARG;
-            u64 cnt = 0;
-            for (int i = 0; i < 8; ++i) cnt |= (u64)in[off + i] << (8 * i);
+            const u64 cnt = host::get_u64le(in + off);
             off += 8;
             if (cnt != nco || !need(cnt * 6 * FB + 1)) return MG_ERR_ARG;
             dst[b]->resize(cw);
             for (size_t k = 0; k < cnt * 6; ++k) {
                 HF v;
-                if (!read_fq<C>(in + off, 0, v)) return MG_ERR_ARG;
+                if (!HF::read_canonical(in + off, 0, v)) return MG_ERR_ARG;
                 v.store_words(dst[b]->data() + k * 2 * N64);
                 off += FB;
             }
@@ -374,37 +433,26 @@ template <class Curve, class K> class VerifierT : public Verifier {
         return upload_alpha_beta();
     }
 
-    // sum_j scalars_j * gamma_abc_g1[j] on the GPU (scalars Montgomery Fr, n <= P)
-    int abc_msm(const u64 *scalars_mont, size_t n, HostPoint *out) {
-        MsmWorkspace *ws = g1_->ws_acquire();
-        if (!ws) return MG_ERR_HIP;
-        // the scalars ride in the workspace's own grow-only buffer, on its stream: no hipMalloc / hipFree per verification
-        // (hipFree synchronises the whole device -- every proof in flight on this GPU would wait for it)
-        int rc = ws->scratch.reserve(n * 32);
-        if (!rc && hipMemcpyAsync(ws->scratch.p, scalars_mont, n * 32, hipMemcpyHostToDevice, ws->stream) != hipSuccess) rc = MG_ERR_HIP;
-        if (!rc) rc = g1_->msm_launch(abc_bs_, ws->scratch.as<u32>(), n, SCALARS_MONT, 0, ws);
-        if (!rc) rc = g1_->msm_finish(ws, out);
-        else hipStreamSynchronize(ws->stream), ws->pending = 0;
-        g1_->ws_release(ws);
-        return rc;
+    // out = sum_j scalars_j * bases_j on the GPU, launched and waited for
+    int msm_now(const BaseSet *bs, const u64 *scalars, size_t n, int scalar_mode, HostPoint *out) {
+        WsScope w(g1_);
+        const int rc = msm_from_host(w, bs, scalars, n, scalar_mode);
+        return rc ? rc : w.finish(out);
     }
 
     int verify(const u64 *inputs, const u64 *proof, int *ok) override {
         if ((!inputs && P_ > 1) || !proof || !ok) return MG_ERR_ARG;
         DeviceScope on_device(dev_);
         *ok = 0;
-        const u64 *A = proof, *B = proof + G1L, *Cc = proof + G1L + G2L;
+        const Row row(proof);
         // e(A, B) and e(C, -delta) do not depend on the public inputs: their Miller loops start first. B is the one G2 point that
         // is new with every proof: its line coefficients are computed next to its Miller loop
-        const u32 *cp[3] = {nullptr, d_delta_neg(), d_gamma_neg()};
-        std::vector<u64> ps(2 * G1L);
-        std::memcpy(ps.data(), A, G1L * 8);
-        std::memcpy(ps.data() + G1L, Cc, G1L * 8);
-        std::vector<u64> qs(3 * G2L, 0);
-        std::memcpy(qs.data(), B, G2L * 8);
-        unsigned char skip[3] = {(unsigned char)is_zero_limbs(B, G2L), 0, 0};
+        Pairs pairs;
+        pairs.fresh(row.a, row.b);
+        pairs.prepared(row.c, d_delta_neg());
+        pairs.prepared(nullptr, d_gamma_neg()); // (the prepared inputs: handed to end())
         void *pp = nullptr;
-        int rc = pe_->pairing_product_begin((const u32 *)ps.data(), cp, (const u32 *)qs.data(), skip, 3, 2, &pp);
+        int rc = pe_->pairing_product_begin(pairs.list(), 2, &pp);
         if (rc) return rc;
         // prepared_inputs = abc[0] + sum_j input_j abc[j+1]: a P-term MSM with the scalar 1 in front, next to those loops
         std::vector<u64> sc(P_ * 4);
@@ -412,7 +460,7 @@ template <class Curve, class K> class VerifierT : public Verifier {
         std::memcpy(sc.data(), one.v, 32);
         if (P_ > 1) std::memcpy(sc.data() + 4, inputs, (P_ - 1) * 32);
         HostPoint pi;
-        rc = abc_msm(sc.data(), P_, &pi);
+        rc = msm_now(abc_bs_, sc.data(), P_, SCALARS_MONT, &pi);
         if (rc) {
             pe_->pairing_product_abandon(pp);
             return rc;
@@ -430,7 +478,6 @@ template <class Curve, class K> class VerifierT : public Verifier {
         if (k == 0 || k > (1u << 20) || (!inputs && P_ > 1) || !proofs || !rand128 || !ok) return MG_ERR_ARG;
         DeviceScope on_device(dev_);
         *ok = 0;
-        const size_t PL = 2 * G1L + G2L; // limbs per proof
         // r_i as Montgomery Fr; s = sum r_i; comb_j = sum_i r_i x_ij
         std::vector<HR> r(k);
         HR s = HR::zero();
@@ -453,11 +500,11 @@ template <class Curve, class K> class VerifierT : public Verifier {
             }
             s = HR::add(s, r[i]);
         }
-        std::vector<u64> cs(k * G1L), as(k * G1L), bs(k * G2L);
+        std::vector<u64> cs(k * G1L), as(k * G1L);
         for (u64 i = 0; i < k; ++i) {
-            std::memcpy(as.data() + i * G1L, proofs + i * PL, G1L * 8);
-            std::memcpy(bs.data() + i * G2L, proofs + i * PL + G1L, G2L * 8);
-            std::memcpy(cs.data() + i * G1L, proofs + i * PL + G1L + G2L, G1L * 8);
+            const Row row(proofs + i * Row::LIMBS);
+            std::memcpy(as.data() + i * G1L, row.a, G1L * 8);
+            std::memcpy(cs.data() + i * G1L, row.c, G1L * 8);
         }
         // r_i A_i, element-wise on the GPU -- k independent 128-bit multiplications, one per lane: a millisecond of pure latency
         // on a handful of wavefronts. It is launched first, on a workspace stream of its own, and the two MSMs below (which fill
@@ -465,17 +512,14 @@ template <class Curve, class K> class VerifierT : public Verifier {
         // affine ones with ONE inversion (Montgomery's trick, ~0.1 ms), where the device spent 0.56 ms on Fermat inversions at
         // one-lane latency. (The base set of the C points is made before the launch: its allocation and synchronous upload would
         // otherwise wait for that kernel.)
-        BaseSet *cb = nullptr;
-        int rc = g1_->bases_create((const u32 *)cs.data(), k, false, 0, &cb);
+        BasesScope cb{g1_};
+        int rc = g1_->bases_create((const u32 *)cs.data(), k, false, 0, &cb.bs);
         if (rc) return rc;
-        MsmWorkspace *wse = g1_->ws_acquire();
-        int rc_a = wse ? g1_->ec_mul_xyzz_begin((const u32 *)as.data(), (const u32 *)r_can.data(), k, wse, glv_ok_ ? glv_beta_std_.data() : nullptr)
-                       : MG_ERR_HIP;
-        if (rc_a) {
-            if (wse) g1_->ws_release(wse);
-            g1_->bases_destroy(cb);
-            return rc_a;
-        }
+        WsScope wse(g1_); // (drained on every way out: nothing of this call stays in flight)
+        if (!wse.ws) return MG_ERR_HIP;
+        wse.in_flight = true;
+        rc = g1_->ec_mul_xyzz_begin((const u32 *)as.data(), (const u32 *)r_can.data(), k, wse.ws, glv_ok_ ? glv_beta_std_.data() : nullptr);
+        if (rc) return rc;
         for (u64 i = 0; i < k; ++i) // (k (P - 1) host products: next to the kernel just launched)
             for (u64 j = 1; j < P_; ++j) {
                 HR x;
@@ -483,21 +527,11 @@ template <class Curve, class K> class VerifierT : public Verifier {
                 comb[j] = HR::add(comb[j], HR::mul(r[i], x));
             }
         comb[0] = s;
-        HostPoint pi;
-        rc = abc_msm((const u64 *)comb.data(), P_, &pi);
+        HostPoint pi, csum, al;
+        if ((rc = msm_now(abc_bs_, (const u64 *)comb.data(), P_, SCALARS_MONT, &pi))) return rc;
         // sum_i r_i C_i: a k-term MSM over the proofs' C points
-        HostPoint csum;
-        if (!rc) {
-            MsmWorkspace *ws = g1_->ws_acquire();
-            rc = ws ? ws->scratch.reserve(k * 32) : MG_ERR_HIP;
-            if (!rc && hipMemcpyAsync(ws->scratch.p, r_full.data(), k * 32, hipMemcpyHostToDevice, ws->stream) != hipSuccess) rc = MG_ERR_HIP;
-            if (!rc) rc = g1_->msm_launch(cb, ws->scratch.as<u32>(), k, SCALARS_CANONICAL, 0, ws);
-            if (!rc) rc = g1_->msm_finish(ws, &csum);
-            else if (ws) hipStreamSynchronize(ws->stream), ws->pending = 0;
-            if (ws) g1_->ws_release(ws);
-        }
+        if ((rc = msm_now(cb.bs, r_full.data(), k, SCALARS_CANONICAL, &csum))) return rc;
         // -(sum r_i) alpha on the host (still next to that kernel)
-        HostPoint al;
         g1_->hp_from_affine(&al, (const u32 *)alpha_.data());
         HR sc = HR::from_mont(s);
         g1_->hp_mul(&al, sc.v);
@@ -505,29 +539,19 @@ template <class Curve, class K> class VerifierT : public Verifier {
         // pairs: (r_i A_i, B_i) ..., (PI, -gamma), (C, -delta), (-s alpha, beta); the three fixed ones are made affine (an inversion
         // each) while the multiplications still run. The k products r_i A_i never leave the device: the Miller kernel waits for
         // their kernel and reads them as (X, Y, ZZ, ZZZ) -- no download, inversion, upload between the two
-        const size_t n = k + 3;
-        std::vector<u64> ps(n * G1L, 0);
-        if (!rc) {
-            g1_->hp_to_affine(&pi, (u32 *)(ps.data() + k * G1L));
-            g1_->hp_to_affine(&csum, (u32 *)(ps.data() + (k + 1) * G1L));
-            g1_->hp_to_affine(&al, (u32 *)(ps.data() + (k + 2) * G1L));
-        }
+        u64 fixed[3][G1L];
+        g1_->hp_to_affine(&pi, (u32 *)fixed[0]);
+        g1_->hp_to_affine(&csum, (u32 *)fixed[1]);
+        g1_->hp_to_affine(&al, (u32 *)fixed[2]);
+        Pairs pairs;
+        for (u64 i = 0; i < k; ++i) pairs.fresh(nullptr, Row(proofs + i * Row::LIMBS).b); // the B_i are prepared on the fly
+        pairs.prepared(fixed[0], d_gamma_neg());
+        pairs.prepared(fixed[1], d_delta_neg());
+        pairs.prepared(fixed[2], d_beta_, beta_inf_);
+        PairList pl = pairs.list();
+        pl.d_p_xyzz = g1_->ec_mul_xyzz_device(wse.ws, k, glv_ok_), pl.n_xyzz = k, pl.producer = (void *)wse.ws->stream;
         std::vector<u32> out(pe_->f12_words());
-        if (!rc) {
-            std::vector<const u32 *> cp(n, nullptr); // the k proof points B_i are prepared on the fly
-            std::vector<unsigned char> skip(n, 0);
-            std::vector<u64> qs(n * G2L, 0);
-            std::memcpy(qs.data(), bs.data(), k * G2L * 8);
-            for (u64 i = 0; i < k; ++i) skip[i] = (unsigned char)is_zero_limbs(bs.data() + i * G2L, G2L);
-            cp[k] = d_gamma_neg(), cp[k + 1] = d_delta_neg(), cp[k + 2] = d_beta_;
-            skip[k + 2] = (unsigned char)is_zero_limbs(beta_.data(), G2L);
-            rc = pe_->pairing_product_xyzz((const u32 *)ps.data(), g1_->ec_mul_xyzz_device(wse, k, glv_ok_), k, (void *)wse->stream, cp.data(),
-                                           (const u32 *)qs.data(), skip.data(), n, true, out.data());
-        }
-        hipStreamSynchronize(wse->stream); // (also on the error paths: nothing of this call stays in flight)
-        g1_->ws_release(wse);
-        g1_->bases_destroy(cb);
-        if (rc) return rc;
+        if ((rc = pe_->pairing_product(pl, true, out.data()))) return rc;
         std::vector<u32> one(out.size(), 0u);
         HF::one().store_words(one.data());
         *ok = std::memcmp(out.data(), one.data(), out.size() * 4) == 0;
@@ -542,7 +566,6 @@ template <class Curve, class K> class VerifierT : public Verifier {
         if (k == 0) return MG_OK;
         if (k > (1u << 20) || (!inputs && P_ > 1) || !proofs || !ok) return MG_ERR_ARG;
         DeviceScope on_device(dev_);
-        const size_t PL = 2 * G1L + G2L; // limbs per proof
         // the chunk: MG_VERIFY_EACH_CHUNK proofs, fewer where the MSM launch takes fewer scalar vectors (65 535 of them, 2^31
         // digit pairs, a key space of 2^24)
         size_t chunk = MG_VERIFY_EACH_CHUNK;
@@ -554,59 +577,39 @@ template <class Curve, class K> class VerifierT : public Verifier {
             if (chunk > most) chunk = (size_t)most;
         }
         if (chunk > k) chunk = (size_t)k;
-        const size_t n = 3 * chunk;
-        std::vector<u64> ps(n * G1L), qs(n * G2L), sc(P_ > 1 ? chunk * P_ * 4 : 0);
-        std::vector<const u32 *> cp(n);
-        std::vector<unsigned char> skip(n);
+        std::vector<u64> sc(P_ > 1 ? chunk * P_ * 4 : 0);
+        Pairs pairs; // (filled once per chunk; its storage serves every chunk)
         const HR one = HR::one();
+        const bool xyzz = P_ > 1; // the L_i come from the MSM, on the device; a key without public inputs has L_i = abc[0]
         for (u64 lo = 0; lo < k; lo += chunk) {
             const size_t m = (size_t)(k - lo < chunk ? k - lo : chunk);
-            MsmWorkspace *ws = nullptr;
-            int rc = MG_OK;
-            if (P_ > 1) { // L_i = abc[0] + sum_j x_ij abc[j + 1]: the scalar 1 in front of every row
+            WsScope w(xyzz ? g1_ : nullptr); // held until pairing_check_groups has returned: the Miller kernel reads its buffers
+            if (xyzz) { // L_i = abc[0] + sum_j x_ij abc[j + 1]: the scalar 1 in front of every row
                 for (size_t i = 0; i < m; ++i) {
                     std::memcpy(&sc[i * P_ * 4], one.v, 32);
                     std::memcpy(&sc[i * P_ * 4 + 4], inputs + (lo + i) * (P_ - 1) * 4, (P_ - 1) * 32);
                 }
-                if (!(ws = g1_->ws_acquire())) return MG_ERR_HIP;
+                if (!w.ws) return MG_ERR_HIP;
                 const size_t xw = (size_t)g1_->xyzz_words();
-                rc = ws->scratch.reserve(m * P_ * 32);
-                if (!rc) rc = ws->folded.reserve(m * xw * 4);
-                if (!rc && hipMemcpyAsync(ws->scratch.p, sc.data(), m * P_ * 32, hipMemcpyHostToDevice, ws->stream) != hipSuccess)
-                    rc = hip_status(hipGetLastError(), "verify_each: scalars");
-                if (!rc) {
-                    rc = g1_->msm_launch(abc_bs_, ws->scratch.as<u32>(), P_, SCALARS_MONT, 0, ws, (u32)m, (size_t)P_ * 8);
-                    // (the key's tables hold every multiple of every window; a key built on plain bases -- the diagnosis
-                    // library's MANTA_VERIFY_ABC_C = 0 -- is refused here: its Horner fold is a host job)
-                    if (!rc) rc = g1_->msm_fold_device(ws, ws->folded.as<u32>(), xw);
-                }
-                if (rc) {
-                    hipStreamSynchronize(ws->stream), ws->pending = 0;
-                    g1_->ws_release(ws);
-                    return rc;
-                }
+                int rc = w.ws->folded.reserve(m * xw * 4);
+                if (!rc) rc = msm_from_host(w, abc_bs_, sc.data(), P_, SCALARS_MONT, (u32)m, (size_t)P_ * 8);
+                // (the key's tables hold every multiple of every window; a key built on plain bases -- the diagnosis
+                // library's MANTA_VERIFY_ABC_C = 0 -- is refused here: its Horner fold is a host job)
+                if (!rc) rc = g1_->msm_fold_device(w.ws, w.ws->folded.as<u32>(), xw);
+                if (rc) return rc;
             }
-            // the Miller launch's upload is assembled while the MSM runs
-            std::memset(qs.data(), 0, 3 * m * G2L * 8);
+            // the Miller launch's upload is assembled while the MSM runs: member-major, all L_i, then all A_i, then all C_i
+            pairs.clear();
+            for (size_t i = 0; i < m; ++i) pairs.prepared(xyzz ? nullptr : abc_.data(), d_gamma_neg());
             for (size_t i = 0; i < m; ++i) {
-                const u64 *pr = proofs + (lo + i) * PL;
-                if (P_ == 1) std::memcpy(&ps[i * G1L], abc_.data(), G1L * 8);
-                else std::memset(&ps[i * G1L], 0, G1L * 8); // (ignored: the XYZZ prefix)
-                std::memcpy(&ps[(m + i) * G1L], pr, G1L * 8);
-                std::memcpy(&ps[(2 * m + i) * G1L], pr + G1L + G2L, G1L * 8);
-                std::memcpy(&qs[(m + i) * G2L], pr + G1L, G2L * 8);
-                cp[i] = d_gamma_neg(), cp[m + i] = nullptr, cp[2 * m + i] = d_delta_neg();
-                skip[i] = 0, skip[m + i] = (unsigned char)is_zero_limbs(pr + G1L, G2L), skip[2 * m + i] = 0;
+                const Row row(proofs + (lo + i) * Row::LIMBS);
+                pairs.fresh(row.a, row.b);
             }
-            const bool xyzz = P_ > 1;
-            rc = pe_->pairing_check_groups((const u32 *)ps.data(), xyzz ? ws->folded.as<u32>() : nullptr, xyzz ? m : 0,
-                                           xyzz ? (void *)ws->stream : nullptr, cp.data(), (const u32 *)qs.data(), skip.data(), 3, m,
-                                           d_alpha_beta_, ok + lo);
-            if (ws) { // (also on the error paths: nothing of this call stays in flight; the host fold is not needed)
-                hipStreamSynchronize(ws->stream), ws->pending = 0;
-                g1_->ws_release(ws);
-            }
-            if (rc) return rc;
+            for (size_t i = 0; i < m; ++i) pairs.prepared(Row(proofs + (lo + i) * Row::LIMBS).c, d_delta_neg());
+            PairList pl = pairs.list();
+            if (xyzz) pl.d_p_xyzz = w.ws->folded.as<u32>(), pl.n_xyzz = m, pl.producer = (void *)w.ws->stream;
+            // (the MSM's host fold is not needed: the scope gives the launch up once the verdicts are back)
+            if (const int rc = pe_->pairing_check_groups(pl, 3, m, d_alpha_beta_, ok + lo)) return rc;
         }
         return MG_OK;
     }
@@ -632,7 +635,7 @@ template <class Curve, class K> class VerifierT : public Verifier {
             g2_->hp_serialize(&hp, out + off, true);
             off += 2 * FB;
         }
-        for (int i = 0; i < 8; ++i) out[off + i] = (uint8_t)(P_ >> (8 * i));
+        host::put_u64le(out + off, P_);
         off += 8;
         for (u64 j = 0; j < P_; ++j) {
             g1_->hp_from_affine(&hp, (const u32 *)(abc_.data() + j * G1L));
@@ -643,7 +646,7 @@ template <class Curve, class K> class VerifierT : public Verifier {
         const std::vector<u32> *co[2] = {&gneg_host_, &dneg_host_};
         const u64 nco = (u64)pe_->n_coeffs();
         for (int b = 0; b < 2; ++b) {
-            for (int i = 0; i < 8; ++i) out[off + i] = (uint8_t)(nco >> (8 * i));
+            host::put_u64le(out + off, nco);
             off += 8;
             for (size_t k = 0; k < nco * 6; ++k, off += FB) write_fq_words(co[b]->data() + k * 2 * N64, out + off);
             out[off++] = 0;
@@ -664,54 +667,29 @@ template <class Curve, class K> class VerifierT : public Verifier {
     }
 };
 
+// a verifier of `curve`, handed out only if init(verifier) succeeds
+template <class Init> int make_verifier(int curve, Verifier **out, Init init) {
+    auto finish = [&](auto *v) {
+        const int rc = init(*v);
+        if (rc) delete v;
+        else *out = v;
+        return rc;
+    };
+    if (curve == 0) return finish(new VerifierT<Bn254, Bn254Pairing>());
+    if (curve == 1) return finish(new VerifierT<Bls381, Bls381Pairing>());
+    return MG_ERR_ARG;
+}
+
 } // namespace
 
 int verifier_create(int curve, const u64 *alpha, const u64 *beta, const u64 *gamma, const u64 *delta, const u64 *abc, u64 P,
                     Verifier **out) {
     if (!out) return MG_ERR_ARG;
-    int rc;
-    if (curve == 0) {
-        auto *v = new VerifierT<Bn254, Bn254Pairing>();
-        if ((rc = v->init_from_points(curve, alpha, beta, gamma, delta, abc, P))) {
-            delete v;
-            return rc;
-        }
-        *out = v;
-        return MG_OK;
-    }
-    if (curve == 1) {
-        auto *v = new VerifierT<Bls381, Bls381Pairing>();
-        if ((rc = v->init_from_points(curve, alpha, beta, gamma, delta, abc, P))) {
-            delete v;
-            return rc;
-        }
-        *out = v;
-        return MG_OK;
-    }
-    return MG_ERR_ARG;
+    return make_verifier(curve, out, [&](auto &v) { return v.init_from_points(curve, alpha, beta, gamma, delta, abc, P); });
 }
 int verifier_create_from_bytes(int curve, const uint8_t *bytes, size_t len, Verifier **out) {
     if (!out || !bytes) return MG_ERR_ARG;
-    int rc;
-    if (curve == 0) {
-        auto *v = new VerifierT<Bn254, Bn254Pairing>();
-        if ((rc = v->init_from_bytes(curve, bytes, len))) {
-            delete v;
-            return rc;
-        }
-        *out = v;
-        return MG_OK;
-    }
-    if (curve == 1) {
-        auto *v = new VerifierT<Bls381, Bls381Pairing>();
-        if ((rc = v->init_from_bytes(curve, bytes, len))) {
-            delete v;
-            return rc;
-        }
-        *out = v;
-        return MG_OK;
-    }
-    return MG_ERR_ARG;
+    return make_verifier(curve, out, [&](auto &v) { return v.init_from_bytes(curve, bytes, len); });
 }
 int proof_decode(int curve, const uint8_t *bytes, u64 *points_out) {
     if (!bytes || !points_out) return MG_ERR_ARG;

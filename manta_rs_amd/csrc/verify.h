@@ -5,6 +5,30 @@
 
 namespace mg {
 
+// A set of n pairs (P_i, Q_i) for the Miller loops, the one argument of every engine call that takes pairs. Plain pointers,
+// borrowed for the call (begin() has staged what it needs before it returns).
+struct PairList {
+    size_t n = 0;
+    // n affine G1 points, host Montgomery words; all zero = infinity, and such a pair contributes 1. The entries of the XYZZ
+    // prefix below, and of the pairs a two-step product takes later, are not read
+    const u32 *p_affine_host = nullptr;
+    // n pointers: d_coeffs[i] = the prepared Q_i in device memory (from prepare()), or null where Q_i is a fresh affine point,
+    // prepared on the fly next to its Miller loop
+    const u32 *const *d_coeffs = nullptr;
+    // n affine G2 points, host Montgomery words, read where d_coeffs[i] is null; may be null when every pair is prepared.
+    // A fresh Q_i that is all zero (infinity) leaves its pair out: the engine sees to that itself
+    const u32 *q_affine_host = nullptr;
+    // optional, n flags: skip[i] != 0 leaves pair i out (it contributes 1) -- the only way to leave out a PREPARED pair,
+    // whose infinity shows in no argument (its coefficient block is all zero and must never be consumed)
+    const unsigned char *skip = nullptr;
+    // optional prefix: the G1 points of the first n_xyzz pairs lie in DEVICE memory as (X, Y, ZZ, ZZZ), 4 fq_words() each, left
+    // there by a kernel on the HIP stream `producer`, which the Miller launch waits for (the lines of such a pair are taken
+    // times ZZ ZZZ, which the final exponentiation removes: no inversion between a scalar multiplication and its pairing)
+    const u32 *d_p_xyzz = nullptr;
+    size_t n_xyzz = 0;
+    void *producer = nullptr;
+};
+
 class PairingEngine {
   public:
     virtual ~PairingEngine() {}
@@ -14,23 +38,12 @@ class PairingEngine {
     virtual int fq_words() const = 0;
     // G2Prepared::from for n affine points (host, Montgomery) -> device array n x n_coeffs x coeff_words (hipFree it)
     virtual int prepare(const u32 *q_affine_host, size_t n, u32 **d_out) = 0;
-    // out = [final_exponentiation] ( prod_i MillerLoop(P_i, Q_i) ): P host affine G1; Q_i either prepared (d_coeffs[i] a
-    // device pointer from prepare()) or, where d_coeffs[i] is null, the affine G2 point q_affine_host[i] (prepared on the
-    // fly next to its Miller loop; q_affine_host may be null when every pair is prepared);
-    // skip[i] != 0 leaves pair i out (its G2 point was infinity)
-    virtual int pairing_product(const u32 *p_affine_host, const u32 *const *d_coeffs, const u32 *q_affine_host,
-                                const unsigned char *skip, size_t n, bool do_final_exp, u32 *out_f12_host) = 0;
-    // the same with the G1 points of the first n_xyzz pairs in DEVICE memory as (X, Y, ZZ, ZZZ), 4 fq_words() each -- left there
-    // by a kernel on the HIP stream `producer` (the lines of such a pair are taken times ZZ ZZZ, which the final
-    // exponentiation removes: no inversion between a scalar multiplication and its pairing)
-    virtual int pairing_product_xyzz(const u32 *p_affine_host, const u32 *d_p_xyzz, size_t n_xyzz, void *producer,
-                                     const u32 *const *d_coeffs, const u32 *q_affine_host, const unsigned char *skip, size_t n,
-                                     bool do_final_exp, u32 *out_f12_host) = 0;
+    // out = [final_exponentiation] ( prod_i MillerLoop(P_i, Q_i) )
+    virtual int pairing_product(const PairList &pairs, bool do_final_exp, u32 *out_f12_host) = 0;
     // the same in two steps: the Miller loops of the first n_early pairs start at once (P points of those only; coefficients /
     // Q / skip of all n); end() takes the G1 points of the other pairs -- which must have prepared coefficients -- and finishes.
     // A handle is consumed by exactly one end() or abandon().
-    virtual int pairing_product_begin(const u32 *p_affine_host, const u32 *const *d_coeffs, const u32 *q_affine_host,
-                                      const unsigned char *skip, size_t n, size_t n_early, void **handle) = 0;
+    virtual int pairing_product_begin(const PairList &pairs, size_t n_early, void **handle) = 0;
     virtual int pairing_product_end(void *handle, const u32 *p_late_affine_host, bool do_final_exp, u32 *out_f12_host) = 0;
     virtual void pairing_product_abandon(void *handle) = 0;
     // *ok = (prod_i e(P_i, Q_i) == 1): all points host affine Montgomery words, every Q_i prepared on the fly; a pair with an
@@ -38,13 +51,11 @@ class PairingEngine {
     virtual int product_is_one(const u32 *p_affine_host, const u32 *q_affine_host, size_t n, int *ok) = 0;
     // n_groups <= MG_VERIFY_EACH_CHUNK independent products of group_size <= 64 pairs each, a verdict each:
     //     verdict_host[t] = (final_exponentiation(prod_{j < group_size} MillerLoop(P_{t,j}, Q_{t,j})) == target)
-    // The pairs lie MEMBER-MAJOR -- pair j of group t at index j * n_groups + t in every array -- and are otherwise given as to
-    // pairing_product_xyzz, the XYZZ prefix included (n_xyzz = n_groups: the first member of every group comes from the
-    // device). d_target: an Fq12 in device memory, null = 1. One Miller launch and one tail launch whatever the verdicts;
-    // only the verdict bytes are downloaded.
-    virtual int pairing_check_groups(const u32 *p_affine_host, const u32 *d_p_xyzz, size_t n_xyzz, void *producer,
-                                     const u32 *const *d_coeffs, const u32 *q_affine_host, const unsigned char *skip, size_t group_size,
-                                     size_t n_groups, const u32 *d_target, unsigned char *verdict_host) = 0;
+    // pairs.n = group_size * n_groups, MEMBER-MAJOR: pair j of group t at index j * n_groups + t in every array (an XYZZ prefix
+    // of n_groups pairs: the first member of every group comes from the device). d_target: an Fq12 in device memory,
+    // null = 1. One Miller launch and one tail launch whatever the verdicts; only the verdict bytes are downloaded.
+    virtual int pairing_check_groups(const PairList &pairs, size_t group_size, size_t n_groups, const u32 *d_target,
+                                     unsigned char *verdict_host) = 0;
     // product_is_one per group: points [n_groups][group_size], group-major as a caller holds them; any n_groups (chunked)
     virtual int product_is_one_each(const u32 *p_affine_host, const u32 *q_affine_host, size_t group_size, size_t n_groups,
                                     unsigned char *ok) = 0;

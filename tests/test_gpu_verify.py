@@ -214,6 +214,52 @@ def test_gpu_batch_verification(gpu, curve, k):
 
 
 @pytest.mark.parametrize("curve", [0, 1])
+def test_gpu_verify_with_infinity_members_in_a_proof_row(gpu, curve):
+    """Proof rows whose points are infinity (all-zero limbs): b, a, or the whole row. The pair with the infinity member
+    contributes 1, so the equation fails: `groth16_verify` says False, `groth16_verify_each` says the same for that row, and
+    `groth16_verify_batch` rejects the block that holds it. The fresh G2 point at infinity is the pairing engine's to leave
+    out -- no caller flags it."""
+    k = 4
+    c0 = synth.make_circuit(curve, 500, 380, 6, seed=950 + curve)
+    pk = keygen.generate(c0, synth.from_mont(H.toxic(curve, seed=32), synth.FR_MODULUS[curve]))
+    ctx = gpu.ProvingContext(curve, pk)
+    ctx.set_r1cs(gpu.R1CS.from_circuit(c0))
+    vctx = gpu.VerifyingContext(curve, pk)
+    R = synth.Reassigner(c0)
+    cs = [R.assign(5000 + q) for q in range(k)]
+    rs = H.rand_fr_mont(curve, 2 * k, seed=97)
+    proofs = gpu.Groth16.prove_batch(ctx, np.stack([x.z for x in cs]), rs[:k], rs[k:])
+    rows = np.stack([gpu.proof_decode(curve, p) for p in proofs])
+    inputs = np.stack([x.z[1:c0.P] for x in cs])
+    rnd = np.random.RandomState(6).randint(1, 1 << 62, size=(k, 2)).astype(np.uint64)
+    assert gpu.groth16_verify_batch(vctx, inputs, rows, rnd) is True
+    assert gpu.groth16_verify_each(vctx, inputs, rows).tolist() == [True] * k
+    w1 = gpu.affine_limbs(curve, 1)
+    for what, sl in (("b", slice(w1, 3 * w1)), ("a", slice(0, w1)), ("row", slice(0, 4 * w1))):
+        bad = rows.copy()
+        bad[1, sl] = 0
+        assert gpu.groth16_verify(vctx, inputs[1], bad[1]) is False, what
+        assert gpu.groth16_verify_each(vctx, inputs[1:2], bad[1:2]).tolist() == [False], what
+        assert gpu.groth16_verify_each(vctx, inputs, bad).tolist() == [True, False, True, True], what
+        assert gpu.groth16_verify_batch(vctx, inputs, bad, rnd) is False, what
+
+
+@pytest.mark.parametrize("curve", [0, 1])
+def test_gpu_pairing_with_beta_at_infinity_is_one(gpu, curve):
+    """e(P, infinity) = 1: a key whose beta_g2 is infinity. Its prepared block is all zero and must never be consumed -- the
+    one pair a caller of the engine has to leave out itself."""
+    r = synth.FR_MODULUS[curve]
+    G1, G2 = O.generator(curve, 1), O.generator(curve, 2)
+    k = _Key()
+    k.alpha_g1 = O.g_mul(curve, 1, G1, synth.ints_to_limbs([0x1234567890abcdef % r], 4)[0])
+    k.beta_g2 = np.zeros_like(G2)
+    k.gamma_g2, k.delta_g2, k.gamma_abc_g1 = G2, G2, np.stack([G1])
+    one = gpu.VerifyingContext(curve, k).alpha_g1_beta_g2()
+    nb = len(one) // 12
+    assert one == (1).to_bytes(nb, "little") + bytes(11 * nb)
+
+
+@pytest.mark.parametrize("curve", [0, 1])
 def test_valid_pairing_ratio_like_the_reference(gpu, curve):
     """manta-crypto/src/arkworks/pairing.rs:295-330 `{bls12_381,bn254}_has_valid_pairing_ratio`: for random g1, g2 and
     scalar, E::same((g1, g2 * scalar), (g1 * scalar, g2)) holds -- on the GPU (`mg_pairing_check`), for several draws,
