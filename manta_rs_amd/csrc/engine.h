@@ -254,7 +254,9 @@ struct MsmWorkspace {
     hipEvent_t t0 = nullptr, t1 = nullptr; // optional timing of the dominant (accumulate) kernel
     bool timed = false;
     bool in_graph_slot = false; // owned by a proof slot (prover_passes.h): its launches never use the engine's side stream
-    bool capturing = false; // msm_launch is being stream-captured: enqueue kernels and copies only, no event records
+    // msm_launch is being stream-captured into a LINEAR unit of a proof slot (prover_slot.h PassUnit; set by build_graphs_locked
+    // alone, for the length of that capture): enqueue kernels and copies only, no event records
+    bool capturing = false;
     // notify: after the staged result a 4-byte token is copied to *h_flag (pinned), so that a host that zeroed it before the
     // launch can see THIS chain end without a stream or event wait (a chain inside a captured multi-branch graph has neither)
     bool notify = false;

@@ -97,6 +97,17 @@ class ProverImpl : public ProverSlots {
     int cq_inflight_ = 0, cq_batched_inflight_ = 0; // passes of this context's coalescing queue on the GPU; those of more than one proof
     bool cq_gathering_ = false; // a leader is waiting for the callers of the pass that has just finished
     size_t cq_last_k_ = 1;      // size of the most recently finished pass
+    // a pass body run where nothing may be thrown further (a coalescing leader, a library thread): exceptions become status codes
+    template <class Fn> static int no_throw(Fn &&body) {
+        try {
+            return body();
+        } catch (const std::bad_alloc &) {
+            return MG_ERR_OOM;
+        } catch (...) {
+            return MG_ERR_STATE;
+        }
+    }
+    size_t proof_bytes() const { return 2 * (size_t)g1_->point_bytes(true) + (size_t)g2_->point_bytes(true); } // compressed A, B, C
     int prove(const uint64_t *z, const uint64_t *r, const uint64_t *s, uint8_t *proof_out) override {
         if (!z || !r || !s || !proof_out) return MG_ERR_ARG;
         if (task_mask_ != 0x1f) return MG_ERR_STATE; // holds some of the MSMs only: partials_launch / assemble
@@ -137,14 +148,8 @@ class ProverImpl : public ProverSlots {
                 ++cq_inflight_;
                 if (batched) ++cq_batched_inflight_;
                 lk.unlock();
-                int rc; // nothing may escape here: the followers of this batch wait on cq_cv_ for their `done`
-                try {
-                    rc = prove_gathered(batch, company);
-                } catch (const std::bad_alloc &) {
-                    rc = MG_ERR_OOM;
-                } catch (...) {
-                    rc = MG_ERR_STATE;
-                }
+                // nothing may escape here: the followers of this batch wait on cq_cv_ for their `done`
+                const int rc = no_throw([&] { return prove_gathered(batch, company); });
                 lk.lock();
                 for (Req *q : batch) q->rc = rc, q->done = true;
                 --cq_inflight_;
@@ -166,7 +171,7 @@ class ProverImpl : public ProverSlots {
         size_t kp = k <= 8 ? k : (k + 3) / 4 * 4;
         if (ab_knob("MANTA_COALESCE_POW2", 0) > 0) // round up to a power of two (the round-2 rule)
             for (kp = 1; kp < k;) kp <<= 1;
-        const size_t pbytes = 2 * (size_t)g1_->point_bytes(true) + (size_t)g2_->point_bytes(true);
+        const size_t pbytes = proof_bytes();
         std::vector<const uint64_t *> zl(kp);
         std::vector<uint64_t> rr(kp * 4), ss(kp * 4);
         std::vector<uint8_t> out(kp * pbytes);
@@ -196,7 +201,7 @@ class ProverImpl : public ProverSlots {
         // (passes of exactly BATCH_CHUNK proofs plus one remainder: every distinct pass size needs its own workspaces and graphs)
         const u64 fl = (u64)batch_inflight(), per = BATCH_CHUNK;
         const u64 chunks = (k64 + per - 1) / per;
-        const size_t pbytes = 2 * (size_t)g1_->point_bytes(true) + (size_t)g2_->point_bytes(true); // compressed A, B, C
+        const size_t pbytes = proof_bytes();
         std::atomic<u64> next{0};
         std::atomic<int> first_rc{MG_OK};
         auto worker = [&]() noexcept {
@@ -205,14 +210,7 @@ class ProverImpl : public ProverSlots {
                 if (c >= chunks || first_rc.load() != MG_OK) return;
                 const u64 lo = c * per, n = std::min(per, k64 - lo);
                 stream_gate_acquire(); // at most `fl` streamed passes in flight per context, however many callers
-                int rc;
-                try {
-                    rc = prove_pass(n, z + lo * V_ * 4, r + lo * 4, s + lo * 4, proofs_out + lo * pbytes);
-                } catch (const std::bad_alloc &) {
-                    rc = MG_ERR_OOM;
-                } catch (...) {
-                    rc = MG_ERR_STATE;
-                }
+                const int rc = no_throw([&] { return prove_pass(n, z + lo * V_ * 4, r + lo * 4, s + lo * 4, proofs_out + lo * pbytes); });
                 stream_gate_release();
                 int ok = MG_OK;
                 if (rc) first_rc.compare_exchange_strong(ok, rc);
@@ -285,6 +283,17 @@ class ProverImpl : public ProverSlots {
         return a.type == hipMemoryTypeHost;
     }
 
+    // the slot's pinned staging copy of the assignment holds at least `bytes`
+    static int reserve_staging(ProveWs *w, size_t bytes) {
+        if (w->h_z_cap >= bytes) return MG_OK;
+        HeavyOp pinned_allocation_not_beside_a_capture;
+        if (w->h_z) hipHostFree(w->h_z);
+        w->h_z = nullptr;
+        w->h_z_cap = 0;
+        if (hipHostMalloc(&w->h_z, bytes, hipHostMallocDefault) != hipSuccess) return MG_ERR_OOM;
+        w->h_z_cap = bytes;
+        return MG_OK;
+    }
     // stage z, enqueue (or replay) the GPU side of k proofs on a slot; returns without waiting
     // (z_list: the k assignments as separate buffers -- coalesced single calls -- gathered into the slot's staging copy)
     int launch_pass(Pass &p, u32 k, const uint64_t *z, const uint64_t *r, const uint64_t *s, uint8_t *out,
@@ -312,14 +321,7 @@ class ProverImpl : public ProverSlots {
                 stage = stage || pageable[q];
             }
             if (stage) {
-                if (w->h_z_cap < zbytes) {
-                    HeavyOp pinned_allocation_not_beside_a_capture;
-                    if (w->h_z) hipHostFree(w->h_z);
-                    w->h_z = nullptr;
-                    w->h_z_cap = 0;
-                    if (hipHostMalloc(&w->h_z, zbytes, hipHostMallocDefault) != hipSuccess) return MG_ERR_OOM;
-                    w->h_z_cap = zbytes;
-                }
+                if (int rc2 = reserve_staging(w, zbytes)) return rc2;
                 for (u32 q = 0; q < k; ++q)
                     if (pageable[q]) {
                         std::memcpy((char *)w->h_z + (size_t)q * V_ * 32, z_list[q], (size_t)V_ * 32);
@@ -329,14 +331,7 @@ class ProverImpl : public ProverSlots {
             stage = false;
         }
         if (stage) {
-            if (w->h_z_cap < zbytes) {
-                HeavyOp pinned_allocation_not_beside_a_capture;
-                if (w->h_z) hipHostFree(w->h_z);
-                w->h_z = nullptr;
-                w->h_z_cap = 0;
-                if (hipHostMalloc(&w->h_z, zbytes, hipHostMallocDefault) != hipSuccess) return MG_ERR_OOM;
-                w->h_z_cap = zbytes;
-            }
+            if ((rc = reserve_staging(w, zbytes))) return rc;
             std::memcpy(w->h_z, z, zbytes);
             z_src = (const uint64_t *)w->h_z;
         }
@@ -348,19 +343,15 @@ class ProverImpl : public ProverSlots {
                 if (!e) ok = ok && hipEventCreate(&e) == hipSuccess;
             w->timed = ok;
         }
-        if (!w->graphs_ready && graph_mode_for(w->k) != GRAPH_OFF && !w->no_graph && w->eager_runs >= 2 && !w->timed) build_graphs(w);
+        if (!w->graphs_ready && w->n_units && !w->no_graph && w->eager_runs >= 2 && !w->timed) build_graphs(w);
         if (w->mw[0]->notify && w->mw[0]->h_flag) { // the combined MSM's end-of-chain token of THIS pass (z3 slots)
             *(volatile u32 *)w->mw[0]->h_flag = 0;
             std::atomic_thread_fence(std::memory_order_seq_cst);
         }
-        if (w->timed) {
-            HeavyOp eager_passes_allocate; // (see below)
-            rc = enqueue_proof(w, z_src, false);
-        } else if (w->graphs_ready) {
-            rc = enqueue_proof(w, z_src, graph_mode_for(w->k) == GRAPH_SPLIT);
+        if (w->graphs_ready && !w->timed) {
+            rc = enqueue_proof(w, z_src);
             if (rc) { // do not trust the graphs again; the failed pass is reported to the caller
-                hipStreamSynchronize(w->stream);
-                for (int i = 0; i < 5; ++i) hipStreamSynchronize(msm_stream(w, i));
+                drain(w);
                 w->drop_graphs();
                 w->no_graph = true;
             }
@@ -369,8 +360,8 @@ class ProverImpl : public ProverSlots {
             // like context creation it must not run while another thread captures (capture_mutex, engine.h) -- with contexts
             // recycled every 2 s the soak saw 70 000 calls fail on a slot whose first pass had met a capture
             HeavyOp eager_passes_allocate;
-            rc = enqueue_proof(w, z_src, false);
-            w->eager_runs++;
+            rc = enqueue_proof(w, z_src);
+            if (!w->timed) w->eager_runs++;
         }
         return rc;
     }
@@ -382,37 +373,29 @@ class ProverImpl : public ProverSlots {
         if (!w) return MG_ERR_HIP;
         int rc = MG_OK;
         hipSetDevice(dev_);
-        hipError_t e = hipStreamSynchronize(part_a ? w->stream : msm_stream(w, 2));
-        if (e != hipSuccess) {
-            set_last_hip_error(e, "prove: hipStreamSynchronize", __FILE__, __LINE__);
-            rc = MG_ERR_HIP;
-        }
+        auto wait = [&](hipStream_t s) {
+            const hipError_t e = hipStreamSynchronize(s);
+            if (e != hipSuccess && !rc) {
+                set_last_hip_error(e, "prove: hipStreamSynchronize", __FILE__, __LINE__);
+                rc = MG_ERR_HIP;
+            }
+        };
+        // Every stream this part of the pass was launched on: the part's own (eager MSM streams are joined into it), then that of
+        // every unit of the part replayed elsewhere -- a linear slot's combined MSM, whose graph runs on a stream nothing joins.
+        // That one is waited on even when finish_pass_body has taken its results already (z3_folded): the end-of-chain token
+        // has been seen, but the RUNTIME only retires a launch when its stream is waited on -- without this the stream is never
+        // synchronised in the slot's whole life and its graph exec could be destroyed with launches the runtime still tracks.
+        hipStream_t part = part_a ? w->stream : msm_stream(w, 2);
+        wait(part);
+        for (int n = 0; w->replayed && n < w->n_units; ++n)
+            if ((w->unit[n].parts & (part_a ? 0x1bu : 0x04u)) && w->unit[n].stream != part) wait(w->unit[n].stream);
         for (int i = 0; i < 5; ++i) {
             if (in_part_a(i) != part_a) continue;
             if (w->z3 && (i == 1 || i == 3)) continue; // part of the combined MSM on mw[0]
-            if (w->z3 && i == 0 && p.z3_folded) { // finish_pass_body took its results when its chain ended
-                // (a linear3 slot: the combined MSM's graph runs on a stream nothing joins; its end-of-chain token has been seen, but
-                // the RUNTIME only retires a launch when its stream is waited on -- without this the stream is never synchronised
-                // in the slot's whole life and its graph exec could be destroyed with launches the runtime still tracks)
-                if (w->linear3) (void)hipStreamSynchronize(msm_stream(w, 0));
-                continue;
-            }
+            if (w->z3 && i == 0 && p.z3_folded) continue; // finish_pass_body took its results when its chain ended
             if (w->z3 && i == 0 && w->mw[0]->pending) { // three results per proof: a, b_g1, l
-                if (w->linear3) { // (its graph runs on a stream of its own, joined by nothing)
-                    const hipError_t e3 = hipStreamSynchronize(msm_stream(w, 0));
-                    if (e3 != hipSuccess && !rc) {
-                        set_last_hip_error(e3, "prove: hipStreamSynchronize", __FILE__, __LINE__);
-                        rc = MG_ERR_HIP;
-                    }
-                }
-                std::vector<HostPoint> t3((size_t)3 * p.k);
-                int rc2 = w->me[0]->msm_finish(w->mw[0], t3.data(), true);
+                int rc2 = finish_z3(w, p.k, res);
                 if (!rc) rc = rc2;
-                for (u32 q = 0; q < p.k; ++q) {
-                    res[(size_t)0 * p.k + q] = t3[(size_t)q * 3 + 0];
-                    res[(size_t)1 * p.k + q] = t3[(size_t)q * 3 + 1];
-                    res[(size_t)3 * p.k + q] = t3[(size_t)q * 3 + 2];
-                }
                 continue;
             }
             if (w->mw[i]->pending) {
@@ -425,14 +408,21 @@ class ProverImpl : public ProverSlots {
         }
         return rc;
     }
+    // the combined MSM's three results per proof (a, b_g1, l), folded into res[0], res[1] and res[3] of res[i * k + q]
+    static int finish_z3(ProveWs *w, u32 k, HostPoint *res) {
+        std::vector<HostPoint> t3((size_t)3 * k);
+        const int rc = w->me[0]->msm_finish(w->mw[0], t3.data(), true);
+        for (u32 q = 0; q < k; ++q) {
+            res[(size_t)0 * k + q] = t3[(size_t)q * 3 + 0];
+            res[(size_t)1 * k + q] = t3[(size_t)q * 3 + 1];
+            res[(size_t)3 * k + q] = t3[(size_t)q * 3 + 2];
+        }
+        return rc;
+    }
     void abandon_pass(Pass &p) { // a pass that will not be assembled: drain its streams, return the slot
         if (!p.w) return;
         hipSetDevice(dev_);
-        hipStreamSynchronize(p.w->stream);
-        for (int i = 0; i < 5; ++i) {
-            hipStreamSynchronize(msm_stream(p.w, i));
-            p.w->mw[i]->pending = 0;
-        }
+        drain(p.w);
         ws_release(p.w);
         p.w = nullptr;
     }
@@ -468,23 +458,21 @@ class ProverImpl : public ProverSlots {
             return rc ? rc : MG_ERR_HIP;
         }
         const size_t sw = slot_words();
-        // the fold of MSM i goes behind it: on its own stream, or -- when the pass was replayed from the two graphs of the
-        // "single" mode -- on the stream its graph was launched on (the G1 MSMs are joined inside that graph)
-        const bool replayed = w->graphs_ready && w->g_all && w->g_g2;
-        auto fold_stream = [&](int i) { return replayed ? (i == 2 ? msm_stream(w, 2) : w->stream) : msm_stream(w, i); };
+        // the fold of MSM i goes behind it, on the stream where its result is complete (another rank's MSM: a pass that holds a
+        // subset of the MSMs is never replayed -- launch_pass -- so that is the stream the MSM would have run on)
         for (int i = 0; i < 5 && !rc; ++i) {
             if (does(i)) {
-                rc = w->me[i]->msm_fold_device(w->mw[i], (u32 *)d_out + (size_t)i * sw, 5 * sw, fold_stream(i));
+                rc = w->me[i]->msm_fold_device(w->mw[i], (u32 *)d_out + (size_t)i * sw, 5 * sw, done_stream(w, i));
             } else { // another rank's MSM: this rank contributes the point at infinity (all-zero XYZZ)
                 for (u64 q = 0; q < k64 && !rc; ++q)
-                    if (hipMemsetAsync((u32 *)d_out + (q * 5 + (u64)i) * sw, 0, sw * 4, fold_stream(i)) != hipSuccess) rc = MG_ERR_HIP;
+                    if (hipMemsetAsync((u32 *)d_out + (q * 5 + (u64)i) * sw, 0, sw * 4, done_stream(w, i)) != hipSuccess) rc = MG_ERR_HIP;
             }
         }
         hipStream_t cs = (hipStream_t)consumer;
         if (!rc) {
             hipError_t e = hipSuccess;
             for (int i = 0; i < 5 && e == hipSuccess; ++i) {
-                hipStream_t ms = fold_stream(i);
+                hipStream_t ms = done_stream(w, i);
                 e = hipEventRecord(w->mw[i]->done, ms);
                 if (e == hipSuccess && cs != ms) e = hipStreamWaitEvent(cs, w->mw[i]->done, 0);
             }
@@ -826,17 +814,15 @@ class ProverImpl : public ProverSlots {
                     break;
                 }
                 // (a failed launch or a device fault never writes the token: every few microseconds ask the stream itself)
-                if ((spin & 1023u) == 1023u && hipStreamQuery(w->linear3 ? msm_stream(w, 0) : w->stream) != hipErrorNotReady) break;
+                if ((spin & 1023u) == 1023u && hipStreamQuery(done_stream(w, 0)) != hipErrorNotReady) break;
                 cpu_relax();
                 if (spin >= 2048u && (spin & 15u) == 15u) std::this_thread::yield();
             }
             if (!seen && *flag) seen = true; // (the stream reported complete: the token was written before that)
             std::atomic_thread_fence(std::memory_order_seq_cst);
             if (seen) {
-                HostPoint t3[3];
-                const int rc2 = w->me[0]->msm_finish(w->mw[0], t3, true);
+                const int rc2 = finish_z3(w, k, res.data());
                 if (!rc2) {
-                    res[0] = t3[0], res[1] = t3[1], res[3] = t3[2];
                     p.z3_folded = true;
                     assemble_g1_early(res.data(), bl[0], r, &early, p.out);
                     have_early = true;

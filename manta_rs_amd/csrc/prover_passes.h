@@ -8,7 +8,7 @@ namespace {
 
 class ProverSlots : public ProverAssembly {
   public:
-    // How a SINGLE proof's slot replays (ProveWs::linear3). 0: the forked graph. 1: three linear graphs -- witness map + h | a|b_g1|l
+    // How a SINGLE proof's slot replays (ProveWs::flavour). 0: the forked graph. 1: three linear graphs -- witness map + h | a|b_g1|l
     // | G2 -- on three high-priority streams: the shortest chain for a LONE proof (company 0: no other pass of this context in
     // flight). 2 / 3: the same beside other passes, with ONE chain on a normal-priority stream -- the combined MSM beside a batched
     // pass (company 2), the G2 MSM beside single proofs only (company 1: two host threads). The streams come from
@@ -49,7 +49,7 @@ class ProverSlots : public ProverAssembly {
             std::lock_guard<std::mutex> g(mu_);
             w->no_graph = no_graph_keys_.count(slot_key(k, z3, lin_flavour(k, z3, company))) != 0; // (a capture of this kind failed for good)
         }
-        static const int z3_high = ab_knob("MANTA_Z3_HIGH", -1); // A/B: the combined MSM's stream of every linear3 slot normal (0) / high (1) priority
+        static const int z3_high = ab_knob("MANTA_Z3_HIGH", -1); // A/B: the combined MSM's stream of every linear slot normal (0) / high (1) priority
         w->flavour = lin_flavour(k, z3, company);
         if (w->flavour && stream_set_acquire(w->sset, z3_high >= 0 ? z3_high != 0 : w->flavour == 1))
             w->stream = w->sset.main, w->side[0] = w->sset.g2, w->side[1] = w->sset.z3;
@@ -77,35 +77,47 @@ class ProverSlots : public ProverAssembly {
         // still running (finish_pass_body). MANTA_Z3_EARLY=0: wait for all of part A first, as before (A/B).
         static const bool z3_early = ab_knob("MANTA_Z3_EARLY", 1) != 0;
         w->mw[0]->notify = z3 && z3_early;
-        // Three streams per proof, not six: the G2 MSM is the critical path (~3x a G1 MSM), so the three
-        // z-MSMs over G1 run back to back beside it and the h MSM follows the witness map on the main stream.
-        // Fewer streams = fewer hardware queues per proof in flight (the runtime multiplexes streams onto
-        // GPU_MAX_HW_QUEUES queues; streams that share one serialise). MANTA_PROVE_STREAMS=6 restores one
-        // stream per MSM.
-        w->mw[2]->run_on = w->side[0]; // the G2 MSM (the critical path) gets a high-priority stream of its own
-        if (w->flavour) {
-            w->linear3 = true;
-            w->mw[0]->run_on = w->side[1]; // the combined MSM: a high-priority pooled stream of its own
-            w->mw[4]->run_on = w->stream;  // the h MSM follows the witness map on the main stream
-        } else
-        if (prove_streams() == 3) {
-            w->mw[0]->run_on = w->side[1];
-            w->mw[1]->run_on = w->side[1];
-            w->mw[2]->run_on = w->side[0];
-            w->mw[3]->run_on = w->side[1];
-            w->mw[4]->run_on = w->stream;
-        } else if (prove_streams() == 1) {
-            for (int i = 0; i < 5; ++i) w->mw[i]->run_on = w->stream;
-        } else if (prove_streams() == 4) { // three branches beside the G2 chain: (a, b_g1) back to back | l | witness map + h
-            w->mw[0]->run_on = w->side[1];
-            w->mw[1]->run_on = w->side[1];
-            w->mw[4]->run_on = w->stream;
-        } else if (prove_streams() == 5) { // (a, l) back to back | b_g1 | witness map + h
-            w->mw[0]->run_on = w->side[1];
-            w->mw[3]->run_on = w->side[1];
-            w->mw[4]->run_on = w->stream;
-        }
+        plan_schedule(w);
         return w;
+    }
+    // The schedule of a new slot: which stream each MSM runs on (MSM_LANES) and the units a pass is captured and replayed as.
+    // Launch, capture, replay, wait and fold read it; nothing after this looks at the graph mode or the flavour to find a stream.
+    void plan_schedule(ProveWs *w) {
+        const hipStream_t lane[4] = {w->stream, w->side[0], w->side[1], nullptr}; // (LANE_OWN: the workspace's own stream)
+        for (int i = 0; i < 5; ++i) w->mw[i]->run_on = lane[MSM_LANES[w->flavour ? 0 : prove_streams()][i]];
+        auto add = [&](hipStream_t s, Gate g, unsigned parts, bool linear = true) {
+            w->unit[w->n_units] = PassUnit{s, g, parts, linear, nullptr};
+            for (int i = 0; i <= WM; ++i)
+                if (parts >> i & 1u) w->unit_of[i] = w->n_units;
+            return w->n_units++;
+        };
+        auto part = [&](int i) { return runs(w, i) ? 1u << i : 0u; };
+        const unsigned wm = 1u << WM, g2 = part(2);
+        if (w->flavour) { // three linear graphs, each behind the upload
+            const int ua = add(w->stream, GATE_NONE, wm | part(4)), uz = add(msm_stream(w, 0), GATE_Z_READY, part(0));
+            const int ub = add(msm_stream(w, 2), GATE_Z_READY, g2);
+            // launch order (MANTA_Z3_ORDER, three letters of a = witness map + h, b = G2, z = combined): the chain that bounds the
+            // proof first -- each hipGraphLaunch is 10-20 us of host time, which the chains launched later start behind
+            static const char *order = [] {
+                const char *e = ab_knob_str("MANTA_Z3_ORDER", "abz");
+                return std::strlen(e) == 3 ? e : "abz";
+            }();
+            for (int t = 0; t < 3; ++t) w->replay_order[t] = order[t] == 'a' ? ua : (order[t] == 'b' ? ub : uz);
+            w->n_replay = 3;
+        } else if (graph_mode_for(w->k) == GRAPH_SINGLE) {
+            // (the forked form; single proofs of z3 slots take the three linear graphs above since the memset-node defect was found:
+            // profiles/r05_linear_graph_defect.txt)
+            const int ua = add(w->stream, GATE_NONE, wm | part(0) | part(1) | part(3) | part(4), false);
+            // the G2 graph goes first: it is the longest chain and its launch is the cheaper of the two
+            w->replay_order[0] = add(msm_stream(w, 2), GATE_Z_READY, g2), w->replay_order[1] = ua;
+            w->n_replay = 2;
+        } else if (graph_mode_for(w->k) == GRAPH_SPLIT) {
+            // the witness map and every MSM a graph of its own, launched (and gated) by the eager fork / join of enqueue_part_a in
+            // place of the kernels; no event records inside the captures: the replay path records `done`
+            add(w->stream, GATE_NONE, wm);
+            for (int i = 0; i < 5; ++i)
+                if (runs(w, i)) add(msm_stream(w, i), GATE_NONE, 1u << i);
+        }
     }
     // Idle slots are cached per exact batch size (their buffers and graphs are sized for it) but the cache is
     // bounded: a slot of an outdated circuit generation is destroyed, and beyond MAX_IDLE_SLOTS the least recently
@@ -191,7 +203,7 @@ class ProverSlots : public ProverAssembly {
     int launch_witness_map(ProveWs *w, bool use_graph = false) {
         int rc;
         if (use_graph) {
-            MG_HIP(hipGraphLaunch(w->g_wm, w->stream));
+            MG_HIP(hipGraphLaunch(w->unit[w->unit_of[WM]].exec, w->stream));
         } else if ((rc = enqueue_witness_map_body(w))) {
             return rc;
         }
@@ -234,6 +246,15 @@ class ProverSlots : public ProverAssembly {
         return rc;
     }
 
+    // passes of up to this many proofs run on the full tables where the key has them (MANTA_FULL_MAX_K; a batch sorts its
+    // pairs by proof -- one radix pass -- and needs 32 additions per scalar where the wide bucket tables need 24)
+    static u32 full_max_k() {
+        static const u32 v = [] {
+            const int e = ab_knob("MANTA_FULL_MAX_K", 1);
+            return (u32)(e >= 0 ? e : 1);
+        }();
+        return v;
+    }
     struct MsmArgs {
         const BaseSet *bs[5];
         const u32 *sc[5];
@@ -255,13 +276,7 @@ class ProverSlots : public ProverAssembly {
         const size_t zlo = shard_lo(V_ - 1), zn = shard_hi(V_ - 1) - zlo, llo = shard_lo(V_ - P_), ln = shard_hi(V_ - P_) - llo;
         const size_t hlo = shard_lo(D), hn = shard_hi(D) - hlo;
         const u32 *sz = dz + (1 + zlo) * 8;
-        // passes of up to this many proofs run on the full tables where the key has them (MANTA_FULL_MAX_K; a batch sorts its
-        // pairs by proof -- one radix pass -- and needs 32 additions per scalar where the wide bucket tables need 24)
-        static const u32 full_max_k = [] {
-            const int v = ab_knob("MANTA_FULL_MAX_K", 1);
-            return (u32)(v >= 0 ? v : 1);
-        }();
-        const bool one = w->k <= full_max_k;
+        const bool one = w->k <= full_max_k();
         auto pick = [&](BaseSet *full, BaseSet *wd, BaseSet *narrow) { return one && full ? full : (wide && wd ? wd : narrow); };
         return MsmArgs{{w->z3 ? z3_bs_full_ : pick(a_bs_full_, a_bs_wide_, a_bs_), pick(b1_bs_full_, b1_bs_wide_, b1_bs_), pick(b2_bs_full_, b2_bs_wide_, b2_bs_),
                         pick(l_bs_full_, l_bs_wide_, l_bs_), pick(h_bs_full_, h_bs_wide_, h_bs_)},
@@ -272,14 +287,29 @@ class ProverSlots : public ProverAssembly {
     // does this slot launch MSM i (a, b_g1, b_g2, l, h)? -- not another rank's (task placement), not folded into the combined one
     bool runs(const ProveWs *w, int i) const { return does(i) && !(w->z3 && (i == 1 || i == 3)); }
     bool wants_z3(u32 k) const {
-        static const u32 full_max_k = [] {
-            const int v = ab_knob("MANTA_FULL_MAX_K", 1);
-            return (u32)(v >= 0 ? v : 1);
-        }();
         // (passes of one proof only: on full tables passes of 2-8 proofs are slower than on the narrow bucket tables)
-        return z3_bs_full_ && k == 1 && full_max_k >= 1 && peers_.empty() && !has_exchange_;
+        return z3_bs_full_ && k == 1 && full_max_k() >= 1 && peers_.empty() && !has_exchange_;
     }
     static hipStream_t msm_stream(const ProveWs *w, int i) { return w->mw[i]->run_on ? w->mw[i]->run_on : w->mw[i]->stream; }
+
+    // The stream on which MSM i's result is complete -- the one to wait on or to fold behind: its own, or, in a pass replayed as
+    // whole units, the launch stream of its unit (the G1 MSMs of a forked part A are joined inside that graph).
+    static hipStream_t done_stream(const ProveWs *w, int i) {
+        return w->replayed && w->unit_of[i] >= 0 ? w->unit[w->unit_of[i]].stream : msm_stream(w, i);
+    }
+    // waits for every stream a pass of this slot can have launched on; nothing of the pass is pending afterwards
+    static void drain(ProveWs *w) {
+        hipStreamSynchronize(w->stream);
+        for (int i = 0; i < 5; ++i) {
+            hipStreamSynchronize(msm_stream(w, i));
+            w->mw[i]->pending = 0;
+        }
+    }
+    // what follows on stream s waits for one of the slot's events (the main stream recorded it: nothing to wait for there)
+    static int gate(ProveWs *w, hipStream_t s, Gate g) {
+        if (g != GATE_NONE && s != w->stream) MG_HIP(hipStreamWaitEvent(s, g == GATE_Z_READY ? w->z_ready : (g == GATE_FORK ? w->fork : w->h_ready), 0));
+        return MG_OK;
+    }
 
     // The GPU side of a pass is two independent pieces that only share the uploaded assignment:
     //   part A, on w->stream: witness map, then the four G1 MSMs (a, b_g1, l from z; h from the witness map)
@@ -292,7 +322,7 @@ class ProverSlots : public ProverAssembly {
     int enqueue_msm(ProveWs *w, const MsmArgs &a, int i, bool use_graphs) {
         if (use_graphs) {
             hipStream_t ms = msm_stream(w, i);
-            MG_HIP(hipGraphLaunch(w->g_msm[i], ms));
+            MG_HIP(hipGraphLaunch(w->unit[w->unit_of[i]].exec, ms));
             MG_HIP(hipEventRecord(w->mw[i]->done, ms));
             w->mw[i]->pending = 1;
             return MG_OK;
@@ -303,18 +333,15 @@ class ProverSlots : public ProverAssembly {
         if (w->timed && !rc) MG_HIP(hipEventRecord(w->tev[4 + 2 * i], msm_stream(w, i)));
         return rc;
     }
-    int enqueue_part_a(ProveWs *w, bool use_graphs) {
+    int enqueue_part_a(ProveWs *w, const MsmArgs &a, bool use_graphs) {
         int rc;
-        const MsmArgs a = msm_args(w);
         MG_HIP(hipEventRecord(w->fork, w->stream)); // z is on the device (upload_z ran on this stream)
         if (w->timed) MG_HIP(hipEventRecord(w->tev[1], w->stream));
         if (does(4) && (rc = launch_witness_map(w, use_graphs))) return rc; // h is only needed by the h MSM
         if (w->timed) MG_HIP(hipEventRecord(w->tev[2], w->stream));
         for (int i = 0; i < 5; ++i) {
             if (!in_part_a(i) || !runs(w, i)) continue;
-            hipStream_t ms = msm_stream(w, i);
-            if (ms != w->stream) MG_HIP(hipStreamWaitEvent(ms, i == 4 ? w->h_ready : w->fork, 0));
-            if ((rc = enqueue_msm(w, a, i, use_graphs))) return rc;
+            if ((rc = gate(w, msm_stream(w, i), i == 4 ? GATE_H_READY : GATE_FORK)) || (rc = enqueue_msm(w, a, i, use_graphs))) return rc;
         }
         for (int i = 0; i < 5; ++i) { // join (after every launch, so that no MSM on the main stream queues behind a wait)
             hipStream_t ms = msm_stream(w, i);
@@ -323,53 +350,39 @@ class ProverSlots : public ProverAssembly {
         if (w->timed) MG_HIP(hipEventRecord(w->tev[13], w->stream));
         return MG_OK;
     }
-    int enqueue_part_b(ProveWs *w, bool use_graphs) { return does(2) ? enqueue_msm(w, msm_args(w), 2, use_graphs) : MG_OK; }
+    // the parts of one unit, enqueued: what its graph captures
+    int enqueue_unit(ProveWs *w, const PassUnit &u, const MsmArgs &a) {
+        if (!u.linear) return enqueue_part_a(w, a, false);
+        int rc = u.parts >> WM & 1u ? enqueue_witness_map_body(w) : MG_OK;
+        for (int i = 0; i < 5 && !rc; ++i)
+            if (u.parts >> i & 1u) rc = enqueue_msm(w, a, i, false);
+        return rc;
+    }
 
-    int enqueue_proof(ProveWs *w, const uint64_t *z_src, bool use_graphs) {
+    // One pass on a slot: the upload, then either the slot's units in their replay order, each behind its gate, or the fork / join
+    // of part A and part B behind it -- kernels (eager, and always when timed: events between the phases), or, with graphs whose
+    // units are its leaves, graph launches.
+    int enqueue_proof(ProveWs *w, const uint64_t *z_src) {
         if (w->timed) MG_HIP(hipEventRecord(w->tev[0], w->stream));
         int rc = upload_z(w, z_src);
         if (rc) return rc;
-        hipStream_t g2s = msm_stream(w, 2);
-        if (w->timed) { // eager launches with events between the phases
-            if ((rc = enqueue_part_a(w, false))) return rc;
-            if (g2s != w->stream) MG_HIP(hipStreamWaitEvent(g2s, w->z_ready, 0));
-            if ((rc = enqueue_part_b(w, false))) return rc;
-            MG_HIP(hipEventRecord(w->tev[14], g2s));
-            return MG_OK;
-        }
-        if (w->linear3 && w->g_all && w->g_g2 && w->g_msm[0]) { // three linear graphs, each behind the upload
-            hipStream_t z3s = msm_stream(w, 0);
-            // launch order (MANTA_Z3_ORDER, three letters of a = witness map + h, b = G2, z = combined): the chain that bounds the
-            // proof first -- each hipGraphLaunch is 10-20 us of host time, which the chains launched later start behind
-            static const char *order = [] {
-                const char *e = ab_knob_str("MANTA_Z3_ORDER", "abz");
-                return std::strlen(e) == 3 ? e : "abz";
-            }();
-            for (int t = 0; t < 3; ++t) {
-                if (order[t] == 'a') {
-                    MG_HIP(hipGraphLaunch(w->g_all, w->stream));
-                } else if (order[t] == 'b') {
-                    if (g2s != w->stream) MG_HIP(hipStreamWaitEvent(g2s, w->z_ready, 0));
-                    MG_HIP(hipGraphLaunch(w->g_g2, g2s));
-                } else {
-                    if (z3s != w->stream) MG_HIP(hipStreamWaitEvent(z3s, w->z_ready, 0));
-                    MG_HIP(hipGraphLaunch(w->g_msm[0], z3s));
-                }
+        const bool use_graphs = w->graphs_ready && !w->timed;
+        w->replayed = use_graphs && w->n_replay > 0;
+        if (w->replayed) {
+            for (int t = 0; t < w->n_replay; ++t) {
+                const PassUnit &u = w->unit[w->replay_order[t]];
+                if ((rc = gate(w, u.stream, u.gate))) return rc;
+                MG_HIP(hipGraphLaunch(u.exec, u.stream));
             }
             for (int i = 0; i < 5; ++i) w->mw[i]->pending = runs(w, i) ? 1 : 0;
             return MG_OK;
         }
-        if (w->g_all && w->g_g2) { // "single" mode replay
-            // the G2 graph goes first: it is the longest chain and its launch is the cheaper of the two
-            if (g2s != w->stream) MG_HIP(hipStreamWaitEvent(g2s, w->z_ready, 0));
-            MG_HIP(hipGraphLaunch(w->g_g2, g2s));
-            MG_HIP(hipGraphLaunch(w->g_all, w->stream));
-            for (int i = 0; i < 5; ++i) w->mw[i]->pending = runs(w, i) ? 1 : 0;
-            return MG_OK;
-        }
-        if ((rc = enqueue_part_a(w, use_graphs))) return rc;
-        if (g2s != w->stream) MG_HIP(hipStreamWaitEvent(g2s, w->z_ready, 0));
-        return enqueue_part_b(w, use_graphs);
+        const MsmArgs a = msm_args(w);
+        hipStream_t g2s = msm_stream(w, 2);
+        if ((rc = enqueue_part_a(w, a, use_graphs)) || (rc = gate(w, g2s, GATE_Z_READY))) return rc;
+        if (does(2) && (rc = enqueue_msm(w, a, 2, use_graphs))) return rc;
+        if (w->timed) MG_HIP(hipEventRecord(w->tev[14], g2s));
+        return MG_OK;
     }
 
     // capture one single-stream segment into an executable graph
@@ -431,72 +444,24 @@ class ProverSlots : public ProverAssembly {
         }
         return ok;
     }
+    // every unit of the slot's schedule, in order, each into its graph; stops at the first failure
     bool build_graphs_locked(ProveWs *w, bool &invalidated) {
-        if (w->linear3) {
-            const MsmArgs a = msm_args(w);
-            w->mw[4]->capturing = true; // linear captures: nothing inside them waits on a `done` event
-            bool ok = capture_segment(w->stream, &w->g_all, [&] {
-                const int rc = enqueue_witness_map_body(w);
-                return rc ? rc : enqueue_msm(w, a, 4, false);
-            });
-            w->mw[4]->capturing = false;
-            if (ok) {
-                w->mw[0]->capturing = true;
-                ok = capture_segment(msm_stream(w, 0), &w->g_msm[0], [&] { return enqueue_msm(w, a, 0, false); });
-                w->mw[0]->capturing = false;
-            }
-            if (ok) {
-                w->mw[2]->capturing = true;
-                ok = capture_segment(msm_stream(w, 2), &w->g_g2, [&] { return enqueue_part_b(w, false); });
-                w->mw[2]->capturing = false;
-            }
-            for (int i = 0; i < 5; ++i) w->mw[i]->pending = 0;
-            if (!ok) {
-                invalidated = capture_invalidated(); // (of the segment that failed: the chain stops at the first failure)
-                w->drop_graphs();
-                w->no_graph = true;
-            }
-            w->graphs_ready = ok;
-            return ok;
-        }
-        if (graph_mode_for(w->k) == GRAPH_SINGLE) {
-            // (the forked form; single proofs of z3 slots take the three linear graphs above since the memset-node defect was found:
-            // profiles/r05_linear_graph_defect.txt)
-            bool ok1 = capture_segment(w->stream, &w->g_all, [&] { return enqueue_part_a(w, false); });
-            if (ok1) {
-                w->mw[2]->capturing = true; // a linear capture: nothing waits on its `done` event
-                ok1 = capture_segment(msm_stream(w, 2), &w->g_g2, [&] { return enqueue_part_b(w, false); });
-                w->mw[2]->capturing = false;
-            }
-            for (int i = 0; i < 5; ++i) w->mw[i]->pending = 0;
-            if (!ok1) {
-                invalidated = capture_invalidated();
-                w->drop_graphs();
-                w->no_graph = true;
-            }
-            w->graphs_ready = ok1;
-            return ok1;
-        }
-        bool ok = capture_segment(w->stream, &w->g_wm, [&] { return enqueue_witness_map_body(w); });
         const MsmArgs a = msm_args(w);
-        for (int i = 0; ok && i < 5; ++i) {
-            if (!runs(w, i)) continue;
-            w->mw[i]->capturing = true; // no event records inside the capture: the replay path records `done`
-            ok = capture_segment(msm_stream(w, i), &w->g_msm[i], [&] {
-                return w->me[i]->msm_launch(a.bs[i], a.sc[i], a.cnt[i], i == 4 ? SCALARS_WORK : SCALARS_MONT, 0, w->mw[i], w->k, a.stride[i], i != 4);
-            });
-            w->mw[i]->capturing = false;
-            w->mw[i]->pending = 0;
+        bool ok = true;
+        for (int n = 0; ok && n < w->n_units; ++n) {
+            PassUnit &u = w->unit[n];
+            for (int i = 0; i < 5; ++i) w->mw[i]->capturing = u.linear && (u.parts >> i & 1u); // the one place that sets it
+            ok = capture_segment(u.stream, &u.exec, [&] { return enqueue_unit(w, u, a); });
         }
+        for (int i = 0; i < 5; ++i) w->mw[i]->capturing = false, w->mw[i]->pending = 0;
         if (!ok) {
-            invalidated = capture_invalidated();
+            invalidated = capture_invalidated(); // (of the unit that failed)
             w->drop_graphs();
             w->no_graph = true;
         }
         w->graphs_ready = ok;
         return ok;
     }
-
 };
 
 } // namespace

@@ -44,6 +44,40 @@ struct Rccl {
     }
 };
 
+// Where an MSM of a pass runs: the slot's main stream, one of its two side streams, or the MSM workspace's own stream. One row per
+// MANTA_PROVE_STREAMS value, and row 0 for a slot that replays three linear graphs (ProveWs::flavour != 0).
+// Three streams per proof, not six: the G2 MSM is the critical path (~3x a G1 MSM), so the three
+// z-MSMs over G1 run back to back beside it and the h MSM follows the witness map on the main stream.
+// Fewer streams = fewer hardware queues per proof in flight (the runtime multiplexes streams onto
+// GPU_MAX_HW_QUEUES queues; streams that share one serialise). MANTA_PROVE_STREAMS=6 restores one
+// stream per MSM. In every row the G2 MSM (the critical path) gets a high-priority stream of its own.
+enum Lane : unsigned char { LANE_MAIN, LANE_SIDE0, LANE_SIDE1, LANE_OWN };
+static constexpr Lane MSM_LANES[7][5] = {
+    // a, b_g1, b_g2, l, h
+    {LANE_SIDE1, LANE_OWN, LANE_SIDE0, LANE_OWN, LANE_MAIN},     // linear: the combined MSM on a stream of its own, h behind the witness map
+    {LANE_MAIN, LANE_MAIN, LANE_MAIN, LANE_MAIN, LANE_MAIN},     // 1: one chain (diagnosis builds only: ProverKey::prove_streams)
+    {LANE_OWN, LANE_OWN, LANE_SIDE0, LANE_OWN, LANE_OWN},        // (2: not a setting; as 6)
+    {LANE_SIDE1, LANE_SIDE1, LANE_SIDE0, LANE_SIDE1, LANE_MAIN}, // 3: (a, b_g1, l) back to back | witness map + h
+    {LANE_SIDE1, LANE_SIDE1, LANE_SIDE0, LANE_OWN, LANE_MAIN},   // 4: three branches beside the G2 chain: (a, b_g1) back to back | l | witness map + h
+    {LANE_SIDE1, LANE_OWN, LANE_SIDE0, LANE_SIDE1, LANE_MAIN},   // 5: (a, l) back to back | b_g1 | witness map + h
+    {LANE_OWN, LANE_OWN, LANE_SIDE0, LANE_OWN, LANE_OWN},        // 6: one stream per MSM
+};
+
+// One unit of a slot's schedule: what is captured into ONE graph and replayed by one hipGraphLaunch.
+enum Gate : unsigned char { GATE_NONE, GATE_Z_READY, GATE_FORK, GATE_H_READY }; // the slot event waited for on a stream other than the main one
+static constexpr int WM = 5;                                                    // the witness map body, numbered after the five MSMs
+struct PassUnit {
+    hipStream_t stream = nullptr; // launch (and capture) stream
+    Gate gate = GATE_NONE;        // before a replay launch
+    unsigned parts = 0;           // bit i: MSM i (a, b_g1, b_g2, l, h) runs inside this unit; bit WM: the witness map body, ahead of them
+    // a linear unit enqueues its parts one behind the other on its stream: nothing inside it waits on a `done` event and none is
+    // recorded, so its MSM workspaces are `capturing` (engine.h) for the length of its capture. The one unit that is not linear
+    // is the forked part A (enqueue_part_a): it forks and joins its MSMs with events inside the capture.
+    bool linear = true;
+    hipGraphExec_t exec = nullptr;
+};
+static constexpr int MAX_UNITS = 6; // "split": the witness map and the five MSMs
+
 // One in-flight proof (or batch of proofs): device scratch for the witness map, its five MSM workspaces (each
 // with its own stream), a pinned copy of z, and -- after two eager runs that size every buffer -- captured
 // hipGraphs of the GPU side (~90 launches: the prover is launch-bound at manta-pay circuit sizes, and
@@ -62,10 +96,14 @@ struct ProveWs {
     GroupEngine *me[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     void *h_z = nullptr; // pinned staging of the assignment
     size_t h_z_cap = 0;
-    hipGraphExec_t g_all = nullptr; // "single" mode: witness map + the four G1 MSMs, forked and joined on `stream`
-    hipGraphExec_t g_g2 = nullptr;  // "single" mode: the G2 MSM, alone on its own stream
-    hipGraphExec_t g_wm = nullptr;                                          // witness map body (main stream)
-    hipGraphExec_t g_msm[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // MSM i on its stream
+    // The slot's schedule, written once when the slot is created (ProverSlots::plan_schedule) together with mw[i]->run_on: the
+    // units a pass is captured as, in capture order, and replay_order, the order whole units are launched in on replay. n_replay
+    // == 0 ("split"): the units are the leaves of the eager fork / join instead. unit_of[i]: the unit part i is in, -1: none.
+    PassUnit unit[MAX_UNITS];
+    int n_units = 0, n_replay = 0;
+    int replay_order[3] = {0, 0, 0};
+    int unit_of[6] = {-1, -1, -1, -1, -1, -1};
+    bool replayed = false; // the pass in flight was launched as whole units (enqueue_proof): see ProverSlots::done_stream
     bool graphs_ready = false;
     u32 k = 1; // proofs per pass (the slot's buffers and its captured graph are sized for exactly this batch)
     // this slot runs the three G1 MSMs over the assignment (a, b_g1, l) as ONE pass of the MSM pipeline over the concatenated
@@ -77,9 +115,8 @@ struct ProveWs {
     // linear one. Round 4 built exactly this and withdrew it because C came out wrong next to other contexts: that was the memset
     // node of the witness map in a packet-captured linear graph (profiles/r05_linear_graph_defect.txt), gone now. MANTA_Z3_LINEAR=0:
     // the forked graph (A/B).
-    bool linear3 = false;
-    int flavour = 0; // lin_flavour(): 0 forked graph, 1 linear3 of a lone proof, 2 / 3 linear3 beside other passes (combined / G2 MSM on the normal-priority stream)
-    StreamSet sset; // linear3 slots: three streams on three different hardware queues (runtime.cpp); id < 0: plain pooled streams
+    int flavour = 0; // lin_flavour(): 0 forked graph, 1 three linear graphs of a lone proof, 2 / 3 the same beside other passes (combined / G2 MSM on the normal-priority stream)
+    StreamSet sset; // linear slots (flavour != 0): three streams on three different hardware queues (runtime.cpp); id < 0: plain pooled streams
     bool poisoned = false; // a stream capture of this slot failed: its streams are not trusted again (dropped, never pooled)
     std::vector<const uint64_t *> z_parts; // this pass's assignments as k separate host buffers (coalesced calls), else empty
     int device = 0;
@@ -92,14 +129,9 @@ struct ProveWs {
     hipEvent_t tev[15] = {};
     bool timed = false;
     void drop_graphs() {
-        if (g_all) hipGraphExecDestroy(g_all);
-        if (g_g2) hipGraphExecDestroy(g_g2);
-        g_all = g_g2 = nullptr;
-        if (g_wm) hipGraphExecDestroy(g_wm);
-        g_wm = nullptr;
-        for (int i = 0; i < 5; ++i) {
-            if (g_msm[i]) hipGraphExecDestroy(g_msm[i]);
-            g_msm[i] = nullptr;
+        for (PassUnit &u : unit) {
+            if (u.exec) hipGraphExecDestroy(u.exec);
+            u.exec = nullptr;
         }
         graphs_ready = false;
     }

@@ -14,7 +14,7 @@ namespace mg {
 // beside another thread's stream capture invalidates that capture), so a per-call allocation cannot exist without it. HeavyOp is
 // re-entrant per thread: callers that already hold one are unaffected. A thread that CAPTURES holds the lock exclusively
 // (prover_passes.h build_graphs) and must therefore never construct a block: taking the shared side would wait for itself. None
-// does -- what runs inside a capture is enqueue_witness_map_body / enqueue_part_a / enqueue_part_b / enqueue_msm, i.e. the Fr
+// does -- what runs inside a capture is enqueue_unit (enqueue_witness_map_body / enqueue_part_a / enqueue_msm), i.e. the Fr
 // engine's passes and msm_launch on the slot's pooled workspaces, while blocks are constructed only by the host-array entry
 // points of the C ABI (field, group, codec, Poseidon / Merkle and embedded-curve calls, mg_ntt), by verifying-key preparation and
 // by key generation, none of which a proof pass calls. The other way round is excluded too: those entry points never prove, so

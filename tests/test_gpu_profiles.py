@@ -242,7 +242,8 @@ def test_per_context_tuning_through_the_abi_leaves_results_unchanged(gpu):
     c, pk, rs, z2, two, _ = _tuning_truth()
     before = gpu.get_tuning().as_dict()
     cases = [dict(graph_mode=gpu.GRAPH_SPLIT), dict(graph_mode=gpu.GRAPH_OFF), dict(graph_mode_batch=gpu.GRAPH_OFF), dict(prove_streams=3),
-             dict(prove_streams=4, linear_chains=0), dict(linear_chains=1), dict(coalesce_inflight=0), dict(coalesce_inflight=4, coalesce_gather_us=0),
+             dict(prove_streams=4, linear_chains=0), dict(prove_streams=5, linear_chains=0), dict(prove_streams=3, graph_mode=gpu.GRAPH_SPLIT),
+             dict(linear_chains=1), dict(coalesce_inflight=0), dict(coalesce_inflight=4, coalesce_gather_us=0),
              dict(batch_inflight=1), dict(queue_aware=0), dict(window_bits_narrow=7), dict(window_bits_wide=9, window_bits_h=10, window_bits_g2=8),
              dict(full_table_bytes=500_000_000), dict(full_table_bytes=0)]
     assert set(k for cs in cases for k in cs) | {"msm_dedicated_queues"} == set(before), "a field of mg_tuning has no case here"
@@ -261,3 +262,28 @@ def test_per_context_tuning_through_the_abi_leaves_results_unchanged(gpu):
     assert gpu.get_tuning().as_dict() == before  # per-context tuning does not leak into the process
     with pytest.raises(gpu.MantaGpuError):
         gpu.ProvingContext(0, pk, tuning=gpu.get_tuning().replace(prove_streams=2))
+
+
+def test_timed_single_proofs_give_the_oracles_bytes_and_a_consistent_phase_split(gpu):
+    """Kernel timing (what bench.py's phase split uses): a timed pass is enqueued eagerly with events between its phases. Two timed
+    proofs on a fresh context give the oracle's bytes and ten finite, non-negative phases -- both whole-part entries (upload to part A
+    joined, upload to the end of the G2 chain) positive, no MSM longer than the longer of the two -- and with timing off again
+    the same slot goes on to capture and replay with the same bytes."""
+    c, pk, rs, z2, two, _ = _tuning_truth()
+    ctx = gpu.ProvingContext(0, pk)
+    ctx.set_r1cs(gpu.R1CS.from_circuit(c))
+    prove = lambda i: gpu.Groth16.prove_with_randomness(ctx, z2 if i & 1 else c.z, rs[2 * (i & 1)], rs[2 * (i & 1) + 1]).hex()
+    gpu.set_kernel_timing(True)
+    try:
+        for i in range(2):
+            assert prove(i) == two[i & 1], i
+            ph = list(gpu.last_prove_phases_ms().values())
+            print("phases", i, ph)
+            assert len(ph) == 10 and all(np.isfinite(v) and v >= 0 for v in ph), ph
+            assert ph[7] > 0 and ph[8] > 0, ph
+            assert max(ph[2:7]) <= max(ph[7], ph[8]), ph
+    finally:
+        gpu.set_kernel_timing(False)
+    for i in range(3):
+        assert prove(i) == two[i & 1], i
+    ctx.close()
