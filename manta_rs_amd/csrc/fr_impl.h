@@ -11,28 +11,15 @@
 #include "fp_dev.h"
 #include "tuning.h"
 #include "fpr_dev.h"
-#include "host_ec.h"
+#include "fr_host.h"
 #include "params_gen.h"
-#include "prover.h"
 #include <algorithm>
 #include <type_traits>
 #include <map>
+#include <memory>
 #include <mutex>
 
 namespace mg {
-
-// out[i] = base^i for i < n, given sq[k] = base^(2^k) (device array of `bits` elements)
-template <class FrC>
-__global__ __launch_bounds__(256) void powers_kernel(u32 *__restrict__ out, const u32 *__restrict__ sq, u32 n,
-                                                     int bits, const u32 *__restrict__ scale /* 8 words or null */) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    typedef Fp<FrC> F;
-    F acc = scale ? F::load(scale) : F::one();
-    for (int k = 0; k < bits; ++k)
-        if ((i >> k) & 1) acc = F::mul(acc, F::load(sq + 8 * k));
-    acc.store(out + (size_t)i * 8);
-}
 
 // ---------------------------------------------------------------------------------------------------
 // Reduced-radix scalar field (round 2). Inside the NTT / witness-map pipeline an Fr element is FpR<FrC>: 9 limbs of
@@ -444,16 +431,32 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MG_NTT_REG_
     ntt_tile_drain<FrC, DIF, true>(sm, TOTP, T, data, post, io, B);
 }
 
-// arkworks-format table (Montgomery, 8 words) -> canonical reduced-radix table with `stride` words per entry
-template <class FrC>
-__global__ __launch_bounds__(256) void std_to_rr_table_kernel(const u32 *__restrict__ in, u32 n, u32 *__restrict__ out, u32 stride) {
+// The one kernel that fills a domain's tables: out[i] = scale * base^e(i), i < n, with e(i) = i or (brev_lg > 0) the reversal of
+// the low brev_lg bits of i. The powers are products of the squarings sq[k] = base^(2^k), k < bits (arkworks format, computed on
+// the host, passed by value). RR = false: the 8 arkworks words of the element; RR = true: its canonical (< p) reduced-radix limbs,
+// `stride` words per entry, pad words zero.
+struct FrPowers {
+    u32 sq[32][8], scale[8];
+};
+template <class FrC, bool RR>
+__global__ __launch_bounds__(256) void domain_table_kernel(u32 *__restrict__ out, u32 stride, u32 n, int bits, unsigned brev_lg,
+                                                           const FrPowers pw) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    typedef Fp<FrC> F;
     typedef FpR<FrC> R;
-    const R r = R::from_std(Fp<FrC>::load(in + (size_t)i * 8)); // canonical (< p)
+    const u32 e = brev_lg ? __brev(i) >> (32 - brev_lg) : i;
+    F acc = F::load(pw.scale);
+    for (int k = 0; k < bits; ++k)
+        if ((e >> k) & 1) acc = F::mul(acc, F::load(pw.sq[k]));
+    if (RR) {
+        const R r = R::from_std(acc);
 #pragma unroll
-    for (int l = 0; l < R::K; ++l) out[(size_t)i * stride + l] = r.v[l];
-    for (u32 l = R::K; l < stride; ++l) out[(size_t)i * stride + l] = 0;
+        for (int l = 0; l < R::K; ++l) out[(size_t)i * stride + l] = r.v[l];
+        for (u32 l = R::K; l < stride; ++l) out[(size_t)i * stride + l] = 0;
+    } else {
+        acc.store(out + (size_t)i * 8);
+    }
 }
 // public-API entry: out_rr[i] = in_std[bitrev(i)] (x pre[bitrev(i)] for the forward coset transform), < 2p
 template <class FrC>
@@ -477,18 +480,6 @@ __global__ __launch_bounds__(256) void rr_to_std_kernel(const u32 *__restrict__ 
     R r = R::load(in_rr + i * R::K);
     if (scale_rr) r = R::mul(r, R::load(scale_rr));
     r.to_std().store(out_std + i * 8);
-}
-
-// out[p] = in[bitrev(p)]
-template <class FrC>
-__global__ __launch_bounds__(256) void permute_bitrev_kernel(u32 *__restrict__ out, const u32 *__restrict__ in, unsigned lg) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (1u << lg)) return;
-    const u32 j = lg ? (__brev(i) >> (32 - lg)) : 0;
-    const uint4 *p = reinterpret_cast<const uint4 *>(in + (size_t)j * 8);
-    uint4 *q = reinterpret_cast<uint4 *>(out + (size_t)i * 8);
-    q[0] = p[0];
-    q[1] = p[1];
 }
 
 // the same for three matrices at once (blockIdx.z): A z, B z, C z of the witness map. Outputs are written in the
@@ -548,40 +539,146 @@ __global__ __launch_bounds__(256) void qap_pointwise_kernel(u32 *__restrict__ a,
     R::mul(ab, R::load(zinv_rr)).store(a + o);
 }
 
-template <class FrC> class FrEngineT : public FrEngine {
+// ---------------------------------------------------------------------------------------------------
+// The passes of one transform, decided on the host before anything is launched (ntt_plan) and launched as decided (run_passes).
+// The tile limits every shape decision and every LDS maximum below derives from:
+constexpr unsigned NTT_PASS_STAGES = 10; // stages per pass at most
+constexpr unsigned NTT_TILE_LG = 11;     // a tile holds at most 2^11 elements = 72 KB of LDS (two workgroups per CU)
+constexpr unsigned NTT_CB_MAX = 3;       // adjacent columns per tile: 2^3 at most
+// the fused witness map (qap_quotient): domains 2^12 .. 2^18, whose high half is at most 2^9 elements for each of a, b, c
+constexpr unsigned NTT_FUSE_LG_MIN = 12, NTT_FUSE_LG_MAX = 18, NTT_FUSE_TILE_LG = NTT_FUSE_LG_MAX - NTT_FUSE_LG_MAX / 2;
+constexpr u32 ntt_padded(u32 tot) { return tot + (tot >> 5); } // the register kernel's tile: one pad word per 32 (ntt_lds_at)
+// a tile of `tot` elements of K words: LDS bytes, and threads -- a butterfly per thread and stage (a full tile: 1024 threads = 4
+// wavefronts per SIMD; a pass is a chain of dependent multiplications, more resident waves hide its latency), a wavefront at least
+template <int K> constexpr size_t ntt_tile_bytes(u32 tot) { return (size_t)(4 * K) * tot; }
+constexpr u32 ntt_tile_threads(u32 tot) { return tot / 2 > 64u ? tot / 2 : 64u; }
+
+// The A/B knobs of the passes (tuning.h ab_knob).
+struct NttKnobs {
+    // stages per LDS round trip. Measured (profiles/r04_ntt_register_stages.txt): the DIT passes gain from two stages per round
+    // trip (2^20 public transform 0.191 -> 0.17 ms; the 3-vector passes of a 32-proof witness map 268 + 428 -> 248 + 313 us), the
+    // DIF passes do not (318 + 415 -> 340 + 433 us: their product comes AFTER the subtraction, the extra live registers cost
+    // occupancy) and three stages per round trip lose everywhere (215-256 VGPRs). MANTA_NTT_R = 0 / 2 / 3 forces one; -1: by direction
+    int reg_bits = -1;
+    u32 threads = 0; // MANTA_NTT_THREADS: threads of an ntt_pass_rr workgroup; 0 = by tile
+    // a SINGLE proof's witness map is a latency chain of six passes over three 2^16-element vectors: with 2048-element tiles a
+    // pass is 32-96 workgroups on 256 CUs. Narrower column groups = more, smaller workgroups (the vectors live in L2: the
+    // coalescing the wide groups buy is worth nothing here). MANTA_NTT_MIN_WGS = workgroups a pass should have.
+    u32 min_wgs = 512;
+    // single-column tiles of a LATENCY-bound launch (one proof's witness map: <= 2 workgroups per CU): twiddles staged in LDS
+    // (E entries of 36 B more). A 2^20 transform is 1 024 workgroups per pass and throughput-bound: there the larger LDS
+    // footprint costs 8 % (0.154 -> 0.166 ms, tools/ntt_ab_r5.sh), so it keeps the per-stage gathers. MANTA_NTT_TWL = 0: never
+    bool twl = true;
+};
+struct NttPass {
+    unsigned s0, ns, cb; // global stages s0 .. s0 + ns - 1 on tiles of 2^ns elements x 2^cb columns
+    u32 blocks, threads;
+    size_t lds; // dynamic LDS bytes: the tile (padded for the register kernel) and, with `twl`, its twiddles behind it
+    int reg;    // 0: ntt_pass_rr; 2 / 3: ntt_pass_reg with that many stages per LDS round trip
+    bool twl;   // NttIo::packed bit 2
+    u32 pack;   // NttIo::packed bits 0 and 1: the public transform's passes hand the vector on in the packed form
+};
+struct NttPlan {
+    unsigned n = 0;
+    NttPass p[4]; // lg <= 32, ten stages per pass
+};
+// every stage of a 2^lg transform (lg >= 1) of `nvec` vectors x `batch` as LDS-fused passes, in launch order: DIT walks the stages
+// upwards, DIF downwards. pub: the public transform (arkworks format in and out, the work vector a scratch vector). K: words per element
+template <int K> inline NttPlan ntt_plan(unsigned lg, int nvec, u32 batch, bool dif, bool pub, const NttKnobs &kn) {
+    NttPlan plan;
+    const unsigned npass = (lg + NTT_PASS_STAGES - 1) / NTT_PASS_STAGES;
+    const int lr = kn.reg_bits >= 0 ? kn.reg_bits : (dif ? 0 : 2);
+    unsigned done = 0;
+    for (unsigned i = 0; i < npass; ++i) {
+        NttPass &p = plan.p[plan.n++];
+        p.ns = (lg - done + (npass - i) - 1) / (npass - i); // balanced split
+        p.s0 = dif ? (lg - done - p.ns + 1) : (done + 1);
+        const unsigned lo_bits = p.s0 - 1;
+        p.cb = std::min(std::min(NTT_TILE_LG - p.ns, lo_bits), NTT_CB_MAX);
+        while (p.cb > 0 && ((((size_t)1 << lg) >> (p.ns + p.cb)) * (size_t)nvec * batch) < kn.min_wgs && (1u << (p.ns + p.cb - 1)) >= 128u)
+            --p.cb;
+        p.blocks = (u32)(((size_t)1 << lg) >> (p.ns + p.cb));
+        const u32 tot = 1u << (p.ns + p.cb);
+        p.twl = kn.twl && p.cb == 0 && p.ns >= 2 && (size_t)p.blocks * nvec * batch <= 512;
+        const size_t twl_bytes = p.twl ? ntt_tile_bytes<K>(1u << p.ns) : 0;
+        p.pack = pub && npass > 1 && !dif ? (i > 0 ? 1u : 0u) | (i + 1 < npass ? 2u : 0u) : 0u;
+        // stages in registers (ntt_pass_reg) for every tile with a full wavefront of 2^lr-element lanes
+        p.reg = lr && tot >= (64u << lr) && p.ns >= (unsigned)lr ? lr : 0;
+        p.threads = p.reg ? std::min<u32>(512u, tot >> lr) : (kn.threads ? kn.threads : ntt_tile_threads(tot));
+        p.lds = ntt_tile_bytes<K>(p.reg ? ntt_padded(tot) : tot) + twl_bytes;
+        done += p.ns;
+    }
+    return plan;
+}
+
+// Domain: one per size, every table of the transforms of 2^log_n elements in ONE device allocation (the members point into it,
+// each on a 16-byte boundary), written once in its final form by domain_table_kernel and never changed. Saturated
+// (arkworks format, 8 words) are only the twiddles the group NTT reads through domain_twiddles; everything the Fr pipeline reads
+// is in its reduced-radix form, canonical values: twiddles 12 words per entry (ntt_load_tw: three 16-byte loads), the rest 9.
+// FrEngineT is the device half of the Fr engine, the domains and the launches; the host half is FrHostT (fr_host.h).
+template <class FrC> class FrEngineT : public FrHostT<FrC> {
   public:
-    typedef host::HFp<FrC> HF;
+    typedef typename FrHostT<FrC>::HF HF;
+    using FrHostT<FrC>::host_load;
+    using FrHostT<FrC>::hpow2k;
+    using FrHostT<FrC>::from_u64;
     struct Domain {
-        u32 *tw_fwd = nullptr, *tw_inv = nullptr; // omega^k, omega^-k, k < n/2
-        u32 *coset_fwd = nullptr;                 // g^i
-        u32 *coset_inv = nullptr;                 // n^-1 * g^-i
-        u32 *consts = nullptr;                    // [0] n^-1, [1] (g^n - 1)^-1
-        u32 *t1_br = nullptr;                     // n^-1 * g^bitrev(p)   (between ifft and coset fft)
-        u32 *t2_br = nullptr;                     // n^-1 * g^-bitrev(p)  (after the final coset ifft)
-        // the same tables in the NTT pipeline's reduced-radix form (canonical values): twiddles 12 words per entry
-        // (three 16-byte loads), everything else 9
-        u32 *tw_fwd_rr = nullptr, *tw_inv_rr = nullptr, *coset_fwd_rr = nullptr, *coset_inv_rr = nullptr, *consts_rr = nullptr,
-            *t1_br_rr = nullptr, *t2_br_rr = nullptr;
-        u32 *scratch_rr = nullptr; // one work vector for the public in-place transform (guarded by scratch_mu_)
+        u32 *tw_fwd = nullptr, *tw_inv = nullptr;             // omega^k, omega^-k, k < n/2, saturated (tw_fwd: the start of the block)
+        u32 *tw_fwd_rr = nullptr, *tw_inv_rr = nullptr;       // the same in the reduced-radix form, TW_WORDS per entry
+        u32 *coset_fwd_rr = nullptr, *coset_inv_rr = nullptr; // g^i; n^-1 g^-i
+        u32 *t1_br_rr = nullptr;                              // n^-1 g^bitrev(p)   (between ifft and coset fft)
+        u32 *t2_br_rr = nullptr;                              // n^-1 g^-bitrev(p)  (after the final coset ifft)
+        u32 *consts_rr = nullptr;                             // [0] n^-1, [1] (g^n - 1)^-1
+        u32 *scratch_rr = nullptr; // its own allocation, made on first use: the public transform's work vector (guarded by scratch_mu_)
     };
     static constexpr int RK = FpR<FrC>::K; // words per reduced-radix element
-    int two_adicity() const override { return FrC::TWO_ADICITY; }
+    static constexpr u32 TW_WORDS = 12;    // words per reduced-radix twiddle record
 
-    static HF host_load(const u32 *w) {
-        HF x;
-        x.load_words(w);
-        return x;
+    // builds the domain of 2^log_n elements: one allocation, its launches on the setup stream, one wait. The allocation belongs
+    // to `own` until the caller has stored the domain.
+    typedef std::unique_ptr<void, hipError_t (*)(void *)> DevOwner;
+    static int make_domain(unsigned log_n, Domain &d, DevOwner &own) {
+        const size_t n = (size_t)1 << log_n, half = n > 1 ? n / 2 : 1;
+        size_t words = 0;
+        auto take = [&](size_t cnt, size_t stride) { // word offset of a sub-array of cnt entries, 16-byte aligned
+            const size_t at = words;
+            words += (cnt * stride + 3) & ~(size_t)3;
+            return at;
+        };
+        const size_t o_tw_fwd = take(half, 8), o_tw_inv = take(half, 8), o_tw_fwd_rr = take(half, TW_WORDS), o_tw_inv_rr = take(half, TW_WORDS),
+                     o_coset_fwd = take(n, RK), o_coset_inv = take(n, RK), o_t1 = take(n, RK), o_t2 = take(n, RK), o_consts = take(2, RK);
+        void *p = nullptr;
+        MG_HIP(hipMalloc(&p, words * 4));
+        own.reset(p);
+        u32 *const blk = (u32 *)p;
+        d.tw_fwd = blk + o_tw_fwd, d.tw_inv = blk + o_tw_inv, d.tw_fwd_rr = blk + o_tw_fwd_rr, d.tw_inv_rr = blk + o_tw_inv_rr;
+        d.coset_fwd_rr = blk + o_coset_fwd, d.coset_inv_rr = blk + o_coset_inv, d.t1_br_rr = blk + o_t1, d.t2_br_rr = blk + o_t2;
+        d.consts_rr = blk + o_consts;
+        const HF root = hpow2k(host_load(FrC::ROOT), FrC::TWO_ADICITY - (int)log_n), gen = host_load(FrC::GEN);
+        const HF n_inv = HF::inv(from_u64((u64)n)), zinv = HF::inv(HF::sub(hpow2k(gen, (int)log_n), HF::one()));
+        // out = scale * base^e(i): squarings of the base on the host, powers on the device
+        auto fill = [&](u32 *out, bool rr, u32 stride, size_t cnt, HF base, const HF &scale, bool brev) {
+            FrPowers pw{};
+            for (unsigned k = 0; k < log_n; ++k) base.store_words(pw.sq[k]), base = HF::sqr(base);
+            scale.store_words(pw.scale);
+            const auto kern = rr ? &domain_table_kernel<FrC, true> : &domain_table_kernel<FrC, false>;
+            hipLaunchKernelGGL(kern, dim3((u32)((cnt + 255) / 256)), dim3(256), 0, setup_stream(), out, stride, (u32)cnt, (int)log_n,
+                               brev ? log_n : 0u, pw);
+        };
+        const HF one = HF::one(), root_inv = HF::inv(root), gen_inv = HF::inv(gen);
+        fill(d.tw_fwd, false, 8, half, root, one, false);
+        fill(d.tw_inv, false, 8, half, root_inv, one, false);
+        fill(d.tw_fwd_rr, true, TW_WORDS, half, root, one, false);
+        fill(d.tw_inv_rr, true, TW_WORDS, half, root_inv, one, false);
+        fill(d.coset_fwd_rr, true, RK, n, gen, one, false);
+        fill(d.coset_inv_rr, true, RK, n, gen_inv, n_inv, false);
+        fill(d.t1_br_rr, true, RK, n, gen, n_inv, true);
+        fill(d.t2_br_rr, true, RK, n, gen_inv, n_inv, true);
+        fill(d.consts_rr, true, RK, 1, one, n_inv, false);
+        fill(d.consts_rr + RK, true, RK, 1, one, zinv, false);
+        MG_HIP(setup_sync());
+        return MG_OK;
     }
-    static HF hpow2k(HF x, int k) {
-        for (int i = 0; i < k; ++i) x = HF::sqr(x);
-        return x;
-    }
-    static HF from_u64(u64 v) {
-        HF x = HF::zero();
-        x.v[0] = v;
-        return HF::to_mont(x);
-    }
-
     int get_domain(unsigned log_n, Domain **out) {
         std::lock_guard<std::mutex> g(mu_);
         auto it = domains_.find(log_n);
@@ -590,182 +687,61 @@ template <class FrC> class FrEngineT : public FrEngine {
             return MG_OK;
         }
         if ((int)log_n > FrC::TWO_ADICITY) return MG_ERR_DOMAIN;
-        const size_t n = (size_t)1 << log_n;
         Domain d;
-        HF root = hpow2k(host_load(FrC::ROOT), FrC::TWO_ADICITY - (int)log_n);
-        HF root_inv = HF::inv(root);
-        HF gen = host_load(FrC::GEN), gen_inv = HF::inv(gen);
-        HF n_inv = HF::inv(from_u64((u64)n));
-        HF zinv = HF::inv(HF::sub(hpow2k(gen, (int)log_n), HF::one()));
-        const size_t half = n > 1 ? n / 2 : 1;
-        MG_HIP(hipMalloc((void **)&d.tw_fwd, half * 32));
-        MG_HIP(hipMalloc((void **)&d.tw_inv, half * 32));
-        MG_HIP(hipMalloc((void **)&d.coset_fwd, n * 32));
-        MG_HIP(hipMalloc((void **)&d.coset_inv, n * 32));
-        MG_HIP(hipMalloc((void **)&d.consts, 64));
-        // squarings of the four bases on the host, powers on the device
-        u32 *d_sq = nullptr;
-        MG_HIP(hipMalloc((void **)&d_sq, 4 * 33 * 32 + 32));
-        std::vector<u32> hsq(4 * 33 * 8 + 8);
-        HF bases[4] = {root, root_inv, gen, gen_inv};
-        for (int b = 0; b < 4; ++b) {
-            HF x = bases[b];
-            for (int k = 0; k < 33; ++k) {
-                x.store_words(&hsq[((size_t)b * 33 + k) * 8]);
-                x = HF::sqr(x);
-            }
-        }
-        n_inv.store_words(&hsq[4 * 33 * 8]);
-        MG_HIP(memcpy_sync(d_sq, hsq.data(), hsq.size() * 4, hipMemcpyHostToDevice));
-        const int bits = (int)log_n;
-        const u32 gh = (u32)((half + 255) / 256), gn = (u32)((n + 255) / 256);
-        hipLaunchKernelGGL((powers_kernel<FrC>), dim3(gh), dim3(256), 0, setup_stream(), d.tw_fwd, d_sq, (u32)half, bits,
-                           (const u32 *)nullptr);
-        hipLaunchKernelGGL((powers_kernel<FrC>), dim3(gh), dim3(256), 0, setup_stream(), d.tw_inv, d_sq + 33 * 8, (u32)half, bits,
-                           (const u32 *)nullptr);
-        hipLaunchKernelGGL((powers_kernel<FrC>), dim3(gn), dim3(256), 0, setup_stream(), d.coset_fwd, d_sq + 2 * 33 * 8, (u32)n,
-                           bits + 1, (const u32 *)nullptr);
-        hipLaunchKernelGGL((powers_kernel<FrC>), dim3(gn), dim3(256), 0, setup_stream(), d.coset_inv, d_sq + 3 * 33 * 8, (u32)n,
-                           bits + 1, (const u32 *)(d_sq + 4 * 33 * 8));
-        u32 hc[16];
-        n_inv.store_words(hc);
-        zinv.store_words(hc + 8);
-        MG_HIP(memcpy_sync(d.consts, hc, 64, hipMemcpyHostToDevice));
-        // bit-reversed scale tables of the permutation-free witness-map pipeline
-        MG_HIP(hipMalloc((void **)&d.t1_br, n * 32));
-        MG_HIP(hipMalloc((void **)&d.t2_br, n * 32));
-        {
-            u32 *tmp = nullptr;
-            MG_HIP(hipMalloc((void **)&tmp, n * 32));
-            hipLaunchKernelGGL((powers_kernel<FrC>), dim3(gn), dim3(256), 0, setup_stream(), tmp, d_sq + 2 * 33 * 8, (u32)n, bits + 1,
-                               (const u32 *)(d_sq + 4 * 33 * 8)); // n^-1 * g^i
-            hipLaunchKernelGGL((permute_bitrev_kernel<FrC>), dim3(gn), dim3(256), 0, setup_stream(), d.t1_br, tmp, log_n);
-            hipLaunchKernelGGL((permute_bitrev_kernel<FrC>), dim3(gn), dim3(256), 0, setup_stream(), d.t2_br, d.coset_inv, log_n);
-            MG_HIP(setup_sync());
-            hipFree(tmp);
-        }
-        MG_HIP(setup_sync());
-        hipFree(d_sq);
-        { // reduced-radix copies
-            struct T {
-                u32 **dst;
-                const u32 *src;
-                size_t cnt;
-                u32 stride;
-            } tabs[] = {{&d.tw_fwd_rr, d.tw_fwd, half, 12},    {&d.tw_inv_rr, d.tw_inv, half, 12},
-                        {&d.coset_fwd_rr, d.coset_fwd, n, RK}, {&d.coset_inv_rr, d.coset_inv, n, RK},
-                        {&d.consts_rr, d.consts, 2, RK},       {&d.t1_br_rr, d.t1_br, n, RK},
-                        {&d.t2_br_rr, d.t2_br, n, RK}};
-            for (T &t : tabs) {
-                MG_HIP(hipMalloc((void **)t.dst, t.cnt * t.stride * 4));
-                hipLaunchKernelGGL((std_to_rr_table_kernel<FrC>), dim3((u32)((t.cnt + 255) / 256)), dim3(256), 0, setup_stream(), t.src, (u32)t.cnt,
-                                   *t.dst, t.stride);
-            }
-            MG_HIP(setup_sync());
-            // the saturated copies the pipeline no longer reads are released (the public NTT keeps none of them either)
-            // (tw_fwd / tw_inv stay: the group-domain NTT reads them)
-            hipFree(d.t1_br), hipFree(d.t2_br), hipFree(d.coset_fwd), hipFree(d.coset_inv);
-            d.t1_br = d.t2_br = d.coset_fwd = d.coset_inv = nullptr;
-        }
-        auto ins = domains_.emplace(log_n, d);
-        *out = &ins.first->second;
+        DevOwner own(nullptr, hipFree);
+        if (const int rc = make_domain(log_n, d, own)) return rc;
+        *out = &domains_.emplace(log_n, d).first->second;
+        own.release();
         return MG_OK;
     }
 
-    // stages per LDS round trip of the NTT passes. Measured (profiles/r04_ntt_register_stages.txt): the DIT passes gain from two
-    // stages per round trip (2^20 public transform 0.191 -> 0.17 ms; the 3-vector passes of a 32-proof witness map 268 + 428 ->
-    // 248 + 313 us), the DIF passes do not (318 + 415 -> 340 + 433 us: their product comes AFTER the subtraction, the extra live
-    // registers cost occupancy) and three stages per round trip lose everywhere (215-256 VGPRs). MANTA_NTT_R = 0 / 2 / 3 forces one.
-    static int ntt_reg_bits(bool dif) {
-        static const int v = [] {
-            const int x = ab_knob("MANTA_NTT_R", -1);
-            return x == 0 || x == 2 || x == 3 ? x : -1;
+    static const NttKnobs &ntt_knobs() {
+        static const NttKnobs k = [] { // read once per process
+            const int r = ab_knob("MANTA_NTT_R", -1), w = ab_knob("MANTA_NTT_MIN_WGS", 512);
+            return NttKnobs{r == 0 || r == 2 || r == 3 ? r : -1, (u32)ab_knob("MANTA_NTT_THREADS", 0), (u32)(w >= 1 ? w : 1),
+                            ab_knob("MANTA_NTT_TWL", 1) != 0};
         }();
-        return v >= 0 ? v : (dif ? 0 : 2);
+        return k;
     }
-    static u32 ntt_threads() {
-        static const u32 v = [] {
-            return (u32)ab_knob("MANTA_NTT_THREADS", 0);
-        }();
-        return v;
+    static void allow_lds(const void *kernel, size_t bytes) { // above the 64 KB default of dynamic LDS
+        hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    }
+    // one launch of a pass kernel as planned; first / last: the transform's I/O options and `post` apply at its ends only
+    template <bool DIF>
+    static void launch_pass(const NttPass &p, u32 *d0, u32 *d1, u32 *d2, int nvec, const u32 *tw_rr, unsigned lg, const u32 *post_rr,
+                            hipStream_t s, u32 batch, const NttIo &io, bool first, bool last) {
+        const NttIo pio{first ? io.in_std : nullptr, first ? io.pre_rr : nullptr, last ? io.out_std : nullptr, last ? io.scale_rr : nullptr,
+                        p.pack | (p.twl ? 4u : 0u)};
+        const auto kern = p.reg == 3 ? &ntt_pass_reg<FrC, DIF, 3> : p.reg == 2 ? &ntt_pass_reg<FrC, DIF, 2> : &ntt_pass_rr<FrC, DIF>;
+        hipLaunchKernelGGL(kern, dim3(p.blocks, nvec, batch), dim3(p.threads), p.lds, s, d0, d1, d2, tw_rr, lg, p.s0, p.ns, p.cb,
+                           last ? post_rr : (const u32 *)nullptr, pio);
     }
     // all stages of one transform over up to 3 reduced-radix vectors as LDS-fused passes of <= 10 stages
     template <bool DIF>
     static void run_passes(u32 *d0, u32 *d1, u32 *d2, int nvec, const u32 *tw_rr, unsigned lg, const u32 *post_rr, hipStream_t s,
                            u32 batch = 1, NttIo io = NttIo{}) {
         if (lg == 0) return;
-        static const bool attr_set = [] { // tiles of 2048 elements x 36 B = 72 KB: above the 64 KB default of dynamic LDS
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&ntt_pass_rr<FrC, DIF>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                36 * 2048);
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&ntt_pass_reg<FrC, DIF, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                36 * (2048 + 64));
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&ntt_pass_reg<FrC, DIF, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                36 * (2048 + 64));
+        static const bool attr_set = [] { // the largest tile, with its padding in the register kernel
+            allow_lds(reinterpret_cast<const void *>(&ntt_pass_rr<FrC, DIF>), ntt_tile_bytes<RK>(1u << NTT_TILE_LG));
+            allow_lds(reinterpret_cast<const void *>(&ntt_pass_reg<FrC, DIF, 3>), ntt_tile_bytes<RK>(ntt_padded(1u << NTT_TILE_LG)));
+            allow_lds(reinterpret_cast<const void *>(&ntt_pass_reg<FrC, DIF, 2>), ntt_tile_bytes<RK>(ntt_padded(1u << NTT_TILE_LG)));
             return true;
         }();
         (void)attr_set;
-        const unsigned npass = (lg + 9) / 10;
-        unsigned done = 0;
-        for (unsigned p = 0; p < npass; ++p) {
-            const unsigned ns = (lg - done + (npass - p) - 1) / (npass - p); // balanced split
-            // DIT walks the stages upwards, DIF downwards
-            const unsigned s0 = DIF ? (lg - done - ns + 1) : (done + 1);
-            const unsigned lo_bits = s0 - 1;
-            unsigned cb = ns >= 11 ? 0 : 11 - ns; // tile <= 2048 elements = 72 KB of LDS (two workgroups per CU)
-            if (cb > lo_bits) cb = lo_bits;
-            if (cb > 3) cb = 3;
-            // a SINGLE proof's witness map is a latency chain of six passes over three 2^16-element vectors: with 2048-element
-            // tiles a pass is 32-96 workgroups on 256 CUs. Narrower column groups = more, smaller workgroups (the vectors live in
-            // L2: the coalescing the wide groups buy is worth nothing here). MANTA_NTT_MIN_WGS = workgroups a pass should have.
-            static const u32 min_wgs = [] {
-                const int v = ab_knob("MANTA_NTT_MIN_WGS", 512);
-                return (u32)(v >= 1 ? v : 1);
-            }();
-            while (cb > 0 && ((((size_t)1 << lg) >> (ns + cb)) * (size_t)nvec * batch) < min_wgs && (1u << (ns + cb - 1)) >= 128u) --cb;
-            const u32 blocks = (u32)(((size_t)1 << lg) >> (ns + cb));
-            const size_t lds = ((size_t)(4 * RK) << (ns + cb));
-            const bool last = p + 1 == npass;
-            // one butterfly per thread and stage when the tile is full (2048 elements -> 1024 threads = 4 wavefronts
-            // per SIMD): a pass is a chain of dependent multiplications, more resident waves hide its latency
-            const u32 tot = 1u << (ns + cb);
-            const u32 threads = ntt_threads() ? ntt_threads() : (tot >= 2048 ? 1024u : tot >= 128 ? tot / 2 : 64u);
-            // public transform (arkworks format in and out, d0 = a scratch vector): the passes hand the vector on in the packed form
-            const bool pack = io.in_std && io.out_std && npass > 1 && !DIF;
-            static const bool twl_on = [] {
-                return ab_knob("MANTA_NTT_TWL", 1) != 0;
-            }();
-            // single-column tiles of a LATENCY-bound launch (one proof's witness map: <= 2 workgroups per CU): twiddles staged in LDS
-            // (E entries of 36 B more). A 2^20 transform is 1 024 workgroups per pass and throughput-bound: there the larger LDS
-            // footprint costs 8 % (0.154 -> 0.166 ms, tools/ntt_ab_r5.sh), so it keeps the per-stage gathers.
-            const bool twl = twl_on && cb == 0 && ns >= 2 && (size_t)blocks * nvec * batch <= 512;
-            const size_t twl_bytes = twl ? ((size_t)(4 * RK) << ns) : 0;
-            NttIo pio{p == 0 ? io.in_std : nullptr, p == 0 ? io.pre_rr : nullptr, last ? io.out_std : nullptr, last ? io.scale_rr : nullptr,
-                      (pack ? (p > 0 ? 1u : 0u) | (last ? 0u : 2u) : 0u) | (twl ? 4u : 0u)};
-            // round 4: three stages per LDS round trip in registers (ntt_pass_reg) for every tile with a full wavefront of
-            // 8-element lanes; MANTA_NTT_R = 0 restores the stage-per-round-trip kernel, 2 = four elements per lane
-            const int lr = ntt_reg_bits(DIF);
-            if (lr && tot >= (64u << lr) && ns >= (unsigned)lr) {
-                const size_t lds_p = (size_t)(4 * RK) * (tot + (tot >> 5)) + twl_bytes;
-                const u32 th = std::min<u32>(512u, tot >> lr);
-                const auto reg = lr == 3 ? &ntt_pass_reg<FrC, DIF, 3> : &ntt_pass_reg<FrC, DIF, 2>;
-                hipLaunchKernelGGL(reg, dim3(blocks, nvec, batch), dim3(th), lds_p, s, d0, d1, d2, tw_rr, lg, s0, ns, cb,
-                                   last ? post_rr : (const u32 *)nullptr, pio);
-            } else
-                hipLaunchKernelGGL((ntt_pass_rr<FrC, DIF>), dim3(blocks, nvec, batch), dim3(threads), lds + twl_bytes, s, d0, d1, d2, tw_rr,
-                                   lg, s0, ns, cb, last ? post_rr : (const u32 *)nullptr, pio);
-            done += ns;
-        }
+        const NttPlan plan = ntt_plan<RK>(lg, nvec, batch, DIF, io.in_std && io.out_std, ntt_knobs());
+        for (unsigned i = 0; i < plan.n; ++i)
+            launch_pass<DIF>(plan.p[i], d0, d1, d2, nvec, tw_rr, lg, post_rr, s, batch, io, i == 0, i + 1 == plan.n);
     }
 
     // single-column tiles of 2^ns elements (one proof's witness map): a butterfly per thread, 36 B of LDS per element
-    static u32 tile_threads(unsigned ns) { return std::max(64u, (1u << ns) / 2); }
-    static size_t tile_lds(unsigned ns) { return (size_t)(4 * RK) << ns; }
+    static u32 tile_threads(unsigned ns) { return ntt_tile_threads(1u << ns); }
+    static size_t tile_lds(unsigned ns) { return ntt_tile_bytes<RK>(1u << ns); }
     // one ntt_pass_rr pass over such tiles: stages s0 .. s0 + ns - 1 of the 2^lg transform of `nvec` vectors, plain work form in and out
     template <bool DIF>
     static void rr_pass(u32 *d0, u32 *d1, u32 *d2, int nvec, const u32 *tw_rr, unsigned lg, unsigned s0, unsigned ns, const u32 *post_rr,
                         hipStream_t s, u32 batch) {
-        hipLaunchKernelGGL((ntt_pass_rr<FrC, DIF>), dim3((1u << lg) >> ns, nvec, batch), dim3(tile_threads(ns)), tile_lds(ns), s, d0, d1, d2,
-                           tw_rr, lg, s0, ns, 0u, post_rr, NttIo{});
+        const NttPass p{s0, ns, 0u, (1u << lg) >> ns, tile_threads(ns), tile_lds(ns), 0, false, 0u};
+        launch_pass<DIF>(p, d0, d1, d2, nvec, tw_rr, lg, post_rr, s, batch, NttIo{}, true, true);
     }
 
     // Radix2EvaluationDomain::{fft, ifft, coset_fft, coset_ifft}_in_place on 2^log_n arkworks-format elements in HBM:
@@ -844,10 +820,9 @@ template <class FrC> class FrEngineT : public FrEngine {
             return ab_knob("MANTA_NTT_FUSE", 3) & 3;
         }();
         const unsigned L = lg / 2, H = lg - L; // low / high stages of every transform
-        if (fuse_on && lg >= 12 && lg <= 18 && (size_t)batch * 3 * ((size_t)n >> (H + 1)) < 512) {
-            static const bool attr_set = [] {
-                hipFuncSetAttribute(reinterpret_cast<const void *>(&ntt_fused_high_pw<FrC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    3 * 36 * 512);
+        if (fuse_on && lg >= NTT_FUSE_LG_MIN && lg <= NTT_FUSE_LG_MAX && (size_t)batch * 3 * ((size_t)n >> (H + 1)) < 512) {
+            static const bool attr_set = [] { // a | b | c tiles of the largest high half
+                allow_lds(reinterpret_cast<const void *>(&ntt_fused_high_pw<FrC>), 3 * tile_lds(NTT_FUSE_TILE_LG));
                 return true;
             }();
             (void)attr_set;
@@ -907,100 +882,6 @@ template <class FrC> class FrEngineT : public FrEngine {
         const HF ninv = HF::from_mont(HF::inv(from_u64((u64)1 << log_n)));
         std::memcpy(n_inv_canonical, ninv.v, 32);
         return MG_OK;
-    }
-    void fr_mul(const u64 a[4], const u64 b[4], u64 out[4]) const override {
-        HF x, y;
-        std::memcpy(x.v, a, 32);
-        std::memcpy(y.v, b, 32);
-        HF r = HF::mul(x, y);
-        std::memcpy(out, r.v, 32);
-    }
-    int setup_scalars(const mg_csr *A, const mg_csr *B, const mg_csr *Cm, u64 m, u64 V, u64 P, unsigned log_d,
-                      const u64 *toxic5, std::vector<u64> &s1, std::vector<u64> &s2) const override {
-        if ((int)log_d > FrC::TWO_ADICITY || V < 2 || P < 1 || P >= V) return MG_ERR_ARG;
-        const size_t D = (size_t)1 << log_d;
-        if (m + P > D) return MG_ERR_ARG;
-        auto ld = [](const u64 *p) {
-            HF x;
-            std::memcpy(x.v, p, 32);
-            return x;
-        };
-        const HF alpha = ld(toxic5), beta = ld(toxic5 + 4), gamma = ld(toxic5 + 8), delta = ld(toxic5 + 12),
-                 tau = ld(toxic5 + 16);
-        if (gamma.is_zero() || delta.is_zero()) return MG_ERR_ARG;
-        HF w; // primitive D-th root of unity
-        w.load_words(FrC::ROOT);
-        for (unsigned i = log_d; i < (unsigned)FrC::TWO_ADICITY; ++i) w = HF::sqr(w);
-        HF tD = tau;
-        for (unsigned i = 0; i < log_d; ++i) tD = HF::sqr(tD);
-        const HF Zt = HF::sub(tD, HF::one()); // Z(tau) = tau^D - 1
-        // L_i(tau) = Z(tau)/D * w^i / (tau - w^i); the D denominators are inverted together
-        std::vector<HF> pw(D), den(D), pref(D + 1);
-        pw[0] = HF::one();
-        for (size_t i = 1; i < D; ++i) pw[i] = HF::mul(pw[i - 1], w);
-        pref[0] = HF::one();
-        for (size_t i = 0; i < D; ++i) {
-            den[i] = HF::sub(tau, pw[i]);
-            if (den[i].is_zero()) return MG_ERR_ARG; // tau inside the domain
-            pref[i + 1] = HF::mul(pref[i], den[i]);
-        }
-        HF inv = HF::inv(pref[D]);
-        HF dD = HF::one();
-        for (unsigned i = 0; i < log_d; ++i) dD = HF::dbl(dD);
-        const HF zd = HF::mul(Zt, HF::inv(dD));
-        std::vector<HF> L(D);
-        for (size_t i = D; i-- > 0;) {
-            const HF di = HF::mul(inv, pref[i]);
-            inv = HF::mul(inv, den[i]);
-            L[i] = HF::mul(HF::mul(zd, pw[i]), di);
-        }
-        std::vector<HF> av(V, HF::zero()), bv(V, HF::zero()), cv(V, HF::zero());
-        const mg_csr *Ms[3] = {A, B, Cm};
-        std::vector<HF> *acc[3] = {&av, &bv, &cv};
-        for (int t = 0; t < 3; ++t) {
-            const mg_csr *M = Ms[t];
-            if (!M || !M->row_ptr || (M->nnz && (!M->col || !M->val)) || M->row_ptr[0] != 0 || M->row_ptr[m] != M->nnz)
-                return MG_ERR_ARG;
-            for (u64 i = 0; i < m; ++i) // the loop below walks row_ptr[i] .. row_ptr[i+1] on the host: monotone or rejected
-                if (M->row_ptr[i] > M->row_ptr[i + 1]) return MG_ERR_ARG;
-            for (u64 i = 0; i < m; ++i)
-                for (u64 k = M->row_ptr[i]; k < M->row_ptr[i + 1]; ++k) {
-                    if (M->col[k] >= V) return MG_ERR_ARG;
-                    HF &x = (*acc[t])[M->col[k]];
-                    x = HF::add(x, HF::mul(ld(M->val + 4 * k), L[i]));
-                }
-        }
-        for (u64 j = 0; j < P; ++j) av[j] = HF::add(av[j], L[m + j]); // input-consistency rows (mpc.rs:299-312)
-        const HF ginv = HF::inv(gamma), dinv = HF::inv(delta);
-        s1.assign((3 + P + 2 * V + (D - 1) + (V - P)) * 4, 0);
-        s2.assign((3 + V) * 4, 0);
-        auto put = [](std::vector<u64> &dst, size_t idx, const HF &x) {
-            const HF c = HF::from_mont(x);
-            std::memcpy(&dst[idx * 4], c.v, 32);
-        };
-        put(s1, 0, alpha), put(s1, 1, beta), put(s1, 2, delta);
-        put(s2, 0, beta), put(s2, 1, gamma), put(s2, 2, delta);
-        size_t o_abc = 3, o_a = o_abc + P, o_b = o_a + V, o_h = o_b + V, o_l = o_h + (D - 1);
-        for (u64 j = 0; j < V; ++j) {
-            const HF ext = HF::add(HF::add(HF::mul(beta, av[j]), HF::mul(alpha, bv[j])), cv[j]);
-            put(s1, o_a + j, av[j]);
-            put(s1, o_b + j, bv[j]);
-            put(s2, 3 + j, bv[j]);
-            if (j < P) put(s1, o_abc + j, HF::mul(ext, ginv));
-            else put(s1, o_l + (j - P), HF::mul(ext, dinv));
-        }
-        HF cur = HF::mul(Zt, dinv);
-        for (size_t i = 0; i + 1 < D; ++i) {
-            put(s1, o_h + i, cur);
-            cur = HF::mul(cur, tau);
-        }
-        return MG_OK;
-    }
-    void fr_to_canonical(const u64 a[4], u64 out[4]) const override {
-        HF x;
-        std::memcpy(x.v, a, 32);
-        HF r = HF::from_mont(x);
-        std::memcpy(out, r.v, 32);
     }
 
   private:

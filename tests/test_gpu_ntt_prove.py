@@ -10,7 +10,7 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("curve", [0, 1])
-@pytest.mark.parametrize("log_n", [0, 1, 2, 5, 10, 13])
+@pytest.mark.parametrize("log_n", [0, 1, 2, 3, 4, 5, 10, 11, 13])
 def test_ntt_matches_oracle(gpu, curve, log_n):
     n = 1 << log_n
     x = H.rand_fr_mont(curve, n, seed=log_n + 1)
@@ -778,6 +778,45 @@ def test_witness_map_matches_oracle_across_domain_sizes(gpu, curve):
         ctx.set_r1cs(gpu.R1CS.from_circuit(c))
         assert (ctx.witness_map(c.z) == O.witness_map(c)).all(), lg
         ctx.close()
+
+
+@pytest.mark.parametrize("curve", [0, 1])
+@pytest.mark.parametrize("lg", [6, 11])
+def test_every_consumer_of_one_domain_in_both_orders(gpu, curve, lg):
+    """A domain's tables are sub-arrays of one device block, and each consumer reads its own: the four public transforms the
+    reduced-radix twiddles, the coset tables and n^-1; the witness map the bit-reversed scale tables and (g^D - 1)^-1; the group
+    NTT (G1, 2^6) the saturated twiddles. All of them on ONE domain in one process, then again in reverse order, each result
+    equal to the oracle's: an offset that is wrong for one consumer, or two sub-arrays that overlap, cannot pass. The witness
+    map's circuit and key are built as in the sweep above."""
+    O.set_threads(O.usable_cpus())
+    n, P = 1 << lg, 5
+    x = H.rand_fr_mont(curve, n, seed=lg + 1)
+    dom = gpu.Radix2EvaluationDomain(curve, n)
+    c = synth.make_circuit(curve, n - P, max(n // 2, 40), P, seed=lg, profile="W")
+    assert c.D == n
+    g1, g2 = O.generator(curve, 1), O.generator(curve, 2)
+
+    class K:
+        pass
+    k = K()
+    k.V, k.P = c.V, c.P
+    for name, cnt, g in (("alpha_g1", 1, g1), ("beta_g1", 1, g1), ("delta_g1", 1, g1), ("beta_g2", 1, g2), ("delta_g2", 1, g2),
+                         ("a_query", c.V, g1), ("b_g1_query", c.V, g1), ("b_g2_query", c.V, g2), ("h_query", n - 1, g1),
+                         ("l_query", c.V - c.P, g1)):
+        setattr(k, name, np.tile(np.asarray(g, dtype=np.uint64).reshape(1, -1), (cnt, 1)))
+    ctx = gpu.ProvingContext(curve, k, full_table_bytes=0)
+    ctx.set_r1cs(gpu.R1CS.from_circuit(c))
+    calls = [(("ntt", inverse, coset), lambda inverse=inverse, coset=coset: dom._run(x, inverse, coset),
+              O.ntt(curve, x, inverse=inverse, coset=coset)) for inverse in (False, True) for coset in (False, True)]
+    calls.append((("witness_map",), lambda: ctx.witness_map(c.z), O.witness_map(c)))
+    if lg == 6:
+        pts = H.random_points(curve, 1, n, seed=40 + lg)
+        calls += [(("group_ntt", inverse), lambda inverse=inverse: gpu.group_ntt(curve, 1, pts, inverse=inverse),
+                   O.group_ntt(curve, 1, pts, inverse=inverse)) for inverse in (False, True)]
+    for order in (calls, calls[::-1]):
+        for what, run, want in order:
+            assert (run() == want).all(), (what, order is calls)
+    ctx.close()
 
 
 _NTT_SIZES = (9, 10, 11, 13, 14)
