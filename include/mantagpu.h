@@ -59,8 +59,12 @@ int mg_device_count(int *count);
 /* Raw HBM buffers, for hosts without a HIP binding (tests, bench). */
 int mg_malloc(void **dptr, size_t bytes);
 int mg_free(void *dptr);
+/* DEVICE INPUTS MUST BE COMPLETE BEFORE THE CALL. The two copies below, mg_ntt_device, mg_fixed_base_mul and mg_field_op run on a
+ * NON-blocking stream of the library's and wait for that stream alone: they do not order themselves against the host's default
+ * (NULL) stream or any other. A caller whose own kernels or copies produced a device input synchronises them first; the
+ * output is complete when the call returns. */
 int mg_memcpy_h2d(void *dptr, const void *hptr, size_t bytes);
-int mg_memcpy_d2h(void *hptr, const void *dptr, size_t bytes);
+int mg_memcpy_d2h(void *hptr, const void *dptr, size_t bytes); /* (dptr: complete before the call, see above) */
 int mg_device_synchronize(void);
 /* Page-locked host memory. An assignment (`z_mont`) that lives in a buffer from mg_host_alloc -- or in any
  * memory the caller registered with HIP -- is DMA'd to the GPU straight from where it is; any other buffer is
@@ -91,7 +95,7 @@ int mg_last_prove_phases_ms(float out10[10]);
  * last MSM result arrived } in ms. A pass whose first figure approaches its wall time is bound by launches, not by kernels. */
 int mg_last_pass_host_ms(float out3[3]);
 /* Introspection: the hardware queues the library found behind the current device's streams -- out2 = { normal priority, high
- * priority }, 0 / 0 before the first proving context exists or with MANTA_QUEUE_AWARE=0. The HIP runtime multiplexes streams onto a
+ * priority }, 0 / 0 before the first proving context with queue_aware = 1 exists. The HIP runtime multiplexes streams onto a
  * few hardware queues per priority level and kernels of streams that share one run one behind the other; the library measures the
  * sharing once per device (csrc/queues.hip) and gives every single-proof slot three streams on three different queues. */
 int mg_hw_queues(int out2[2]);
@@ -147,7 +151,8 @@ int mg_xyzz_sum(mg_curve_t curve, int group, const uint64_t *xyzz, size_t n, uin
 /* sum of the registered points themselves (multi-GPU partial-point reduction, tests) */
 int mg_points_sum(mg_curve_t curve, int group, const uint64_t *affine_mont, size_t n, uint64_t *out_affine_mont);
 /* [k_i] * base for n canonical scalars in HBM -> n affine points in HBM (fixed-base batch multiply:
- * synthetic base generation; key generation as in ark-groth16 generate_parameters) */
+ * synthetic base generation; key generation as in ark-groth16 generate_parameters). d_scalars: complete before the call
+ * (see mg_memcpy_h2d). */
 int mg_fixed_base_mul(mg_curve_t curve, int group, const uint64_t *base_affine_mont, const uint64_t *d_scalars,
                       size_t n, uint64_t *d_out_affine_mont);
 /* Element-wise group operations on host arrays of n affine points, computed on the GPU with the MSM kernels' own
@@ -188,6 +193,7 @@ int mg_ec_elementwise(mg_curve_t curve, int group, int op, const uint64_t *a_aff
 #define MG_FIELD_FROM_CANONICAL 5
 #define MG_FIELD_TO_CANONICAL 6
 #define MG_FIELD_INV 7
+/* a, b, out: device memory; a and b complete before the call (see mg_memcpy_h2d) */
 int mg_field_op(int field, int op, int repr, int lazy_a, int lazy_b, const uint64_t *a, const uint64_t *b, size_t n,
                 uint64_t *out);
 /* The reduced-radix routines of the MSM kernels on RAW limb vectors: a, b, c, d and out are [n][K] uint32 limbs of LB bits
@@ -250,6 +256,7 @@ int mg_point_serialize(mg_curve_t curve, int group, const uint64_t *affine_mont,
  *      coset_ifft}_in_place (ark-poly 0.3.0; used 7x per proof by R1CStoQAP::witness_map) ------------ */
 /* data: 2^log_n Montgomery Fr elements, natural order in and out, transformed in place. */
 int mg_ntt(mg_curve_t curve, uint64_t *data_mont, unsigned log_n, int inverse, int coset);
+/* the same on data resident in HBM, which must be complete before the call (see mg_memcpy_h2d) */
 int mg_ntt_device(mg_curve_t curve, uint64_t *d_data_mont, unsigned log_n, int inverse, int coset);
 
 /* ---- Groth16 proving context: replaces ProvingContext<E>{proving_key} (groth16.rs:216-245) +
@@ -368,6 +375,9 @@ int mg_ctx_create(mg_curve_t curve, const mg_pk_view *pk, mg_ctx **out);
  *      MANTA_GRAPH_BATCH, MANTA_PROVE_STREAMS, MANTA_Z3_LINEAR, MANTA_COALESCE, MANTA_COALESCE_GATHER_US, MANTA_BATCH_INFLIGHT,
  *      MANTA_QUEUE_AWARE, MANTA_MSM_DEDICATED_QUEUES, MANTA_PROVE_C / _CW / _CH / _CG2, MANTA_FULL_TABLE_GB. Every other knob of
  *      the measurement campaigns is compiled in at its measured optimum (a unit rebuilt with -DMG_DIAG reads it again).
+ *      A variable applies only if its WHOLE string parses as the field's kind (a decimal integer that fits 32 bits; off | single |
+ *      split | 0 | 1 | 2 for a graph mode; a finite number of GB whose byte count fits 64 bits, negative = -1) and the field's
+ *      range accepts the value; anything else is ignored and the default stays.
  *   struct_size           sizeof(mg_tuning), written by mg_tuning_init / mg_get_tuning
  *   graph_mode            replay of a pass's GPU side as hipGraphs: 1 = two graphs per pass (default), 2 = six single-stream graphs,
  *                         0 = eager launches
@@ -378,13 +388,15 @@ int mg_ctx_create(mg_curve_t curve, const mg_pk_view *pk, mg_ctx **out);
  *   coalesce_inflight     passes of coalesced concurrent mg_groth16_prove calls on the GPU: 0 = no coalescing, default 2, <= 4
  *   coalesce_gather_us    how long the leader of such a pass waits for the callers of the pass that has just ended (default 100)
  *   batch_inflight        passes of one mg_groth16_prove_batch call in flight (default 3)
- *   queue_aware           1 (default): single-proof slots get streams on measured hardware queues; 0: plain pooled streams
+ *   queue_aware           1 (default): single-proof slots get streams on measured hardware queues; 0: plain pooled streams.
+ *                         Per context: a context follows its own value, whatever the process-wide one is
  *   msm_dedicated_queues  a stand-alone MSM (mg_msm_launch) on a stream with a hardware queue of its own: its pipelined rate then no
  *                         longer depends on the streams the rest of the process created (390-398 Mscalar/s at 2^20 for every
  *                         creation order against 317-394). 1 (default) = only while NO proving / verifying context is alive in
  *                         the process (beside proof passes the dedicated queues cost far more than they give), 2 = always,
  *                         0 = never. Such streams are BLOCKING streams: they order themselves against the host's NULL-stream work
- *                         (the library itself puts nothing on the NULL stream)
+ *                         (the library itself puts nothing on the NULL stream). Process-wide by nature: a stand-alone MSM has
+ *                         no context, so the value in mg_ctx_opts.tuning is not consulted
  *   window_bits_*         window widths of a context's key tables, 0 = the library's choice: narrow = the latency tables of
  *                         a / b_g1 / l (setting it forces ONE width for every bucket table and leaves the full and wide tables
  *                         out), wide = the batched-pass tables, h = the h query, g2 = b_g2

@@ -104,8 +104,8 @@ MG_API int mg_set_kernel_timing(int on) {
     set_kernel_timing(on != 0);
     return MG_SUCCESS;
 }
-MG_API float mg_last_accumulate_ms(void) { return last_accumulate_ms(); }
-MG_API float mg_last_accumulate_mhz(void) { return last_accumulate_mhz(); }
+MG_API float mg_last_accumulate_ms(void) { return last_times().accumulate_ms; }
+MG_API float mg_last_accumulate_mhz(void) { return last_times().accumulate_mhz; }
 namespace mg {
 int clock_probe(u32 iters, double *memtime_mhz, double *mad_issue_per_us_per_simd, double *ms);
 }
@@ -117,7 +117,7 @@ MG_API int mg_clock_probe(unsigned iters, double *memtime_mhz, double *mad_issue
 }
 MG_API int mg_last_ntt_ms(float out4[4]) {
     if (!out4) return MG_ERROR_INVALID_ARGUMENT;
-    get_last_ntt_ms(out4);
+    std::memcpy(out4, last_times().ntt_ms, sizeof(float[4]));
     return MG_SUCCESS;
 }
 MG_API int mg_hw_queues(int out2[2]) {
@@ -128,12 +128,12 @@ MG_API int mg_hw_queues(int out2[2]) {
 }
 MG_API int mg_last_pass_host_ms(float out3[3]) {
     if (!out3) return MG_ERROR_INVALID_ARGUMENT;
-    get_last_pass_host_ms(out3);
+    std::memcpy(out3, last_times().pass_host_ms, sizeof(float[3]));
     return MG_SUCCESS;
 }
 MG_API int mg_last_prove_phases_ms(float out10[10]) {
     if (!out10) return MG_ERROR_INVALID_ARGUMENT;
-    get_last_prove_ms(out10);
+    std::memcpy(out10, last_times().prove_ms, sizeof(float[10]));
     return MG_SUCCESS;
 }
 

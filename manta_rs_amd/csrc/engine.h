@@ -3,6 +3,7 @@
 // C ABI (include/mantagpu.h) can dispatch on (curve, group) at run time.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "status.h"
 #include <shared_mutex>
 #include <atomic>
 #include <cstddef>
@@ -30,8 +31,6 @@ typedef uint64_t u64;
 #endif
 #define MG_PRIO_FOR(F) MG_PRIO_HIGH()
 
-enum { MG_OK = 0, MG_ERR_ARG = 1, MG_ERR_HIP = 2, MG_ERR_OOM = 3, MG_ERR_DOMAIN = 4, MG_ERR_STATE = 5 };
-
 void set_last_hip_error(hipError_t e, const char *expr, const char *file, int line);
 // a failed HIP call -> the library's status; `what` and the caller's position are kept for mg_last_error()
 inline int hip_status(hipError_t e, const char *what, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
@@ -48,21 +47,19 @@ void set_last_error_text(const char *text); // detail for mg_last_error() of a f
 // roofline leg); off by default.
 void set_kernel_timing(bool on);
 bool kernel_timing();
-void set_last_accumulate_ms(float ms);
-float last_accumulate_ms();
-void set_last_accumulate_mhz(float mhz); // shader clock of the same launch: s_memtime ticks of its first wavefront per wall-clock second
-float last_accumulate_mhz();
-// with kernel timing on: the last mg_ntt / mg_ntt_device of this thread -- [0] whole call on the device, [1] conversion in,
-// [2] butterfly passes, [3] conversion out (ms); and the last single proof of this thread, run with eager launches --
-// [0] upload of z, [1] witness map, [2..6] MSM a, b_g1, b_g2, l, h (each on its own stream), [7] part A (everything but
-// the G2 MSM) from upload to join, [8] G2 MSM from upload to its end, [9] host assembly after the GPU (ms)
-void set_last_ntt_ms(const float v[4]);
-void get_last_ntt_ms(float v[4]);
-void set_last_pass_host_ms(const float v[3]); // host side of the calling thread's last pass: enqueue, wait for the GPU, assembly
-void get_last_pass_host_ms(float v[3]);
-void set_last_prove_ms(const float v[10]);
-void get_last_prove_ms(float v[10]);
-// process-lifetime pool of non-blocking streams for proof slots (returned, never destroyed -- runtime.cpp)
+// What the calling thread measured last (the mg_last_* hooks of the C ABI), with kernel timing on except pass_host_ms.
+struct LastTimes {
+    float accumulate_ms = 0.f;  // the accumulate kernel of the last MSM
+    float accumulate_mhz = 0.f; // shader clock of the same launch: s_memtime ticks of its first wavefront per wall-clock second
+    // the last mg_ntt / mg_ntt_device: [0] whole call on the device, [1] conversion in, [2] butterfly passes, [3] conversion out (ms)
+    float ntt_ms[4] = {};
+    float pass_host_ms[3] = {}; // host side of the last pass: enqueue, wait for the GPU, assembly
+    // the last single proof, run with eager launches: [0] upload of z, [1] witness map, [2..6] MSM a, b_g1, b_g2, l, h (each on
+    // its own stream), [7] part A (everything but the G2 MSM) from upload to join, [8] G2 MSM from upload to its end, [9] host
+    // assembly after the GPU (ms)
+    float prove_ms[10] = {};
+};
+LastTimes &last_times();
 constexpr int MAX_DEVICES = 16;
 int current_device(); // hipGetDevice, clamped to the engine tables
 // Stream capture against the rest of the process (round 5, found by tools/soak.py): while ANY thread captures a proof slot's graphs,
@@ -102,9 +99,10 @@ inline int sync_status(hipStream_t s, hipError_t e, const char *what, const char
     if (e == hipSuccess) e = e2;
     return e == hipSuccess ? MG_OK : hip_status(e, what, file, line);
 }
-hipStream_t stream_pool_get();
+// process-lifetime pools of non-blocking streams (streams.cpp): returned, NEVER destroyed; put() of a stream no pool created drops it
+hipStream_t stream_pool_get(); // high priority: the streams of proof slots
 void stream_pool_put(hipStream_t s);
-hipStream_t stream_pool_get_normal(); // normal-priority streams: pooled and never destroyed either (runtime.cpp)
+hipStream_t stream_pool_get_normal(); // normal priority: MSM workspaces, setup streams and every other short-lived stream
 void stream_pool_put_normal(hipStream_t s);
 // Proving / verifying contexts alive in this process. A stand-alone MSM takes its dedicated-queue stream only while there is NONE
 // (tuning msm_dedicated_queues = 1, the default; 2 = always, 0 = never): beside proof passes the dedicated queues cost far more than
@@ -121,7 +119,7 @@ struct GraphClient { // a member of every proving / verifying context
 int graph_clients_alive();
 hipStream_t stream_pool_get_dedicated(); // a stream on a hardware queue of its own (MsmWorkspace::solo); nullptr: off / refused
 void stream_pool_put_dedicated(hipStream_t s);
-// Queue-aware streams of a single-proof slot (queues.hip, runtime.cpp): three streams on three DIFFERENT hardware queues, chosen so
+// Queue-aware streams of a single-proof slot (queues.hip, streams.cpp): three streams on three DIFFERENT hardware queues, chosen so
 // that slots with neighbouring ids share as few queues as the hardware has (set i: high-priority classes 2i and 2i+1 for the
 // witness map + h chain and the G2 chain, normal-priority class i -- or high-priority class 2i+2 -- for the combined MSM).
 struct StreamSet {
@@ -129,7 +127,8 @@ struct StreamSet {
     int id = -1, dev = 0;
     bool z3_high = false;
 };
-bool stream_sets_ready();                            // probes the current device's queues on first use; false: disabled / failed
+// (whether a context uses them at all is its own Tuning::queue_aware: the prover asks before it calls either function)
+bool stream_sets_ready();                            // probes the current device's queues on first use; false: the probe failed
 int stream_queue_counts(int *normal, int *high);     // hardware queues found per priority level (0: not probed)
 bool stream_set_acquire(StreamSet &s, bool z3_high); // false: queues unknown -- use the plain pools
 void stream_set_release(StreamSet &s);

@@ -791,7 +791,7 @@ template <class FrC> class FrEngineT : public FrHostT<FrC> {
                 hipEventElapsedTime(&v[2], ev[1], ev[2]);
                 hipEventElapsedTime(&v[3], ev[2], ev[3]);
             }
-            set_last_ntt_ms(v);
+            std::memcpy(last_times().ntt_ms, v, sizeof(v));
             for (auto &x : ev) hipEventDestroy(x);
         }
         if (e != hipSuccess) {

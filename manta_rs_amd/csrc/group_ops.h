@@ -297,7 +297,7 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupOpsT : public GroupEn
         const size_t ab = n * AW_IO * 4, bb = op == EC_MUL ? n * 32 : (op == EC_MUL_FIXED ? 32 : ab);
         // a stream of its own (not stream 0: a synchronous copy anywhere else in the process -- another thread creating a base
         // set, say -- would wait for this kernel, a millisecond of one-lane latency for 128-bit multipliers)
-        hipStream_t st = stream_pool_get_normal(); // (pooled: the library destroys no stream, runtime.cpp)
+        hipStream_t st = stream_pool_get_normal(); // (pooled: the library destroys no stream, streams.cpp)
         if (!st) return hip_status(hipErrorOutOfMemory, "ec_elementwise");
         DevBlock m; // a | b | XYZZ results | affine results
         int rc = m.alloc({ab, bb, n * XW_IO * 4, ab}, "ec_elementwise");

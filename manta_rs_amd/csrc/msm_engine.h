@@ -442,12 +442,12 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         ws->pending = 0;
         if (ws->timed && !already_synced) {
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, ws->t0, ws->t1) == hipSuccess) set_last_accumulate_ms(ms);
+            if (hipEventElapsedTime(&ms, ws->t0, ws->t1) == hipSuccess) last_times().accumulate_ms = ms;
             const unsigned long long ck[2] = {((volatile unsigned long long *)ws->h_clk)[0], ((volatile unsigned long long *)ws->h_clk)[1]};
             int khz = 0, dev = 0;
             if (ck[1] && hipGetDevice(&dev) == hipSuccess &&
                 hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess)
-                set_last_accumulate_mhz((float)((double)ck[0] / (double)ck[1] * (double)khz / 1e3));
+                last_times().accumulate_mhz = (float)((double)ck[0] / (double)ck[1] * (double)khz / 1e3);
         }
         const MsmPlan &pl = ws->plan;
         const MsmTail &t = ws->tail;

@@ -867,13 +867,12 @@ class ProverImpl : public ProverSlots {
             }
         if (rc) return rc;
         if (!g2_early) assemble_g2(k, res.data(), bl.data(), p.out);
-        {
-            const float hv[3] = {p.enqueue_ms, wait_ms, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host).count()};
-            set_last_pass_host_ms(hv);
-        }
+        LastTimes &lt = last_times();
+        lt.pass_host_ms[0] = p.enqueue_ms, lt.pass_host_ms[1] = wait_ms;
+        lt.pass_host_ms[2] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host).count();
         if (timed) {
             phases[9] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host).count();
-            set_last_prove_ms(phases);
+            std::memcpy(lt.prove_ms, phases, sizeof(lt.prove_ms));
         }
         return MG_OK;
     }

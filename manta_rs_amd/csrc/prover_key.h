@@ -44,7 +44,7 @@ class ProverKey : public Prover {
     u64 V_ = 0, P_ = 0, h_len_ = 0, m_ = 0;
     unsigned log_d_ = 0;
     bool have_r1cs_ = false;
-    bool sets_ok_ = false; // queue-aware stream sets available on this device (runtime.cpp)
+    bool sets_ok_ = false; // this context wants queue-aware stream sets (tn_.queue_aware) and the device has them (streams.cpp)
     BaseSet *a_bs_ = nullptr, *b1_bs_ = nullptr, *b2_bs_ = nullptr, *h_bs_ = nullptr, *l_bs_ = nullptr;
     BaseSet *h_bs_wide_ = nullptr; // the h query again with wider windows, for batched passes (nullptr: same as h_bs_)
     // the z queries again with 10-bit windows for batched passes (fewer mixed additions; single proofs want the
@@ -231,7 +231,7 @@ class ProverKey : public Prover {
         g1_ = get_engine(curve, 1);
         g2_ = get_engine(curve, 2);
         if (!fr_ || !g1_ || !g2_) return MG_ERR_ARG;
-        sets_ok_ = stream_sets_ready(); // (the caller holds HeavyOp; the first context of a device probes its hardware queues)
+        sets_ok_ = tn_.queue_aware && stream_sets_ready(); // (the caller holds HeavyOp; the first context of a device probes its hardware queues)
         V_ = pk->n_vars;
         P_ = pk->n_inputs;
         h_len_ = pk->h_len;

@@ -12,7 +12,7 @@ class ProverSlots : public ProverAssembly {
     // | G2 -- on three high-priority streams: the shortest chain for a LONE proof (company 0: no other pass of this context in
     // flight). 2 / 3: the same beside other passes, with ONE chain on a normal-priority stream -- the combined MSM beside a batched
     // pass (company 2), the G2 MSM beside single proofs only (company 1: two host threads). The streams come from
-    // stream_set_acquire (runtime.cpp): three DIFFERENT hardware queues per slot, and the two slots that two host threads keep in
+    // stream_set_acquire (streams.cpp): three DIFFERENT hardware queues per slot, and the two slots that two host threads keep in
     // flight share none -- before, which chains of the two proofs met on one queue was decided by the order in which the process
     // had created its streams (profiles/r05_hw_queues.txt). A normal-priority chain costs a lone proof 18 %: flavour 1 keeps all
     // three high; which chain yields beside others was measured per company (same file, item 7).
@@ -51,7 +51,7 @@ class ProverSlots : public ProverAssembly {
         }
         static const int z3_high = ab_knob("MANTA_Z3_HIGH", -1); // A/B: the combined MSM's stream of every linear slot normal (0) / high (1) priority
         w->flavour = lin_flavour(k, z3, company);
-        if (w->flavour && stream_set_acquire(w->sset, z3_high >= 0 ? z3_high != 0 : w->flavour == 1))
+        if (w->flavour && tn_.queue_aware && stream_set_acquire(w->sset, z3_high >= 0 ? z3_high != 0 : w->flavour == 1))
             w->stream = w->sset.main, w->side[0] = w->sset.g2, w->side[1] = w->sset.z3;
         if (w->sset.id >= 0 && w->flavour == 3 && !w->sset.z3_high) std::swap(w->side[0], w->side[1]); // the G2 chain takes the normal-priority stream
         if ((w->sset.id < 0 && (!(w->stream = stream_pool_get()) || !(w->side[0] = stream_pool_get()) ||

@@ -116,7 +116,7 @@ struct ProveWs {
     // node of the witness map in a packet-captured linear graph (profiles/r05_linear_graph_defect.txt), gone now. MANTA_Z3_LINEAR=0:
     // the forked graph (A/B).
     int flavour = 0; // lin_flavour(): 0 forked graph, 1 three linear graphs of a lone proof, 2 / 3 the same beside other passes (combined / G2 MSM on the normal-priority stream)
-    StreamSet sset; // linear slots (flavour != 0): three streams on three different hardware queues (runtime.cpp); id < 0: plain pooled streams
+    StreamSet sset; // linear slots (flavour != 0): three streams on three different hardware queues (streams.cpp); id < 0: plain pooled streams
     bool poisoned = false; // a stream capture of this slot failed: its streams are not trusted again (dropped, never pooled)
     std::vector<const uint64_t *> z_parts; // this pass's assignments as k separate host buffers (coalesced calls), else empty
     int device = 0;

@@ -264,6 +264,57 @@ def test_per_context_tuning_through_the_abi_leaves_results_unchanged(gpu):
         gpu.ProvingContext(0, pk, tuning=gpu.get_tuning().replace(prove_streams=2))
 
 
+_QUEUE_AWARE_SCRIPT = '''
+import os, sys
+sys.path.insert(0, r"{root}"); sys.path.insert(0, os.path.join(r"{root}", "tests"))
+import numpy as np
+import helpers as H
+from manta_rs_amd import api as gpu, synth, keygen
+gpu.init(0)
+assert gpu.get_tuning().queue_aware == 1
+c = synth.make_shape(0, "to_public", profile="W")
+pk = keygen.generate(c, synth.from_mont(H.toxic(0, seed=6), synth.FR_MODULUS[0]))
+r1cs = gpu.R1CS.from_circuit(c)
+rs = H.rand_fr_mont(0, 4, seed=98)
+rs[2][:] = 0
+z2 = synth.Reassigner(c).assign(0x5EED).z
+def leg(name, **kw):
+    ctx = gpu.ProvingContext(0, pk, **kw)
+    ctx.set_r1cs(r1cs)
+    for i in range(5):
+        print(name, "PROOF", gpu.Groth16.prove_with_randomness(ctx, z2 if i & 1 else c.z, rs[2 * (i & 1)], rs[2 * (i & 1) + 1]).hex())
+    got = gpu.Groth16.prove_batch(ctx, np.stack([c.z, z2] * 4), np.stack([rs[0], rs[2]] * 4), np.stack([rs[1], rs[3]] * 4))
+    print(name, "BATCH", " ".join(g.hex() for g in got))
+    print(name, "QUEUES", *gpu.hw_queues())
+    ctx.close()
+leg("OFF", tuning=dict(queue_aware=0))   # process-wide 1, this context 0
+leg("DEFAULT")
+gpu.set_tuning(queue_aware=0)
+leg("ON", tuning=dict(queue_aware=1))    # process-wide 0, this context 1
+'''
+
+
+def test_queue_aware_is_each_contexts_own_choice(gpu):
+    """mg_tuning.queue_aware is per context (mantagpu.h): in a fresh process -- whether the hardware queues were probed is process
+    state -- a context created with queue_aware = 0 under a process-wide 1 proves on plain pooled streams: the oracle's bytes, and
+    hw_queues() still (0, 0) afterwards, because no probe ran and no stream set was taken. A default context after it, and a
+    context with queue_aware = 1 under a process-wide 0, give the oracle's bytes too (nothing is asserted about their queues: on a
+    shared GPU the probe may fall back, see test_hardware_queues_are_probed_and_slots_get_their_own)."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    c, pk, rs, z2, two, _ = _tuning_truth()
+    base = {k: v for k, v in os.environ.items() if not k.startswith("MANTA_")}
+    out = subprocess.run([sys.executable, "-c", _QUEUE_AWARE_SCRIPT.format(root=root)], env=base, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = [ln.split() for ln in out.stdout.split("\n")]
+    for name in ("OFF", "DEFAULT", "ON"):
+        assert [ln[2] for ln in lines if ln[:2] == [name, "PROOF"]] == [two[i & 1] for i in range(5)], name
+        assert [ln[2:] for ln in lines if ln[:2] == [name, "BATCH"]] == [two * 4], name
+    assert [ln[2:] for ln in lines if ln[:2] == ["OFF", "QUEUES"]] == [["0", "0"]], "a context with queue_aware = 0 probed the hardware queues"
+
+
 def test_timed_single_proofs_give_the_oracles_bytes_and_a_consistent_phase_split(gpu):
     """Kernel timing (what bench.py's phase split uses): a timed pass is enqueued eagerly with events between its phases. Two timed
     proofs on a fresh context give the oracle's bytes and ten finite, non-negative phases -- both whole-part entries (upload to part A

@@ -463,3 +463,22 @@ def test_tuning_crosses_the_abi_and_the_library_reads_fifteen_variables():
     env = dict(os.environ, MANTA_GRAPH="split", MANTA_COALESCE="0", MANTA_FULL_TABLE_GB="3.5", MANTA_PROVE_STREAMS="9")  # 9: out of range, ignored
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
     assert out.returncode == 0 and "tuning ok" in out.stdout, out.stdout + out.stderr
+    # the list, in the table's order
+    assert names == ["MANTA_GRAPH", "MANTA_GRAPH_BATCH", "MANTA_PROVE_STREAMS", "MANTA_Z3_LINEAR", "MANTA_COALESCE", "MANTA_COALESCE_GATHER_US",
+                     "MANTA_BATCH_INFLIGHT", "MANTA_QUEUE_AWARE", "MANTA_MSM_DEDICATED_QUEUES", "MANTA_PROVE_C", "MANTA_PROVE_CW", "MANTA_PROVE_CH",
+                     "MANTA_PROVE_CG2", "MANTA_FULL_TABLE_GB", "MANTA_RCCL_LIB"]
+    # a value applies only if its whole string parses as the field's kind and the range accepts it: anything else leaves the default
+    base = {k: v for k, v in os.environ.items() if not k.startswith("MANTA_")}
+    show = "import sys; sys.path.insert(0, %r)\nfrom manta_rs_amd import api\nprint('TUNING', api.get_tuning().as_dict())\n" % ROOT
+
+    def tuning_under(**env):
+        out = subprocess.run([sys.executable, "-c", show], capture_output=True, text=True, env=dict(base, **env), timeout=300)
+        assert out.returncode == 0, out.stdout + out.stderr
+        return eval([ln for ln in out.stdout.split("\n") if ln.startswith("TUNING")][0][7:])
+
+    t = tuning_under(MANTA_COALESCE="abc", MANTA_BATCH_INFLIGHT="2x", MANTA_GRAPH_BATCH="bogus", MANTA_FULL_TABLE_GB="1e12", MANTA_GRAPH="2",
+                     MANTA_PROVE_CW="9")
+    assert t["coalesce_inflight"] == 2 and t["batch_inflight"] == 3 and t["graph_mode_batch"] == -1 and t["full_table_bytes"] == -1, t
+    assert t["graph_mode"] == 2 and t["window_bits_wide"] == 9, t
+    assert tuning_under(MANTA_FULL_TABLE_GB="nan")["full_table_bytes"] == -1
+    assert tuning_under(MANTA_FULL_TABLE_GB="-3")["full_table_bytes"] == -1
