@@ -409,13 +409,29 @@ template <class F, bool ALLOW_DOUBLE = true> struct CoopAdd {
         const auto Y3 = b_fit<BY>(bv<BM>(r[0]) - bv<BM>(r[1]));
         XYZZ<F> sum{X3.v, Y3.v, ZZ3, r[2]};
         // exceptional cases, decided identically in every wave
+        const bool doubles = !o_inf && !a_inf && p0 && r0;
         if (o_inf) {
             sum = acc;
         } else if (a_inf) {
             sum = o;
         } else if (p0) {
-            if (r0) sum = XYZZ<F>::dbl(acc);
+            if constexpr (F::EXT) sum = XYZZ<F>::inf(); // (a doubling lane: replaced below)
+            else if (r0) sum = XYZZ<F>::dbl(acc);
             else sum = XYZZ<F>::inf();
+        }
+        // Over Fp2 the doubling is a call, and it must not sit under a divergent mask here: around such a call hipcc (ROCm 7.2)
+        // saves the VGPR of its spilled SGPRs with ALL lanes enabled -- into a register that is dead on the path through the call
+        // but, in the lanes outside the branch, still holds a word of `o`, which the lanes with an infinite accumulator (sum = o)
+        // read afterwards. BLS12-381 G2: a wave with a doubling lane and an `a_inf` lane in one addition got a wrong sum
+        // (tests/test_gpu_msm_degenerate.py; the instructions and the probe table: profiles/coopadd_fp2_divergent_call.txt).
+        // So: one call for the whole wave when any lane doubles, and a select per lane. Every caller reaches add() with all 64
+        // lanes enabled (TailAdd<F, true>::add_if, accumulate_single), and dbl holds no barrier.
+        // The SAME SHAPE -- an Fp2 call under a divergent mask -- remains at: TailAdd<F, false>::add_if (msm_reduce.h: add_call
+        // under `if (take)`), XYZZ::add_body (dbl_call under the p0 / r0 branch), XYZZ::madd_body (dbl_affine_call likewise).
+        // Those kernels are correct on this compiler (the same tests, plain knob sets, and test_gpu_accumulate_loop.py); the
+        // hazard depends on register allocation, so re-examine them -- rerun those tests -- on a toolchain bump.
+        if constexpr (F::EXT) {
+            if (__any(doubles)) sum = XYZZ<F>::select(doubles, XYZZ<F>::dbl(acc), sum);
         }
         acc = sum;
     }

@@ -29,6 +29,23 @@ def test_group_ntt_matches_oracle(gpu, curve, group):
 
 
 @pytest.mark.parametrize("curve,group", CASES)
+def test_group_ntt_of_a_constant_vector(gpu, curve, group):
+    """All entries the same point P: every twiddle-1 butterfly is a + a and a - a (a doubling and a cancellation), and the
+    forward transform is [n]P at index 0 and infinity elsewhere -- the closed form, and the oracle's; the inverse returns the
+    constant vector."""
+    P = H.random_points(curve, group, 1, seed=47)[0]
+    for n in (2, 4, 64):
+        pts = np.stack([P] * n)
+        want = np.zeros_like(pts)
+        want[0] = O.g_mul(curve, group, P, synth.ints_to_limbs([n], 4)[0])
+        got = gpu.group_ntt(curve, group, pts)
+        assert (got == want).all(), n
+        assert (O.group_ntt(curve, group, pts) == want).all(), n
+        assert (gpu.group_ntt(curve, group, got, inverse=True) == pts).all(), n
+        assert (gpu.group_ntt(curve, group, pts, inverse=True) == O.group_ntt(curve, group, pts, inverse=True)).all(), n
+
+
+@pytest.mark.parametrize("curve,group", CASES)
 def test_batch_mul_fixed_scalar_and_pointwise(gpu, curve, group):
     r = synth.FR_MODULUS[curve]
     pts = H.random_points(curve, group, 50, seed=60)

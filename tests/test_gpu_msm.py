@@ -29,8 +29,10 @@ def test_msm_matches_oracle_uniform(gpu, curve, group, n):
 
 @pytest.mark.parametrize("curve,group", CASES)
 def test_msm_witness_like_and_infinity(gpu, curve, group):
-    """0/1-heavy scalars (booleans dominate real witnesses), infinity bases (variables absent from B),
-    repeated bases (P+P inside a bucket) and P + (-P)."""
+    """0/1-heavy scalars (booleans dominate real witnesses), infinity bases (variables absent from B), a base that occurs twice
+    and [5]P + [-5]P. With witness-like scalars bucket "1" already holds many earlier entries when entries 40 and 41 arrive, so the
+    accumulator is a sum by then and the repeated base is no doubling; true doublings and cancellations are the business of
+    test_gpu_accumulate_loop.py (the accumulate loop) and test_gpu_msm_degenerate.py (every addition behind it)."""
     n = 600
     pts = H.random_points(curve, group, n, seed=77)
     pts[5] = 0
@@ -38,7 +40,7 @@ def test_msm_witness_like_and_infinity(gpu, curve, group):
     pts[40] = pts[41]    # equal points
     pts[50] = pts[51]
     sc = synth.msm_scalars(curve, n, "W", seed=9)
-    sc[40] = sc[41] = np.array([1, 0, 0, 0], dtype=np.uint64)  # forces P+P in bucket "1"
+    sc[40] = sc[41] = np.array([1, 0, 0, 0], dtype=np.uint64)  # the same base twice in bucket "1"
     p = synth.FR_MODULUS[curve]
     sc[50] = synth.ints_to_limbs([5], 4)[0]
     sc[51] = synth.ints_to_limbs([p - 5], 4)[0]                # [5]P + [-5]P = 0
@@ -288,8 +290,9 @@ def test_msm_tail_kernel_twins_agree(gpu, tmp_path, curve, group, n, pre, env):
     """Every tail kernel (merge_partials, tile_reduce, serial_reduce, reduce_level1; msm_reduce.h) is one body instantiated with the
     plain and with the cooperative addition, and which of the two runs is otherwise decided by size alone. The same MSMs with every
     tail forced plain, forced cooperative and at the defaults (knobs are read once per process, hence the child processes; the
-    diagnosis twin reads them), each equal to the oracle and so to each other. The inputs reach the exceptional branches of both
-    adders: repeated bases (P + P inside a bucket), infinity, P and -P in one bucket, beside uniform and witness-like scalars."""
+    diagnosis twin reads them), each equal to the oracle and so to each other. Repeated bases, infinity, P and -P in one bucket
+    reach the exceptional branches of the accumulate loop's madd only: the bucket sums and partials that the TAIL adders (XYZZ::add,
+    CoopAdd) see are distinct random points or infinity -- their doubling and cancellation branches are test_gpu_msm_degenerate.py's."""
     import subprocess
     import sys
     r = synth.FR_MODULUS[curve]
@@ -302,7 +305,7 @@ def test_msm_tail_kernel_twins_agree(gpu, tmp_path, curve, group, n, pre, env):
     data = {"pts": pts}
     for dist in ("U", "W"):
         sc = synth.msm_scalars(curve, n, dist, seed=92)
-        sc[40] = sc[41] = np.array([1, 0, 0, 0], dtype=np.uint64)  # P + P in bucket "1"
+        sc[40] = sc[41] = np.array([1, 0, 0, 0], dtype=np.uint64)  # the same base twice in bucket "1"
         sc[50] = synth.ints_to_limbs([5], 4)[0]
         sc[51] = synth.ints_to_limbs([r - 5], 4)[0]                # [5]P + [-5]P = 0
         data["sc" + dist] = sc
