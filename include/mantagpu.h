@@ -527,6 +527,25 @@ int mg_groth16_prove_batch(const mg_ctx *ctx, uint64_t k, const uint64_t *z_mont
                            const uint64_t *s_mont, uint8_t *proofs_out);
 /* h = R1CStoQAP::witness_map(z): D x 4 u64 Montgomery coefficients (tests / parity) */
 int mg_witness_map(const mg_ctx *ctx, const uint64_t *z_mont, uint64_t *h_out_mont);
+/* `R1CS::is_satisfied` (manta-crypto/src/constraint.rs:30,41; manta-crypto/src/arkworks/constraint/mod.rs:130-132 -> ark-relations
+ * ConstraintSystem::is_satisfied / which_is_unsatisfied) for k assignments at once, on the GPU: first_unsatisfied[j] = the lowest
+ * row i < num_constraints of assignment j with <A_i, z> <B_i, z> != <C_i, z>, or MG_R1CS_SATISFIED; n_unsatisfied[j] (the array
+ * may be NULL) = the number of such rows. Only the constraint rows are looked at, as in ark-relations: not the prover's
+ * input-consistency rows, not z_0. z = k assignments back to back (k x V x 4 u64 Montgomery, every element below the modulus: as
+ * for mg_groth16_prove a larger one is the caller's error and its verdict unspecified -- memory stays safe). mg_groth16_prove
+ * turns an unsatisfied assignment into a non-verifying proof with status 0, as ark-groth16 does in release builds; these calls
+ * restore what its debug_assert! would have said, per assignment and with the row.
+ * mg_ctx_r1cs_check: against the matrices resident in the context (MG_ERROR_STATE before mg_ctx_set_r1cs); safe beside proofs in
+ * flight on the same context. mg_r1cs_check: no proving key needed -- the reference's R1CS::is_satisfied has none either; the
+ * matrices (checked like mg_ctx_set_r1cs's, against n_vars columns) are uploaded for the call.
+ * MG_ERROR_INVALID_ARGUMENT before any device work, the outputs untouched: a NULL context, z or first_unsatisfied with k > 0, a
+ * malformed matrix, n_vars = 0, an unknown curve. k = 0 succeeds and num_constraints = 0 reports every assignment satisfied,
+ * both without device work. */
+#define MG_R1CS_SATISFIED UINT64_MAX
+int mg_ctx_r1cs_check(const mg_ctx *ctx, uint64_t k, const uint64_t *z_mont, uint64_t *first_unsatisfied,
+                      uint64_t *n_unsatisfied);
+int mg_r1cs_check(mg_curve_t curve, const mg_csr *a, const mg_csr *b, const mg_csr *c, uint64_t num_constraints,
+                  uint64_t n_vars, uint64_t k, const uint64_t *z_mont, uint64_t *first_unsatisfied, uint64_t *n_unsatisfied);
 uint64_t mg_ctx_domain_size(const mg_ctx *ctx);
 /* HBM held by the context's key tables, bytes: out[0] = bucket tables (2^(c*w)*P per window, two widths), out[1] = FULL tables
  * (every multiple of every window; single proofs run on them; mg_ctx_opts.full_table_bytes bounds them, 0 = none). The h

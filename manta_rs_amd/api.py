@@ -84,6 +84,7 @@ EXPORTS = [
     "mg_light_notes_encrypt", "mg_light_notes_open", "mg_outgoing_notes_encrypt", "mg_outgoing_notes_open",
     "mg_qap_columns", "mg_mpc_initialize", "mg_fpr_raw_op", "mg_fpr_column_plan",
     "mg_pairing_check_each", "mg_groth16_verify_each",
+    "mg_ctx_r1cs_check", "mg_r1cs_check",
 ]
 
 
@@ -609,6 +610,16 @@ class R1CS:
     def from_circuit(cls, c):
         return cls(c.curve, c.A, c.B, c.C, c.m, c.P, c.z)
 
+    def which_is_unsatisfied(self):
+        """The lowest constraint row the compiler's own assignment fails, or None (ark-relations `which_is_unsatisfied`,
+        which names the row; checked on the GPU by `mg_r1cs_check`, no proving key needed)."""
+        first, _ = r1cs_check(self.curve, self.A, self.B, self.C, self.num_constraints, self.z.size // 4, self.z)
+        return None if first[0] < 0 else int(first[0])
+
+    def is_satisfied(self) -> bool:
+        """`R1CS::is_satisfied` (manta-crypto/src/arkworks/constraint/mod.rs:130-132)."""
+        return self.which_is_unsatisfied() is None
+
 
 class _PkOut(ctypes.Structure):
     _fields_ = [(n, _vp) for n in ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1",
@@ -657,6 +668,31 @@ def _csr(M):
     col = np.ascontiguousarray(M.col, dtype=np.uint32)
     val = _u64(M.val)
     return (rp, col, val), _Csr(_p(rp), _p(col), _p(val), len(col))
+
+
+R1CS_SATISFIED = (1 << 64) - 1  # MG_R1CS_SATISFIED
+
+
+def _r1cs_verdicts(first, count):
+    """the C ABI's u64 outputs -> (first, counts) as int64 arrays, -1 for a satisfied assignment"""
+    return np.where(first == np.uint64(R1CS_SATISFIED), np.int64(-1), first.astype(np.int64)), count.astype(np.int64)
+
+
+def r1cs_check(curve, A, B, C, m, n_vars, zs):
+    """`mg_r1cs_check`: which of the assignments zs (k x n_vars x 4 u64 Montgomery) satisfy the m constraint rows of A, B, C
+    (matrices with row_ptr / col / val). Returns (first, counts): per assignment the lowest failing row (-1: satisfied) and
+    the number of failing rows."""
+    zs = _u64(zs)
+    n_vars = int(n_vars)
+    if n_vars > 0 and zs.size % (n_vars * 4):
+        raise ValueError(f"assignments hold {zs.size} u64 words, no multiple of n_vars x 4 = {n_vars * 4}")
+    k = zs.size // (n_vars * 4) if n_vars > 0 else 0
+    keep = [_csr(M) for M in (A, B, C)]
+    first, count = np.zeros(k, dtype=np.uint64), np.zeros(k, dtype=np.uint64)
+    _chk(LIB.mg_r1cs_check(curve, ctypes.byref(keep[0][1]), ctypes.byref(keep[1][1]), ctypes.byref(keep[2][1]),
+                           ctypes.c_uint64(int(m)), ctypes.c_uint64(n_vars), ctypes.c_uint64(k), _p(zs), _p(first), _p(count)),
+         "mg_r1cs_check")
+    return _r1cs_verdicts(first, count)
 
 
 def qap_columns(curve, group, bases, mats, n_cols, entries_per_lane=0) -> np.ndarray:
@@ -936,6 +972,17 @@ class ProvingContext:
         z = self._check_assignment(z)
         _chk(LIB.mg_witness_map(self.handle, _p(z), _p(h)), "mg_witness_map")
         return h
+
+    def check_assignments(self, zs):
+        """`mg_ctx_r1cs_check`: zs = any number of assignments of the context's circuit (k x V x 4 u64) against the matrices
+        of the last set_r1cs. Returns (first, counts) as int64 arrays: per assignment the lowest unsatisfied constraint row
+        (-1: satisfied -- what ark-groth16's debug_assert! in create_proof checks) and the number of unsatisfied rows."""
+        zs = np.ascontiguousarray(zs, dtype=np.uint64)
+        k = zs.size // (self.num_variables * 4)
+        zs = self._check_assignment(zs, k)
+        first, count = np.zeros(k, dtype=np.uint64), np.zeros(k, dtype=np.uint64)
+        _chk(LIB.mg_ctx_r1cs_check(self.handle, ctypes.c_uint64(k), _p(zs), _p(first), _p(count)), "mg_ctx_r1cs_check")
+        return _r1cs_verdicts(first, count)
 
     def close(self):
         if self.handle is not None:

@@ -788,6 +788,19 @@ MG_API int mg_witness_map(const mg_ctx *ctx, const uint64_t *z, uint64_t *h_out)
     return ctx->p->witness_map_host(z, h_out);
     MG_CATCH
 }
+MG_API int mg_ctx_r1cs_check(const mg_ctx *ctx, uint64_t k, const uint64_t *z, uint64_t *first, uint64_t *count) {
+    MG_TRY
+    if (!ctx || (k && (!z || !first))) return MG_ERROR_INVALID_ARGUMENT;
+    if (k == 0) return MG_SUCCESS;
+    return ctx->p->r1cs_check_host(k, z, first, count);
+    MG_CATCH
+}
+MG_API int mg_r1cs_check(mg_curve_t curve, const mg_csr *a, const mg_csr *b, const mg_csr *c, uint64_t m, uint64_t n_vars, uint64_t k,
+                         const uint64_t *z, uint64_t *first, uint64_t *count) {
+    MG_TRY
+    return r1cs_check((int)curve, a, b, c, m, n_vars, k, z, first, count);
+    MG_CATCH
+}
 MG_API uint64_t mg_ctx_domain_size(const mg_ctx *ctx) { return ctx ? ctx->p->domain_size() : 0; }
 MG_API int mg_ctx_table_bytes(const mg_ctx *ctx, uint64_t out2[2]) {
     if (!ctx || !out2) return MG_ERROR_INVALID_ARGUMENT;

@@ -524,6 +524,47 @@ __global__ __launch_bounds__(256) void spmv3_kernel(Csr3 M, const u32 *__restric
     R::from_std_shift(acc).store(out + (size_t)i * R::K);
 }
 
+// R1CS satisfaction (R1CS::is_satisfied, manta-crypto/src/arkworks/constraint/mod.rs:130-132 -> ark-relations
+// ConstraintSystem::which_is_unsatisfied): <A_i, z> <B_i, z> == <C_i, z> for the m constraint rows of one assignment per blockIdx.y.
+// Nothing else is looked at -- not the input-consistency rows a[m + j] = z_j, not the padding up to the domain size, not z_0 -- as
+// in ark-relations. One row per lane, its three dot products one after the other in the arithmetic of spmv3_kernel (canonical
+// Fp values, the coefficient-equals-one shortcut); the row loop is a copy of that kernel's on purpose: spmv3_kernel is on the
+// path that bounds a single proof and its code stays what it was measured as.
+// The verdict: rows rise with the lane, so the lowest set bit of the wavefront's 64-bit ballot is its first failing row. Only a
+// wavefront that has one touches memory: a minimum into first[y] (0xFFFFFFFF before: r1cs_check) and its population count added
+// to count[y]. Both are order-independent, so the result is the same on every run; a satisfied batch issues no atomic at all.
+template <class FrC> MG_DEV Fp<FrC> r1cs_row_dot(const u32 *__restrict__ row_ptr, const u32 *__restrict__ col, const u32 *__restrict__ val,
+                                                 const u32 *__restrict__ z, u32 i) {
+    typedef Fp<FrC> F;
+    const F one = F::one();
+    F acc = F::zero();
+    for (u32 k = row_ptr[i]; k < row_ptr[i + 1]; ++k) {
+        F c = F::load(val + (size_t)k * 8);
+        F x = F::load(z + (size_t)col[k] * 8);
+        acc = F::add(acc, c == one ? x : F::mul(x, c));
+    }
+    return acc;
+}
+template <class FrC>
+__global__ __launch_bounds__(256) void r1cs_check_kernel(Csr3 M, const u32 *__restrict__ z, u32 m, size_t z_stride, u32 *__restrict__ first,
+                                                         u32 *__restrict__ count) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    z += (size_t)blockIdx.y * z_stride; // batch member
+    typedef Fp<FrC> F;
+    bool bad = false;
+    if (i < m) {
+        const F a = r1cs_row_dot<FrC>(M.row_ptr[0], M.col[0], M.val[0], z, i), b = r1cs_row_dot<FrC>(M.row_ptr[1], M.col[1], M.val[1], z, i),
+                c = r1cs_row_dot<FrC>(M.row_ptr[2], M.col[2], M.val[2], z, i);
+        bad = !(F::mul(a, b) == c);
+    }
+    // (no lane has left: workgroups are 256 lanes, four whole wavefronts, and rows past m merely vote "fine")
+    const u64 failing = __ballot(bad);
+    if (failing && (threadIdx.x & 63u) == 0) {
+        atomicMin(first + blockIdx.y, i + (u32)__ffsll((unsigned long long)failing) - 1u);
+        atomicAdd(count + blockIdx.y, (u32)__popcll(failing));
+    }
+}
+
 // a[i] = (a[i] b[i] - c[i]) * (g^D - 1)^-1, reduced-radix vectors (inputs < 4p, output < 2p)
 template <class FrC>
 __global__ __launch_bounds__(256) void qap_pointwise_kernel(u32 *__restrict__ a, const u32 *__restrict__ b,
@@ -865,6 +906,20 @@ template <class FrC> class FrEngineT : public FrHostT<FrC> {
         Csr3 M{{A.row_ptr, B.row_ptr, C.row_ptr}, {A.col, B.col, C.col}, {A.val, B.val, C.val}, {d_a, d_b, d_c}};
         hipLaunchKernelGGL((spmv3_kernel<FrC>), dim3((u32)((rows_total + 255) / 256), batch, 3), dim3(256), 0, s, M, d_z, (u32)m, (u32)P,
                            z_stride, out_stride, (u32)rows_total);
+        MG_HIP(hipGetLastError());
+        return MG_OK;
+    }
+    int r1cs_check(const DevCsr &A, const DevCsr &B, const DevCsr &C, const u32 *d_z, u64 m, hipStream_t s, u32 batch, size_t z_stride,
+                   u32 *d_first, u32 *d_count) override {
+        if (batch == 0) return MG_OK;
+        if (batch > FrEngine::R1CS_CHECK_MAX_BATCH || m >= ((u64)1 << 32)) return MG_ERR_ARG; // (the grid's y limit; rows are 32-bit, 2^32 - 1 = "none")
+        // the result words, in front of the kernel on its stream (nothing here is ever captured: a memset is fine)
+        MG_HIP(hipMemsetAsync(d_first, 0xFF, (size_t)batch * 4, s));
+        MG_HIP(hipMemsetAsync(d_count, 0, (size_t)batch * 4, s));
+        if (m == 0) return MG_OK; // no row, nothing fails
+        Csr3 M{{A.row_ptr, B.row_ptr, C.row_ptr}, {A.col, B.col, C.col}, {A.val, B.val, C.val}, {nullptr, nullptr, nullptr}};
+        hipLaunchKernelGGL((r1cs_check_kernel<FrC>), dim3((u32)((m + 255) / 256), batch), dim3(256), 0, s, M, d_z, (u32)m, z_stride, d_first,
+                           d_count);
         MG_HIP(hipGetLastError());
         return MG_OK;
     }

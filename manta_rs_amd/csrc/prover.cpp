@@ -13,6 +13,7 @@
 // An unsatisfied witness is not an error (ark-groth16 only debug_asserts it): a non-verifying proof
 // comes back, exactly like the reference in release builds.
 #include "prover.h"
+#include "staging.h"
 #include "tuning.h"
 // The six RCCL entry points this file calls, declared here from NCCL's stable C ABI (ncclResult_t 0 = success, ncclUint64 = 5):
 // librccl.so is loaded on demand (Rccl::get) and never linked, and its header is not a build dependency of a single-GPU host
@@ -961,6 +962,63 @@ int prover_create_sharded(int curve, const mg_pk_view *pk, const int *devices, i
     ProverOptions o;
     o.devices = devices, o.n_devices = n_devices;
     return prover_create_ex(curve, pk, o, out);
+}
+
+// ---- R1CS::is_satisfied (manta-crypto/src/constraint.rs:30,41; arkworks/constraint/mod.rs:130-132) ------------------------------------
+// k assignments from host memory against matrices on the current device, through the chunk loop of staging.h. A launch covers at
+// most R1CS_CHECK_MAX_BATCH assignments (the grid's y limit) and at most R1CS_CHECK_Z_BYTES of z: the loop copies, launches and
+// waits chunk by chunk without overlap, so a larger block buys nothing but footprint once a chunk fills the device -- 64 MiB is 59
+// PrivateTransfer assignments (V = 35 175) x 65 509 rows = 3.9 M lanes, seven times the 524 288 lanes the 256 CUs hold -- and the call
+// stays small beside a context whose key tables are sized to a tenth of the HBM.
+static constexpr size_t R1CS_CHECK_Z_BYTES = (size_t)64 << 20;
+int r1cs_check_chunks(FrEngine *fr, const DevCsr &A, const DevCsr &B, const DevCsr &C, u64 m, u64 V, u64 k, const u64 *z, u64 *first,
+                      u64 *count) {
+    if (k == 0) return MG_OK;
+    const size_t zb = (size_t)V * 32;
+    const size_t lanes = std::min<size_t>(FrEngine::R1CS_CHECK_MAX_BATCH, std::max<size_t>(1, R1CS_CHECK_Z_BYTES / zb));
+    std::vector<u32> f32(k), c32(k);
+    int inner = MG_OK; // (the loop's callback speaks hipError_t; the engine's own status is kept beside it)
+    const int rc = run_chunks(Staging{lanes, false}, k, nullptr, 0, {Span::in(z, zb), Span::out(f32.data(), 4), Span::out(c32.data(), 4)}, 0,
+                              [&](const Chunk &c) {
+                                  inner = fr->r1cs_check(A, B, C, (const u32 *)c.a[0], m, c.stream, (u32)c.n, zb / 4, (u32 *)c.a[1], (u32 *)c.a[2]);
+                                  return inner == MG_OK ? hipSuccess : hipErrorUnknown;
+                              });
+    if (inner || rc) return inner ? inner : rc;
+    for (u64 q = 0; q < k; ++q) {
+        first[q] = f32[q] == 0xFFFFFFFFu ? MG_R1CS_SATISFIED : (u64)f32[q];
+        if (count) count[q] = c32[q];
+    }
+    return MG_OK;
+}
+
+int r1cs_check(int curve, const mg_csr *a, const mg_csr *b, const mg_csr *c, u64 m, u64 V, u64 k, const u64 *z, u64 *first, u64 *count) {
+    if ((curve != 0 && curve != 1) || V == 0 || V >= ((u64)1 << 32) || m >= ((u64)1 << 32) || (k && (!z || !first))) return MG_ERR_ARG;
+    int rc;
+    if ((rc = validate_csr(a, m, V)) || (rc = validate_csr(b, m, V)) || (rc = validate_csr(c, m, V))) return rc;
+    if (k == 0) return MG_OK;
+    if (m == 0) { // no row: every assignment satisfies it, and no device is asked
+        for (u64 q = 0; q < k; ++q) first[q] = MG_R1CS_SATISFIED;
+        if (count) std::memset(count, 0, (size_t)k * 8);
+        return MG_OK;
+    }
+    FrEngine *fr = get_ntt_engine(curve);
+    if (!fr) return MG_ERR_ARG;
+    const mg_csr *src[3] = {a, b, c};
+    DevBlock d; // row_ptr | col | val of A, B, C: the call's, freed on every path out
+    std::vector<size_t> bytes;
+    for (const mg_csr *s : src) bytes.push_back((size_t)(m + 1) * 4), bytes.push_back((size_t)s->nnz * 4), bytes.push_back((size_t)s->nnz * 32);
+    if ((rc = d.alloc(bytes, "mg_r1cs_check"))) return rc;
+    DevCsr M[3];
+    for (int t = 0; t < 3; ++t) {
+        const void *from[3] = {src[t]->row_ptr, src[t]->col, src[t]->val};
+        for (int j = 0; j < 3; ++j) {
+            if (!bytes[3 * t + j]) continue;
+            const hipError_t e = memcpy_sync(d.dev(3 * t + j), from[j], bytes[3 * t + j], hipMemcpyHostToDevice);
+            if (e != hipSuccess) return hip_status(e, "mg_r1cs_check");
+        }
+        M[t].row_ptr = d.dev<u32>(3 * t), M[t].col = d.dev<u32>(3 * t + 1), M[t].val = d.dev<u32>(3 * t + 2), M[t].nnz = src[t]->nnz;
+    }
+    return r1cs_check_chunks(fr, M[0], M[1], M[2], m, V, k, z, first, count);
 }
 
 } // namespace mg

@@ -41,6 +41,12 @@ class FrEngine {
     virtual int work_words() const = 0;
     virtual int spmv3(const DevCsr &A, const DevCsr &B, const DevCsr &C, const u32 *d_z, u32 *d_a, u32 *d_b, u32 *d_c, u64 m, u64 P,
                       hipStream_t s, u32 batch = 1, size_t z_stride = 0, size_t out_stride = 0, u64 rows_total = 0) = 0;
+    // R1CS::is_satisfied for `batch` assignments (z vectors z_stride u32 apart, batch <= R1CS_CHECK_MAX_BATCH) against the m
+    // constraint rows: d_first[q] = the lowest row of assignment q with <A_i, z> <B_i, z> != <C_i, z>, 0xFFFFFFFF if there is none;
+    // d_count[q] = how many rows fail. Both are initialised here, on `s`, in front of the kernel.
+    static constexpr u32 R1CS_CHECK_MAX_BATCH = 65535;
+    virtual int r1cs_check(const DevCsr &A, const DevCsr &B, const DevCsr &C, const u32 *d_z, u64 m, hipStream_t s, u32 batch,
+                           size_t z_stride, u32 *d_first, u32 *d_count) = 0;
     // a, b, c = constraint evaluations over the domain (work form) -> a = coefficients of h = (AB - C)/Z in
     // bit-reversed order, work form, < 2p (ifft, coset fft x3, pointwise, coset ifft; fused, permutation-free)
     // batch > 1: a, b, c each hold `batch` vectors back to back
@@ -75,6 +81,9 @@ class Prover {
     // field elements each, proofs_out = k encoded proofs back to back
     virtual int prove_batch(u64 k, const uint64_t *z, const uint64_t *r, const uint64_t *s, uint8_t *proofs_out) = 0;
     virtual int witness_map_host(const uint64_t *z, uint64_t *h_out) = 0;
+    // the context's matrices against k assignments in host memory: first[q] = the lowest unsatisfied row of assignment q or
+    // MG_R1CS_SATISFIED, count[q] (count may be null) = the number of unsatisfied rows
+    virtual int r1cs_check_host(u64 k, const uint64_t *z, uint64_t *first, uint64_t *count) = 0;
     virtual u64 domain_size() const = 0;
     virtual void table_bytes(u64 out2[2]) const = 0; // bucket tables, full tables (all shards)
     virtual u64 n_vars() const = 0;
@@ -110,6 +119,12 @@ int prover_create_from_bytes_ex(int curve, const uint8_t *bytes, size_t len, con
 // Groth16 key generation from explicit toxic waste and group generators (setup.cpp)
 int groth16_setup(int curve, const mg_csr *a, const mg_csr *b, const mg_csr *c, u64 m, u64 n_vars, u64 n_inputs,
                   const u64 *toxic5, const u64 *g1_gen, const u64 *g2_gen, const mg_pk_out *out);
+// R1CS::is_satisfied without a key: k assignments of n_vars elements in host memory against matrices in host memory (uploaded for
+// the call), and the part it shares with Prover::r1cs_check_host: the chunk loop over assignments against matrices on the device
+int r1cs_check(int curve, const mg_csr *a, const mg_csr *b, const mg_csr *c, u64 m, u64 n_vars, u64 k, const u64 *z, u64 *first,
+               u64 *count);
+int r1cs_check_chunks(FrEngine *fr, const DevCsr &A, const DevCsr &B, const DevCsr &C, u64 m, u64 n_vars, u64 k, const u64 *z, u64 *first,
+                      u64 *count);
 // the phase-2 key of a circuit from a KZG accumulator, and its sparse half alone (mpc.cpp)
 int qap_columns(int curve, int group, size_t n_terms, const u64 *const *bases_affine, const mg_csr *const *mats, u64 m, u64 n_cols,
                 u32 entries_per_lane, u64 *out_affine);

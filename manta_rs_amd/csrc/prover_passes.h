@@ -246,6 +246,18 @@ class ProverSlots : public ProverAssembly {
         return rc;
     }
 
+    // R1CS::is_satisfied for k assignments against the matrices of this context -- of its first shard: a circuit is on all shards or
+    // none. Shared shape lock like a pass, so it is safe beside proofs in flight and waits out a set_r1cs. It takes no proof slot:
+    // a slot's z buffer is sized for the slot's batch and its address is baked into the slot's captured graphs, so it cannot hold
+    // a chunk of another size; the assignments go through the call-scoped block of the chunk loop on this thread's setup stream.
+    int r1cs_check_host(u64 k, const uint64_t *z, uint64_t *first, uint64_t *count) override {
+        DeviceGuard restore_callers_device;
+        MG_HIP(hipSetDevice(dev_));
+        std::shared_lock<std::shared_mutex> shape_lock(shape_mu_);
+        if (!have_r1cs_) return MG_ERR_STATE;
+        return r1cs_check_chunks(fr_, A_, B_, C_, m_, V_, k, z, first, count);
+    }
+
     // passes of up to this many proofs run on the full tables where the key has them (MANTA_FULL_MAX_K; a batch sorts its
     // pairs by proof -- one radix pass -- and needs 32 additions per scalar where the wide bucket tables need 24)
     static u32 full_max_k() {

@@ -18,6 +18,7 @@ pub const MG_ERROR_OUT_OF_MEMORY: c_int = 3;
 pub const MG_ERROR_DOMAIN_TOO_LARGE: c_int = 4;
 pub const MG_ERROR_STATE: c_int = 5;
 pub const MG_ERROR_CHECKSUM: c_int = 6;
+pub const MG_R1CS_SATISFIED: u64 = u64::MAX;
 pub const MG_TASK_A: c_uint = 1;
 pub const MG_TASK_B_G1: c_uint = 2;
 pub const MG_TASK_B_G2: c_uint = 4;
@@ -505,6 +506,20 @@ extern "C" {
         proofs_out: *mut u8,
     ) -> c_int;
     pub fn mg_witness_map(ctx: *const mg_ctx, z_mont: *const u64, h_out_mont: *mut u64) -> c_int;
+    /// `R1CS::is_satisfied` for k assignments: the lowest unsatisfied row of each, or `MG_R1CS_SATISFIED`; `n_unsatisfied` may be null.
+    pub fn mg_ctx_r1cs_check(ctx: *const mg_ctx, k: u64, z_mont: *const u64, first_unsatisfied: *mut u64, n_unsatisfied: *mut u64) -> c_int;
+    pub fn mg_r1cs_check(
+        curve: mg_curve_t,
+        a: *const mg_csr,
+        b: *const mg_csr,
+        c: *const mg_csr,
+        num_constraints: u64,
+        n_vars: u64,
+        k: u64,
+        z_mont: *const u64,
+        first_unsatisfied: *mut u64,
+        n_unsatisfied: *mut u64,
+    ) -> c_int;
     pub fn mg_ctx_domain_size(ctx: *const mg_ctx) -> u64;
     pub fn mg_ctx_table_bytes(ctx: *const mg_ctx, out2: *mut u64) -> c_int;
     pub fn mg_ctx_num_variables(ctx: *const mg_ctx) -> u64;
