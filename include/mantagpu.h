@@ -618,6 +618,43 @@ int mg_groth16_verify_each(const mg_vk *vk, uint64_t k, const uint64_t *inputs_m
  * G1, Q_i affine G2 (Montgomery limbs; an all-zero point is infinity and its pair contributes 1). n Miller loops
  * (one wavefront each, every Q_i prepared alongside by a second one) and one final exponentiation. */
 int mg_pairing_check(mg_curve_t curve, const uint64_t *g1_affine, const uint64_t *g2_affine, size_t n, int *ok);
+/* The pairing's building blocks, each alone over host arrays: a parity-test surface for the device functions every
+ * pairing runs (as mg_field_op and mg_fpr_raw_op are for the fields), not needed by the shim. Synchronous, one launch on
+ * the calling thread's setup stream. All values are Montgomery words (uint32), canonical (below q); an Fq12 is twelve Fq
+ * in arkworks' memory order (slot 3 i + j = the coefficient of w^(i + 2 j), each c0 then c1), as mg_vk_alpha_beta's
+ * value before serialisation.
+ *   Fq12 operations, one element per single-wavefront workgroup, a and out [n][12 Fq]:
+ *     MUL12 a b (b [n][12 Fq])   SQR12 a^2   CYC_SQR12 a^2 for a in the cyclotomic subgroup
+ *     ELL a times the line b = [n][3 Fq2], coefficient t at w^t (BN254: w^0, w^1, w^3; BLS12-381: w^0, w^2, w^3) -- the
+ *         Miller loop's line product with the coefficients as they come out of their scaling by the G1 point
+ *     FROB12_k a^(q^k)   CONJ12 a^(q^6)   INV12 1/a (a != 0)
+ *     EXP_BY_X a^x for a in the cyclotomic subgroup, x the curve's signed parameter   FINAL_EXP arkworks' final_exponentiation
+ *   Fq and Fq2 helpers, one element per lane:
+ *     FQ_INV_EUCLID 1/a (a, out [n][Fq], a != 0)   FQ_HALF a/2   FQ2_MUL a b (a, b, out [n][Fq2])   FQ2_MUL_XI xi a
+ *     FQ_LINCOMB sum_m coeffs[i][m] a[i][m]: a [n][10][Fq], coeffs [n][10] in -255..255, out [n][Fq] -- one `lincomb` of
+ *         ten operands as the second stage of the squarings and the line product calls it
+ * MG_ERROR_INVALID_ARGUMENT before any device work: an unknown curve or op, a missing operand, n = 0 or above
+ * MG_PAIRING_OP_MAX, a row of coefficients whose positive or negative sum reaches 256. */
+#define MG_PAIRING_MUL12 0
+#define MG_PAIRING_SQR12 1
+#define MG_PAIRING_CYC_SQR12 2
+#define MG_PAIRING_ELL 3
+#define MG_PAIRING_FROB12_1 4
+#define MG_PAIRING_FROB12_2 5
+#define MG_PAIRING_FROB12_3 6
+#define MG_PAIRING_CONJ12 7
+#define MG_PAIRING_INV12 8
+#define MG_PAIRING_EXP_BY_X 9
+#define MG_PAIRING_FINAL_EXP 10
+#define MG_PAIRING_FQ_INV_EUCLID 11
+#define MG_PAIRING_FQ_HALF 12
+#define MG_PAIRING_FQ2_MUL 13
+#define MG_PAIRING_FQ2_MUL_XI 14
+#define MG_PAIRING_FQ_LINCOMB 15
+#define MG_PAIRING_LINCOMB_OPERANDS 10
+#define MG_PAIRING_OP_MAX 65536
+int mg_pairing_op(mg_curve_t curve, int op, const uint32_t *a, const uint32_t *b, const int16_t *coeffs, size_t n,
+                  uint32_t *out);
 /* `Proof::deserialize` (arkworks compressed a | b | c) -> a | b | c affine Montgomery limbs; rejects non-canonical
  * encodings, points off the curve or outside the subgroup. */
 int mg_proof_decode(mg_curve_t curve, const uint8_t *proof_bytes, uint64_t *points_out);

@@ -83,7 +83,7 @@ EXPORTS = [
     "mg_blake2s", "mg_aes256_gcm", "mg_address_partitions", "mg_merkle_shard_indices",
     "mg_light_notes_encrypt", "mg_light_notes_open", "mg_outgoing_notes_encrypt", "mg_outgoing_notes_open",
     "mg_qap_columns", "mg_mpc_initialize", "mg_fpr_raw_op", "mg_fpr_column_plan",
-    "mg_pairing_check_each", "mg_groth16_verify_each",
+    "mg_pairing_check_each", "mg_groth16_verify_each", "mg_pairing_op",
     "mg_ctx_r1cs_check", "mg_r1cs_check",
 ]
 
@@ -487,6 +487,40 @@ def fpr_raw_op(field, op, a, b=None, c=None, d=None, chain=False) -> np.ndarray:
     out = np.zeros_like(arrs[0])
     _chk(LIB.mg_fpr_raw_op(FIELD_IDS[field], FPR_OPS[op], int(bool(chain)), _p(arrs[0]), _p(arrs[1]), _p(arrs[2]), _p(arrs[3]),
                            _sz(arrs[0].shape[0]), _p(out)), "mg_fpr_raw_op")
+    return out
+
+
+PAIRING_OPS = {"mul12": 0, "sqr12": 1, "cyc_sqr12": 2, "ell": 3, "frob12_1": 4, "frob12_2": 5, "frob12_3": 6, "conj12": 7, "inv12": 8,
+               "exp_by_x": 9, "final_exp": 10, "fq_inv_euclid": 11, "fq_half": 12, "fq2_mul": 13, "fq2_mul_xi": 14, "fq_lincomb": 15}
+PAIRING_LINCOMB_OPERANDS = 10
+
+
+def pairing_op(curve, op, a, b=None, coeffs=None) -> np.ndarray:
+    """One building block of the pairing over n elements (`mg_pairing_op`): uint32 Montgomery words in and out, N = 8 / 12 per
+    Fq. Fq12 operations (a = [n, 12 N], arkworks memory order): "mul12" (b = [n, 12 N]), "sqr12", "cyc_sqr12", "ell" (b = [n, 6 N],
+    the line's three Fq2 coefficients), "frob12_1" .. "frob12_3", "conj12", "inv12", "exp_by_x", "final_exp". Fq / Fq2 helpers:
+    "fq_inv_euclid", "fq_half" (a = [n, N]), "fq2_mul" (a, b = [n, 2 N]), "fq2_mul_xi" (a = [n, 2 N]), "fq_lincomb" (a = [n, 10, N],
+    coeffs = [n, 10] integers in -255..255 whose positive and negative sums stay below 256 -> [n, N])."""
+    N = 2 * FQ_LIMBS[curve]
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    n = a.shape[0]
+    if op == "fq_lincomb":
+        assert a.shape == (n, PAIRING_LINCOMB_OPERANDS, N), a.shape
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.int16)
+        assert coeffs.shape == (n, PAIRING_LINCOMB_OPERANDS), coeffs.shape
+        out = np.zeros((n, N), dtype=np.uint32)
+    else:
+        wa = {"fq_inv_euclid": N, "fq_half": N, "fq2_mul": 2 * N, "fq2_mul_xi": 2 * N}.get(op, 12 * N)
+        assert a.shape == (n, wa), (op, a.shape)
+        coeffs = None
+        out = np.zeros_like(a)
+    wb = {"mul12": 12 * N, "ell": 6 * N, "fq2_mul": 2 * N}.get(op)
+    if wb is not None:
+        b = np.ascontiguousarray(b, dtype=np.uint32)
+        assert b.shape == (n, wb), (op, b.shape)
+    else:
+        b = None
+    _chk(LIB.mg_pairing_op(curve, PAIRING_OPS[op], _p(a), _p(b), _p(coeffs), _sz(n), _p(out)), "mg_pairing_op")
     return out
 
 

@@ -884,6 +884,17 @@ MG_API int mg_pairing_check(mg_curve_t curve, const uint64_t *g1_affine, const u
     return pe->product_is_one((const u32 *)g1_affine, (const u32 *)g2_affine, n, ok);
     MG_CATCH
 }
+// the pairing's building blocks one at a time (a parity-test surface; pairing_impl.h tower_op)
+MG_API int mg_pairing_op(mg_curve_t curve, int op, const uint32_t *a, const uint32_t *b, const int16_t *coeffs, size_t n,
+                         uint32_t *out) {
+    MG_TRY
+    if ((int)curve < 0 || (int)curve > 1) return MG_ERROR_INVALID_ARGUMENT;
+    if (const int rc = pairing_op_check(op, a, b, coeffs, n, out)) return rc; // (before the engine, which asks for the device)
+    PairingEngine *pe = get_pairing_engine((int)curve);
+    if (!pe) return MG_ERROR_INVALID_ARGUMENT;
+    return pe->tower_op(op, a, b, coeffs, n, out);
+    MG_CATCH
+}
 MG_API int mg_pairing_check_each(mg_curve_t curve, const uint64_t *g1_affine, const uint64_t *g2_affine, size_t group_size,
                                  size_t n_groups, uint8_t *ok) {
     MG_TRY

@@ -36,6 +36,15 @@ template <int M_, int BITS, int X_ = 0> struct LaneTab {
     MG_DEV u32 cf(int e) const { return (w[SW + e / 4] >> (8 * (e % 4))) & 255u; }
     MG_DEV u32 pos(int e) const { return (cf(e) & MINUS) ? 0u : cf(e); }
     MG_DEV u32 neg(int e) const { return (cf(e) & MINUS) ? cf(e) & 0x7fu : 0u; }
+    // what `lincomb` needs of an entry: the positive and the negative coefficients add up to less than 256 each
+    constexpr bool sums_fit() const {
+        u32 p = 0, n = 0;
+        for (int e = 0; e < M + X; ++e) {
+            const u32 c = (w[SW + e / 4] >> (8 * (e % 4))) & 255u;
+            (c & MINUS ? n : p) += c & 0x7fu;
+        }
+        return p < 256u && n < 256u;
+    }
 };
 
 template <class K> struct PairingWave {
@@ -240,11 +249,13 @@ template <class K> struct PairingWave {
     template <auto ENTRY> static MG_DEV auto lane_tab() {
         struct Entries {
             decltype(ENTRY(0)) e[12] = {};
+            bool fit = true;
             constexpr Entries() {
-                for (int l = 0; l < 12; ++l) e[l] = ENTRY(l);
+                for (int l = 0; l < 12; ++l) e[l] = ENTRY(l), fit = fit && e[l].sums_fit();
             }
         };
         constexpr Entries t;
+        static_assert(t.fit, "a table entry's positive or negative coefficient sum reaches 256: lincomb's t would pass 2^9 p");
         return lane_select(t.e);
     }
     // The second stage of a product level whose first stage left one Fq product per lane in the product area: twelve lanes,

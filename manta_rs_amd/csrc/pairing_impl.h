@@ -133,10 +133,101 @@ __global__ __launch_bounds__(64) void pairing_group_tail_kernel(const u32 *__res
     if (threadIdx.x == 0) verdict[t] = same ? 1 : 0;
 }
 
+// ---- the building blocks one at a time (`mg_pairing_op`): whole pairings only ever hand them random-looking elements, so the
+// tests feed zeros, ones, p - 1 and sparse elements through these two kernels and compare with plain integers.
+// workgroup i (one wavefront): out[i] = op(a[i] [, b[i]]) on Fq12 registers in LDS, called the way the pairing calls them; the
+// line of ELL lies in ring entry 0 as wave 1 of the Miller kernel would have left it (the LDS block is the Miller kernel's or
+// the final exponentiation's, whichever is larger; ELL uses register 0 alone, in front of the ring)
+template <class K>
+__global__ __launch_bounds__(64) void pairing_f12_op_kernel(int op, const u32 *__restrict__ a, const u32 *__restrict__ b,
+                                                            u32 *__restrict__ out) {
+    typedef Pairing<K> P;
+    typedef PairingWave<K> w;
+    const size_t i = blockIdx.x;
+    const int l = (int)threadIdx.x, r0 = w::R(0), r1 = w::R(1);
+    if (l < 6) w::st(r0 + l, P::F2::load(a + i * P::F12W + l * P::F2W));
+    if (op == MG_PAIRING_MUL12 && l < 6) w::st(r1 + l, P::F2::load(b + i * P::F12W + l * P::F2W));
+    if (op == MG_PAIRING_ELL && l < 3) P::F2::load(b + i * P::COEFFW + l * P::F2W).store(w::ring_slot(0) + l * P::F2W);
+    w::sync();
+    int res = r0;
+    switch (op) { // uniform over the launch
+    case MG_PAIRING_MUL12: w::mul12(r0, r0, r1); break;
+    case MG_PAIRING_SQR12: w::sqr12(r0, r0, w::template lane_tab<w::sq_entry>()); break;
+    case MG_PAIRING_CYC_SQR12: w::cyc_sqr12(r0, r0, w::template lane_tab<w::cyc_entry>()); break;
+    case MG_PAIRING_ELL: w::ell(r0, 0, w::template lane_tab<w::ell_entry>()); break;
+    case MG_PAIRING_FROB12_1: w::template frob12<1>(r0); break;
+    case MG_PAIRING_FROB12_2: w::template frob12<2>(r0); break;
+    case MG_PAIRING_FROB12_3: w::template frob12<3>(r0); break;
+    case MG_PAIRING_CONJ12: w::conj12(r0); break;
+    case MG_PAIRING_INV12: w::inv12(res = r1, r0, w::R(2), w::R(3)); break;
+    case MG_PAIRING_EXP_BY_X: w::exp_by_x(res = r1, r0, w::template lane_tab<w::cyc_entry>()); break;
+    case MG_PAIRING_FINAL_EXP: w::final_exp(); break;
+    }
+    if (l < 6) w::ld(res + l).store(out + i * P::F12W + l * P::F2W);
+}
+// lane i: out[i] = op(a[i] [, b[i]]) on Fq / Fq2 values in registers
+template <class K>
+__global__ __launch_bounds__(64) void pairing_fq_op_kernel(int op, const u32 *__restrict__ a, const u32 *__restrict__ b,
+                                                           const int16_t *__restrict__ coeffs, size_t n, u32 *__restrict__ out) {
+    typedef Pairing<K> P;
+    typedef PairingWave<K> w;
+    typedef typename P::F F;
+    typedef typename P::F2 F2;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr int M = MG_PAIRING_LINCOMB_OPERANDS;
+    switch (op) {
+    case MG_PAIRING_FQ_INV_EUCLID: w::inv_euclid(F::load(a + i * P::N)).store(out + i * P::N); break;
+    case MG_PAIRING_FQ_HALF: w::half(F::load(a + i * P::N)).store(out + i * P::N); break;
+    case MG_PAIRING_FQ2_MUL: w::mul2(F2::load(a + i * P::F2W), F2::load(b + i * P::F2W)).store(out + i * P::F2W); break;
+    case MG_PAIRING_FQ2_MUL_XI: w::mul2_xi(F2::load(a + i * P::F2W)).store(out + i * P::F2W); break;
+    case MG_PAIRING_FQ_LINCOMB: { // as `combine` calls it: ten operands, the unused ones at coefficient zero
+        F v[M];
+        u32 cp[M], cn[M];
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            const int c = coeffs[i * M + m];
+            v[m] = F::load(a + (i * M + m) * P::N);
+            cp[m] = c > 0 ? (u32)c : 0u, cn[m] = c < 0 ? (u32)-c : 0u;
+        }
+        w::template lincomb<M>(v, cp, cn).store(out + i * P::N);
+        break;
+    }
+    }
+}
+
 template <class K> class PairingEngineT : public PairingEngine {
   public:
     typedef Pairing<K> P;
     typedef PairingWave<K> PW;
+    int tower_op(int op, const u32 *a, const u32 *b, const int16_t *coeffs, size_t n, u32 *out) override {
+        if (const int rc = pairing_op_check(op, a, b, coeffs, n, out)) return rc;
+        const bool f12 = op <= MG_PAIRING_FINAL_EXP;
+        // words per element: a, b, out
+        size_t wa = f12 ? P::F12W : P::F2W, wb = 0, wo = wa;
+        if (op == MG_PAIRING_MUL12) wb = P::F12W;
+        if (op == MG_PAIRING_ELL) wb = P::COEFFW;
+        if (op == MG_PAIRING_FQ2_MUL) wb = P::F2W;
+        if (op == MG_PAIRING_FQ_INV_EUCLID || op == MG_PAIRING_FQ_HALF) wa = wo = P::N;
+        if (op == MG_PAIRING_FQ_LINCOMB) wa = (size_t)MG_PAIRING_LINCOMB_OPERANDS * P::N, wo = P::N;
+        const size_t cb = op == MG_PAIRING_FQ_LINCOMB ? n * MG_PAIRING_LINCOMB_OPERANDS * sizeof(int16_t) : 0;
+        DevBlock m; // out | a | b | coefficients (absent operands take no room)
+        if (const int rc = m.alloc({n * wo * 4, n * wa * 4, n * wb * 4, cb}, "mg_pairing_op")) return rc;
+        hipError_t e = memcpy_sync(m.dev(1), a, n * wa * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && wb) e = memcpy_sync(m.dev(2), b, n * wb * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && cb) e = memcpy_sync(m.dev(3), coeffs, cb, hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            constexpr size_t lds = PW::lds_bytes(PW::FINAL_EXP_REGS) > PW::miller_lds_bytes() ? PW::lds_bytes(PW::FINAL_EXP_REGS) : PW::miller_lds_bytes();
+            if (f12)
+                hipLaunchKernelGGL((pairing_f12_op_kernel<K>), dim3((unsigned)n), dim3(64), lds, setup_stream(), op, m.dev<u32>(1), m.dev<u32>(2),
+                                   m.dev<u32>(0));
+            else
+                hipLaunchKernelGGL((pairing_fq_op_kernel<K>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, setup_stream(), op, m.dev<u32>(1),
+                                   m.dev<u32>(2), m.dev<int16_t>(3), n, m.dev<u32>(0));
+            e = memcpy_sync(out, m.dev(0), n * wo * 4, hipMemcpyDeviceToHost);
+        }
+        return e == hipSuccess ? MG_OK : hip_status(e, "mg_pairing_op");
+    }
     int n_coeffs() const override { return P::NCOEFF; }
     int coeff_words() const override { return P::COEFFW; }
     int f12_words() const override { return P::F12W; }

@@ -59,7 +59,27 @@ class PairingEngine {
     // product_is_one per group: points [n_groups][group_size], group-major as a caller holds them; any n_groups (chunked)
     virtual int product_is_one_each(const u32 *p_affine_host, const u32 *q_affine_host, size_t group_size, size_t n_groups,
                                     unsigned char *ok) = 0;
+    // one building block of the pairing over n elements (mantagpu.h mg_pairing_op): host arrays in and out, one launch
+    virtual int tower_op(int op, const u32 *a, const u32 *b, const int16_t *coeffs, size_t n, u32 *out) = 0;
 };
+// what mg_pairing_op refuses, decided on the host before any device work
+inline int pairing_op_check(int op, const void *a, const void *b, const int16_t *coeffs, size_t n, const void *out) {
+    if (op < MG_PAIRING_MUL12 || op > MG_PAIRING_FQ_LINCOMB || !a || !out || n == 0 || n > MG_PAIRING_OP_MAX) return MG_ERR_ARG;
+    if ((op == MG_PAIRING_MUL12 || op == MG_PAIRING_ELL || op == MG_PAIRING_FQ2_MUL) && !b) return MG_ERR_ARG;
+    if (op == MG_PAIRING_FQ_LINCOMB) { // `lincomb` needs the positive and the negative coefficient sum below 256 each
+        if (!coeffs) return MG_ERR_ARG;
+        for (size_t i = 0; i < n; ++i) {
+            int pos = 0, neg = 0;
+            for (int m = 0; m < MG_PAIRING_LINCOMB_OPERANDS; ++m) {
+                const int c = coeffs[i * MG_PAIRING_LINCOMB_OPERANDS + m];
+                if (c < -255 || c > 255) return MG_ERR_ARG;
+                pos += c > 0 ? c : 0, neg += c < 0 ? -c : 0;
+            }
+            if (pos >= 256 || neg >= 256) return MG_ERR_ARG;
+        }
+    }
+    return MG_OK;
+}
 PairingEngine *make_pairing_engine_bn254();
 PairingEngine *make_pairing_engine_bls381();
 PairingEngine *get_pairing_engine(int curve); // per (device, curve)

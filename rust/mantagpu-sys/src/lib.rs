@@ -332,6 +332,15 @@ extern "C" {
         n: usize,
         out: *mut u32,
     ) -> c_int;
+    pub fn mg_pairing_op(
+        curve: mg_curve_t,
+        op: c_int,
+        a: *const u32,
+        b: *const u32,
+        coeffs: *const i16,
+        n: usize,
+        out: *mut u32,
+    ) -> c_int;
     pub fn mg_fpr_column_plan(
         field: c_int,
         kind: c_int,
