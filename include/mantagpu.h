@@ -245,6 +245,17 @@ int mg_msm_digits(mg_curve_t curve, const uint64_t *scalars, size_t batch, size_
                   uint32_t *vals, uint32_t *count, uint32_t layout[4]);
 int mg_sort_pairs(const uint32_t *keys, const uint32_t *vals, size_t n, int end_bit, const uint32_t *count, uint32_t lowmask,
                   uint32_t inv_from, uint32_t *keys_out, uint32_t *vals_out);
+/* The fused front end a stand-alone MSM takes where mg_msm_dense_front_applies: both stages as one, no unsorted pairs in memory.
+ * mg_msm_dense_front_applies: 1 if a launch of `batch` scalar vectors over a set of n_sets queries with `windows` windows and
+ *   the given table_mode (as above), compaction asked for (MG_SCALARS_SPARSE) or not, has the shape for it, else 0. A pure
+ *   function: no device is touched.
+ * mg_msm_dense_front: one vector of n_scalars scalars against n stored bases with a table per window -> the W * n pairs of ALL
+ *   digits SORTED by key in keys / vals (uploaded first, as above). A zero digit is the pair (key 0, layout[3]): layout =
+ *   {W, B, bucket keys, the index of the infinity record behind the last table = W * n}. The order inside a run of equal keys
+ *   is unspecified. MG_ERROR_INVALID_ARGUMENT for a shape mg_msm_dense_front_applies turns down and for what a launch refuses. */
+int mg_msm_dense_front_applies(size_t batch, size_t n_sets, int windows, int table_mode, int sparse);
+int mg_msm_dense_front(mg_curve_t curve, const uint64_t *scalars, size_t n_scalars, int scalar_flags, int window_bits, size_t n,
+                       const uint32_t *map, size_t set_len, uint32_t *keys, uint32_t *vals, uint32_t layout[4]);
 /* Radix-2 (inverse) NTT over a vector of 2^log_n GROUP elements, natural order in and out: ark-poly
  * `Radix2EvaluationDomain::{fft, ifft}` applied to points -- how `mpc::initialize` turns the powers of tau into the
  * Lagrange basis (manta-trusted-setup/src/groth16/mpc.rs:378-381). Host arrays of affine Montgomery points. */

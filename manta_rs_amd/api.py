@@ -61,7 +61,7 @@ EXPORTS = [
     "mg_init", "mg_strerror", "mg_last_error", "mg_device_count", "mg_malloc", "mg_free", "mg_memcpy_h2d",
     "mg_memcpy_d2h", "mg_device_synchronize", "mg_host_alloc", "mg_host_free", "mg_set_kernel_timing", "mg_last_accumulate_ms", "mg_bases_create", "mg_bases_destroy", "mg_bases_device_bytes",
     "mg_msm", "mg_msm_launch", "mg_msm_finish", "mg_points_sum", "mg_fixed_base_mul", "mg_ec_elementwise", "mg_point_serialize", "mg_ntt",
-    "mg_msm_digits", "mg_sort_pairs",
+    "mg_msm_digits", "mg_sort_pairs", "mg_msm_dense_front_applies", "mg_msm_dense_front",
     "mg_ntt_device", "mg_groth16_setup", "mg_ctx_create", "mg_ctx_create_from_bytes", "mg_ctx_set_r1cs", "mg_groth16_prove", "mg_groth16_prove_batch", "mg_witness_map", "mg_ctx_domain_size", "mg_ctx_table_bytes",
     "mg_ctx_destroy", "mg_bases_create_sharded", "mg_bases_num_shards", "mg_bases_shard", "mg_msm_launch_sharded",
     "mg_ctx_create_sharded", "mg_ctx_create_from_bytes_sharded", "mg_ctx_num_variables", "mg_ctx_num_inputs",
@@ -566,6 +566,28 @@ def msm_digits(curve, scalars, c, n, mont=False, table_mode=0, map=None, n_sets=
     assert layout[0] == W
     return dict(W=int(layout[0]), B=int(layout[1]), seg_keys=int(layout[2]), invalid=int(layout[3]), keys=k, vals=v,
                 count=int(count.value) if compact else None)
+
+
+def msm_dense_front_applies(batch, n_sets, windows, table_mode, sparse):
+    """Whether a launch of this shape takes the fused front end (`mg_msm_dense_front_applies`; no device involved)"""
+    return bool(LIB.mg_msm_dense_front_applies(_sz(batch), _sz(n_sets), int(windows), int(table_mode), int(bool(sparse))))
+
+
+def msm_dense_front(curve, scalars, c, n, mont=False, map=None, set_len=None, keys=None, vals=None):
+    """The fused front end alone (`mg_msm_dense_front`): scalars = [n_scalars, 4] uint64 against n stored bases with a table per
+    window -> dict(W, B, seg_keys, inf_index, keys, vals): the W * n pairs of all digits, sorted by key; a zero digit is
+    (0, inf_index). keys / vals: what the device arrays hold before the launch (default zeros)."""
+    sc = _u64(scalars)
+    assert sc.ndim == 2 and sc.shape[1] == 4, sc.shape
+    bits = 254 if curve == BN254 else 255
+    W = (bits + c - 1) // c if c > 0 else 0
+    k, v = _u32_buffer(keys, W * n, "keys"), _u32_buffer(vals, W * n, "vals")
+    mp = None if map is None else np.ascontiguousarray(map, dtype=np.uint32)
+    assert mp is None or mp.shape == (n,), mp.shape
+    layout = (ctypes.c_uint32 * 4)()
+    _chk(LIB.mg_msm_dense_front(curve, _p(sc), _sz(sc.shape[0]), int(bool(mont)), int(c), _sz(n), _p(mp), _sz(n if set_len is None else set_len),
+                                _p(k), _p(v), layout), "mg_msm_dense_front")
+    return dict(W=int(layout[0]), B=int(layout[1]), seg_keys=int(layout[2]), inf_index=int(layout[3]), keys=k, vals=v)
 
 
 def sort_pairs(keys, vals, end_bit, count=None, lowmask=0xFFFFFFFF, inv_from=0xFFFFFFFF, keys_out=None, vals_out=None):

@@ -460,6 +460,21 @@ MG_API int mg_msm_digits(mg_curve_t curve, const uint64_t *scalars, size_t batch
     return e->msm_digits(c);
     MG_CATCH
 }
+MG_API int mg_msm_dense_front_applies(size_t batch, size_t n_sets, int windows, int table_mode, int sparse) {
+    const size_t lim = (size_t)1 << 31;
+    return batch < lim && n_sets < lim && msm_dense_front_applies((u32)batch, (u32)n_sets, windows, table_mode, sparse != 0) ? 1 : 0;
+}
+MG_API int mg_msm_dense_front(mg_curve_t curve, const uint64_t *scalars, size_t n_scalars, int scalar_flags, int window_bits, size_t n,
+                              const uint32_t *map, size_t set_len, uint32_t *keys, uint32_t *vals, uint32_t layout[4]) {
+    MG_TRY
+    GroupEngine *e = get_engine((int)curve, 1); // (the front end depends on the scalar field alone)
+    const size_t lim = (size_t)1 << 31;
+    if (!e || n_scalars >= lim || n >= lim || set_len >= lim || (scalar_flags & ~MG_SCALARS_MONT)) return MG_ERROR_INVALID_ARGUMENT;
+    const MsmDigitsCall c{(const u32 *)scalars, 1u, (u32)n_scalars, (scalar_flags & MG_SCALARS_MONT) ? SCALARS_MONT : SCALARS_CANONICAL,
+                          window_bits, 1, (u32)n, map, 1u, (u32)set_len, false, keys, vals, nullptr, layout};
+    return e->msm_dense_front(c);
+    MG_CATCH
+}
 MG_API int mg_sort_pairs(const uint32_t *keys, const uint32_t *vals, size_t n, int end_bit, const uint32_t *count, uint32_t lowmask,
                          uint32_t inv_from, uint32_t *keys_out, uint32_t *vals_out) {
     MG_TRY

@@ -190,6 +190,9 @@ struct BaseSet {
     u32 *d_map = nullptr; // compacted sets: stored point i belongs to scalar d_map[i]; nullptr = identity
     u32 *d_pts = nullptr; // affine AoS; with precompute: W tables of n points, table w = 2^(c w) * P
     int pre_c = 0, pre_W = 0; // 0 = no precompute
+    // window tables (not full ones): one all-zero record = the point at infinity behind the last table, index pre_W * n -- the
+    // summand of a zero digit where the pair stream is not compacted (msm_dense_front_applies)
+    bool inf_record = false;
     bool full = false;        // with precompute: the B = 2^(c-1) multiples m 2^(c w) P of every window too, entry ((w n + i) B + m - 1)
     // Round 4: a set may be the CONCATENATION of n_sets queries of set_len entries each that are multiplied by the SAME scalar
     // vector (a_query | b_g1_query | l_query of a proving key): entry j belongs to query j / set_len and to scalar j % set_len,
@@ -276,7 +279,18 @@ inline hipStream_t msm_stream_of(const MsmWorkspace *ws) {
     return ws->run_on ? ws->run_on : (ws->use_solo && ws->solo ? ws->solo : ws->stream);
 }
 
-// mg_msm_digits (mantagpu.h): the digit kernel of msm_launch alone, host arrays in and out
+// Which front end an MSM launch takes, as far as its shape decides (msm_launch adds: a stand-alone launch, MANTA_DENSE_FRONT):
+// true = the fused one (msm_digits.h digits_hist / digits_scatter: no unsorted pair stream, no compaction, zero digits point at
+// the infinity record) -- one scalar vector over one query, window tables of at most 16 windows (a lane of the first radix pass
+// holds a scalar's digits as its items: sort_scatter.h SORT_ITEMS), and a caller that did not ask for compaction. false = the
+// digit kernel and the whole sort. table_mode: 0 plain bases, 1 window tables, 2 full tables.
+constexpr int MSM_DENSE_MAX_WINDOWS = 16;
+inline bool msm_dense_front_applies(u32 batch, u32 n_sets, int windows, int table_mode, bool sparse) {
+    return batch == 1 && n_sets == 1 && table_mode == 1 && windows >= 1 && windows <= MSM_DENSE_MAX_WINDOWS && !sparse;
+}
+
+// mg_msm_digits (mantagpu.h): the digit kernel of msm_launch alone, host arrays in and out; mg_msm_dense_front: the fused front
+// end alone (batch = n_sets = 1, table_mode = 1, not compact: keys / vals come back SORTED, layout[3] = the infinity index)
 struct MsmDigitsCall {
     const u32 *scalars; // [batch][n_scalars][8]
     u32 batch, n_scalars;
@@ -347,6 +361,8 @@ class GroupEngine {
     // The first stage of msm_launch on its own -- the plan, the key layout and the digit-kernel launch of a set of c.n stored bases,
     // no points involved -- as a parity-test surface (tests/test_gpu_msm_frontend.py)
     virtual int msm_digits(const MsmDigitsCall &c) = 0;
+    // the fused front end of a dense launch on its own, up to the sorted pairs (tests/test_gpu_msm_dense_front.py)
+    virtual int msm_dense_front(const MsmDigitsCall &c) = 0;
 
     // host-point helpers (type-erased)
     virtual void hp_set_inf(HostPoint *p) const = 0;
@@ -424,11 +440,22 @@ GroupEngine *make_engine_bls381_g2();
 GroupEngine *get_engine(int curve, int group); // cached singleton per (curve, group)
 
 // radix sort of (key,val) pairs, keys < 2^end_bit (sort.hip: hand-written wave64 LSD radix sort)
-size_t sort_pairs_temp_bytes(size_t n);
+// A sort whose first 8-bit pass is the caller's own over tiles of its own (the MSM's fused digits_hist / digits_scatter, 256
+// scalars a tile: msm_digits.h): `tiles1` such tiles size the histogram, sort_scratch names the parts of the scratch block, the
+// caller's histogram kernel fills hist[digit][tile], sort_scan_hist scans it, the caller's scatter writes pass 0's output -- the
+// scratch pair when the passes are even in number, else (keys_out, vals_out) -- and sort_pairs(first_pass = 1) runs the rest.
+struct SortScratch {
+    u32 *keys, *vals, *hist, *totals;
+};
+size_t sort_pairs_temp_bytes(size_t n, size_t tiles1 = 0);
+SortScratch sort_scratch(void *tmp, size_t n, size_t tiles1 = 0);
+void sort_scan_hist(const SortScratch &t, u32 ntiles, hipStream_t s);
 // d_count (optional): the number of pairs actually present, on the device (n is then the capacity)
 bool sort_pairs_takes_device_count(int end_bit);
+// (lowmask, inv_from): sort by key & lowmask, keys >= inv_from last -- sort.hip sort_key; first_pass: the first pass that is run
+// (keys_in, vals_in: its input)
 int sort_pairs(const u32 *keys_in, u32 *keys_out, const u32 *vals_in, u32 *vals_out, size_t n, int end_bit,
                void *tmp, size_t tmp_bytes, hipStream_t s, const u32 *d_count = nullptr, u32 lowmask = 0xffffffffu,
-               u32 inv_from = 0xffffffffu); // (lowmask, inv_from): sort by key & lowmask, keys >= inv_from last -- sort.hip sort_key
+               u32 inv_from = 0xffffffffu, int first_pass = 0, size_t tiles1 = 0);
 
 } // namespace mg

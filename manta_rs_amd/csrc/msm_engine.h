@@ -81,6 +81,9 @@ struct MsmKnobs {
     // workgroup of the compacting digit kernel, 256 / 512 / 1024 -- measured: 256 beats 512 and 1024 on the same box
     u32 digits_threads = [](int v) { return (u32)(v == 256 || v == 512 || v == 1024 ? v : 256); }(ab_knob("MANTA_DIGITS_THREADS", 0));
     bool z3_sort = ab_knob("MANTA_Z3_SORT", 0) != 0;
+    // the fused front end wherever msm_dense_front_applies and the launch is stand-alone; 0: the compacting digit kernel and the
+    // whole sort for those launches too (profiles/dense_front_ab.txt)
+    bool dense_front = ab_knob_in("MANTA_DENSE_FRONT", 0, 1, 1) != 0;
 };
 static const MsmKnobs &msm_knobs() {
     static const MsmKnobs k; // (first use: the first MSM of the process)
@@ -154,8 +157,14 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         }
         const u32 FB = full ? 1u << (pre_c - 1) : 1u; // table entries per (window, base)
         if (full && (pre_c < 2 || pre_c > 12 || (size_t)W * n * FB >= ((size_t)1 << 31))) return MG_ERR_ARG;
-        bs->bytes = (size_t)W * n * FB * AWS * 4;
+        bs->inf_record = pre_c > 0 && !full;
+        if (bs->inf_record && (size_t)W * n + 1 >= ((size_t)1 << 31)) return MG_ERR_ARG; // (key_layout refuses the launch too)
+        bs->bytes = ((size_t)W * n * FB + (bs->inf_record ? 1u : 0u)) * AWS * 4;
         hipError_t e = hipMalloc((void **)&bs->d_pts, bs->bytes);
+        if (e == hipSuccess && bs->inf_record) {
+            const std::vector<u32> zero(AWS, 0u);
+            e = memcpy_sync(bs->d_pts + (size_t)W * n * AWS, zero.data(), (size_t)AWS * 4, hipMemcpyHostToDevice);
+        }
         u32 *&win_pts = guard.win_pts; // full: the window tables are an intermediate
         if (e == hipSuccess && full) e = hipMalloc((void **)&win_pts, (size_t)W * n * AWS * 4);
         if (e != hipSuccess) return hip_failure(e, "hipMalloc(bases)", MG_ERR_OOM);
@@ -556,6 +565,49 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         return rc;
     }
 
+    // The fused front end alone, likewise for a base set that exists as a description only: what launch_reserve and launch_sort do
+    // for a dense launch, up to the sorted pairs (n W of them; a zero digit is the pair (0, layout[3] = the infinity index)). The
+    // output arrays start as the caller's. MG_ERR_ARG for a shape msm_dense_front_applies turns down.
+    int msm_dense_front(const MsmDigitsCall &c) override {
+        if (!c.scalars || !c.keys || !c.vals || !c.layout || c.n == 0 || c.n_scalars == 0 || c.c < 1 || c.c > 24 || c.set_len == 0 ||
+            (c.scalar_mode != SCALARS_CANONICAL && c.scalar_mode != SCALARS_MONT) ||
+            !msm_dense_front_applies(c.batch, c.n_sets, windows_of(c.c), c.table_mode, c.compact))
+            return MG_ERR_ARG;
+        BaseSet bs;
+        bs.curve = CURVE_ID, bs.group = GROUP, bs.device = current_device();
+        bs.n = c.n, bs.n_orig = c.set_len, bs.set_len = c.set_len;
+        bs.pre_c = c.c, bs.pre_W = windows_of(c.c), bs.inf_record = true;
+        if (bs.n > bs.n_orig || (!c.map && bs.n != bs.n_orig) || c.n_scalars > bs.n_orig) return MG_ERR_ARG;
+        for (size_t i = 0; c.map && i < c.n; ++i)
+            if (c.map[i] >= bs.n_orig) return MG_ERR_ARG;
+        Launch r{&bs, nullptr, nullptr, nullptr, nullptr, c.n, c.n_scalars, 0, c.scalar_mode, 1, 1, false, false, plan_for(&bs, c.n, c.c, 1)};
+        if (const int rc = key_layout(r)) return rc;
+        r.end_bit = 1;
+        while (r.nb > 1 && (1u << r.end_bit) <= r.nb - 1) ++r.end_bit; // (launch_reserve: the bits of the last bucket key)
+        c.layout[0] = (u32)r.pl.W, c.layout[1] = r.pl.B, c.layout[2] = r.seg_keys, c.layout[3] = (u32)((size_t)r.pl.W * c.n);
+        hipStream_t s = r.s = setup_stream();
+        if (!s) return MG_ERR_OOM;
+        const size_t sb = (size_t)c.n_scalars * 32, pb = r.M * 4;
+        DevBlock m; // scalars | map | sorted keys | sorted vals | the sort's scratch
+        if (const int rc = m.alloc({sb, c.map ? (size_t)c.n * 4 : 0, pb, pb, sort_pairs_temp_bytes(r.M, cdiv(c.n, 256))}, "mg_msm_dense_front"))
+            return rc;
+        r.d_scalars = m.dev<u32>(0), bs.d_map = c.map ? m.dev<u32>(1) : nullptr;
+        hipError_t e = hipMemcpyAsync(m.dev(0), c.scalars, sb, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && c.map) e = hipMemcpyAsync(bs.d_map, c.map, (size_t)c.n * 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(m.dev(2), c.keys, pb, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(m.dev(3), c.vals, pb, hipMemcpyHostToDevice, s);
+        int rc = MG_OK;
+        if (e == hipSuccess) {
+            rc = enqueue_dense_front(r, m.dev(4), m.dev<u32>(2), m.dev<u32>(3));
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && !rc) e = hipMemcpyAsync(c.keys, m.dev(2), pb, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && !rc) e = hipMemcpyAsync(c.vals, m.dev(3), pb, hipMemcpyDeviceToHost, s);
+        const int synced = sync_status(s, e, "mg_msm_dense_front");
+        bs.d_map = nullptr; // the block's
+        return rc ? rc : synced;
+    }
+
     // ---------------------------------------------------------------- QAP column sums (qap_columns.h)
     void scalar_one_mont(u64 out[4]) const override {
         const host::HFp<FrC> one = host::HFp<FrC>::one();
@@ -647,6 +699,7 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         int end_bit;
         u32 KB, seg_keys, nb, invalid, T, sort_mask = 0xffffffffu, sort_inv = 0xffffffffu; // sort_pairs: the full key unless masked
         bool direct, per_query, acc_single;
+        bool dense; // the fused front end (msm_dense_front_applies): n W pairs, zero digits included, no device count
         u32 *d_count;
         const u32 *skeys, *svals; // the sorted pairs
         u32 parts;                // partials the accumulate kernel leaves for the merge levels
@@ -665,7 +718,8 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         r.KB = pl.full ? 1u : pl.B; // bucket keys per bucket window
         if (r.M >= (1ull << 31) || (size_t)r.batch * r.nsets * pl.Wb * r.KB >= (1ull << 24)) return MG_ERR_ARG;
         // with precomputed tables the base index is w*stride + i: table w starts bs->n points after w-1
-        if ((size_t)pl.W * r.bs->n * (pl.full ? pl.B : 1u) >= (1ull << 31)) return MG_ERR_ARG;
+        // (window tables: + the infinity record behind the last one)
+        if ((size_t)pl.W * r.bs->n * (pl.full ? pl.B : 1u) + (pl.precomp && !pl.full ? 1u : 0u) >= (1ull << 31)) return MG_ERR_ARG;
         r.seg_keys = (u32)pl.Wb * r.KB;            // bucket keys per (scalar vector, query)
         r.nb = r.batch * r.nsets * r.seg_keys;     // real buckets; key nb = INVALID
         r.invalid = r.nb;
@@ -678,12 +732,23 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         int rc;
         if ((rc = key_layout(r))) return rc;
         const size_t M = r.M;
+        // A dense single MSM on window tables, stand-alone (not a proof slot's, not on a caller's stream, not being captured): the
+        // fused front end. Every digit is a pair -- a zero digit points at the infinity record -- so there is no `invalid` key, no
+        // pair count on the device and no unsorted stream to reserve.
+        hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+        const bool stand_alone = !ws->capturing && !ws->run_on && !ws->in_graph_slot &&
+                                 hipStreamIsCapturing(r.s, &cst) == hipSuccess && cst == hipStreamCaptureStatusNone;
+        // (the witness map's work form -- the h MSM of a proof pass, never stand-alone -- is not compiled into the fused kernels)
+        r.dense = msm_knobs().dense_front && stand_alone && r.bs->inf_record && r.scalar_mode != SCALARS_WORK &&
+                  msm_dense_front_applies(r.batch, r.nsets, pl.W, pl.full ? 2 : (pl.precomp ? 1 : 0), r.sparse);
         if (pl.full) r.sparse = true; // compacting digit kernel: no invalid keys, so a single MSM needs no sort at all
         const u32 seg_keys = r.seg_keys, nb = r.nb, invalid = r.invalid;
-        if ((rc = ws->keys_in.reserve(M * 4)) || (rc = ws->keys_out.reserve(M * 4)) ||
-            (rc = ws->vals_in.reserve(M * 4)) || (rc = ws->vals_out.reserve(M * 4)))
+        if ((rc = ws->keys_out.reserve(M * 4)) || (rc = ws->vals_out.reserve(M * 4)) ||
+            (!r.dense && ((rc = ws->keys_in.reserve(M * 4)) || (rc = ws->vals_in.reserve(M * 4)))))
             return rc;
-        if ((rc = ws->sort_tmp.reserve(sort_pairs_temp_bytes(M))) || (rc = ws->buckets.reserve((size_t)(nb + 1) * XW * 4))) return rc;
+        if ((rc = ws->sort_tmp.reserve(sort_pairs_temp_bytes(M, r.dense ? cdiv(r.n, 256) : 0))) ||
+            (rc = ws->buckets.reserve((size_t)(nb + 1) * XW * 4)))
+            return rc;
         const u32 T = r.T = cdiv(M, pl.L);
         if ((rc = ws->pkeys[0].reserve((size_t)2 * T * 4)) || (rc = ws->ppts[0].reserve((size_t)2 * T * XW * 4)))
             return rc;
@@ -699,8 +764,8 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         // over the digits is a fifth of a radix pass
         int end_bit_real = 1;
         while (nb > 1 && (1u << end_bit_real) <= nb - 1) ++end_bit_real;
-        if ((end_bit + 7) / 8 > (end_bit_real + 7) / 8) r.sparse = true;
-        if (r.sparse) end_bit = end_bit_real; // no pair carries the invalid key there
+        if ((end_bit + 7) / 8 > (end_bit_real + 7) / 8 && !r.dense) r.sparse = true;
+        if (r.sparse || r.dense) end_bit = end_bit_real; // no pair carries the invalid key there
         // Several scalar vectors in the fixed layout (the dense h MSM of a batched pass): the digit kernel writes vector q's pairs
         // behind vector q - 1's, and key = q * seg_keys + bucket with seg_keys a power of two -- a stable sort by the BUCKET bits
         // (+ one value for the invalid key) keeps every (q, bucket) run contiguous and needs bits(seg_keys) + 1 bits instead of
@@ -743,7 +808,7 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         zr.p[2] = ws->timed ? (u32 *)ws->h_clk : nullptr, zr.n[2] = ws->timed ? 4u : 0u;
         const u32 most = zr.n[1] > 4u ? zr.n[1] : 4u;
         hipLaunchKernelGGL((zero_ranges<F>), dim3(most > 256u * 1024u ? 1024u : cdiv(most, 256)), dim3(256), 0, s, zr);
-        enqueue_digits(r, ws->keys_in.as<u32>(), ws->vals_in.as<u32>());
+        if (!r.dense) enqueue_digits(r, ws->keys_in.as<u32>(), ws->vals_in.as<u32>()); // (dense: launch_sort makes the pairs)
         r.batch *= r.nsets; // from here on every (vector, query) pair is a vector of its own: its keys, its window sums, its result
     }
     // the digit kernel of a launch, writing its pairs to (keys, vals); sets r.per_query
@@ -774,8 +839,29 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
                                r.scalar_stride_words, r.seg_keys, r.d_count, nsets, (u32)bs->set_len);
     }
 
+    // The fused front end of a dense launch: the scalars -> the pairs sorted by key in (keys_out, vals_out). Pass 0 of the sort
+    // runs over tiles of 256 scalars whose pairs both kernels compute (msm_digits.h); the later passes are the sort's own.
+    static int enqueue_dense_front(const Launch &r, void *sort_tmp, u32 *keys_out, u32 *vals_out) {
+        const MsmPlan &pl = r.pl; const BaseSet *const bs = r.bs; hipStream_t s = r.s;
+        const u32 tiles1 = cdiv(r.n, 256);
+        const SortScratch t = sort_scratch(sort_tmp, r.M, tiles1);
+        const DenseFront a{r.d_scalars, bs->d_map, (u32)r.n, (u32)r.n_scalars, pl.c, pl.W, r.scalar_mode,
+                           pl.B, (u32)bs->n, (u32)((size_t)pl.W * bs->n)};
+        const bool to_out = ((r.end_bit + 7) / 8 - 1) % 2 == 0; // where sort_pairs would have its pass 0 write
+        hipLaunchKernelGGL((digits_hist<FrC>), dim3(tiles1), dim3(256), 0, s, a, tiles1, t.hist);
+        sort_scan_hist(t, tiles1, s);
+        u32 *const k0 = to_out ? keys_out : t.keys, *const v0 = to_out ? vals_out : t.vals;
+        hipLaunchKernelGGL((digits_scatter<FrC>), dim3(tiles1), dim3(256), 0, s, a, tiles1, (const u32 *)t.hist, (const u32 *)t.totals, k0, v0);
+        return sort_pairs(k0, keys_out, v0, vals_out, r.M, r.end_bit, sort_tmp, sort_pairs_temp_bytes(r.M, tiles1), s, nullptr,
+                          0xffffffffu, 0xffffffffu, 1, tiles1);
+    }
+
     int launch_sort(Launch &r) {
         MsmWorkspace *const ws = r.ws;
+        if (r.dense) {
+            r.skeys = ws->keys_out.as<u32>(), r.svals = ws->vals_out.as<u32>();
+            return enqueue_dense_front(r, ws->sort_tmp.p, ws->keys_out.as<u32>(), ws->vals_out.as<u32>());
+        }
         // one key in all (a single MSM on full tables, pairs compacted): any order is sorted; one digit launch per query: sorted
         const bool no_sort = (r.nb == 1 || r.per_query) && r.d_count;
         r.skeys = no_sort ? ws->keys_in.as<u32>() : ws->keys_out.as<u32>();
@@ -793,7 +879,7 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         // rounds of 6 dependent additions where one round of 9 does, and 1.4 wavefronts per SIMD for a batched pass where two
         // balanced ones do. Launch one round of lanes and let the kernel derive the chunk length from the pair count.
         u32 Tl = r.T, adapt = 0;
-        u32 Lk = pl.L; // the chunk length the kernel starts from
+        u32 Lk = pl.L; // the chunk length the kernel starts from (all of it where the pair count is the host's: no count, no adapt)
         // single-key MSMs sum inside the workgroup: one partial per workgroup (MANTA_ACC_SINGLE=0: the general kernel, A/B)
         const bool acc_single_on = ((msm_knobs().acc_single >> (GROUP - 1)) & 1) != 0;
         const int dev_now = current_device();

@@ -23,7 +23,8 @@
 //
 // Layout (round 6: the 2 400-line header split along its seams):
 //   msm_common.h      includes, register-cap attributes shared by the kernels
-//   msm_digits.h      K5   digits_kernel
+//   msm_digits.h      K5   digits_kernel; digits_hist / digits_scatter, K5 fused into the first radix pass of K6 (dense single MSMs)
+//   sort_scatter.h    K6   the tile body of a radix scatter over loaded or computed pairs, shared with sort.hip
 //   msm_accumulate.h  K7a  accumulate_chunks / accumulate_single
 //   msm_reduce.h      K7b-K9 merge_partials*, tile_reduce*, serial_reduce*, reduce_level1* (each plain / _coop pair: one body, two
 //                     instantiations), fold_windows

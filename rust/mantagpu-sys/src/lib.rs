@@ -379,6 +379,20 @@ extern "C" {
         keys_out: *mut u32,
         vals_out: *mut u32,
     ) -> c_int;
+    pub fn mg_msm_dense_front_applies(batch: usize, n_sets: usize, windows: c_int, table_mode: c_int, sparse: c_int) -> c_int;
+    pub fn mg_msm_dense_front(
+        curve: mg_curve_t,
+        scalars: *const u64,
+        n_scalars: usize,
+        scalar_flags: c_int,
+        window_bits: c_int,
+        n: usize,
+        map: *const u32,
+        set_len: usize,
+        keys: *mut u32,
+        vals: *mut u32,
+        layout: *mut u32,
+    ) -> c_int;
     pub fn mg_group_ntt(
         curve: mg_curve_t,
         group: c_int,
