@@ -481,23 +481,19 @@ MG_API int mg_sort_pairs(const uint32_t *keys, const uint32_t *vals, size_t n, i
     if (!keys || !vals || !keys_out || !vals_out || end_bit < 1 || end_bit > 32 || n >= ((size_t)1 << 32) || (count && *count > n))
         return MG_ERROR_INVALID_ARGUMENT;
     if (n == 0) return MG_SUCCESS;
-    hipStream_t s = setup_stream();
-    if (!s) return MG_ERROR_OUT_OF_MEMORY;
     const size_t pb = n * 4, tb = sort_pairs_temp_bytes(n);
-    DevBlock m; // keys | values | sorted keys | sorted values | the sort's scratch | element count
-    if (const int rc = m.alloc({pb, pb, pb, pb, tb, count ? 4u : 0u}, "mg_sort_pairs")) return rc;
-    const void *const src[5] = {keys, vals, keys_out, vals_out, count};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 5 && e == hipSuccess; ++i)
-        if (src[i]) e = hipMemcpyAsync(m.dev(i < 4 ? i : 5), src[i], i < 4 ? pb : 4, hipMemcpyHostToDevice, s);
-    int rc = MG_OK;
-    if (e == hipSuccess)
-        rc = sort_pairs(m.dev<u32>(0), m.dev<u32>(2), m.dev<u32>(1), m.dev<u32>(3), n, end_bit, m.dev(4), tb, s, m.dev<u32>(5), lowmask, inv_from);
-    if (e == hipSuccess && !rc) e = hipMemcpyAsync(keys_out, m.dev(2), pb, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && !rc) e = hipMemcpyAsync(vals_out, m.dev(3), pb, hipMemcpyDeviceToHost, s);
-    const hipError_t e2 = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = e2;
-    return rc ? rc : e == hipSuccess ? MG_SUCCESS : hip_status(e, "mg_sort_pairs");
+    DevCall m; // keys | values | sorted keys | sorted values | the sort's scratch | element count
+    if (const int rc = m.begin({pb, pb, pb, pb, tb, count ? 4u : 0u}, "mg_sort_pairs")) return rc;
+    const void *const src[4] = {keys, vals, keys_out, vals_out};
+    for (int i = 0; i < 4; ++i) m.up(i, src[i], pb);
+    m.up(5, count, 4);
+    m.run([&] {
+        return sort_pairs(m.dev<u32>(0), m.dev<u32>(2), m.dev<u32>(1), m.dev<u32>(3), n, end_bit, m.dev(4), tb, m.stream(), m.dev<u32>(5), lowmask,
+                          inv_from);
+    });
+    m.down(keys_out, 2, pb);
+    m.down(vals_out, 3, pb);
+    return m.finish();
     MG_CATCH
 }
 
@@ -516,15 +512,15 @@ MG_API int mg_ntt_device(mg_curve_t curve, uint64_t *d_data, unsigned log_n, int
 MG_API int mg_ntt(mg_curve_t curve, uint64_t *data, unsigned log_n, int inverse, int coset) {
     MG_TRY
     if (!data || log_n > 32) return MG_ERROR_INVALID_ARGUMENT;
+    NttEngine *ntt = get_ntt_engine((int)curve);
+    if (!ntt) return MG_ERROR_INVALID_ARGUMENT;
     const size_t bytes = ((size_t)1 << log_n) * 32;
-    DevBlock m;
-    int rc = m.alloc({bytes}, "mg_ntt");
-    if (rc) return rc;
-    void *d = m.dev(0);
-    if (memcpy_sync(d, data, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = MG_ERROR_HIP;
-    if (!rc) rc = mg_ntt_device(curve, (uint64_t *)d, log_n, inverse, coset);
-    if (!rc && memcpy_sync(data, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = MG_ERROR_HIP;
-    return rc;
+    DevCall m;
+    if (const int rc = m.begin({bytes}, "mg_ntt")) return rc;
+    m.up(0, data, bytes);
+    m.run([&] { return ntt->transform(m.dev<u32>(0), log_n, inverse != 0, coset != 0, m.stream()); });
+    m.down(data, 0, bytes);
+    return m.finish();
     MG_CATCH
 }
 

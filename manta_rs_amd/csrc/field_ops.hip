@@ -93,17 +93,14 @@ __global__ __launch_bounds__(256) void field_op_kernel(int op, int repr, int laz
 
 template <class C> static int run(int op, int repr, int lazy_a, int lazy_b, const u32 *a, const u32 *b, size_t n, u32 *out) {
     const size_t bytes = n * Fp<C>::N * 4;
-    DevBlock m; // a | out | b (binary operations only)
-    if (const int rc = m.alloc({bytes, bytes, b ? bytes : 0}, "mg_field_op")) return rc;
-    u32 *da = m.dev<u32>(0), *dout = m.dev<u32>(1), *db = m.dev<u32>(2);
-    hipError_t e = memcpy_sync(da, a, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && b) e = memcpy_sync(db, b, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((field_op_kernel<C>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, setup_stream(), op, repr, lazy_a, lazy_b, da, db,
-                           dout, n);
-        e = memcpy_sync(out, dout, bytes, hipMemcpyDeviceToHost);
-    }
-    return e == hipSuccess ? MG_OK : hip_status(e, "mg_field_op");
+    DevCall m; // a | out | b (binary operations only)
+    if (const int rc = m.begin({bytes, bytes, b ? bytes : 0}, "mg_field_op")) return rc;
+    m.up(0, a, bytes);
+    m.up(2, b, bytes);
+    m.launch(field_op_kernel<C>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, op, repr, lazy_a, lazy_b, m.dev<u32>(0), m.dev<u32>(2),
+             m.dev<u32>(1), n);
+    m.down(out, 1, bytes);
+    return m.finish();
 }
 
 int field_op(int field, int op, int repr, int lazy_a, int lazy_b, const u32 *a, const u32 *b, size_t n, u32 *out) {
@@ -144,18 +141,13 @@ __global__ __launch_bounds__(256) void fpr_raw_op_kernel(int op, int coding, con
 
 template <class C> static int run_raw(int op, int coding, const u32 *const (&in)[4], size_t n, u32 *out) {
     const size_t bytes = n * FpR<C>::K * 4;
-    DevBlock m; // out | a | b | c | d (absent operands take no room)
-    if (const int rc = m.alloc({bytes, bytes, in[1] ? bytes : 0, in[2] ? bytes : 0, in[3] ? bytes : 0}, "mg_fpr_raw_op")) return rc;
-    u32 *dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 4 && e == hipSuccess; ++k)
-        if (in[k]) e = memcpy_sync(dev[k] = m.dev<u32>(k + 1), in[k], bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((fpr_raw_op_kernel<C>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, setup_stream(), op, coding, dev[0], dev[1],
-                           dev[2], dev[3], m.dev<u32>(0), n);
-        e = memcpy_sync(out, m.dev<u32>(0), bytes, hipMemcpyDeviceToHost);
-    }
-    return e == hipSuccess ? MG_OK : hip_status(e, "mg_fpr_raw_op");
+    DevCall m; // out | a | b | c | d (absent operands take no room, and the kernel gets nullptr for them)
+    if (const int rc = m.begin({bytes, bytes, in[1] ? bytes : 0, in[2] ? bytes : 0, in[3] ? bytes : 0}, "mg_fpr_raw_op")) return rc;
+    for (int k = 0; k < 4; ++k) m.up(k + 1, in[k], bytes);
+    m.launch(fpr_raw_op_kernel<C>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, op, coding, m.dev<u32>(1), m.dev<u32>(2), m.dev<u32>(3),
+             m.dev<u32>(4), m.dev<u32>(0), n);
+    m.down(out, 0, bytes);
+    return m.finish();
 }
 
 int fpr_raw_op(int field, int op, int coding, const u32 *a, const u32 *b, const u32 *c, const u32 *d, size_t n, u32 *out) {
@@ -228,9 +220,6 @@ int clock_probe(u32 iters, double *memtime_mhz, double *mad_issue_per_us_per_sim
     MG_HIP(hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, dev));
     const u32 blocks = (u32)cus * 2; // 256 threads = 4 wavefronts per block, two blocks per CU: two wavefronts per SIMD
     const size_t waves = (size_t)blocks * 4;
-    DevBlock m;
-    if (const int rc = m.alloc({waves * 3 * sizeof(unsigned long long)}, "clock probe")) return rc;
-    unsigned long long *d = m.dev<unsigned long long>(0);
     struct Events { // destroyed on every path
         hipEvent_t e0 = nullptr, e1 = nullptr;
         ~Events() {
@@ -240,13 +229,16 @@ int clock_probe(u32 iters, double *memtime_mhz, double *mad_issue_per_us_per_sim
     } ev;
     MG_HIP(hipEventCreate(&ev.e0));
     MG_HIP(hipEventCreate(&ev.e1));
-    hipLaunchKernelGGL(clock_probe_kernel, dim3(blocks), dim3(256), 0, setup_stream(), 64u, 1u, d); // warm-up
-    MG_HIP(hipEventRecord(ev.e0, setup_stream()));
-    hipLaunchKernelGGL(clock_probe_kernel, dim3(blocks), dim3(256), 0, setup_stream(), iters, 2u, d);
-    MG_HIP(hipEventRecord(ev.e1, setup_stream()));
-    MG_HIP(hipEventSynchronize(ev.e1));
     std::vector<unsigned long long> h(waves * 3);
-    MG_HIP(memcpy_sync(h.data(), d, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    DevCall m;
+    if (const int rc = m.begin({h.size() * sizeof(unsigned long long)}, "clock probe")) return rc;
+    unsigned long long *d = m.dev<unsigned long long>(0);
+    m.launch(clock_probe_kernel, dim3(blocks), dim3(256), 0, 64u, 1u, d); // warm-up
+    m.run([&] { return hipEventRecord(ev.e0, m.stream()); });
+    m.launch(clock_probe_kernel, dim3(blocks), dim3(256), 0, iters, 2u, d);
+    m.run([&] { return hipEventRecord(ev.e1, m.stream()); });
+    m.down(h.data(), 0, h.size() * sizeof(unsigned long long));
+    if (const int rc = m.finish()) return rc;
     float t = 0.f;
     hipEventElapsedTime(&t, ev.e0, ev.e1);
     double ratio = 0;

@@ -268,12 +268,13 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupOpsT : public GroupEn
     // ---------------------------------------------------------------- fixed-base batch mul
     int fixed_base_mul(const u32 *base_affine_host, const u32 *d_scalars, size_t n, u32 *d_out_affine,
                        hipStream_t s) override {
-        if (!s) s = setup_stream(); // (never the NULL stream: engine.h)
-        DevBlock m, table; // base | XYZZ results; the 32 x 255 multiples of the base as XYZZ | affine
-        if (const int rc = m.alloc({AW_IO * 4, n * XW_IO * 4}, "hipMalloc(fixed_base_mul)")) return rc;
+        DevBlock table; // the 32 x 255 multiples of the base as XYZZ | affine
+        DevCall m;      // base | XYZZ results; on the caller's stream, or the setup stream (never the NULL stream: engine.h)
+        if (const int rc = m.begin({AW_IO * 4, n * XW_IO * 4}, "fixed_base_mul", false, s)) return rc;
+        s = m.stream();
         u32 *d_base = m.dev<u32>(0), *tmp = m.dev<u32>(1);
-        hipError_t e = hipMemcpyAsync(d_base, base_affine_host, AW_IO * 4, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) {
+        m.up(0, base_affine_host, AW_IO * 4);
+        m.run([&] {
             constexpr size_t TN = 32 * 255;
             // many multiples of one base: 32 table additions each instead of ~380 group operations -- when the table's memory can be had
             if (n >= fixed_base_table_min() && table.try_alloc({TN * XW_IO * 4, TN * AW_IO * 4})) {
@@ -285,9 +286,8 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupOpsT : public GroupEn
                 hipLaunchKernelGGL((fixed_base_mul_kernel<FIO>), dim3(cdiv(n, 256)), dim3(256), 0, s, d_base, d_scalars, n, tmp);
             }
             xyzz_to_affine_launch<FIO>(s, tmp, n, d_out_affine, AW_IO);
-            e = hipGetLastError();
-        }
-        return sync_status(s, e, "fixed_base_mul"); // (before the blocks go, whatever failed)
+        });
+        return m.finish();
     }
 
     // ---------------------------------------------------------------- element-wise operations
@@ -299,20 +299,17 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupOpsT : public GroupEn
         // set, say -- would wait for this kernel, a millisecond of one-lane latency for 128-bit multipliers)
         hipStream_t st = stream_pool_get_normal(); // (pooled: the library destroys no stream, streams.cpp)
         if (!st) return hip_status(hipErrorOutOfMemory, "ec_elementwise");
-        DevBlock m; // a | b | XYZZ results | affine results
-        int rc = m.alloc({ab, bb, n * XW_IO * 4, ab}, "ec_elementwise");
+        DevCall m; // a | b | XYZZ results | affine results
+        int rc = m.begin({ab, bb, n * XW_IO * 4, ab}, "ec_elementwise", false, st);
         if (!rc) {
-            u32 *da = m.dev<u32>(0), *db = m.dev<u32>(1), *tmp = m.dev<u32>(2), *dout = m.dev<u32>(3);
-            hipError_t e = hipMemcpyAsync(da, a_host, ab, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess && op != EC_DOUBLE) e = hipMemcpyAsync(db, b_host, bb, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL((ec_elementwise_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, (EcOp)op, da, db, n, tmp);
-                xyzz_to_affine_launch<FIO>(st, tmp, n, dout, AW_IO);
-                e = hipMemcpyAsync(out_affine_host, dout, ab, hipMemcpyDeviceToHost, st);
-            }
-            rc = sync_status(st, e, "ec_elementwise");
+            m.up(0, a_host, ab);
+            if (op != EC_DOUBLE) m.up(1, b_host, bb);
+            m.launch(ec_elementwise_kernel<F>, dim3(cdiv(n, 256)), dim3(256), 0, (EcOp)op, m.dev<u32>(0), m.dev<u32>(1), n, m.dev<u32>(2));
+            m.run([&] { xyzz_to_affine_launch<FIO>(st, m.dev<u32>(2), n, m.dev<u32>(3), AW_IO); });
+            m.down(out_affine_host, 3, ab);
+            rc = m.finish();
         }
-        stream_pool_put_normal(st);
+        stream_pool_put_normal(st); // (finished: nothing of the call is in flight on it)
         return rc;
     }
 
@@ -351,41 +348,38 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupOpsT : public GroupEn
                   u32 *out_affine_host) override {
         if (!in_affine_host || !out_affine_host || lg > 26 || (lg > 0 && !d_twiddles_mont)) return MG_ERR_ARG;
         const size_t n = (size_t)1 << lg, ab = n * AW_IO * 4;
-        DevBlock m; // affine in | affine out
-        if (const int rc = m.alloc({ab, ab}, "group_ntt")) return rc;
-        hipError_t e = memcpy_sync(m.dev(0), in_affine_host, ab, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_status(e, "group_ntt");
-        if (const int rc = group_ntt_device(m.dev<u32>(0), lg, d_twiddles_mont, n_inv_canonical, m.dev<u32>(1))) return rc;
-        e = memcpy_sync(out_affine_host, m.dev(1), ab, hipMemcpyDeviceToHost);
-        return e == hipSuccess ? MG_OK : hip_status(e, "group_ntt");
+        DevCall m; // affine in | affine out
+        if (const int rc = m.begin({ab, ab}, "group_ntt")) return rc;
+        m.up(0, in_affine_host, ab);
+        m.run([&] { return group_ntt_device(m.dev<u32>(0), lg, d_twiddles_mont, n_inv_canonical, m.dev<u32>(1)); });
+        m.down(out_affine_host, 1, ab);
+        return m.finish();
     }
     // the transform itself, device array to device array (`mpc::initialize`: the Lagrange bases never leave HBM)
     int group_ntt_device(const u32 *d_in, unsigned lg, const u32 *d_twiddles_mont, const u32 *n_inv_canonical, u32 *d_out) override {
         if (!d_in || !d_out || lg > 26 || (lg > 0 && !d_twiddles_mont)) return MG_ERR_ARG;
-        hipStream_t st = setup_stream();
-        if (!st) return MG_ERR_OOM;
         const size_t n = (size_t)1 << lg;
-        DevBlock m; // working XYZZ | arkworks-format XYZZ | n^-1 (inverse transform only)
-        if (const int rc = m.alloc({n * XW * 4, n * XW_IO * 4, n_inv_canonical ? 32u : 0u}, "group_ntt")) return rc;
+        DevCall m; // working XYZZ | arkworks-format XYZZ | n^-1 (inverse transform only)
+        if (const int rc = m.begin({n * XW * 4, n * XW_IO * 4, n_inv_canonical ? 32u : 0u}, "group_ntt")) return rc;
+        hipStream_t st = m.stream();
         u32 *d_pts = m.dev<u32>(0), *d_std = m.dev<u32>(1), *d_sc = m.dev<u32>(2);
-        const hipError_t e = n_inv_canonical ? memcpy_sync(d_sc, n_inv_canonical, 32, hipMemcpyHostToDevice) : hipSuccess;
-        if (e != hipSuccess) return hip_status(e, "group_ntt");
-        hipLaunchKernelGGL((group_ntt_load_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, d_in, lg, d_pts);
-        for (unsigned s = 1; s <= lg; ++s)
-            hipLaunchKernelGGL((group_ntt_stage_kernel<F, FrC>), dim3(cdiv(n / 2, 256)), dim3(256), 0, st, d_pts, d_twiddles_mont, lg, s);
-        hipLaunchKernelGGL((group_scale_store_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, d_pts, (const u32 *)d_sc, n, d_std);
-        xyzz_to_affine_launch<FIO>(st, d_std, n, d_out, AW_IO);
-        return sync_status(st, hipGetLastError(), "group_ntt");
+        m.up(2, n_inv_canonical, 32);
+        m.run([&] {
+            hipLaunchKernelGGL((group_ntt_load_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, d_in, lg, d_pts);
+            for (unsigned s = 1; s <= lg; ++s)
+                hipLaunchKernelGGL((group_ntt_stage_kernel<F, FrC>), dim3(cdiv(n / 2, 256)), dim3(256), 0, st, d_pts, d_twiddles_mont, lg, s);
+            hipLaunchKernelGGL((group_scale_store_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, d_pts, (const u32 *)d_sc, n, d_std);
+            xyzz_to_affine_launch<FIO>(st, d_std, n, d_out, AW_IO);
+        });
+        return m.finish();
     }
     int sub_device(const u32 *d_a, const u32 *d_b, size_t n, u32 *d_out) override {
         if (!d_a || !d_b || !d_out || n == 0) return MG_ERR_ARG;
-        hipStream_t st = setup_stream();
-        if (!st) return MG_ERR_OOM;
-        DevBlock m; // XYZZ results
-        if (const int rc = m.alloc({n * XW_IO * 4}, "sub_device")) return rc;
-        hipLaunchKernelGGL((ec_elementwise_kernel<F>), dim3(cdiv(n, 256)), dim3(256), 0, st, EC_SUB_MIXED, d_a, d_b, n, m.dev<u32>(0));
-        xyzz_to_affine_launch<FIO>(st, m.dev<u32>(0), n, d_out, AW_IO);
-        return sync_status(st, hipGetLastError(), "sub_device");
+        DevCall m; // XYZZ results
+        if (const int rc = m.begin({n * XW_IO * 4}, "sub_device")) return rc;
+        m.launch(ec_elementwise_kernel<F>, dim3(cdiv(n, 256)), dim3(256), 0, EC_SUB_MIXED, d_a, d_b, n, m.dev<u32>(0));
+        m.run([&] { xyzz_to_affine_launch<FIO>(m.stream(), m.dev<u32>(0), n, d_out, AW_IO); });
+        return m.finish();
     }
 };
 

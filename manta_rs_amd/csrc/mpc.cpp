@@ -53,13 +53,11 @@ int qap_columns(int curve, int group, size_t n_terms, const u64 *const *bases, c
     EntryList en;
     en.reserve(total);
     for (size_t t = 0; t < n_terms; ++t) en.add_matrix(mats[t], m, 0u, (u32)(t * m));
-    DevBlock d; // the bases of all terms, one behind the other
-    if (const int rc = d.alloc({n_terms * (size_t)m * pt}, "mg_qap_columns")) return rc;
-    for (size_t t = 0; t < n_terms; ++t) {
-        const hipError_t er = memcpy_sync(d.dev(0) + t * (size_t)m * pt, bases[t], (size_t)m * pt, hipMemcpyHostToDevice);
-        if (er != hipSuccess) return hip_status(er, "mg_qap_columns");
-    }
-    return e->qap_columns(d.dev<u32>(0), n_terms * (size_t)m, en.view(), n_cols, entries_per_lane, (u32 *)out);
+    DevCall d; // the bases of all terms, one behind the other
+    if (const int rc = d.begin({n_terms * (size_t)m * pt}, "mg_qap_columns")) return rc;
+    for (size_t t = 0; t < n_terms; ++t) d.up(0, bases[t], (size_t)m * pt, t * (size_t)m * pt);
+    d.run([&] { return e->qap_columns(d.dev<u32>(0), n_terms * (size_t)m, en.view(), n_cols, entries_per_lane, (u32 *)out); });
+    return d.finish();
 }
 
 int mpc_initialize(int curve, const mg_kzg_view *pw, const mg_csr *a, const mg_csr *b, const mg_csr *c, u64 m, u64 V, u64 P, u64 h_len,
@@ -93,18 +91,17 @@ int mpc_initialize(int curve, const mg_kzg_view *pw, const mg_csr *a, const mg_c
     std::vector<u32> h(h_len * p1 / 4), s1(3 * V * p1 / 4), s2(V * p2 / 4);
     {
         // G1: tau^i G (D + h_len of them) | alpha tau^i G | beta tau^i G | the Lagrange bases tauL, alphaL, betaL | h_query
-        DevBlock d;
-        if ((rc = d.alloc({(D + h_len) * p1, D * p1, D * p1, 3 * D * p1, h_len * p1}, "mg_mpc_initialize"))) return rc;
-        hipError_t e = memcpy_sync(d.dev(0), pw->tau_powers_g1, (D + h_len) * p1, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = memcpy_sync(d.dev(1), pw->alpha_tau_powers_g1, D * p1, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = memcpy_sync(d.dev(2), pw->beta_tau_powers_g1, D * p1, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_status(e, "mg_mpc_initialize");
+        DevCall d;
+        if ((rc = d.begin({(D + h_len) * p1, D * p1, D * p1, 3 * D * p1, h_len * p1}, "mg_mpc_initialize"))) return rc;
+        d.up(0, pw->tau_powers_g1, (D + h_len) * p1);
+        d.up(1, pw->alpha_tau_powers_g1, D * p1);
+        d.up(2, pw->beta_tau_powers_g1, D * p1);
         u32 *const lag = d.dev<u32>(3);
         // h_query[i] = tau^(i+D) G - tau^i G (:372-377)
-        if ((rc = g1->sub_device(d.dev<u32>(0) + D * (p1 / 4), d.dev<u32>(0), h_len, d.dev<u32>(4)))) return rc;
+        d.run([&] { return g1->sub_device(d.dev<u32>(0) + D * (p1 / 4), d.dev<u32>(0), h_len, d.dev<u32>(4)); });
         for (int v = 0; v < 3; ++v) // :378-381
-            if ((rc = g1->group_ntt_device(d.dev<u32>(v), lg, tw, (const u32 *)ninv, lag + (size_t)v * D * (p1 / 4)))) return rc;
-        if ((e = memcpy_sync(h.data(), d.dev(4), h_len * p1, hipMemcpyDeviceToHost)) != hipSuccess) return hip_status(e, "mg_mpc_initialize");
+            d.run([&] { return g1->group_ntt_device(d.dev<u32>(v), lg, tw, (const u32 *)ninv, lag + (size_t)v * D * (p1 / 4)); });
+        d.down(h.data(), 4, h_len * p1);
         // ONE column-sum call for the three G1 results: columns [0, V) a_query = A^T tauL (+ dummies), [V, 2V) b_g1_query = B^T tauL,
         // [2V, 3V) ext = A^T betaL + B^T alphaL + C^T tauL (+ dummies); basis rows [0, D) tauL, [D, 2D) alphaL, [2D, 3D) betaL
         EntryList en;
@@ -114,18 +111,19 @@ int mpc_initialize(int curve, const mg_kzg_view *pw, const mg_csr *a, const mg_c
         en.add_matrix(b, m, v, 0u);
         en.add_matrix(a, m, 2 * v, 2 * d32), en.add_matrix(b, m, 2 * v, d32), en.add_matrix(c, m, 2 * v, 0u);
         en.add_dummies(P, 2 * v, 2 * d32 + (u32)m, one);
-        if ((rc = g1->qap_columns(lag, 3 * D, en.view(), 3 * V, 0, s1.data()))) return rc;
+        d.run([&] { return g1->qap_columns(lag, 3 * D, en.view(), 3 * V, 0, s1.data()); });
+        if ((rc = d.finish())) return rc;
     }
     {
-        DevBlock d; // G2: tau^i G2 | tauL2
-        if ((rc = d.alloc({D * p2, D * p2}, "mg_mpc_initialize"))) return rc;
-        const hipError_t e = memcpy_sync(d.dev(0), pw->tau_powers_g2, D * p2, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_status(e, "mg_mpc_initialize");
-        if ((rc = g2->group_ntt_device(d.dev<u32>(0), lg, tw, (const u32 *)ninv, d.dev<u32>(1)))) return rc;
+        DevCall d; // G2: tau^i G2 | tauL2
+        if ((rc = d.begin({D * p2, D * p2}, "mg_mpc_initialize"))) return rc;
+        d.up(0, pw->tau_powers_g2, D * p2);
+        d.run([&] { return g2->group_ntt_device(d.dev<u32>(0), lg, tw, (const u32 *)ninv, d.dev<u32>(1)); });
         EntryList en;
         en.reserve(b->nnz);
         en.add_matrix(b, m, 0u, 0u);
-        if ((rc = g2->qap_columns(d.dev<u32>(1), D, en.view(), V, 0, s2.data()))) return rc;
+        d.run([&] { return g2->qap_columns(d.dev<u32>(1), D, en.view(), V, 0, s2.data()); });
+        if ((rc = d.finish())) return rc;
     }
     // everything succeeded: the key
     const unsigned char *q1 = (const unsigned char *)s1.data();

@@ -540,29 +540,20 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
                  c.compact, plan_for(&bs, c.n, c.c, c.batch)};
         if (const int rc = key_layout(r)) return rc;
         c.layout[0] = (u32)r.pl.W, c.layout[1] = r.pl.B, c.layout[2] = r.seg_keys, c.layout[3] = r.invalid;
-        hipStream_t s = r.s = setup_stream();
-        if (!s) return MG_ERR_OOM;
         const size_t sb = (size_t)c.batch * c.n_scalars * 32, pb = r.M * 4;
-        DevBlock m; // scalars | map | keys | vals | pair count
-        if (const int rc = m.alloc({sb, c.map ? (size_t)c.n * 4 : 0, pb, pb, c.compact ? 4u : 0u}, "mg_msm_digits")) return rc;
-        u32 *const d_keys = m.dev<u32>(2), *const d_vals = m.dev<u32>(3);
-        r.d_scalars = m.dev<u32>(0), bs.d_map = m.dev<u32>(1), r.d_count = m.dev<u32>(4);
-        const u32 zero = 0;
-        hipError_t e = hipMemcpyAsync(m.dev(0), c.scalars, sb, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess && c.map) e = hipMemcpyAsync(bs.d_map, c.map, (size_t)c.n * 4, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_keys, c.keys, pb, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_vals, c.vals, pb, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess && c.compact) e = hipMemcpyAsync(r.d_count, &zero, 4, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) {
-            enqueue_digits(r, d_keys, d_vals);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(c.keys, d_keys, pb, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(c.vals, d_vals, pb, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && c.compact) e = hipMemcpyAsync(c.count, r.d_count, 4, hipMemcpyDeviceToHost, s);
-        const int rc = sync_status(s, e, "mg_msm_digits");
-        bs.d_map = nullptr; // the block's
-        return rc;
+        DevCall m; // scalars | map | keys | vals | pair count
+        if (const int rc = m.begin({sb, c.map ? (size_t)c.n * 4 : 0, pb, pb, c.compact ? 4u : 0u}, "mg_msm_digits")) return rc;
+        r.s = m.stream(), r.d_scalars = m.dev<u32>(0), bs.d_map = m.dev<u32>(1), r.d_count = m.dev<u32>(4);
+        m.up(0, c.scalars, sb);
+        m.up(1, c.map, (size_t)c.n * 4);
+        m.up(2, c.keys, pb);
+        m.up(3, c.vals, pb);
+        m.zero(4);
+        m.run([&] { enqueue_digits(r, m.dev<u32>(2), m.dev<u32>(3)); });
+        m.down(c.keys, 2, pb);
+        m.down(c.vals, 3, pb);
+        m.down(c.count, 4, 4);
+        return m.finish();
     }
 
     // The fused front end alone, likewise for a base set that exists as a description only: what launch_reserve and launch_sort do
@@ -585,27 +576,19 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         r.end_bit = 1;
         while (r.nb > 1 && (1u << r.end_bit) <= r.nb - 1) ++r.end_bit; // (launch_reserve: the bits of the last bucket key)
         c.layout[0] = (u32)r.pl.W, c.layout[1] = r.pl.B, c.layout[2] = r.seg_keys, c.layout[3] = (u32)((size_t)r.pl.W * c.n);
-        hipStream_t s = r.s = setup_stream();
-        if (!s) return MG_ERR_OOM;
         const size_t sb = (size_t)c.n_scalars * 32, pb = r.M * 4;
-        DevBlock m; // scalars | map | sorted keys | sorted vals | the sort's scratch
-        if (const int rc = m.alloc({sb, c.map ? (size_t)c.n * 4 : 0, pb, pb, sort_pairs_temp_bytes(r.M, cdiv(c.n, 256))}, "mg_msm_dense_front"))
+        DevCall m; // scalars | map | sorted keys | sorted vals | the sort's scratch
+        if (const int rc = m.begin({sb, c.map ? (size_t)c.n * 4 : 0, pb, pb, sort_pairs_temp_bytes(r.M, cdiv(c.n, 256))}, "mg_msm_dense_front"))
             return rc;
-        r.d_scalars = m.dev<u32>(0), bs.d_map = c.map ? m.dev<u32>(1) : nullptr;
-        hipError_t e = hipMemcpyAsync(m.dev(0), c.scalars, sb, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess && c.map) e = hipMemcpyAsync(bs.d_map, c.map, (size_t)c.n * 4, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(m.dev(2), c.keys, pb, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(m.dev(3), c.vals, pb, hipMemcpyHostToDevice, s);
-        int rc = MG_OK;
-        if (e == hipSuccess) {
-            rc = enqueue_dense_front(r, m.dev(4), m.dev<u32>(2), m.dev<u32>(3));
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess && !rc) e = hipMemcpyAsync(c.keys, m.dev(2), pb, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && !rc) e = hipMemcpyAsync(c.vals, m.dev(3), pb, hipMemcpyDeviceToHost, s);
-        const int synced = sync_status(s, e, "mg_msm_dense_front");
-        bs.d_map = nullptr; // the block's
-        return rc ? rc : synced;
+        r.s = m.stream(), r.d_scalars = m.dev<u32>(0), bs.d_map = m.dev<u32>(1);
+        m.up(0, c.scalars, sb);
+        m.up(1, c.map, (size_t)c.n * 4);
+        m.up(2, c.keys, pb);
+        m.up(3, c.vals, pb);
+        m.run([&] { return enqueue_dense_front(r, m.dev(4), m.dev<u32>(2), m.dev<u32>(3)); });
+        m.down(c.keys, 2, pb);
+        m.down(c.vals, 3, pb);
+        return m.finish();
     }
 
     // ---------------------------------------------------------------- QAP column sums (qap_columns.h)
@@ -635,8 +618,6 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
             std::memset(out_affine_host, 0, out_bytes);
             return MG_OK;
         }
-        hipStream_t st = setup_stream();
-        if (!st) return MG_ERR_OOM;
         const u32 L = entries_per_lane ? entries_per_lane : qap_entries_per_lane(N);
         const u32 T = cdiv(N, L), waves1 = cdiv((size_t)2 * T, 64), invalid = (u32)n_cols;
         int end_bit = 1;
@@ -645,40 +626,38 @@ template <class Curve, int CURVE_ID, int GROUP> class GroupEngineT : public Grou
         for (size_t e = 0; e < N; ++e) ids[e] = (u32)e;
         const size_t sort_bytes = sort_pairs_temp_bytes(N);
         enum { SRC, VAL, KEYS, IDS, SKEYS, SIDS, SORT, PROD, PK0, PP0, PK1, PP1, SUMS, STD, AFF };
-        DevBlock m;
-        if (const int rc = m.alloc({N * 4, N * 32, N * 4, N * 4, N * 4, N * 4, sort_bytes, N * XW * 4, (size_t)2 * T * 4,
+        std::vector<u32> stage((size_t)n_cols * AW_IO); // (out_affine_host is written only if the call succeeds)
+        DevCall m;
+        if (const int rc = m.begin({N * 4, N * 32, N * 4, N * 4, N * 4, N * 4, sort_bytes, N * XW * 4, (size_t)2 * T * 4,
                                     (size_t)2 * T * XW * 4, (size_t)2 * waves1 * 4, (size_t)2 * waves1 * XW * 4,
                                     (size_t)(n_cols + 1) * XW * 4, (size_t)n_cols * XW_IO * 4, out_bytes},
                                    "qap_columns"))
             return rc;
-        std::vector<u32> stage((size_t)n_cols * AW_IO);
-        hipError_t e = hipMemcpyAsync(m.dev(SRC), en.src, N * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(m.dev(VAL), en.val, N * 32, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(m.dev(KEYS), en.col, N * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(m.dev(IDS), ids.data(), N * 4, hipMemcpyHostToDevice, st);
-        int rc = MG_OK;
-        if (e == hipSuccess) {
-            u32 *const sums = m.dev<u32>(SUMS);
+        hipStream_t st = m.stream();
+        m.up(SRC, en.src, N * 4);
+        m.up(VAL, en.val, N * 32);
+        m.up(KEYS, en.col, N * 4);
+        m.up(IDS, ids.data(), N * 4);
+        u32 *const sums = m.dev<u32>(SUMS);
+        m.run([&] {
             ZeroRanges zr{};
             zr.p[0] = sums, zr.n[0] = (u32)((size_t)(n_cols + 1) * XW);
             hipLaunchKernelGGL((zero_ranges<F>), dim3(zr.n[0] > 256u * 1024u ? 1024u : cdiv(zr.n[0], 256)), dim3(256), 0, st, zr);
-            rc = sort_pairs(m.dev<u32>(KEYS), m.dev<u32>(SKEYS), m.dev<u32>(IDS), m.dev<u32>(SIDS), N, end_bit, m.dev(SORT), sort_bytes, st);
-            if (!rc) {
-                hipLaunchKernelGGL((qap_entry_kernel<F, FrC>), dim3(cdiv(N, 256)), dim3(256), 0, st, m.dev<u32>(SIDS), (u32)N, m.dev<u32>(SRC),
-                                   m.dev<u32>(VAL), d_bases, m.dev<u32>(PROD));
-                hipLaunchKernelGGL((qap_segsum_kernel<F>), dim3(cdiv(T, 256)), dim3(256), 0, st, m.dev<u32>(SKEYS), m.dev<u32>(PROD), (u32)N, L,
-                                   invalid, sums, m.dev<u32>(PK0), m.dev<u32>(PP0), T);
-                u32 *pk[2] = {m.dev<u32>(PK0), m.dev<u32>(PK1)}, *pp[2] = {m.dev<u32>(PP0), m.dev<u32>(PP1)};
-                merge_levels(st, pk, pp, 2 * T, merge_g1(N), invalid, sums, (u32 *)nullptr);
-                hipLaunchKernelGGL((group_scale_store_kernel<F>), dim3(cdiv(n_cols, 256)), dim3(256), 0, st, sums, (const u32 *)nullptr,
-                                   (size_t)n_cols, m.dev<u32>(STD));
-                xyzz_to_affine_launch<FIO>(st, m.dev<u32>(STD), (size_t)n_cols, m.dev<u32>(AFF), AW_IO);
-                e = hipGetLastError();
-                if (e == hipSuccess) e = hipMemcpyAsync(stage.data(), m.dev(AFF), out_bytes, hipMemcpyDeviceToHost, st);
-            }
-        }
-        const int synced = sync_status(st, e, "qap_columns"); // (before the block goes, whatever failed)
-        if (rc || synced) return rc ? rc : synced;
+            return sort_pairs(m.dev<u32>(KEYS), m.dev<u32>(SKEYS), m.dev<u32>(IDS), m.dev<u32>(SIDS), N, end_bit, m.dev(SORT), sort_bytes, st);
+        });
+        m.run([&] {
+            hipLaunchKernelGGL((qap_entry_kernel<F, FrC>), dim3(cdiv(N, 256)), dim3(256), 0, st, m.dev<u32>(SIDS), (u32)N, m.dev<u32>(SRC),
+                               m.dev<u32>(VAL), d_bases, m.dev<u32>(PROD));
+            hipLaunchKernelGGL((qap_segsum_kernel<F>), dim3(cdiv(T, 256)), dim3(256), 0, st, m.dev<u32>(SKEYS), m.dev<u32>(PROD), (u32)N, L,
+                               invalid, sums, m.dev<u32>(PK0), m.dev<u32>(PP0), T);
+            u32 *pk[2] = {m.dev<u32>(PK0), m.dev<u32>(PK1)}, *pp[2] = {m.dev<u32>(PP0), m.dev<u32>(PP1)};
+            merge_levels(st, pk, pp, 2 * T, merge_g1(N), invalid, sums, (u32 *)nullptr);
+            hipLaunchKernelGGL((group_scale_store_kernel<F>), dim3(cdiv(n_cols, 256)), dim3(256), 0, st, sums, (const u32 *)nullptr,
+                               (size_t)n_cols, m.dev<u32>(STD));
+            xyzz_to_affine_launch<FIO>(st, m.dev<u32>(STD), (size_t)n_cols, m.dev<u32>(AFF), AW_IO);
+        });
+        m.down(stage.data(), AFF, out_bytes);
+        if (const int rc = m.finish()) return rc;
         std::memcpy(out_affine_host, stage.data(), out_bytes);
         return MG_OK;
     }

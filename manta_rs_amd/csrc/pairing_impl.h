@@ -211,22 +211,18 @@ template <class K> class PairingEngineT : public PairingEngine {
         if (op == MG_PAIRING_FQ_INV_EUCLID || op == MG_PAIRING_FQ_HALF) wa = wo = P::N;
         if (op == MG_PAIRING_FQ_LINCOMB) wa = (size_t)MG_PAIRING_LINCOMB_OPERANDS * P::N, wo = P::N;
         const size_t cb = op == MG_PAIRING_FQ_LINCOMB ? n * MG_PAIRING_LINCOMB_OPERANDS * sizeof(int16_t) : 0;
-        DevBlock m; // out | a | b | coefficients (absent operands take no room)
-        if (const int rc = m.alloc({n * wo * 4, n * wa * 4, n * wb * 4, cb}, "mg_pairing_op")) return rc;
-        hipError_t e = memcpy_sync(m.dev(1), a, n * wa * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && wb) e = memcpy_sync(m.dev(2), b, n * wb * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && cb) e = memcpy_sync(m.dev(3), coeffs, cb, hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            constexpr size_t lds = PW::lds_bytes(PW::FINAL_EXP_REGS) > PW::miller_lds_bytes() ? PW::lds_bytes(PW::FINAL_EXP_REGS) : PW::miller_lds_bytes();
-            if (f12)
-                hipLaunchKernelGGL((pairing_f12_op_kernel<K>), dim3((unsigned)n), dim3(64), lds, setup_stream(), op, m.dev<u32>(1), m.dev<u32>(2),
-                                   m.dev<u32>(0));
-            else
-                hipLaunchKernelGGL((pairing_fq_op_kernel<K>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, setup_stream(), op, m.dev<u32>(1),
-                                   m.dev<u32>(2), m.dev<int16_t>(3), n, m.dev<u32>(0));
-            e = memcpy_sync(out, m.dev(0), n * wo * 4, hipMemcpyDeviceToHost);
-        }
-        return e == hipSuccess ? MG_OK : hip_status(e, "mg_pairing_op");
+        DevCall m; // out | a | b | coefficients (absent operands take no room)
+        if (const int rc = m.begin({n * wo * 4, n * wa * 4, n * wb * 4, cb}, "mg_pairing_op")) return rc;
+        m.up(1, a, n * wa * 4);
+        m.up(2, b, n * wb * 4);
+        m.up(3, coeffs, cb);
+        constexpr size_t lds = PW::lds_bytes(PW::FINAL_EXP_REGS) > PW::miller_lds_bytes() ? PW::lds_bytes(PW::FINAL_EXP_REGS) : PW::miller_lds_bytes();
+        if (f12) m.launch(pairing_f12_op_kernel<K>, dim3((unsigned)n), dim3(64), lds, op, m.dev<u32>(1), m.dev<u32>(2), m.dev<u32>(0));
+        else
+            m.launch(pairing_fq_op_kernel<K>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, op, m.dev<u32>(1), m.dev<u32>(2), m.dev<int16_t>(3), n,
+                     m.dev<u32>(0));
+        m.down(out, 0, n * wo * 4);
+        return m.finish();
     }
     int n_coeffs() const override { return P::NCOEFF; }
     int coeff_words() const override { return P::COEFFW; }
@@ -236,16 +232,13 @@ template <class K> class PairingEngineT : public PairingEngine {
     int prepare(const u32 *q_affine_host, size_t n, u32 **d_out) override {
         if (!q_affine_host || !n || !d_out) return MG_ERR_ARG;
         const size_t qb = n * 2 * P::F2W * 4, cb = n * (size_t)P::NCOEFF * P::COEFFW * 4;
-        DevBlock q, c; // the points, needed for this call only; the coefficients, which become the caller's
-        int rc = q.alloc({qb}, "pairing prepare");
+        DevBlock c; // the coefficients, which become the caller's
+        DevCall q;  // the points, needed for this call only
+        int rc = q.begin({qb}, "pairing prepare");
         if (rc || (rc = c.alloc({cb}, "pairing prepare"))) return rc;
-        hipError_t e = memcpy_sync(q.dev(0), q_affine_host, qb, hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL((g2_prepare_kernel<K>), dim3((unsigned)n), dim3(64), PW::prep_lds_bytes(), setup_stream(), q.dev<u32>(0), n,
-                               c.dev<u32>(0));
-            e = setup_sync();
-        }
-        if (e != hipSuccess) return hip_status(e, "pairing prepare");
+        q.up(0, q_affine_host, qb);
+        q.launch(g2_prepare_kernel<K>, dim3((unsigned)n), dim3(64), PW::prep_lds_bytes(), q.dev<u32>(0), n, c.dev<u32>(0));
+        if ((rc = q.finish())) return rc;
         *d_out = (u32 *)c.release();
         return MG_OK;
     }

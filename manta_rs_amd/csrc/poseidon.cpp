@@ -75,54 +75,45 @@ int merkle_grow(const mg_poseidon *h, unsigned height, size_t nt, const MerkleWo
         total[l] = base - off[l * T1];
         if (l0 < 0 && (mx <= (u64)MERKLE_TOP || l == H - 1)) l0 = (int)l;
     }
-    hipStream_t s = setup_stream();
-    if (!s) return MG_ERR_OOM;
     const size_t pb = prm_bytes(h), n_req = w.k + w.m, path_bytes = len * 32;
     const bool gather = n_req || w.new_last || w.new_paths;
     // parameters | table | counts old, new | last leaves | current paths | chain | nodes | roots | requests | paths | new last
-    const std::vector<size_t> bytes{pb, off.size() * 8, nt * 8, nt * 8, nt * 32, nt * path_bytes, nt * 32, base * 32, nt * 32,
-                                    n_req * 8, n_req * 8, gather ? (n_req + nt) * path_bytes : 0, gather ? nt * 32 : 0};
-    DevBlock d;
-    if (const int rc = d.alloc(bytes, "hipMalloc(merkle)")) return rc;
-    const auto up = [&](size_t i, const void *src, size_t n, size_t at = 0) {
-        return n ? hipMemcpyAsync(d.dev(i) + at, src, n, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    const auto zero = [&](size_t i) { return bytes[i] ? hipMemsetAsync(d.dev(i), 0, bytes[i], s) : hipSuccess; };
-    MG_HIP(up(0, h->prm.data(), pb));
-    MG_HIP(up(1, off.data(), off.size() * 8));
+    DevCall d;
+    if (const int rc = d.begin({pb, off.size() * 8, nt * 8, nt * 8, nt * 32, nt * path_bytes, nt * 32, base * 32, nt * 32, n_req * 8,
+                                n_req * 8, gather ? (n_req + nt) * path_bytes : 0, gather ? nt * 32 : 0},
+                               "hipMalloc(merkle)"))
+        return rc;
+    hipStream_t s = d.stream();
+    d.up(0, h->prm.data(), pb);
+    d.up(1, off.data(), off.size() * 8);
     if (w.old_counts) {
-        MG_HIP(up(2, w.old_counts, nt * 8));
-        MG_HIP(up(4, w.old_last, nt * 32));
-        MG_HIP(up(5, w.old_paths, nt * path_bytes));
-        MG_HIP(hipMemcpyAsync(d.dev(6), d.dev(4), nt * 32, hipMemcpyDeviceToDevice, s)); // the chain starts at the last leaf
+        d.up(2, w.old_counts, nt * 8);
+        d.up(4, w.old_last, nt * 32);
+        d.up(5, w.old_paths, nt * path_bytes);
+        d.copy(6, 4, nt * 32); // the chain starts at the last leaf
     } else // the empty state, filled in on the device: a tree that stays empty has it copied through
-        for (const size_t i : {2, 4, 5, 6}) MG_HIP(zero(i));
-    MG_HIP(up(3, w.n_new, nt * 8));
-    MG_HIP(up(7, w.leaves, total[0] * 32));
-    MG_HIP(w.path_trees ? up(9, w.path_trees, w.k * 8) : zero(9));
-    MG_HIP(up(9, w.refresh_trees, w.m * 8, w.k * 8));
-    MG_HIP(up(10, w.path_indices, w.k * 8));
-    MG_HIP(up(10, w.refresh_indices, w.m * 8, w.k * 8));
-    MG_HIP(up(11, w.refresh_paths, w.m * path_bytes, w.k * path_bytes)); // refreshed in place
+        for (const size_t i : {2, 4, 5, 6}) d.zero(i);
+    d.up(3, w.n_new, nt * 8);
+    d.up(7, w.leaves, total[0] * 32);
+    w.path_trees ? d.up(9, w.path_trees, w.k * 8) : d.zero(9);
+    d.up(9, w.refresh_trees, w.m * 8, w.k * 8);
+    d.up(10, w.path_indices, w.k * 8);
+    d.up(10, w.refresh_indices, w.m * 8, w.k * 8);
+    d.up(11, w.refresh_paths, w.m * path_bytes, w.k * path_bytes); // refreshed in place
     const PoseidonDev hd = on_device(h, d.dev(0));
     const MerkleForest t{d.dev<const u64>(2), d.dev<const u64>(3), d.dev<const u32>(4), d.dev<const u32>(5), d.dev<u32>(6),
                          d.dev<u32>(7),       d.dev<const u64>(1), (int)nt,             (int)H};
-    for (int l = 0; l < l0; ++l) MG_HIP(on_field(h, [&](auto K) { return K.merkle_level(s, hd, t, l, total[l + 1]); }));
-    MG_HIP(on_field(h, [&](auto K) { return K.merkle_top(s, hd, t, l0, d.dev<u32>(8)); }));
+    const auto launch = [&](auto f) { d.run([&] { return on_field(h, f); }); };
+    for (int l = 0; l < l0; ++l) launch([&](auto K) { return K.merkle_level(s, hd, t, l, total[l + 1]); });
+    launch([&](auto K) { return K.merkle_top(s, hd, t, l0, d.dev<u32>(8)); });
     if (gather)
-        MG_HIP(on_field(h, [&](auto K) {
-            return K.merkle_gather(s, t, d.dev<const u64>(9), d.dev<const u64>(10), n_req, d.dev<u32>(11), d.dev<u32>(12));
-        }));
-    const auto down = [&](void *dst, size_t i, size_t n, size_t at = 0) { // what the caller wants back: not null, not empty
-        return dst && n ? hipMemcpyAsync(dst, d.dev(i) + at, n, hipMemcpyDeviceToHost, s) : hipSuccess;
-    };
-    MG_HIP(down(w.roots_out, 8, nt * 32));
-    MG_HIP(down(w.paths_out, 11, w.k * path_bytes));
-    MG_HIP(down(w.refresh_paths, 11, w.m * path_bytes, w.k * path_bytes));
-    MG_HIP(down(w.new_paths, 11, nt * path_bytes, n_req * path_bytes));
-    MG_HIP(down(w.new_last, 12, nt * 32));
-    MG_HIP(hipStreamSynchronize(s));
-    return MG_OK;
+        launch([&](auto K) { return K.merkle_gather(s, t, d.dev<const u64>(9), d.dev<const u64>(10), n_req, d.dev<u32>(11), d.dev<u32>(12)); });
+    d.down(w.roots_out, 8, nt * 32); // what the caller wants back: not null, not empty
+    d.down(w.paths_out, 11, w.k * path_bytes);
+    d.down(w.refresh_paths, 11, w.m * path_bytes, w.k * path_bytes);
+    d.down(w.new_paths, 11, nt * path_bytes, n_req * path_bytes);
+    d.down(w.new_last, 12, nt * 32);
+    return d.finish();
 }
 
 } // namespace
@@ -160,15 +151,12 @@ int poseidon_hash(const mg_poseidon *h, const u64 *inputs, size_t n, u64 *out) {
 int poseidon_hash_device(const mg_poseidon *h, const u64 *d_in, size_t n, u64 *d_out) {
     if (!h || (n && (!d_in || !d_out))) return MG_ERR_ARG;
     if (n == 0) return MG_OK;
-    hipStream_t s = setup_stream();
-    if (!s) return MG_ERR_OOM;
-    DevBlock m;
-    if (const int rc = m.alloc({prm_bytes(h)}, "hipMalloc(poseidon parameters)")) return rc;
-    MG_HIP(hipMemcpyAsync(m.dev(0), h->prm.data(), prm_bytes(h), hipMemcpyHostToDevice, s));
+    DevCall m;
+    if (const int rc = m.begin({prm_bytes(h)}, "hipMalloc(poseidon parameters)")) return rc;
+    m.up(0, h->prm.data(), prm_bytes(h));
     const PoseidonDev hd = on_device(h, m.dev(0));
-    MG_HIP(on_field(h, [&](auto K) { return K.hash(s, hd, (const u32 *)d_in, n, (u32 *)d_out); }));
-    MG_HIP(hipStreamSynchronize(s));
-    return MG_OK;
+    m.run([&] { return on_field(h, [&](auto K) { return K.hash(m.stream(), hd, (const u32 *)d_in, n, (u32 *)d_out); }); });
+    return m.finish();
 }
 
 // one tree built from its leaves: the append to one empty tree, the k indices as requests on it

@@ -977,13 +977,11 @@ int r1cs_check_chunks(FrEngine *fr, const DevCsr &A, const DevCsr &B, const DevC
     const size_t zb = (size_t)V * 32;
     const size_t lanes = std::min<size_t>(FrEngine::R1CS_CHECK_MAX_BATCH, std::max<size_t>(1, R1CS_CHECK_Z_BYTES / zb));
     std::vector<u32> f32(k), c32(k);
-    int inner = MG_OK; // (the loop's callback speaks hipError_t; the engine's own status is kept beside it)
     const int rc = run_chunks(Staging{lanes, false}, k, nullptr, 0, {Span::in(z, zb), Span::out(f32.data(), 4), Span::out(c32.data(), 4)}, 0,
                               [&](const Chunk &c) {
-                                  inner = fr->r1cs_check(A, B, C, (const u32 *)c.a[0], m, c.stream, (u32)c.n, zb / 4, (u32 *)c.a[1], (u32 *)c.a[2]);
-                                  return inner == MG_OK ? hipSuccess : hipErrorUnknown;
+                                  return fr->r1cs_check(A, B, C, (const u32 *)c.a[0], m, c.stream, (u32)c.n, zb / 4, (u32 *)c.a[1], (u32 *)c.a[2]);
                               });
-    if (inner || rc) return inner ? inner : rc;
+    if (rc) return rc;
     for (u64 q = 0; q < k; ++q) {
         first[q] = f32[q] == 0xFFFFFFFFu ? MG_R1CS_SATISFIED : (u64)f32[q];
         if (count) count[q] = c32[q];
@@ -1004,21 +1002,18 @@ int r1cs_check(int curve, const mg_csr *a, const mg_csr *b, const mg_csr *c, u64
     FrEngine *fr = get_ntt_engine(curve);
     if (!fr) return MG_ERR_ARG;
     const mg_csr *src[3] = {a, b, c};
-    DevBlock d; // row_ptr | col | val of A, B, C: the call's, freed on every path out
+    DevCall d; // row_ptr | col | val of A, B, C: the call's, freed on every path out
     std::vector<size_t> bytes;
     for (const mg_csr *s : src) bytes.push_back((size_t)(m + 1) * 4), bytes.push_back((size_t)s->nnz * 4), bytes.push_back((size_t)s->nnz * 32);
-    if ((rc = d.alloc(bytes, "mg_r1cs_check"))) return rc;
+    if ((rc = d.begin(bytes, "mg_r1cs_check"))) return rc;
     DevCsr M[3];
     for (int t = 0; t < 3; ++t) {
         const void *from[3] = {src[t]->row_ptr, src[t]->col, src[t]->val};
-        for (int j = 0; j < 3; ++j) {
-            if (!bytes[3 * t + j]) continue;
-            const hipError_t e = memcpy_sync(d.dev(3 * t + j), from[j], bytes[3 * t + j], hipMemcpyHostToDevice);
-            if (e != hipSuccess) return hip_status(e, "mg_r1cs_check");
-        }
+        for (int j = 0; j < 3; ++j) d.up(3 * t + j, from[j], bytes[3 * t + j]);
         M[t].row_ptr = d.dev<u32>(3 * t), M[t].col = d.dev<u32>(3 * t + 1), M[t].val = d.dev<u32>(3 * t + 2), M[t].nnz = src[t]->nnz;
     }
-    return r1cs_check_chunks(fr, M[0], M[1], M[2], m, V, k, z, first, count);
+    d.run([&] { return r1cs_check_chunks(fr, M[0], M[1], M[2], m, V, k, z, first, count); });
+    return d.finish();
 }
 
 } // namespace mg

@@ -13,15 +13,13 @@ namespace mg {
 
 static int mul_all(GroupEngine *e, const u64 *gen, const std::vector<u64> &scalars, std::vector<u32> &out) {
     const size_t n = scalars.size() / 4, aw = (size_t)e->affine_words();
-    DevBlock m; // scalars | points
-    if (const int rc = m.alloc({n * 32, n * aw * 4}, "groth16_setup")) return rc;
-    u32 *d_s = m.dev<u32>(0), *d_o = m.dev<u32>(1);
-    hipError_t er = memcpy_sync(d_s, scalars.data(), n * 32, hipMemcpyHostToDevice);
-    int rc = MG_OK;
-    if (er == hipSuccess) rc = e->fixed_base_mul((const u32 *)gen, d_s, n, d_o, nullptr);
     out.resize(n * aw);
-    if (er == hipSuccess && !rc) er = memcpy_sync(out.data(), d_o, n * aw * 4, hipMemcpyDeviceToHost);
-    return er == hipSuccess ? rc : hip_status(er, "groth16_setup");
+    DevCall m; // scalars | points
+    if (const int rc = m.begin({n * 32, n * aw * 4}, "groth16_setup")) return rc;
+    m.up(0, scalars.data(), n * 32);
+    m.run([&] { return e->fixed_base_mul((const u32 *)gen, m.dev<u32>(0), n, m.dev<u32>(1), nullptr); });
+    m.down(out.data(), 1, n * aw * 4);
+    return m.finish();
 }
 
 int groth16_setup(int curve, const mg_csr *a, const mg_csr *b, const mg_csr *c, u64 m, u64 V, u64 P, const u64 *toxic5,

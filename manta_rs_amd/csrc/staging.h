@@ -1,9 +1,10 @@
-// Host side of the "arrays in the caller's memory in, arrays out" entry points: the device memory of one call (DevBlock), the
-// chunk loop over the lanes of a call (run_chunks) and the small pieces such calls share. Host-only; no kernel lives here.
+// Host side of the "arrays in the caller's memory in, arrays out" entry points: the device memory of one call (DevBlock), its
+// copies, launches and one wait (DevCall), the chunk loop over the lanes of a call (run_chunks) and small shared pieces. Host-only.
 #pragma once
 #include "engine.h"
 #include "host_ec.h"
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 namespace mg {
@@ -42,6 +43,7 @@ class DevBlock {
     // array i on the device / in the pinned twin; an array of zero bytes is nullptr
     template <class T = uint8_t> T *dev(size_t i) const { return len_[i] ? (T *)(d_ + off_[i]) : nullptr; }
     template <class T = uint8_t> T *pin(size_t i) const { return len_[i] ? (T *)(h_ + off_[i]) : nullptr; }
+    size_t bytes(size_t i) const { return len_[i]; }
     // hands the device memory to the caller, who hipFrees it (it starts at array 0)
     void *release() {
         void *p = d_;
@@ -62,6 +64,69 @@ class DevBlock {
     HeavyOp no_capture_meanwhile_;
     uint8_t *d_ = nullptr, *h_ = nullptr;
     std::vector<size_t> off_, len_;
+};
+
+// One call's work on the device: its block, the stream everything goes to and the first error. Every step after a failure is
+// skipped, so a call is written straight down and asks once, at finish().
+// The exit rule: a call that enqueued anything waits for its stream on every path out, BEFORE its memory goes -- in finish(), or,
+// when a path leaves without it, in the destructor, whose body runs before the block member frees device and pinned memory.
+// The lifetime rule that follows: host memory that a copy of the scope reads or writes is declared BEFORE the scope and so
+// outlives it (the destructor may still be waiting for those copies when locals declared later are already gone).
+// begin() asks for the stream first and the block second: where there is no device a call ends with MG_ERR_OOM, nothing allocated.
+class DevCall {
+  public:
+    ~DevCall() {
+        if (busy_) hipStreamSynchronize(s_);
+    }
+    // bytes[i] = the size of array i, `what` names the call in mg_last_error(), on = its stream (none: the thread's setup stream)
+    int begin(const std::vector<size_t> &bytes, const char *what, bool pinned = false, hipStream_t on = nullptr) {
+        what_ = what;
+        if (!(s_ = on ? on : setup_stream())) return MG_ERR_OOM;
+        return m_.alloc(bytes, what, pinned);
+    }
+    hipStream_t stream() const { return s_; }
+    template <class T = uint8_t> T *dev(size_t i) const { return m_.dev<T>(i); }
+    template <class T = uint8_t> T *pin(size_t i) const { return m_.pin<T>(i); }
+    // host -> array i (from byte `at` on), array -> array, array i -> host, zeros -> array i; no bytes or a null side: nothing to do
+    void up(size_t i, const void *src, size_t n, size_t at = 0) { cp(dev_at(i, at), src, n, hipMemcpyHostToDevice); }
+    void copy(size_t to, size_t from, size_t n) { cp(dev(to), dev(from), n, hipMemcpyDeviceToDevice); }
+    void down(void *dst, size_t i, size_t n, size_t at = 0) { cp(dst, dev_at(i, at), n, hipMemcpyDeviceToHost); }
+    void zero(size_t i) {
+        if (dev(i)) run([&] { return hipMemsetAsync(dev(i), 0, m_.bytes(i), s_); });
+    }
+    // `enqueue()` puts kernels on stream() and returns nothing, a hipError_t or a library status (a nested engine call, which may
+    // wait for the stream itself); hipGetLastError() is read behind it. launch: one kernel, the arguments of hipLaunchKernelGGL
+    template <class F> void run(F enqueue) {
+        if (failed()) return;
+        busy_ = true;
+        if constexpr (std::is_void<decltype(enqueue())>::value) enqueue();
+        else note(enqueue());
+        note(hipGetLastError());
+    }
+    template <class Kernel, class... A> void launch(Kernel kernel, dim3 grid, dim3 block, size_t lds, A... a) {
+        run([&] { hipLaunchKernelGGL(kernel, grid, block, lds, s_, a...); });
+    }
+    // The one wait of the call (of a chunk, in run_chunks) and its first error, a library status from inside a launch as it came
+    int finish() {
+        const int synced = sync_status(s_, e_, what_);
+        busy_ = false;
+        return rc_ ? rc_ : synced;
+    }
+
+  private:
+    bool failed() const { return rc_ || e_ != hipSuccess; }
+    void note(hipError_t e) { e_ = failed() ? e_ : e; }
+    void note(int rc) { rc_ = failed() ? rc_ : rc; }
+    uint8_t *dev_at(size_t i, size_t at) const { return dev(i) ? dev(i) + at : nullptr; }
+    void cp(void *dst, const void *src, size_t n, hipMemcpyKind kind) {
+        if (n && dst && src) run([&] { return hipMemcpyAsync(dst, src, n, kind, s_); });
+    }
+    DevBlock m_;
+    hipStream_t s_ = nullptr;
+    const char *what_ = "";
+    hipError_t e_ = hipSuccess;
+    int rc_ = MG_OK;
+    bool busy_ = false; // something may be in flight on s_
 };
 
 // ---- the chunk loop ----------------------------------------------------------------------------------------------------
@@ -86,8 +151,8 @@ struct Chunk { // what the launch callback gets: the device side of one chunk
 };
 
 // The n lanes of a call, st.chunk at a time on the calling thread's setup stream: `consts` is uploaded once, then per chunk the
-// input arrays are copied in, `launch(const Chunk &) -> hipError_t` enqueues the kernels, the output arrays are copied back and
-// the stream is waited for. Device memory of a call = consts + min(n, st.chunk) x (sum of the strides + scratch_stride), each
+// input arrays are copied in, `launch(const Chunk &)` enqueues the kernels (DevCall::run: a hipError_t or a library status comes
+// back), the output arrays are copied back and the stream is waited for, on a failure too. Device memory of a call = consts + min(n, st.chunk) x (sum of the strides + scratch_stride), each
 // array rounded up to 256 bytes; with st.pinned as much page-locked host memory again.
 template <class Launch>
 int run_chunks(Staging st, size_t n, const void *consts, size_t const_bytes, const std::vector<Span> &arrays, size_t scratch_stride,
@@ -100,10 +165,10 @@ int run_chunks(Staging st, size_t n, const void *consts, size_t const_bytes, con
     for (const Span &x : arrays) bytes.push_back(cap * x.stride);
     bytes.push_back(const_bytes);
     bytes.push_back(cap * scratch_stride);
-    DevBlock m;
-    if (const int rc = m.alloc(bytes, "hipMalloc(chunk arrays)", st.pinned)) return rc;
-    if (const_bytes) MG_HIP(hipMemcpyAsync(m.dev(na), consts, const_bytes, hipMemcpyHostToDevice, s));
-    Chunk c{m.dev(na), {}, m.dev(na + 1), 0, s};
+    DevCall m;
+    if (const int rc = m.begin(bytes, "hipMalloc(chunk arrays)", st.pinned)) return rc;
+    m.up(na, consts, const_bytes);
+    Chunk c{m.dev(na), {}, m.dev(na + 1), 0, m.stream()};
     for (size_t i = 0; i < na; ++i) c.a.push_back(m.dev(i));
     for (size_t off = 0; off < n; off += cap) {
         c.n = n - off < cap ? n - off : cap;
@@ -112,16 +177,12 @@ int run_chunks(Staging st, size_t n, const void *consts, size_t const_bytes, con
             if (!x.src) continue;
             const void *from = (const uint8_t *)x.src + off * x.stride;
             if (st.pinned) from = std::memcpy(m.pin(i), from, c.n * x.stride);
-            MG_HIP(hipMemcpyAsync(c.a[i], from, c.n * x.stride, hipMemcpyHostToDevice, s));
+            m.up(i, from, c.n * x.stride);
         }
-        MG_HIP(launch(c));
-        for (size_t i = 0; i < na; ++i) {
-            const Span &x = arrays[i];
-            if (!x.dst) continue;
-            void *to = st.pinned ? m.pin(i) : (uint8_t *)x.dst + off * x.stride;
-            MG_HIP(hipMemcpyAsync(to, c.a[i], c.n * x.stride, hipMemcpyDeviceToHost, s));
-        }
-        MG_HIP(hipStreamSynchronize(s));
+        m.run([&] { return launch(c); });
+        for (size_t i = 0; i < na; ++i)
+            if (arrays[i].dst) m.down(st.pinned ? m.pin(i) : (uint8_t *)arrays[i].dst + off * arrays[i].stride, i, c.n * arrays[i].stride);
+        if (const int rc = m.finish()) return rc;
         for (size_t i = 0; st.pinned && i < na; ++i)
             if (arrays[i].dst) std::memcpy((uint8_t *)arrays[i].dst + off * arrays[i].stride, m.pin(i), c.n * arrays[i].stride);
     }
