@@ -28,6 +28,152 @@ class MantaGpuError(RuntimeError):
         super().__init__(f"{where}: {LIB.mg_strerror(status).decode()} ({status}) {detail}")
 
 
+# The C ABI's types, stated here and nowhere else: "return:parameters" per entry point of include/mantagpu.h, in the header's
+# order (tests/test_host.py parses the header and holds this table to it). Letters: i int / mg_curve_t, u unsigned / uint32_t,
+# z size_t, q uint64_t, f float, v void, s const char * returned, n mg_tuning_env_names' list, p any pointer, array or handle.
+# ctypes converts by these, so a count of 2^32 + 5 arrives as that and not as 5; it checks no range: the wrappers do.
+_KINDS = {"i": ctypes.c_int, "u": ctypes.c_uint32, "z": ctypes.c_size_t, "q": ctypes.c_uint64, "f": ctypes.c_float, "v": None,
+          "s": ctypes.c_char_p, "n": ctypes.POINTER(ctypes.c_char_p), "p": ctypes.c_void_p}
+_SIGNATURES = {
+    "mg_init": "i:i",
+    "mg_strerror": "s:i",
+    "mg_last_error": "s:",
+    "mg_device_count": "i:p",
+    "mg_malloc": "i:pz",
+    "mg_free": "i:p",
+    "mg_memcpy_h2d": "i:ppz",
+    "mg_memcpy_d2h": "i:ppz",
+    "mg_device_synchronize": "i:",
+    "mg_host_alloc": "i:pz",
+    "mg_host_free": "i:p",
+    "mg_set_kernel_timing": "i:i",
+    "mg_last_accumulate_ms": "f:",
+    "mg_last_accumulate_mhz": "f:",
+    "mg_clock_probe": "i:uppp",
+    "mg_last_ntt_ms": "i:p",
+    "mg_last_prove_phases_ms": "i:p",
+    "mg_last_pass_host_ms": "i:p",
+    "mg_hw_queues": "i:p",
+    "mg_bases_create": "i:iipziip",
+    "mg_bases_create_sharded": "i:iipzpiip",
+    "mg_bases_num_shards": "i:p",
+    "mg_bases_shard": "i:pippp",
+    "mg_bases_destroy": "v:p",
+    "mg_bases_device_bytes": "z:p",
+    "mg_msm": "i:ppzp",
+    "mg_msm_launch": "i:ppziip",
+    "mg_msm_launch_sharded": "i:ppiip",
+    "mg_msm_finish": "i:pp",
+    "mg_msm_result_to_device": "i:ppp",
+    "mg_xyzz_limbs": "z:ii",
+    "mg_xyzz_sum": "i:iipzp",
+    "mg_points_sum": "i:iipzp",
+    "mg_fixed_base_mul": "i:iippzp",
+    "mg_ec_elementwise": "i:iiippzp",
+    "mg_field_op": "i:iiiiippzp",
+    "mg_fpr_raw_op": "i:iiippppzp",
+    "mg_fpr_column_plan": "i:iippppp",
+    "mg_msm_digits": "i:ipzziiizpzzipppp",
+    "mg_sort_pairs": "i:ppzipuupp",
+    "mg_msm_dense_front_applies": "i:zziii",
+    "mg_msm_dense_front": "i:ipziizpzppp",
+    "mg_group_ntt": "i:iipuip",
+    "mg_point_serialize": "i:iipip",
+    "mg_ntt": "i:ipuii",
+    "mg_ntt_device": "i:ipuii",
+    "mg_groth16_setup": "i:ipppqqqpppp",
+    "mg_qap_columns": "i:iizppqqup",
+    "mg_mpc_initialize": "i:ippppqqqqppp",
+    "mg_ctx_create": "i:ipp",
+    "mg_tuning_init": "i:p",
+    "mg_get_tuning": "i:p",
+    "mg_set_tuning": "i:p",
+    "mg_tuning_env_names": "n:",
+    "mg_ctx_opts_init": "i:p",
+    "mg_ctx_create_ex": "i:ippp",
+    "mg_ctx_create_from_bytes_ex": "i:ipzppp",
+    "mg_ctx_create_sharded": "i:ippip",
+    "mg_ctx_create_from_bytes_sharded": "i:ipzpip",
+    "mg_ctx_create_shard": "i:ipiip",
+    "mg_ctx_create_task": "i:ipup",
+    "mg_partials_slot_limbs": "z:p",
+    "mg_groth16_partials_launch": "i:pqpppp",
+    "mg_groth16_partials_finish": "i:p",
+    "mg_groth16_assemble": "i:pqipppp",
+    "mg_ctx_create_from_bytes": "i:ipzp",
+    "mg_ctx_create_from_bytes_checked": "i:ipzpp",
+    "mg_blake3": "i:pzp",
+    "mg_blake2s256": "i:pzp",
+    "mg_blake2s": "i:pzzp",
+    "mg_aes256_gcm": "i:pppzipp",
+    "mg_ctx_set_r1cs": "i:ppppq",
+    "mg_groth16_prove": "i:ppppp",
+    "mg_groth16_prove_batch": "i:pqpppp",
+    "mg_witness_map": "i:ppp",
+    "mg_ctx_r1cs_check": "i:pqppp",
+    "mg_r1cs_check": "i:ipppqqqppp",
+    "mg_ctx_domain_size": "q:p",
+    "mg_ctx_table_bytes": "i:pp",
+    "mg_ctx_num_variables": "q:p",
+    "mg_ctx_num_inputs": "q:p",
+    "mg_ctx_num_shards": "i:p",
+    "mg_ctx_destroy": "v:p",
+    "mg_vk_create": "i:ipppppqp",
+    "mg_vk_create_from_bytes": "i:ipzp",
+    "mg_vk_encoded_size": "z:p",
+    "mg_vk_encode": "i:pp",
+    "mg_vk_alpha_beta": "i:pp",
+    "mg_vk_num_inputs": "q:p",
+    "mg_vk_destroy": "v:p",
+    "mg_groth16_verify": "i:pppp",
+    "mg_groth16_verify_batch": "i:pqpppp",
+    "mg_pairing_check_each": "i:ippzzp",
+    "mg_groth16_verify_each": "i:pqppp",
+    "mg_pairing_check": "i:ippzp",
+    "mg_pairing_op": "i:iipppzp",
+    "mg_proof_decode": "i:ipp",
+    "mg_points_decode": "i:iipziippp",
+    "mg_points_check": "i:iipzpp",
+    "mg_points_encode": "i:iipzip",
+    "mg_proofs_decode": "i:ipzpp",
+    "mg_ppot_points_decode": "i:iipziippp",
+    "mg_ppot_points_encode": "i:iipzip",
+    "mg_blake2b512": "i:pzp",
+    "mg_poseidon_create": "i:iiiipzp",
+    "mg_poseidon_destroy": "v:p",
+    "mg_poseidon_permute": "i:ppz",
+    "mg_poseidon_hash": "i:ppzp",
+    "mg_poseidon_hash_device": "i:ppzp",
+    "mg_merkle_tree": "i:pupzppzp",
+    "mg_merkle_forest_roots": "i:puppzp",
+    "mg_merkle_forest_append": "i:puzpppppppzpppzp",
+    "mg_edwards_decode": "i:ipzippp",
+    "mg_edwards_encode": "i:ipzp",
+    "mg_edwards_check": "i:ipzpp",
+    "mg_edwards_mul": "i:iipzpzp",
+    "mg_edwards_add": "i:ippzp",
+    "mg_note_cipher_create": "i:ipzpp",
+    "mg_note_cipher_destroy": "v:p",
+    "mg_notes_encrypt": "i:ppppzppp",
+    "mg_notes_decrypt": "i:pppppzppp",
+    "mg_utxo_model_create": "i:ipp",
+    "mg_utxo_model_destroy": "v:p",
+    "mg_utxos_mint": "i:ppppzppp",
+    "mg_utxos_open": "i:pppppzpppp",
+    "mg_viewing_keys": "i:ppzpp",
+    "mg_schnorr_challenges": "i:ppppzpzp",
+    "mg_signatures_verify": "i:pppppzpzpp",
+    "mg_signatures_sign": "i:ppppzpzppp",
+    "mg_address_partitions": "i:ppzp",
+    "mg_merkle_shard_indices": "i:ipzp",
+    "mg_light_notes_encrypt": "i:ppppzppp",
+    "mg_light_notes_open": "i:pppppzpppp",
+    "mg_outgoing_notes_encrypt": "i:ppppzppp",
+    "mg_outgoing_notes_open": "i:ppppzppp",
+}
+EXPORTS = list(_SIGNATURES)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -38,54 +184,16 @@ def _load():
     except Exception:  # pragma: no cover
         pass
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    lib.mg_strerror.restype = ctypes.c_char_p
-    lib.mg_last_error.restype = ctypes.c_char_p
-    lib.mg_bases_device_bytes.restype = ctypes.c_size_t
-    lib.mg_ctx_domain_size.restype = ctypes.c_uint64
-    lib.mg_ctx_num_variables.restype = ctypes.c_uint64
-    lib.mg_ctx_num_inputs.restype = ctypes.c_uint64
-    lib.mg_last_accumulate_ms.restype = ctypes.c_float
-    lib.mg_last_accumulate_mhz.restype = ctypes.c_float
-    lib.mg_vk_encoded_size.restype = ctypes.c_size_t
-    lib.mg_vk_num_inputs.restype = ctypes.c_uint64
-    lib.mg_xyzz_limbs.restype = ctypes.c_size_t
-    lib.mg_partials_slot_limbs.restype = ctypes.c_size_t
+    for name, sig in _SIGNATURES.items():
+        ret, params = sig.split(":")
+        fn = getattr(lib, name)  # a symbol the library lacks fails the import here
+        fn.restype, fn.argtypes = _KINDS[ret], [_KINDS[k] for k in params]
     return lib
 
 
 LIB = _load()
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
-
-EXPORTS = [
-    "mg_init", "mg_strerror", "mg_last_error", "mg_device_count", "mg_malloc", "mg_free", "mg_memcpy_h2d",
-    "mg_memcpy_d2h", "mg_device_synchronize", "mg_host_alloc", "mg_host_free", "mg_set_kernel_timing", "mg_last_accumulate_ms", "mg_bases_create", "mg_bases_destroy", "mg_bases_device_bytes",
-    "mg_msm", "mg_msm_launch", "mg_msm_finish", "mg_points_sum", "mg_fixed_base_mul", "mg_ec_elementwise", "mg_point_serialize", "mg_ntt",
-    "mg_msm_digits", "mg_sort_pairs", "mg_msm_dense_front_applies", "mg_msm_dense_front",
-    "mg_ntt_device", "mg_groth16_setup", "mg_ctx_create", "mg_ctx_create_from_bytes", "mg_ctx_set_r1cs", "mg_groth16_prove", "mg_groth16_prove_batch", "mg_witness_map", "mg_ctx_domain_size", "mg_ctx_table_bytes",
-    "mg_ctx_destroy", "mg_bases_create_sharded", "mg_bases_num_shards", "mg_bases_shard", "mg_msm_launch_sharded",
-    "mg_ctx_create_sharded", "mg_ctx_create_from_bytes_sharded", "mg_ctx_num_variables", "mg_ctx_num_inputs",
-    "mg_ctx_num_shards", "mg_field_op", "mg_vk_create", "mg_vk_create_from_bytes", "mg_vk_encoded_size", "mg_vk_encode",
-    "mg_vk_alpha_beta", "mg_vk_num_inputs", "mg_vk_destroy", "mg_groth16_verify", "mg_groth16_verify_batch", "mg_pairing_check", "mg_proof_decode", "mg_group_ntt",
-    "mg_msm_result_to_device", "mg_xyzz_limbs", "mg_xyzz_sum", "mg_ctx_create_shard", "mg_partials_slot_limbs",
-    "mg_groth16_partials_launch", "mg_groth16_partials_finish", "mg_groth16_assemble", "mg_blake3", "mg_ctx_create_from_bytes_checked",
-    "mg_last_ntt_ms", "mg_hw_queues", "mg_last_prove_phases_ms", "mg_clock_probe", "mg_last_accumulate_mhz", "mg_ctx_create_task",
-    "mg_ctx_opts_init", "mg_ctx_create_ex", "mg_ctx_create_from_bytes_ex", "mg_last_pass_host_ms",
-    "mg_tuning_init", "mg_get_tuning", "mg_set_tuning", "mg_tuning_env_names",
-    "mg_points_decode", "mg_points_check", "mg_points_encode", "mg_proofs_decode",
-    "mg_ppot_points_decode", "mg_ppot_points_encode", "mg_blake2b512",
-    "mg_poseidon_create", "mg_poseidon_destroy", "mg_poseidon_permute", "mg_poseidon_hash", "mg_poseidon_hash_device",
-    "mg_merkle_tree", "mg_merkle_forest_roots", "mg_merkle_forest_append",
-    "mg_edwards_decode", "mg_edwards_encode", "mg_edwards_check", "mg_edwards_mul", "mg_edwards_add",
-    "mg_note_cipher_create", "mg_note_cipher_destroy", "mg_notes_encrypt", "mg_notes_decrypt",
-    "mg_utxo_model_create", "mg_utxo_model_destroy", "mg_utxos_mint", "mg_utxos_open", "mg_viewing_keys",
-    "mg_blake2s256", "mg_schnorr_challenges", "mg_signatures_verify", "mg_signatures_sign",
-    "mg_blake2s", "mg_aes256_gcm", "mg_address_partitions", "mg_merkle_shard_indices",
-    "mg_light_notes_encrypt", "mg_light_notes_open", "mg_outgoing_notes_encrypt", "mg_outgoing_notes_open",
-    "mg_qap_columns", "mg_mpc_initialize", "mg_fpr_raw_op", "mg_fpr_column_plan",
-    "mg_pairing_check_each", "mg_groth16_verify_each", "mg_pairing_op",
-    "mg_ctx_r1cs_check", "mg_r1cs_check",
-]
 
 
 def _chk(rc, where):
@@ -113,7 +221,7 @@ def _addr(x):
 
 
 def init(device=0):
-    _chk(LIB.mg_init(int(device)), "mg_init")
+    _chk(LIB.mg_init(device), "mg_init")
 
 
 def device_count():
@@ -123,7 +231,7 @@ def device_count():
 
 
 def set_kernel_timing(on):
-    _chk(LIB.mg_set_kernel_timing(int(bool(on))), "mg_set_kernel_timing")
+    _chk(LIB.mg_set_kernel_timing(bool(on)), "mg_set_kernel_timing")
 
 
 def last_accumulate_ms():
@@ -138,7 +246,7 @@ def clock_probe(iters=200000):
     """`mg_clock_probe`: (MHz the s_memtime counter ran at, wave-level v_mad_u64_u32 issued per SIMD and microsecond, probe ms)
     under an all-SIMD integer multiply-add load of two wavefronts per SIMD"""
     a, b, c = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
-    _chk(LIB.mg_clock_probe(ctypes.c_uint(iters), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "mg_clock_probe")
+    _chk(LIB.mg_clock_probe(iters, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "mg_clock_probe")
     return a.value, b.value, c.value
 
 
@@ -184,7 +292,7 @@ class PinnedArray:
     def __init__(self, shape, dtype=np.uint64):
         self.nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
         ptr = _vp()
-        _chk(LIB.mg_host_alloc(ctypes.byref(ptr), _sz(self.nbytes)), "mg_host_alloc")
+        _chk(LIB.mg_host_alloc(ctypes.byref(ptr), self.nbytes), "mg_host_alloc")
         self._ptr = ptr
         buf = (ctypes.c_uint8 * self.nbytes).from_address(ptr.value)
         self.array = np.frombuffer(buf, dtype=dtype).reshape(shape)
@@ -215,19 +323,19 @@ class DeviceBuffer:
     def __init__(self, nbytes):
         self.nbytes = int(nbytes)
         ptr = _vp()
-        _chk(LIB.mg_malloc(ctypes.byref(ptr), _sz(self.nbytes)), "mg_malloc")
+        _chk(LIB.mg_malloc(ctypes.byref(ptr), self.nbytes), "mg_malloc")
         self.ptr = ptr
 
     @classmethod
     def from_numpy(cls, arr):
         arr = np.ascontiguousarray(arr)
         b = cls(arr.nbytes)
-        _chk(LIB.mg_memcpy_h2d(b.ptr, _p(arr), _sz(arr.nbytes)), "mg_memcpy_h2d")
+        _chk(LIB.mg_memcpy_h2d(b.ptr, _p(arr), arr.nbytes), "mg_memcpy_h2d")
         return b
 
     def to_numpy(self, dtype=np.uint64, shape=None):
         out = np.empty(self.nbytes // np.dtype(dtype).itemsize, dtype=dtype)
-        _chk(LIB.mg_memcpy_d2h(_p(out), self.ptr, _sz(self.nbytes)), "mg_memcpy_d2h")
+        _chk(LIB.mg_memcpy_d2h(_p(out), self.ptr, self.nbytes), "mg_memcpy_d2h")
         return out if shape is None else out.reshape(shape)
 
     def offset(self, nbytes):
@@ -263,19 +371,17 @@ class Bases:
             assert pts.ndim == 2 and pts.shape[1] == affine_limbs(curve, group), pts.shape
             self.n = pts.shape[0]
             dv = (ctypes.c_int * len(devices))(*devices)
-            _chk(LIB.mg_bases_create_sharded(curve, group, _p(pts), _sz(self.n), dv, len(devices),
-                                             int(precompute_window_bits), ctypes.byref(h)), "mg_bases_create_sharded")
+            _chk(LIB.mg_bases_create_sharded(curve, group, _p(pts), self.n, dv, len(devices), precompute_window_bits,
+                                             ctypes.byref(h)), "mg_bases_create_sharded")
         elif on_device:
             ptr, n = points
-            _chk(LIB.mg_bases_create(curve, group, ptr, _sz(n), 1, int(precompute_window_bits), ctypes.byref(h)),
-                 "mg_bases_create")
+            _chk(LIB.mg_bases_create(curve, group, ptr, n, 1, precompute_window_bits, ctypes.byref(h)), "mg_bases_create")
             self.n = n
         else:
             pts = _u64(points)
             assert pts.ndim == 2 and pts.shape[1] == affine_limbs(curve, group), pts.shape
             self.n = pts.shape[0]
-            _chk(LIB.mg_bases_create(curve, group, _p(pts), _sz(self.n), 0, int(precompute_window_bits),
-                                     ctypes.byref(h)), "mg_bases_create")
+            _chk(LIB.mg_bases_create(curve, group, _p(pts), self.n, 0, precompute_window_bits, ctypes.byref(h)), "mg_bases_create")
         self.handle = h
         self.precompute_window_bits = int(precompute_window_bits)
 
@@ -335,7 +441,7 @@ class VariableBaseMSM:
         infinity = zeros). Like arkworks, zips to the shorter of bases/scalars."""
         sc = _u64(scalars)
         out = np.zeros(affine_limbs(bases.curve, bases.group), dtype=np.uint64)
-        _chk(LIB.mg_msm(bases.handle, _p(sc), _sz(sc.shape[0]), _p(out)), "mg_msm")
+        _chk(LIB.mg_msm(bases.handle, _p(sc), sc.shape[0], _p(out)), "mg_msm")
         return out
 
     @staticmethod
@@ -343,8 +449,7 @@ class VariableBaseMSM:
         """Scalars already in HBM (DeviceBuffer or raw pointer); returns a job to `finish()`."""
         ptr = d_scalars.ptr if isinstance(d_scalars, DeviceBuffer) else d_scalars
         h = _vp()
-        _chk(LIB.mg_msm_launch(bases.handle, ptr, _sz(n), int(bool(scalars_mont)) | (2 if sparse else 0), int(window_bits),
-                               ctypes.byref(h)),
+        _chk(LIB.mg_msm_launch(bases.handle, ptr, n, bool(scalars_mont) | (2 if sparse else 0), window_bits, ctypes.byref(h)),
              "mg_msm_launch")
         return MsmJob(bases, h)
 
@@ -354,15 +459,15 @@ class VariableBaseMSM:
         ptrs = [d.ptr if isinstance(d, DeviceBuffer) else d for d in d_scalars_per_shard]
         arr = (_vp * len(ptrs))(*ptrs)
         h = _vp()
-        _chk(LIB.mg_msm_launch_sharded(bases.handle, arr, int(bool(scalars_mont)) | (2 if sparse else 0), int(window_bits),
-                                       ctypes.byref(h)), "mg_msm_launch_sharded")
+        _chk(LIB.mg_msm_launch_sharded(bases.handle, arr, bool(scalars_mont) | (2 if sparse else 0), window_bits, ctypes.byref(h)),
+             "mg_msm_launch_sharded")
         return MsmJob(bases, h)
 
 
 def blake3(data: bytes) -> bytes:
     """`blake3::hash` (manta-parameters' checksum, lib.rs:173-177), computed by the library's host code"""
     out = ctypes.create_string_buffer(32)
-    _chk(LIB.mg_blake3(bytes(data), _sz(len(data)), out), "mg_blake3")
+    _chk(LIB.mg_blake3(bytes(data), len(data), out), "mg_blake3")
     return out.raw
 
 
@@ -371,10 +476,10 @@ def blake2s(data: bytes, digest_size=None) -> bytes:
     digest_size (1..32) the same hash with a digest of that length (`mg_blake2s`), which is no prefix of the 32-byte one"""
     if digest_size is None:
         out = ctypes.create_string_buffer(32)
-        _chk(LIB.mg_blake2s256(bytes(data), _sz(len(data)), out), "mg_blake2s256")
+        _chk(LIB.mg_blake2s256(bytes(data), len(data), out), "mg_blake2s256")
         return out.raw
     out = ctypes.create_string_buffer(32)
-    _chk(LIB.mg_blake2s(bytes(data), _sz(len(data)), _sz(int(digest_size)), out), "mg_blake2s")
+    _chk(LIB.mg_blake2s(bytes(data), len(data), digest_size, out), "mg_blake2s")
     return out.raw[:int(digest_size)]
 
 
@@ -385,7 +490,7 @@ def aes256_gcm_encrypt(key: bytes, nonce: bytes, plaintext: bytes) -> bytes:
     if len(key) != 32 or len(nonce) != 12:
         raise ValueError("aes256_gcm: a 32-byte key and a 12-byte nonce")
     out = ctypes.create_string_buffer(len(plaintext) + 16)
-    _chk(LIB.mg_aes256_gcm(key, nonce, plaintext, _sz(len(plaintext)), 0, out, None), "mg_aes256_gcm")
+    _chk(LIB.mg_aes256_gcm(key, nonce, plaintext, len(plaintext), 0, out, None), "mg_aes256_gcm")
     return out.raw
 
 
@@ -396,7 +501,7 @@ def aes256_gcm_decrypt(key: bytes, nonce: bytes, sealed: bytes):
         raise ValueError("aes256_gcm: a 32-byte key, a 12-byte nonce and at least the 16 bytes of a tag")
     out = ctypes.create_string_buffer(max(1, len(sealed) - 16))
     ok = ctypes.c_int(0)
-    _chk(LIB.mg_aes256_gcm(key, nonce, sealed, _sz(len(sealed)), 1, out, ctypes.byref(ok)), "mg_aes256_gcm")
+    _chk(LIB.mg_aes256_gcm(key, nonce, sealed, len(sealed), 1, out, ctypes.byref(ok)), "mg_aes256_gcm")
     return out.raw[:len(sealed) - 16], bool(ok.value)
 
 
@@ -408,20 +513,20 @@ def xyzz_sum(curve, group, xyzz) -> np.ndarray:
     """sum of XYZZ points (arkworks Montgomery limbs X | Y | ZZ | ZZZ, ZZ = 0: infinity) -> one affine point"""
     pts = _u64(xyzz).reshape(-1, xyzz_limbs(curve, group))
     out = np.zeros(affine_limbs(curve, group), dtype=np.uint64)
-    _chk(LIB.mg_xyzz_sum(curve, group, _p(pts), _sz(pts.shape[0]), _p(out)), "mg_xyzz_sum")
+    _chk(LIB.mg_xyzz_sum(curve, group, _p(pts), pts.shape[0], _p(out)), "mg_xyzz_sum")
     return out
 
 
 def points_sum(curve, group, points):
     pts = _u64(points)
     out = np.zeros(affine_limbs(curve, group), dtype=np.uint64)
-    _chk(LIB.mg_points_sum(curve, group, _p(pts), _sz(pts.shape[0]), _p(out)), "mg_points_sum")
+    _chk(LIB.mg_points_sum(curve, group, _p(pts), pts.shape[0], _p(out)), "mg_points_sum")
     return out
 
 
 def fixed_base_mul(curve, group, base, d_scalars: DeviceBuffer, n) -> DeviceBuffer:
     out = DeviceBuffer(n * affine_limbs(curve, group) * 8)
-    _chk(LIB.mg_fixed_base_mul(curve, group, _p(_u64(base)), d_scalars.ptr, _sz(n), out.ptr), "mg_fixed_base_mul")
+    _chk(LIB.mg_fixed_base_mul(curve, group, _p(_u64(base)), d_scalars.ptr, n, out.ptr), "mg_fixed_base_mul")
     return out
 
 
@@ -435,7 +540,7 @@ def group_ntt(curve, group, points, inverse=False) -> np.ndarray:
     lg = n.bit_length() - 1
     assert 1 << lg == n and pts.shape[1] == affine_limbs(curve, group)
     out = np.zeros_like(pts)
-    _chk(LIB.mg_group_ntt(curve, group, _p(pts), lg, int(bool(inverse)), _p(out)), "mg_group_ntt")
+    _chk(LIB.mg_group_ntt(curve, group, _p(pts), lg, bool(inverse), _p(out)), "mg_group_ntt")
     return out
 
 
@@ -446,7 +551,7 @@ def ec_elementwise(curve, group, op, a, b=None) -> np.ndarray:
     n = a.shape[0]
     out = np.zeros_like(a)
     bb = _p(_u64(b)) if b is not None else None
-    _chk(LIB.mg_ec_elementwise(curve, group, op, _p(a), bb, _sz(n), _p(out)), "mg_ec_elementwise")
+    _chk(LIB.mg_ec_elementwise(curve, group, op, _p(a), bb, n, _p(out)), "mg_ec_elementwise")
     return out
 
 
@@ -464,8 +569,7 @@ def field_op(field, op, a, b=None, repr=0, lazy_a=0, lazy_b=0) -> np.ndarray:
     out = np.zeros_like(a)
     bb = None if b is None else _u64(b)
     assert bb is None or bb.shape == a.shape
-    _chk(LIB.mg_field_op(FIELD_IDS[field], FIELD_OPS[op], int(repr), int(lazy_a), int(lazy_b), _p(a), _p(bb), _sz(a.shape[0]),
-                         _p(out)), "mg_field_op")
+    _chk(LIB.mg_field_op(FIELD_IDS[field], FIELD_OPS[op], repr, lazy_a, lazy_b, _p(a), _p(bb), a.shape[0], _p(out)), "mg_field_op")
     return out
 
 
@@ -485,8 +589,8 @@ def fpr_raw_op(field, op, a, b=None, c=None, d=None, chain=False) -> np.ndarray:
     for x in arrs[:need]:
         assert x is not None and x.ndim == 2 and x.shape == arrs[0].shape and x.shape[1] == K, (op, None if x is None else x.shape)
     out = np.zeros_like(arrs[0])
-    _chk(LIB.mg_fpr_raw_op(FIELD_IDS[field], FPR_OPS[op], int(bool(chain)), _p(arrs[0]), _p(arrs[1]), _p(arrs[2]), _p(arrs[3]),
-                           _sz(arrs[0].shape[0]), _p(out)), "mg_fpr_raw_op")
+    _chk(LIB.mg_fpr_raw_op(FIELD_IDS[field], FPR_OPS[op], bool(chain), _p(arrs[0]), _p(arrs[1]), _p(arrs[2]), _p(arrs[3]),
+                           arrs[0].shape[0], _p(out)), "mg_fpr_raw_op")
     return out
 
 
@@ -520,7 +624,7 @@ def pairing_op(curve, op, a, b=None, coeffs=None) -> np.ndarray:
         assert b.shape == (n, wb), (op, b.shape)
     else:
         b = None
-    _chk(LIB.mg_pairing_op(curve, PAIRING_OPS[op], _p(a), _p(b), _p(coeffs), _sz(n), _p(out)), "mg_pairing_op")
+    _chk(LIB.mg_pairing_op(curve, PAIRING_OPS[op], _p(a), _p(b), _p(coeffs), n, _p(out)), "mg_pairing_op")
     return out
 
 
@@ -560,8 +664,8 @@ def msm_digits(curve, scalars, c, n, mont=False, table_mode=0, map=None, n_sets=
     assert mp is None or mp.shape == (n,), mp.shape
     count = ctypes.c_uint32(0)
     layout = (ctypes.c_uint32 * 4)()
-    _chk(LIB.mg_msm_digits(curve, _p(sc), _sz(batch), _sz(n_scalars), int(bool(mont)), int(c), int(table_mode), _sz(n), _p(mp), _sz(n_sets),
-                           _sz(n if set_len is None else set_len), int(bool(compact)), _p(k), _p(v), ctypes.byref(count) if compact else None,
+    _chk(LIB.mg_msm_digits(curve, _p(sc), batch, n_scalars, bool(mont), c, table_mode, n, _p(mp), n_sets,
+                           n if set_len is None else set_len, bool(compact), _p(k), _p(v), ctypes.byref(count) if compact else None,
                            layout), "mg_msm_digits")
     assert layout[0] == W
     return dict(W=int(layout[0]), B=int(layout[1]), seg_keys=int(layout[2]), invalid=int(layout[3]), keys=k, vals=v,
@@ -570,7 +674,7 @@ def msm_digits(curve, scalars, c, n, mont=False, table_mode=0, map=None, n_sets=
 
 def msm_dense_front_applies(batch, n_sets, windows, table_mode, sparse):
     """Whether a launch of this shape takes the fused front end (`mg_msm_dense_front_applies`; no device involved)"""
-    return bool(LIB.mg_msm_dense_front_applies(_sz(batch), _sz(n_sets), int(windows), int(table_mode), int(bool(sparse))))
+    return bool(LIB.mg_msm_dense_front_applies(batch, n_sets, windows, table_mode, bool(sparse)))
 
 
 def msm_dense_front(curve, scalars, c, n, mont=False, map=None, set_len=None, keys=None, vals=None):
@@ -585,8 +689,8 @@ def msm_dense_front(curve, scalars, c, n, mont=False, map=None, set_len=None, ke
     mp = None if map is None else np.ascontiguousarray(map, dtype=np.uint32)
     assert mp is None or mp.shape == (n,), mp.shape
     layout = (ctypes.c_uint32 * 4)()
-    _chk(LIB.mg_msm_dense_front(curve, _p(sc), _sz(sc.shape[0]), int(bool(mont)), int(c), _sz(n), _p(mp), _sz(n if set_len is None else set_len),
-                                _p(k), _p(v), layout), "mg_msm_dense_front")
+    _chk(LIB.mg_msm_dense_front(curve, _p(sc), sc.shape[0], bool(mont), c, n, _p(mp), n if set_len is None else set_len, _p(k), _p(v),
+                                layout), "mg_msm_dense_front")
     return dict(W=int(layout[0]), B=int(layout[1]), seg_keys=int(layout[2]), inf_index=int(layout[3]), keys=k, vals=v)
 
 
@@ -600,15 +704,14 @@ def sort_pairs(keys, vals, end_bit, count=None, lowmask=0xFFFFFFFF, inv_from=0xF
     assert v.shape == (n,)
     ko, vo = _u32_buffer(keys_out, n, "keys_out"), _u32_buffer(vals_out, n, "vals_out")
     cnt = None if count is None else ctypes.byref(ctypes.c_uint32(count))
-    _chk(LIB.mg_sort_pairs(_p(k), _p(v), _sz(n), int(end_bit), cnt, ctypes.c_uint32(lowmask), ctypes.c_uint32(inv_from), _p(ko), _p(vo)),
-         "mg_sort_pairs")
+    _chk(LIB.mg_sort_pairs(_p(k), _p(v), n, end_bit, cnt, lowmask, inv_from, _p(ko), _p(vo)), "mg_sort_pairs")
     return ko, vo
 
 
 def point_serialize(curve, group, point, compressed=True):
     nb = FQ_LIMBS[curve] * 8 * (2 if group == 2 else 1) * (1 if compressed else 2)
     out = ctypes.create_string_buffer(nb)
-    _chk(LIB.mg_point_serialize(curve, group, _p(_u64(point)), int(compressed), out), "mg_point_serialize")
+    _chk(LIB.mg_point_serialize(curve, group, _p(_u64(point)), bool(compressed), out), "mg_point_serialize")
     return out.raw
 
 
@@ -623,7 +726,7 @@ class Radix2EvaluationDomain:
     def _run(self, data, inverse, coset):
         d = np.array(data, dtype=np.uint64, copy=True)
         assert d.shape == (self.size, 4)
-        _chk(LIB.mg_ntt(self.curve, _p(d), self.log_size, int(inverse), int(coset)), "mg_ntt")
+        _chk(LIB.mg_ntt(self.curve, _p(d), self.log_size, inverse, coset), "mg_ntt")
         return d
 
     def fft(self, data):
@@ -639,7 +742,7 @@ class Radix2EvaluationDomain:
         return self._run(data, True, True)
 
     def fft_device(self, dbuf: DeviceBuffer, inverse=False, coset=False):
-        _chk(LIB.mg_ntt_device(self.curve, dbuf.ptr, self.log_size, int(inverse), int(coset)), "mg_ntt_device")
+        _chk(LIB.mg_ntt_device(self.curve, dbuf.ptr, self.log_size, bool(inverse), bool(coset)), "mg_ntt_device")
 
 
 # ------------------------------------------------------------------------------------------------ Groth16
@@ -712,9 +815,8 @@ def groth16_setup(r1cs: "R1CS", n_vars, toxic_mont, g1_generator, g2_generator) 
         val = _u64(M.val)
         ms.append((rp, col, val, _Csr(_p(rp), _p(col), _p(val), len(col))))
     tox = _u64(toxic_mont).reshape(5, 4)
-    _chk(LIB.mg_groth16_setup(curve, ctypes.byref(ms[0][3]), ctypes.byref(ms[1][3]), ctypes.byref(ms[2][3]),
-                              ctypes.c_uint64(m), ctypes.c_uint64(V), ctypes.c_uint64(P), _p(tox), _p(_u64(g1_generator)),
-                              _p(_u64(g2_generator)), ctypes.byref(out)), "mg_groth16_setup")
+    _chk(LIB.mg_groth16_setup(curve, ctypes.byref(ms[0][3]), ctypes.byref(ms[1][3]), ctypes.byref(ms[2][3]), m, V, P, _p(tox),
+                              _p(_u64(g1_generator)), _p(_u64(g2_generator)), ctypes.byref(out)), "mg_groth16_setup")
     return pk
 
 
@@ -745,9 +847,8 @@ def r1cs_check(curve, A, B, C, m, n_vars, zs):
     k = zs.size // (n_vars * 4) if n_vars > 0 else 0
     keep = [_csr(M) for M in (A, B, C)]
     first, count = np.zeros(k, dtype=np.uint64), np.zeros(k, dtype=np.uint64)
-    _chk(LIB.mg_r1cs_check(curve, ctypes.byref(keep[0][1]), ctypes.byref(keep[1][1]), ctypes.byref(keep[2][1]),
-                           ctypes.c_uint64(int(m)), ctypes.c_uint64(n_vars), ctypes.c_uint64(k), _p(zs), _p(first), _p(count)),
-         "mg_r1cs_check")
+    _chk(LIB.mg_r1cs_check(curve, ctypes.byref(keep[0][1]), ctypes.byref(keep[1][1]), ctypes.byref(keep[2][1]), m, n_vars, k, _p(zs),
+                           _p(first), _p(count)), "mg_r1cs_check")
     return _r1cs_verdicts(first, count)
 
 
@@ -768,8 +869,7 @@ def qap_columns(curve, group, bases, mats, n_cols, entries_per_lane=0) -> np.nda
     bp = (ctypes.c_void_p * max(len(bases), 1))(*[b.ctypes.data for b in bases])
     mp = (ctypes.POINTER(_Csr) * max(len(mats), 1))(*[ctypes.pointer(k[1]) for k in keep])
     out = np.zeros((int(n_cols), affine_limbs(curve, group)), dtype=np.uint64)
-    _chk(LIB.mg_qap_columns(curve, group, _sz(len(bases)), bp, mp, ctypes.c_uint64(m), ctypes.c_uint64(int(n_cols)),
-                            ctypes.c_uint32(int(entries_per_lane)), _p(out)), "mg_qap_columns")
+    _chk(LIB.mg_qap_columns(curve, group, len(bases), bp, mp, m, n_cols, entries_per_lane, _p(out)), "mg_qap_columns")
     return out
 
 
@@ -802,9 +902,8 @@ def mpc_initialize(curve, tau_powers_g1, tau_powers_g2, alpha_tau_powers_g1, bet
     out = _PkOut(*[_p(getattr(pk, k)) for k, _ in _PkOut._fields_])
     keep = [_csr(M) for M in (r1cs.A, r1cs.B, r1cs.C)]
     _chk(LIB.mg_mpc_initialize(curve, ctypes.byref(view), ctypes.byref(keep[0][1]), ctypes.byref(keep[1][1]),
-                               ctypes.byref(keep[2][1]), ctypes.c_uint64(m), ctypes.c_uint64(V), ctypes.c_uint64(P),
-                               ctypes.c_uint64(h_len), _p(_u64(g1_generator)), _p(_u64(g2_generator)), ctypes.byref(out)),
-         "mg_mpc_initialize")
+                               ctypes.byref(keep[2][1]), m, V, P, h_len, _p(_u64(g1_generator)), _p(_u64(g2_generator)),
+                               ctypes.byref(out)), "mg_mpc_initialize")
     return pk
 
 
@@ -856,7 +955,6 @@ def set_tuning(t: Tuning = None, **kw):
 
 def tuning_env_names() -> list:
     """the environment variables the shipped library reads (mg_tuning_env_names)"""
-    LIB.mg_tuning_env_names.restype = ctypes.POINTER(ctypes.c_char_p)
     arr, out, i = LIB.mg_tuning_env_names(), [], 0
     while arr[i]:
         out.append(arr[i].decode())
@@ -916,7 +1014,7 @@ class ProvingContext:
         v = _PkView(pk.V, pk.P, self._keep[8].shape[0], *[_p(a) for a in self._keep])
         h = _vp()
         if task_mask is not None and int(task_mask) == 0:  # a rank beyond the fifth owns no MSM: the struct reads 0 as "all five"
-            _chk(LIB.mg_ctx_create_task(curve, ctypes.byref(v), ctypes.c_uint(0), ctypes.byref(h)), "mg_ctx_create_task")
+            _chk(LIB.mg_ctx_create_task(curve, ctypes.byref(v), 0, ctypes.byref(h)), "mg_ctx_create_task")
         elif shard is not None and int(shard[1]) == 1 and devices is None and task_mask is None and full_table_bytes is None and tuning is None:
             # a world of one driven through the partials interface: the entry point that says so (no combined a | b_g1 | l table)
             _chk(LIB.mg_ctx_create_shard(curve, ctypes.byref(v), 0, 1, ctypes.byref(h)), "mg_ctx_create_shard")
@@ -942,7 +1040,7 @@ class ProvingContext:
         if checksum is not None and len(checksum) != 32:
             raise ValueError("a BLAKE3 digest is 32 bytes")
         o, keep = _ctx_opts(devices, None, None, full_table_bytes, exchange, tuning)
-        _chk(LIB.mg_ctx_create_from_bytes_ex(curve, bytes(data), _sz(len(data)), None if checksum is None else bytes(checksum),
+        _chk(LIB.mg_ctx_create_from_bytes_ex(curve, bytes(data), len(data), None if checksum is None else bytes(checksum),
                                              ctypes.byref(o), ctypes.byref(h)), "mg_ctx_create_from_bytes_ex")
         del keep
         self.handle = h
@@ -977,7 +1075,7 @@ class ProvingContext:
             val = _u64(M.val)
             ms.append((rp, col, val, _Csr(_p(rp), _p(col), _p(val), len(col))))
         _chk(LIB.mg_ctx_set_r1cs(self.handle, ctypes.byref(ms[0][3]), ctypes.byref(ms[1][3]), ctypes.byref(ms[2][3]),
-                                 ctypes.c_uint64(r1cs.num_constraints)), "mg_ctx_set_r1cs")
+                                 r1cs.num_constraints), "mg_ctx_set_r1cs")
         import weakref
         self._r1cs_ref = weakref.ref(r1cs)  # the uploaded matrices belong to exactly this R1CS object
 
@@ -1001,8 +1099,8 @@ class ProvingContext:
         ([k][5][slot] u64); `stream` waits for them. Returns a handle for partials_finish()."""
         zs = self._check_assignment(zs, k)
         h = _vp()
-        _chk(LIB.mg_groth16_partials_launch(self.handle, ctypes.c_uint64(k), _p(zs), _addr(d_out_ptr), _addr(stream),
-                                            ctypes.byref(h)), "mg_groth16_partials_launch")
+        _chk(LIB.mg_groth16_partials_launch(self.handle, k, _p(zs), _addr(d_out_ptr), _addr(stream), ctypes.byref(h)),
+             "mg_groth16_partials_launch")
         return h
 
     @staticmethod
@@ -1019,8 +1117,7 @@ class ProvingContext:
         parts = np.ascontiguousarray(parts, dtype=np.uint64).reshape(-1, k, 5, slot)
         n = PROOF_BYTES[self.curve]
         out = ctypes.create_string_buffer(n * k)
-        _chk(LIB.mg_groth16_assemble(self.handle, ctypes.c_uint64(k), int(parts.shape[0]), _p(parts), _p(rs), _p(ss), out),
-             "mg_groth16_assemble")
+        _chk(LIB.mg_groth16_assemble(self.handle, k, parts.shape[0], _p(parts), _p(rs), _p(ss), out), "mg_groth16_assemble")
         return [out.raw[i * n:(i + 1) * n] for i in range(k)]
 
     def witness_map(self, z):
@@ -1037,7 +1134,7 @@ class ProvingContext:
         k = zs.size // (self.num_variables * 4)
         zs = self._check_assignment(zs, k)
         first, count = np.zeros(k, dtype=np.uint64), np.zeros(k, dtype=np.uint64)
-        _chk(LIB.mg_ctx_r1cs_check(self.handle, ctypes.c_uint64(k), _p(zs), _p(first), _p(count)), "mg_ctx_r1cs_check")
+        _chk(LIB.mg_ctx_r1cs_check(self.handle, k, _p(zs), _p(first), _p(count)), "mg_ctx_r1cs_check")
         return _r1cs_verdicts(first, count)
 
     def close(self):
@@ -1095,8 +1192,7 @@ class Groth16:
         zs = context._check_assignment(zs, k)
         n = PROOF_BYTES[context.curve]
         out = ctypes.create_string_buffer(n * k)
-        _chk(LIB.mg_groth16_prove_batch(context.handle, ctypes.c_uint64(k), _p(zs), _p(rs), _p(ss), out),
-             "mg_groth16_prove_batch")
+        _chk(LIB.mg_groth16_prove_batch(context.handle, k, _p(zs), _p(rs), _p(ss), out), "mg_groth16_prove_batch")
         return [out.raw[i * n:(i + 1) * n] for i in range(k)]
 
 
@@ -1108,7 +1204,7 @@ def pairing_check(curve, g1_points, g2_points) -> bool:
     if g1.shape[0] != g2.shape[0] or g1.shape[0] == 0:
         raise ValueError("pairing_check: as many G1 as G2 points, at least one")
     ok = ctypes.c_int(0)
-    _chk(LIB.mg_pairing_check(curve, _p(g1), _p(g2), ctypes.c_size_t(g1.shape[0]), ctypes.byref(ok)), "mg_pairing_check")
+    _chk(LIB.mg_pairing_check(curve, _p(g1), _p(g2), g1.shape[0], ctypes.byref(ok)), "mg_pairing_check")
     return bool(ok.value)
 
 
@@ -1143,8 +1239,7 @@ def points_decode(curve, group, data, compressed=True, checked=True):
     n = len(data) // nb
     out = np.zeros((n, affine_limbs(curve, group)), dtype=np.uint64)
     st = np.zeros(n, dtype=np.uint8)
-    _chk(LIB.mg_points_decode(curve, group, data, _sz(n), int(compressed), int(checked), _p(out), _p(st), None),
-         "mg_points_decode")
+    _chk(LIB.mg_points_decode(curve, group, data, n, bool(compressed), bool(checked), _p(out), _p(st), None), "mg_points_decode")
     return out, st
 
 
@@ -1152,7 +1247,7 @@ def points_check(curve, group, points) -> np.ndarray:
     """`C::check` / `State::check` on the GPU (`mg_points_check`): status [n] uint8 (POINT_*) of affine Montgomery points."""
     pts = _u64(points).reshape(-1, affine_limbs(curve, group))
     st = np.zeros(pts.shape[0], dtype=np.uint8)
-    _chk(LIB.mg_points_check(curve, group, _p(pts), _sz(pts.shape[0]), _p(st), None), "mg_points_check")
+    _chk(LIB.mg_points_check(curve, group, _p(pts), pts.shape[0], _p(st), None), "mg_points_check")
     return st
 
 
@@ -1161,7 +1256,7 @@ def points_encode(curve, group, points, compressed=True) -> bytes:
     `point_serialize`."""
     pts = _u64(points).reshape(-1, affine_limbs(curve, group))
     out = ctypes.create_string_buffer(max(1, pts.shape[0] * point_bytes(curve, group, compressed)))
-    _chk(LIB.mg_points_encode(curve, group, _p(pts), _sz(pts.shape[0]), int(compressed), out), "mg_points_encode")
+    _chk(LIB.mg_points_encode(curve, group, _p(pts), pts.shape[0], bool(compressed), out), "mg_points_encode")
     return out.raw[:pts.shape[0] * point_bytes(curve, group, compressed)]
 
 
@@ -1189,8 +1284,7 @@ def ppot_points_decode(group, data, compressed, checked=True):
     n = view.size // nb
     out = np.zeros((n, affine_limbs(BN254, group)), dtype=np.uint64)
     st = np.zeros(n, dtype=np.uint8)
-    _chk(LIB.mg_ppot_points_decode(BN254, group, _p(view), _sz(n), int(compressed), int(checked), _p(out), _p(st), None),
-         "mg_ppot_points_decode")
+    _chk(LIB.mg_ppot_points_decode(BN254, group, _p(view), n, bool(compressed), bool(checked), _p(out), _p(st), None), "mg_ppot_points_decode")
     return out, st
 
 
@@ -1199,7 +1293,7 @@ def ppot_points_encode(group, points, compressed) -> bytes:
     pts = _u64(points).reshape(-1, affine_limbs(BN254, group))
     nb = pts.shape[0] * ppot_point_bytes(group, compressed)
     out = ctypes.create_string_buffer(max(1, nb))
-    _chk(LIB.mg_ppot_points_encode(BN254, group, _p(pts), _sz(pts.shape[0]), int(compressed), out), "mg_ppot_points_encode")
+    _chk(LIB.mg_ppot_points_encode(BN254, group, _p(pts), pts.shape[0], bool(compressed), out), "mg_ppot_points_encode")
     return out.raw[:nb]
 
 
@@ -1208,7 +1302,7 @@ def blake2b512(data) -> bytes:
     PPoT file headers and responses"""
     view = _byte_view(data)
     out = ctypes.create_string_buffer(64)
-    _chk(LIB.mg_blake2b512(_p(view), _sz(view.size), out), "mg_blake2b512")
+    _chk(LIB.mg_blake2b512(_p(view), view.size, out), "mg_blake2b512")
     return out.raw
 
 
@@ -1223,7 +1317,7 @@ def proofs_decode(curve, proofs):
     k = len(data) // pb
     out = np.zeros((k, 2 * affine_limbs(curve, 1) + affine_limbs(curve, 2)), dtype=np.uint64)
     ok = np.zeros(k, dtype=np.uint8)
-    _chk(LIB.mg_proofs_decode(curve, data, _sz(k), _p(out), _p(ok)), "mg_proofs_decode")
+    _chk(LIB.mg_proofs_decode(curve, data, k, _p(out), _p(ok)), "mg_proofs_decode")
     return out, ok.astype(bool)
 
 
@@ -1246,7 +1340,7 @@ class PoseidonHasher:
         self._h = _vp()
         self.curve, self.width, self.full_rounds, self.partial_rounds = curve, width, full_rounds, partial_rounds
         data = bytes(data)
-        _chk(LIB.mg_poseidon_create(curve, int(width), int(full_rounds), int(partial_rounds), data, _sz(len(data)),
+        _chk(LIB.mg_poseidon_create(curve, width, full_rounds, partial_rounds, data, len(data),
                                     ctypes.byref(self._h)), "mg_poseidon_create")
 
     @classmethod
@@ -1265,21 +1359,21 @@ class PoseidonHasher:
     def permute(self, states) -> np.ndarray:
         """[n, width, 4] states -> the permuted states (mg_poseidon_permute)"""
         st = np.array(_u64(states).reshape(-1, self.width, 4))
-        _chk(LIB.mg_poseidon_permute(self._h, _p(st), _sz(st.shape[0])), "mg_poseidon_permute")
+        _chk(LIB.mg_poseidon_permute(self._h, _p(st), st.shape[0]), "mg_poseidon_permute")
         return st
 
     def hash(self, inputs) -> np.ndarray:
         """[n, width - 1, 4] inputs -> [n, 4] digests (mg_poseidon_hash)"""
         x = _u64(inputs).reshape(-1, self.width - 1, 4)
         out = np.zeros((x.shape[0], 4), dtype=np.uint64)
-        _chk(LIB.mg_poseidon_hash(self._h, _p(x), _sz(x.shape[0]), _p(out)), "mg_poseidon_hash")
+        _chk(LIB.mg_poseidon_hash(self._h, _p(x), x.shape[0], _p(out)), "mg_poseidon_hash")
         return out
 
     def hash_device(self, d_inputs, n, d_out=None) -> "DeviceBuffer":
         """n x (width - 1) inputs already in HBM -> n digests in HBM (mg_poseidon_hash_device); d_out is allocated if None"""
         if d_out is None:
             d_out = DeviceBuffer(max(1, n) * 32)
-        _chk(LIB.mg_poseidon_hash_device(self._h, _addr(d_inputs), _sz(n), _addr(d_out)), "mg_poseidon_hash_device")
+        _chk(LIB.mg_poseidon_hash_device(self._h, _addr(d_inputs), n, _addr(d_out)), "mg_poseidon_hash_device")
         return d_out
 
     def close(self):
@@ -1302,8 +1396,7 @@ def merkle_tree(hasher: PoseidonHasher, height, leaves, indices=()):
     idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
     root = np.zeros(4, dtype=np.uint64)
     paths = np.zeros((idx.shape[0], max(0, int(height) - 1), 4), dtype=np.uint64)
-    _chk(LIB.mg_merkle_tree(hasher._h, ctypes.c_uint(int(height)), _p(lv), _sz(lv.shape[0]), _p(root), _p(idx), _sz(idx.shape[0]),
-                            _p(paths)), "mg_merkle_tree")
+    _chk(LIB.mg_merkle_tree(hasher._h, height, _p(lv), lv.shape[0], _p(root), _p(idx), idx.shape[0], _p(paths)), "mg_merkle_tree")
     return root, paths
 
 
@@ -1313,8 +1406,7 @@ def merkle_forest_roots(hasher: PoseidonHasher, height, leaves, offsets) -> np.n
     off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
     nt = max(0, off.shape[0] - 1)
     roots = np.zeros((nt, 4), dtype=np.uint64)
-    _chk(LIB.mg_merkle_forest_roots(hasher._h, ctypes.c_uint(int(height)), _p(lv), _p(off), _sz(nt), _p(roots)),
-         "mg_merkle_forest_roots")
+    _chk(LIB.mg_merkle_forest_roots(hasher._h, height, _p(lv), _p(off), nt, _p(roots)), "mg_merkle_forest_roots")
     return roots
 
 
@@ -1393,9 +1485,9 @@ def merkle_forest_append(hasher: PoseidonHasher, height, state: MerkleState, lea
     roots = np.zeros((nt, 4), dtype=np.uint64)
     paths = np.zeros((pt.shape[0], plen, 4), dtype=np.uint64)
     old_c, new_c = state._c(), new._c()
-    _chk(LIB.mg_merkle_forest_append(hasher._h, ctypes.c_uint(height), _sz(nt), ctypes.byref(old_c), _p(lv), _p(off), _p(roots),
-                                     ctypes.byref(new_c), _p(pt), _p(pi), _sz(pt.shape[0]), _p(paths), _p(rt), _p(ri),
-                                     _sz(rt.shape[0]), _p(rp)), "mg_merkle_forest_append")
+    _chk(LIB.mg_merkle_forest_append(hasher._h, height, nt, ctypes.byref(old_c), _p(lv), _p(off), _p(roots), ctypes.byref(new_c),
+                                     _p(pt), _p(pi), pt.shape[0], _p(paths), _p(rt), _p(ri), rt.shape[0], _p(rp)),
+         "mg_merkle_forest_append")
     return roots, new, paths, rp
 
 
@@ -1431,7 +1523,7 @@ def edwards_decode(data, checked=True, curve=BN254):
     n = len(data) // 32
     out = np.zeros((n, 8), dtype=np.uint64)
     st = np.zeros(n, dtype=np.uint8)
-    _chk(LIB.mg_edwards_decode(curve, data, _sz(n), int(checked), _p(out), _p(st), None), "mg_edwards_decode")
+    _chk(LIB.mg_edwards_decode(curve, data, n, bool(checked), _p(out), _p(st), None), "mg_edwards_decode")
     return out, st
 
 
@@ -1439,7 +1531,7 @@ def edwards_encode(points, curve=BN254) -> bytes:
     """[n, 8] affine Montgomery points -> their 32-byte encodings back to back (`mg_edwards_encode`)"""
     pts = _ed_points(points)
     out = ctypes.create_string_buffer(max(1, pts.shape[0] * 32))
-    _chk(LIB.mg_edwards_encode(curve, _p(pts), _sz(pts.shape[0]), out), "mg_edwards_encode")
+    _chk(LIB.mg_edwards_encode(curve, _p(pts), pts.shape[0], out), "mg_edwards_encode")
     return out.raw[:pts.shape[0] * 32]
 
 
@@ -1447,7 +1539,7 @@ def edwards_check(points, curve=BN254) -> np.ndarray:
     """status [n] uint8 (POINT_*) of affine Montgomery points: reduced, on the curve, in the subgroup (`mg_edwards_check`)"""
     pts = _ed_points(points)
     st = np.zeros(pts.shape[0], dtype=np.uint8)
-    _chk(LIB.mg_edwards_check(curve, _p(pts), _sz(pts.shape[0]), _p(st), None), "mg_edwards_check")
+    _chk(LIB.mg_edwards_check(curve, _p(pts), pts.shape[0], _p(st), None), "mg_edwards_check")
     return st
 
 
@@ -1463,7 +1555,7 @@ def edwards_mul(mode, points, scalars, curve=BN254) -> np.ndarray:
     pts, sc = _ed_points(points), _u64(scalars).reshape(-1, 4)
     n = pts.shape[0] if mode == EDWARDS_MUL_SHARED_SCALAR else sc.shape[0]
     out = np.zeros((n, 8), dtype=np.uint64)
-    _chk(LIB.mg_edwards_mul(curve, int(mode), _p(pts), _sz(pts.shape[0]), _p(sc), _sz(sc.shape[0]), _p(out)), "mg_edwards_mul")
+    _chk(LIB.mg_edwards_mul(curve, mode, _p(pts), pts.shape[0], _p(sc), sc.shape[0], _p(out)), "mg_edwards_mul")
     return out
 
 
@@ -1473,7 +1565,7 @@ def edwards_add(a, b, curve=BN254) -> np.ndarray:
     if a.shape != b.shape:
         raise ValueError("edwards_add: as many points in a as in b")
     out = np.zeros_like(a)
-    _chk(LIB.mg_edwards_add(curve, _p(a), _p(b), _sz(a.shape[0]), _p(out)), "mg_edwards_add")
+    _chk(LIB.mg_edwards_add(curve, _p(a), _p(b), a.shape[0], _p(out)), "mg_edwards_add")
     return out
 
 
@@ -1488,7 +1580,7 @@ class NoteCipher:
         g = _u64(generator).reshape(-1)
         if g.size != 8:
             raise ValueError("generator: one affine point (8 x u64)")
-        _chk(LIB.mg_note_cipher_create(curve, data, _sz(len(data)), _p(g), ctypes.byref(self._h)), "mg_note_cipher_create")
+        _chk(LIB.mg_note_cipher_create(curve, data, len(data), _p(g), ctypes.byref(self._h)), "mg_note_cipher_create")
 
     def encrypt(self, recv_keys, randomness, plaintexts):
         """n notes: recv_keys [n, 8], randomness [n, 4] scalars, plaintexts [n, 3, 4] Montgomery -> (epk [n, 8], ciphertext
@@ -1498,7 +1590,7 @@ class NoteCipher:
         if rnd.shape[0] != n or pt.shape[0] != n:
             raise ValueError("encrypt: one key, one randomness and one plaintext per note")
         epk, ct, tag = (np.zeros(s, dtype=np.uint64) for s in ((n, 8), (n, 3, 4), (n, 4)))
-        _chk(LIB.mg_notes_encrypt(self._h, _p(rk), _p(rnd), _p(pt), _sz(n), _p(epk), _p(ct), _p(tag)), "mg_notes_encrypt")
+        _chk(LIB.mg_notes_encrypt(self._h, _p(rk), _p(rnd), _p(pt), n, _p(epk), _p(ct), _p(tag)), "mg_notes_encrypt")
         return epk, ct, tag
 
     def decrypt(self, viewing_key, epks, ciphertexts, tags):
@@ -1510,7 +1602,7 @@ class NoteCipher:
             raise ValueError("decrypt: one viewing key; one epk, ciphertext and tag per note")
         pt = np.zeros((n, 3, 4), dtype=np.uint64)
         ok, st = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
-        _chk(LIB.mg_notes_decrypt(self._h, _p(vk), _p(ep), _p(ct), _p(tg), _sz(n), _p(pt), _p(ok), _p(st)), "mg_notes_decrypt")
+        _chk(LIB.mg_notes_decrypt(self._h, _p(vk), _p(ep), _p(ct), _p(tg), n, _p(pt), _p(ok), _p(st)), "mg_notes_decrypt")
         return pt, ok.astype(bool), st
 
     def close(self):
@@ -1577,7 +1669,7 @@ class UtxoModel:
         if pt.shape[0] != n or fl.shape[0] != n:
             raise ValueError("mint: one key, one plaintext and one flag per UTXO")
         utxos, items, st = np.zeros((n, 4, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64), np.zeros(n, dtype=np.uint8)
-        _chk(LIB.mg_utxos_mint(self._h, _p(rk), _p(pt), _p(fl), _sz(n), _p(utxos), _p(items), _p(st)), "mg_utxos_mint")
+        _chk(LIB.mg_utxos_mint(self._h, _p(rk), _p(pt), _p(fl), n, _p(utxos), _p(items), _p(st)), "mg_utxos_mint")
         return utxos, items, st
 
     def open(self, viewing_key, plaintexts, utxos, pak=None):
@@ -1595,7 +1687,7 @@ class UtxoModel:
         st, items = np.zeros(n, dtype=np.uint8), np.zeros((n, 4), dtype=np.uint64)
         nul = None if pak is None else np.zeros((n, 4), dtype=np.uint64)
         n_ok = _sz(0)
-        _chk(LIB.mg_utxos_open(self._h, _p(vk), _p(pak), _p(pt), _p(ut), _sz(n), _p(st), _p(items), _p(nul), ctypes.byref(n_ok)),
+        _chk(LIB.mg_utxos_open(self._h, _p(vk), _p(pak), _p(pt), _p(ut), n, _p(st), _p(items), _p(nul), ctypes.byref(n_ok)),
              "mg_utxos_open")
         return st, items, nul, int(n_ok.value)
 
@@ -1606,7 +1698,7 @@ class UtxoModel:
         n = pk.shape[0]
         vks = np.zeros((n, 4), dtype=np.uint64)
         rks = np.zeros((n, 8), dtype=np.uint64) if recv_keys else None
-        _chk(LIB.mg_viewing_keys(self._h, _p(pk), _sz(n), _p(vks), _p(rks)), "mg_viewing_keys")
+        _chk(LIB.mg_viewing_keys(self._h, _p(pk), n, _p(vks), _p(rks)), "mg_viewing_keys")
         return vks, rks
 
     def schnorr_challenges(self, pks, nonce_points, messages, lengths=None):
@@ -1618,8 +1710,7 @@ class UtxoModel:
             raise ValueError("schnorr_challenges: one key and one nonce point per signature")
         msg, stride, lens = _messages(messages, lengths, n)
         out = np.zeros((n, 4), dtype=np.uint64)
-        _chk(LIB.mg_schnorr_challenges(self._h, _p(pk), _p(rp), _p(msg), _sz(stride), _p(lens), _sz(n), _p(out)),
-             "mg_schnorr_challenges")
+        _chk(LIB.mg_schnorr_challenges(self._h, _p(pk), _p(rp), _p(msg), stride, _p(lens), n, _p(out)), "mg_schnorr_challenges")
         return out
 
     def verify_signatures(self, pks, nonce_points, scalars, messages, lengths=None):
@@ -1632,7 +1723,7 @@ class UtxoModel:
         msg, stride, lens = _messages(messages, lengths, n)
         st = np.zeros(n, dtype=np.uint8)
         n_ok = _sz(0)
-        _chk(LIB.mg_signatures_verify(self._h, _p(pk), _p(rp), _p(sc), _p(msg), _sz(stride), _p(lens), _sz(n), _p(st),
+        _chk(LIB.mg_signatures_verify(self._h, _p(pk), _p(rp), _p(sc), _p(msg), stride, _p(lens), n, _p(st),
                                       ctypes.byref(n_ok)), "mg_signatures_verify")
         return st, int(n_ok.value)
 
@@ -1646,7 +1737,7 @@ class UtxoModel:
         msg, stride, lens = _messages(messages, lengths, n)
         s, rp = np.zeros((n, 4), dtype=np.uint64), np.zeros((n, 8), dtype=np.uint64)
         pk = np.zeros((n, 8), dtype=np.uint64) if pks else None
-        _chk(LIB.mg_signatures_sign(self._h, _p(sk), _p(k), _p(msg), _sz(stride), _p(lens), _sz(n), _p(s), _p(rp), _p(pk)),
+        _chk(LIB.mg_signatures_sign(self._h, _p(sk), _p(k), _p(msg), stride, _p(lens), n, _p(s), _p(rp), _p(pk)),
              "mg_signatures_sign")
         return s, rp, pk
 
@@ -1654,7 +1745,7 @@ class UtxoModel:
         """`AddressPartitionFunction::partition` of n receiving keys [n, 8] -> [n] uint8 (`mg_address_partitions`)"""
         rk = _ed_points(recv_keys)
         out = np.zeros(rk.shape[0], dtype=np.uint8)
-        _chk(LIB.mg_address_partitions(self._h, _p(rk), _sz(rk.shape[0]), _p(out)), "mg_address_partitions")
+        _chk(LIB.mg_address_partitions(self._h, _p(rk), rk.shape[0], _p(out)), "mg_address_partitions")
         return out
 
     def light_encrypt(self, recv_keys, randomness, plaintexts, epks=True):
@@ -1667,7 +1758,7 @@ class UtxoModel:
             raise ValueError("light_encrypt: one key, one randomness and one plaintext per note")
         epk = np.zeros((n, 8), dtype=np.uint64) if epks else None
         ct, st = np.zeros((n, LIGHT_NOTE_BYTES), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
-        _chk(LIB.mg_light_notes_encrypt(self._h, _p(rk), _p(rnd), _p(pt), _sz(n), _p(epk), _p(ct), _p(st)), "mg_light_notes_encrypt")
+        _chk(LIB.mg_light_notes_encrypt(self._h, _p(rk), _p(rnd), _p(pt), n, _p(epk), _p(ct), _p(st)), "mg_light_notes_encrypt")
         return epk, ct, st
 
     def light_open(self, viewing_key, epks, notes, partitions=None):
@@ -1686,7 +1777,7 @@ class UtxoModel:
         pt = np.zeros((n, 3, 4), dtype=np.uint64)
         ok, st = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
         tried = _sz(0)
-        _chk(LIB.mg_light_notes_open(self._h, _p(vk), _p(ep), _p(ct), _p(partitions), _sz(n), _p(pt), _p(ok), _p(st),
+        _chk(LIB.mg_light_notes_open(self._h, _p(vk), _p(ep), _p(ct), _p(partitions), n, _p(pt), _p(ok), _p(st),
                                      ctypes.byref(tried)), "mg_light_notes_open")
         return pt, ok.astype(bool), st, int(tried.value)
 
@@ -1699,7 +1790,7 @@ class UtxoModel:
         if rk.size != 8 or a.shape[0] != n:
             raise ValueError("outgoing_encrypt: one receiving key; one randomness and one asset per note")
         epk, ct, st = np.zeros((n, 8), dtype=np.uint64), np.zeros((n, OUTGOING_NOTE_BYTES), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
-        _chk(LIB.mg_outgoing_notes_encrypt(self._h, _p(rk), _p(rnd), _p(a), _sz(n), _p(epk), _p(ct), _p(st)),
+        _chk(LIB.mg_outgoing_notes_encrypt(self._h, _p(rk), _p(rnd), _p(a), n, _p(epk), _p(ct), _p(st)),
              "mg_outgoing_notes_encrypt")
         return epk, ct, st
 
@@ -1713,7 +1804,7 @@ class UtxoModel:
             raise ValueError("outgoing_open: one viewing key; one epk and one note per lane")
         a = np.zeros((n, 2, 4), dtype=np.uint64)
         ok, st = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
-        _chk(LIB.mg_outgoing_notes_open(self._h, _p(vk), _p(ep), _p(ct), _sz(n), _p(a), _p(ok), _p(st)), "mg_outgoing_notes_open")
+        _chk(LIB.mg_outgoing_notes_open(self._h, _p(vk), _p(ep), _p(ct), n, _p(a), _p(ok), _p(st)), "mg_outgoing_notes_open")
         return a, ok.astype(bool), st
 
     def close(self):
@@ -1733,7 +1824,7 @@ def merkle_shard_indices(leaves, curve=BN254) -> np.ndarray:
     leaves by to build the `offsets` of merkle_forest_roots (`mg_merkle_shard_indices`)"""
     lv = _u64(leaves).reshape(-1, 4)
     out = np.zeros(lv.shape[0], dtype=np.uint8)
-    _chk(LIB.mg_merkle_shard_indices(curve, _p(lv), _sz(lv.shape[0]), _p(out)), "mg_merkle_shard_indices")
+    _chk(LIB.mg_merkle_shard_indices(curve, _p(lv), lv.shape[0], _p(out)), "mg_merkle_shard_indices")
     return out
 
 
@@ -1747,8 +1838,8 @@ class VerifyingContext:
         self.curve = curve
         arrs = [_u64(getattr(vk, k)) for k in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")]
         h = _vp()
-        _chk(LIB.mg_vk_create(curve, *[_p(a) for a in arrs], ctypes.c_uint64(arrs[4].reshape(-1, affine_limbs(curve, 1)).shape[0]),
-                              ctypes.byref(h)), "mg_vk_create")
+        _chk(LIB.mg_vk_create(curve, *[_p(a) for a in arrs], arrs[4].reshape(-1, affine_limbs(curve, 1)).shape[0], ctypes.byref(h)),
+             "mg_vk_create")
         self.handle = h
 
     @classmethod
@@ -1760,7 +1851,7 @@ class VerifyingContext:
         self = cls.__new__(cls)
         self.curve = curve
         h = _vp()
-        _chk(LIB.mg_vk_create_from_bytes(curve, bytes(data), _sz(len(data)), ctypes.byref(h)), "mg_vk_create_from_bytes")
+        _chk(LIB.mg_vk_create_from_bytes(curve, bytes(data), len(data), ctypes.byref(h)), "mg_vk_create_from_bytes")
         self.handle = h
         return self
 
@@ -1816,7 +1907,7 @@ def groth16_verify_batch(context: VerifyingContext, inputs, proofs, rand128) -> 
     pts = np.stack([_proof_points(context.curve, p) for p in proofs])
     rnd = _u64(rand128).reshape(k, 2)
     ok = ctypes.c_int(0)
-    _chk(LIB.mg_groth16_verify_batch(context.handle, ctypes.c_uint64(k), _p(inp), _p(_u64(pts)), _p(rnd), ctypes.byref(ok)),
+    _chk(LIB.mg_groth16_verify_batch(context.handle, k, _p(inp), _p(_u64(pts)), _p(rnd), ctypes.byref(ok)),
          "mg_groth16_verify_batch")
     return bool(ok.value)
 
@@ -1845,7 +1936,7 @@ def groth16_verify_each(context: VerifyingContext, inputs, proofs, out=None) -> 
     inp = inp.reshape(k, n_in, 4)
     ok = _verdicts(k, out)
     pts = _u64(np.stack([_proof_points(context.curve, p) for p in proofs])) if k else np.zeros((0, 1), dtype=np.uint64)
-    _chk(LIB.mg_groth16_verify_each(context.handle, ctypes.c_uint64(k), _p(inp) if n_in and k else None, _p(pts) if k else None,
+    _chk(LIB.mg_groth16_verify_each(context.handle, k, _p(inp) if n_in and k else None, _p(pts) if k else None,
                                     _p(ok)), "mg_groth16_verify_each")
     return ok[:k].astype(bool)
 
@@ -1859,6 +1950,5 @@ def pairing_check_each(curve, g1_points, g2_points, out=None) -> np.ndarray:
         raise ValueError("pairing_check_each: [n_groups, group_size, limbs] arrays, as many G1 as G2 points")
     n, g = g1.shape[:2]
     ok = _verdicts(n, out)
-    _chk(LIB.mg_pairing_check_each(curve, _p(g1) if n else None, _p(g2) if n else None, ctypes.c_size_t(g), ctypes.c_size_t(n),
-                                   _p(ok)), "mg_pairing_check_each")
+    _chk(LIB.mg_pairing_check_each(curve, _p(g1) if n else None, _p(g2) if n else None, g, n, _p(ok)), "mg_pairing_check_each")
     return ok[:n].astype(bool)

@@ -15,7 +15,65 @@ from manta_rs_amd import synth
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _header_statements():
+    """mantagpu.h without comments and preprocessor lines, whitespace collapsed"""
+    src = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "mantagpu.h")).read(), flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+    return re.sub(r"\s+", " ", " ".join(ln for ln in src.split("\n") if not ln.lstrip().startswith("#")))
+
+
+def _c_kind(decl, where, named=True):
+    """the ctypes class a C declaration crosses the ABI as (ctypes.c_void_p: any pointer or array); `named`: the declaration ends
+    in the parameter's or field's name. A type outside the header's vocabulary fails the test."""
+    import ctypes
+    scalars = {"int": ctypes.c_int, "mg_curve_t": ctypes.c_int, "unsigned": ctypes.c_uint32, "uint32_t": ctypes.c_uint32,
+               "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "uint64_t": ctypes.c_uint64,
+               "float": ctypes.c_float}
+    if "*" in decl or "[" in decl:
+        return ctypes.c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    kind = " ".join(words[:-1] if named else words)
+    assert kind in scalars, f"{where}: cannot classify {decl!r}"
+    return scalars[kind]
+
+
+def _header_prototypes():
+    """{name: (restype, [argtypes])} of every `ret mg_name(params);` of the header"""
+    import ctypes
+    returns = {"void": None, "const char *": ctypes.c_char_p, "const char *const *": ctypes.POINTER(ctypes.c_char_p)}
+    protos = {}
+    for st in _header_statements().split(";"):
+        m = re.fullmatch(r"((?:const )?\w+ (?:\*(?:const \*)?)?) ?(mg_\w+) ?\(([^()]*)\)", st.strip())
+        if not m:
+            assert not re.search(r"\bmg_\w+ ?\(", st), f"a prototype the parser does not read: {st.strip()!r}"
+            continue
+        ret, name, params = (g.strip() for g in m.groups())
+        restype = returns[ret] if ret in returns else _c_kind(ret, name, named=False)
+        protos[name] = (restype, [] if params == "void" else [_c_kind(p.strip(), name) for p in params.split(",")])
+    return protos
+
+
+def _header_struct_fields(struct):
+    """[(field name, ctypes class or nested struct name)] of `typedef struct [tag] { ... } struct;`, one entry per declarator"""
+    src = _header_statements()
+    end = src.index("} %s;" % struct)
+    body = src[src.rindex("typedef struct", 0, end):end].split("{", 1)[1]
+    fields = []
+    for st in filter(None, (s.strip() for s in body.split(";"))):
+        first, *more = (d.strip() for d in st.split(","))  # `const uint64_t *a, *b` declares two fields of the first one's type
+        base = first[:re.search(r"\*?\w+$", first).start()]
+        for d in [first] + [base + x for x in more]:
+            name = re.search(r"\w+$", d).group(0)
+            nested = re.fullmatch(r"(mg_\w+) \w+", d)
+            fields.append((name, nested.group(1) if nested else _c_kind(d, f"{struct}.{name}")))
+    return fields
+
+
 def test_library_exports_every_declared_symbol():
+    """The header's names are the library's and the binding's, and what the header says of every entry point's return value and
+    parameters, and of every struct that crosses the ABI, is what manta_rs_amd/api.py tells ctypes: a parameter left undeclared
+    would be passed as a 32-bit int whatever its C type."""
+    import ctypes
     from manta_rs_amd import api
     hdr = open(os.path.join(ROOT, "include", "mantagpu.h")).read()
     declared = set(re.findall(r"\b(mg_[a-z0-9_]+)\s*\(", hdr))
@@ -23,6 +81,37 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(api.LIB, name), f"{name} declared in mantagpu.h but not exported"
     assert declared == set(api.EXPORTS)
+    protos = _header_prototypes()
+    assert list(protos) == api.EXPORTS, "the binding's table lists the header's prototypes, in the header's order"
+    for name, (restype, argtypes) in protos.items():
+        fn = getattr(api.LIB, name)
+        assert fn.restype == restype, (name, fn.restype, restype)
+        assert fn.argtypes is not None and list(fn.argtypes) == argtypes, (name, fn.argtypes, argtypes)
+    mirrors = {"mg_pk_view": api._PkView, "mg_csr": api._Csr, "mg_pk_out": api._PkOut, "mg_kzg_view": api._KzgView, "mg_tuning": api.Tuning,
+               "mg_ctx_opts": api._CtxOpts, "mg_merkle_state": api._MerkleStateC, "mg_utxo_file": api._UtxoFile,
+               "mg_utxo_files": api._UtxoFiles}
+    for struct, mirror in mirrors.items():
+        want, got = _header_struct_fields(struct), mirror._fields_
+        assert len(got) == len(want), (struct, got, want)
+        for (cname, ckind), (pname, ptype) in zip(want, got):
+            if isinstance(ckind, str):  # a struct by value: the mirror of that struct
+                assert ptype is mirrors[ckind], (struct, cname, ptype)
+            elif ckind is ctypes.c_void_p:  # any ctypes pointer type
+                assert issubclass(ptype, (ctypes.c_void_p, ctypes.c_char_p, ctypes._Pointer)), (struct, cname, ptype)
+            else:  # same width, same signedness: ctypes has one class for each
+                assert ptype is ckind, (struct, cname, ptype, ckind)
+        if mirror is api.Tuning:
+            assert [p for p, _ in got] == [c for c, _ in want]
+
+
+def test_a_count_beyond_32_bits_reaches_the_library_whole():
+    """mg_msm_dense_front_applies (no device involved) turns down a batch or a set count of 2^31 or more. Called raw with plain
+    integers, 2^32 + 1 must arrive as that: without declared parameter types ctypes passes it as the 32-bit int 1, and the answer
+    is that of a single vector against a single set."""
+    from manta_rs_amd import api
+    assert api.LIB.mg_msm_dense_front_applies(1, 1, 8, 1, 0) == 1
+    assert api.LIB.mg_msm_dense_front_applies(2**32 + 1, 1, 8, 1, 0) == 0
+    assert api.LIB.mg_msm_dense_front_applies(1, 2**32 + 1, 8, 1, 0) == 0
 
 
 def test_no_gpu_is_an_error_not_a_fallback():
